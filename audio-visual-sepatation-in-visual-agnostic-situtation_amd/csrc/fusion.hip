@@ -257,12 +257,24 @@ __global__ __launch_bounds__(256) void fusion_av_bwd_kernel(FusArgs a, const flo
         atomicAdd(&s_E[((c ^ best) * 2 + c) * HW + hw], dmaps[((long long)b * 2 + c) * HW + hw]);
       }
   }
-  if (a.kind == 0)  // attended vector: f = v[d,h*] * att[c][h*]
-    for (int i = tid; i < D; i += 256) {
-      int c = i / Dc, d = i % Dc, h = sel_idx[(long long)b * D + i];
-      float vv = (c == 0 ? a.v0 : a.v1)[((long long)b * Dc + d) * HW + h];
-      atomicAdd(&s_E[((c ^ best) * 2 + c) * HW + h], dfeat[(long long)b * D + i] * vv);
+  if (a.kind == 0) {  // attended vector: f = v[d,h*] * att[c][h*]
+    // Many channels d select the same position h: one thread per (c, h) adds their terms in channel order after the two
+    // contributions above (at most two per element from zero: exact in either order).  Atomics here made the order, and so
+    // the rounding, differ from run to run, and a training run from one seed did not repeat.
+    int* s_sel = (int*)(s_S + 8);        // [D]: the s_ga region, first written after the barriers below
+    for (int i = tid; i < D; i += 256) s_sel[i] = sel_idx[(long long)b * D + i];
+    __syncthreads();
+    for (int t = tid; t < 2 * HW; t += 256) {
+      const int c = t / HW, h = t % HW;
+      const float* vp = (c == 0 ? a.v0 : a.v1) + (long long)b * Dc * HW + h;
+      const float* df = dfeat + (long long)b * D + c * Dc;
+      const int* sel = s_sel + c * Dc;
+      float acc = s_E[((c ^ best) * 2 + c) * HW + h];
+      for (int d = 0; d < Dc; ++d)
+        if (sel[d] == h) acc += df[d] * vp[(long long)d * HW];
+      s_E[((c ^ best) * 2 + c) * HW + h] = acc;
     }
+  }
   __syncthreads();
   const float inv_sqrt = 1.f / sqrtf((float)Dc);
   if (a.att == 1) {  // through the sigmoid: G = E * m(1-m)/sqrt(Dc)

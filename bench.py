@@ -8,21 +8,26 @@ batch 64, 65535-sample waveforms -> HIP STFT (1022/256) -> 512x256 magnitudes ->
 tiles, 3 RGB frames at 224^2 per source; one step = zero_grad + NetWrapper.forward (AV: visual encoder on 2x3
 frames, TWO U-Net passes over a shared encoder, fusion, BCE) + backward + SGD(momentum, wd) (reference
 main.py:557-569).  Inputs are resident in HBM before the timed region.  The reference computes in fp32, so fp32 is
-the headline arithmetic; the same run then times, outside the headline's timed region and explicitly labelled:
+the headline arithmetic.  A plain run times the headline and nothing else; with --full the same run then times, outside the
+headline's timed region and explicitly labelled:
   * "bf16": configs[2] as BASELINE.json names it — bf16 conv operands AND bf16 channel-blocked activation / gradient images
     in HBM (AVSEP_FMT_B16), fp32 accumulation / BatchNorm statistics / loss / master weights / SGD — with the loss
     difference to the fp32 path;
   * with --compare-miopen only: "f32_miopen_hybrid", round 1's configs[1] path (visual convolutions on PyTorch-ROCm /
     MIOpen through tools/miopen_compare, which patches the trunk of that one model instance), for comparison;
-  * the audio-only step and the 1:1 AV/AO alternation the shipped flags produce.
+  * the audio-only step and the 1:1 AV/AO alternation the shipped flags produce;
+  * BASELINE configs[4], "SDR on synthetic val" and the CPU baseline (the oracle's train step on this host's cores).
 
 Launch: python bench.py --gpus N --steps K --warmup W.  With N > 1 and no WORLD_SIZE in the environment bench.py
 starts its own N ranks (python -m torch.distributed.run on 127.0.0.1, one process per GPU) BEFORE anything touches the
 GPU and relays rank 0's line; under an external torch.distributed.run it is a rank.  Prints ONE JSON line on rank 0.
 
-The headline is timed WITHOUT per-kernel instrumentation; a second pass of the same configuration with HIP-event pairs
-around every convolution launch gives `roofline` / `by_kernel` (its own ms/step is reported as
+The headline is timed WITHOUT per-kernel instrumentation; with --full (or --layers) a second pass of the same configuration
+with HIP-event pairs around every convolution launch gives `roofline` / `by_kernel` (its own ms/step is reported as
 `instrumented_ms_per_step`, so the cost of the event pairs is visible).
+
+--dump-outputs DIR writes what the headline's last timed step returned (loss and the outputs dict of NetWrapper.forward) and
+the parameters it left, as DIR/<name>.npy, so that two builds can be compared output for output on identical seeded inputs.
 """
 import argparse
 import gc
@@ -43,6 +48,45 @@ BATCH_PER_GPU = 64
 
 
 CONFIG5_BATCH = 32       # BASELINE.json configs[4] / SURVEY 8: per-device batch 32
+DUMP_BYTES = 64 << 20    # --dump-outputs: at most this much in all
+DUMP_HEADER_BYTES = 4096 # reserved per file for its .npy header (numpy writes 128 bytes or a multiple of 64)
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy: float64 stays float64, floating types become float32, the rest float64.
+    An array larger than its share of DUMP_BYTES (less DUMP_HEADER_BYTES for its .npy header) is replaced by a fixed sample
+    of its flattened elements: the index space is cut into as many equal strata as the share allows and one position is
+    drawn in each from a generator of fixed seed, so every run with the same shapes writes the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    files = max(1, len(arrays))
+    cap = (DUMP_BYTES - DUMP_HEADER_BYTES * files) // (8 * files)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            n, rng = t.numel(), np.random.default_rng(0)
+            edges = np.arange(cap + 1, dtype=np.int64) * n // cap
+            idx = edges[:-1] + (rng.random(cap) * (edges[1:] - edges[:-1])).astype(np.int64)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        dt = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        np.save(os.path.join(path, name + ".npy"), t.to(dt).cpu().numpy())
+
+
+def step_arrays(err, outputs, nets):
+    """The arrays one train step hands its caller: the loss, every tensor of the outputs dict (lists as <key>_<i>) and a
+    flat view of the parameters it updated."""
+    arrays = {"loss": err}
+
+    def add(name, v):
+        if torch.is_tensor(v):
+            arrays[name] = v
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                add("%s_%d" % (name, i), x)
+    for k, v in outputs.items():
+        add(k, v)
+    arrays["params"] = torch.cat([p.detach().reshape(-1) for net in nets for p in net.parameters()])
+    return arrays
 
 
 def step_args(P, config=3):
@@ -294,8 +338,10 @@ def rehearse(o):
         dist.destroy_process_group()
 
 
-def run_config(P, dev, world, seed, rank, prec, backend, B, steps, warmup, timer=None, use_vis=True, config=3, force=False):
-    """Build the model from `seed`, run `warmup` untimed + `steps` timed train steps; returns the measurements."""
+def run_config(P, dev, world, seed, rank, prec, backend, B, steps, warmup, timer=None, use_vis=True, config=3, force=False,
+               dump=None):
+    """Build the model from `seed`, run `warmup` untimed + `steps` timed train steps; returns the measurements.  `dump`: a
+    directory that receives what the last timed step returned (dump_outputs), written after the timed region."""
     import torch.distributed as dist
     P.kernels.set_precision(prec)
     a, snd, frm, wrap = build(P, dev, seed, backend, config)
@@ -325,7 +371,7 @@ def run_config(P, dev, world, seed, rank, prec, backend, B, steps, warmup, timer
         timer.on = True
     t0 = time.perf_counter()
     for _ in range(steps):
-        err, match, _ = P.net_wrapper.train_step_async(wrap, batch(), opt, use_vis, a)
+        err, match, outs = P.net_wrapper.train_step_async(wrap, batch(), opt, use_vis, a)
     sync()
     dt = time.perf_counter() - t0
     if timer is not None:
@@ -347,7 +393,9 @@ def run_config(P, dev, world, seed, rank, prec, backend, B, steps, warmup, timer
             dist.all_reduce(opt.flat_grad)
         sync()
         res["allreduce_ms"] = (time.perf_counter() - t1) * 100.0
-    del wrap, opt, snd, frm, raw
+    if dump is not None:
+        dump_outputs(dump, step_arrays(err, outs, (snd, frm)))
+    del wrap, opt, snd, frm, raw, outs
     gc.collect()
     torch.cuda.empty_cache()
     P.kernels.set_precision("f32")
@@ -509,10 +557,11 @@ def main():
     ap.add_argument("--compare-miopen", action="store_true", help="also time the step with the visual convolutions on MIOpen "
                     "(tools/miopen_compare; comparison only, never the headline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the legs after the instrumented pass")
     ap.add_argument("--no-instrumented", action="store_true", help="profiling runs under rocprofv3: only the un-instrumented "
                     "headline pass (no HIP-event pairs, no per-kernel tables in the line)")
-    ap.add_argument("--layers", default=None, help="write a per-convolution-call table of the headline step to this file")
+    ap.add_argument("--layers", default=None, help="run the instrumented pass and write its per-convolution-call table of the "
+                    "headline step to this file")
     ap.add_argument("--config", type=int, default=3, choices=[3, 5], help="3: BASELINE configs[2] shape (headline); 5: configs[4] "
                     "(3 sources, 5 frames, 512x256, batch 32) as the headline workload of this run")
     ap.add_argument("--rehearse", action="store_true", help="launcher / rendezvous / all-reduce rehearsal without a train step "
@@ -523,7 +572,16 @@ def main():
     ap.add_argument("--sdr-only", action="store_true", help="run only the 'SDR on synthetic val' leg and print its JSON")
     ap.add_argument("--force-collective", action="store_true", help="--gpus 1 only: create a 1-rank RCCL group and issue the "
                     "step's early + late gradient all-reduce anyway; the line carries allreduce_ms and the no-collective time")
+    ap.add_argument("--full", action="store_true", help="after the headline also run the instrumented pass (roofline, by_kernel) "
+                    "and, on one GPU, the other precision, the audio-only step, configs[4], SDR on synthetic val and the CPU "
+                    "baseline (--no-instrumented / --no-extra / --no-cpu-baseline drop legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline's last timed step returned "
+                    "(loss, outputs, updated parameters; a fixed sample of large arrays, at most 64 MB in all) as DIR/<name>.npy")
     o = ap.parse_args()
+    if o.compare_miopen and not o.full:
+        ap.error("--compare-miopen is one of the --full legs")
+    if o.dump_outputs and (o.rehearse or o.sdr_only or o.force_collective):
+        ap.error("--dump-outputs writes the headline step's outputs: not with --rehearse, --sdr-only or --force-collective")
 
     if o.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(o))                 # before anything touches the GPU
@@ -563,14 +621,30 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         return
-    # headline: un-instrumented.  Then the same configuration once more with HIP-event pairs around every conv launch
-    head = run_config(P, dev, world, seed, rank, o.precision, o.backend, B, o.steps, o.warmup, config=o.config)
-    if o.no_instrumented:
+    # headline: un-instrumented.  With --full (or --layers) the same configuration once more with HIP-event pairs around
+    # every conv launch; with --full the other legs after it
+    head = run_config(P, dev, world, seed, rank, o.precision, o.backend, B, o.steps, o.warmup, config=o.config,
+                      dump=o.dump_outputs if rank == 0 else None)
+    vis = "visual trunk on this library (no MIOpen kernel in the step)"
+    line = {
+        "metric": "mixtures/sec (train step, 2-src MUSIC shape)", "value": head["value"],
+        "unit": "mixtures/s", "n_gpus": world, "steps": o.steps, "warmup": o.warmup,
+        "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "n_ranks_seen": dist.get_world_size() if world > 1 else 1,
+        "allreduce_bytes_per_step": head["allreduce_bytes_per_step"],      # ONE flat fp32 gradient all-reduce per step and rank
+        "dtype": o.precision, "data": "synthetic",
+        "config": {"workload": ("full HIP path, AV train step: 2-source mix, batch %d/GPU (BASELINE configs[2] shape), 65535-sample "
+                                "waveforms -> HIP STFT 1022/256 -> 256x256 log-freq tiles, 3x224^2 frames/source, unet7+hidsep(sig)+"
+                                "resnet18dilated, BCE, SGD; %s arithmetic; %s" if o.config != 5 else
+                                "full HIP path, AV train step: 3-source mix, batch %d/GPU (BASELINE configs[4]), 512x256 tiles, "
+                                "5x224^2 frames/source, unet7+hidsep(sig) N-source fusion+resnet18dilated; %s arithmetic; %s")
+                   % (B, o.precision, vis),
+                   "global_batch": world * B, "parallelism": f"dp{world}"},
+        "loss": head["loss"], "match_loss": head["match_loss"], "first_step_loss": head["first_step_loss"],
+    }
+    if o.no_instrumented or not (o.full or o.layers):
         if rank == 0:
-            print(json.dumps({"metric": "mixtures/sec (train step, 2-src MUSIC shape)", "value": head["value"], "unit": "mixtures/s",
-                              "n_gpus": world, "steps": o.steps, "warmup": o.warmup, "ms_per_step": head["ms_per_step"],
-                              "dtype": o.precision, "config": {"workload": "headline pass only (--no-instrumented), batch %d" % B},
-                              "loss": head["loss"]}))
+            print(json.dumps(line))
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -586,7 +660,7 @@ def main():
                 f.write("%-44s %-6s %-62s %5.1f %8.3f %7.1f\n" % (" ".join(map(str, layer)), mode, family[:62], n / o.steps, ms,
                                                                    fl / (ms * 1e-3) / 1e12 if ms else 0.0))
     extras = {}
-    if world == 1 and not o.no_extra:
+    if world == 1 and o.full and not o.no_extra:
         other = "bf16" if o.precision == "f32" else "f32"
         r = run_config(P, dev, world, seed, rank, other, "hip", B, o.steps, o.warmup, config=o.config)
         r_inst = run_config(P, dev, world, seed, rank, other, "hip", B, o.steps, 1, timer, config=o.config)
@@ -615,26 +689,11 @@ def main():
     if rank == 0:
         roof, roof_step, hbm = roofline_of(kernels, o.precision, head["ms_per_step"], B)
         add_traffic(roof, o.precision, B)
-        vis = "visual trunk on this library (no MIOpen kernel in the step)"
-        out = {
-            "metric": "mixtures/sec (train step, 2-src MUSIC shape)", "value": head["value"],
-            "unit": "mixtures/s", "n_gpus": world, "steps": o.steps, "warmup": o.warmup,
-            "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "n_ranks_seen": dist.get_world_size() if world > 1 else 1,
-            "allreduce_bytes_per_step": head["allreduce_bytes_per_step"],      # ONE flat fp32 gradient all-reduce per step and rank
+        out = dict(line, **{
             # the pass `roofline` / `by_kernel` come from: event pairs around every conv, every pass of the step on ONE stream
             # (kernel durations exclusive); the headline runs the independent passes on forked streams
             "instrumented_ms_per_step": inst["ms_per_step"],
             "streams": "headline: visual trunk per-source passes + the two decoder passes on forked HIP streams; instrumented: one stream",
-            "dtype": o.precision, "data": "synthetic",
-            "config": {"workload": ("full HIP path, AV train step: 2-source mix, batch %d/GPU (BASELINE configs[2] shape), 65535-sample "
-                                    "waveforms -> HIP STFT 1022/256 -> 256x256 log-freq tiles, 3x224^2 frames/source, unet7+hidsep(sig)+"
-                                    "resnet18dilated, BCE, SGD; %s arithmetic; %s" if o.config != 5 else
-                                    "full HIP path, AV train step: 3-source mix, batch %d/GPU (BASELINE configs[4]), 512x256 tiles, "
-                                    "5x224^2 frames/source, unet7+hidsep(sig) N-source fusion+resnet18dilated; %s arithmetic; %s")
-                       % (B, o.precision, vis),
-                       "global_batch": world * B, "parallelism": f"dp{world}"},
-            "loss": head["loss"], "match_loss": head["match_loss"], "first_step_loss": head["first_step_loss"],
             # dominant kernel = the MFMA kernel family with the largest time per step; achieved = its algorithmic FLOPs /
             # its HIP-event time (events on the launch stream, inside the timed region)
             "roofline": roof,
@@ -645,8 +704,8 @@ def main():
             "by_kernel": {k: {"ms_per_step": round(v["ms_per_step"], 3), "tflops": round(v["tflops"], 1),
                               "launches_per_step": v["launches_per_step"]} for k, v in kernels.items()},
             "extra": extras or None,
-        }
-        if world == 1 and not o.no_cpu_baseline:
+        })
+        if world == 1 and o.full and not o.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(P, seed)
         print(json.dumps(out))
     if world > 1:

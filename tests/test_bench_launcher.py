@@ -52,3 +52,26 @@ def test_bench_world_size_mismatch_is_an_error():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """--dump-outputs: small arrays as they are (float32, or float64), a large one as the same sorted sample positions on
+    every run, and at most bench.DUMP_BYTES in all."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"loss": torch.tensor([0.25]), "mask": torch.rand(2, 3), "big": torch.arange(20_000_000, dtype=torch.float64),
+              "idx": torch.arange(4), "half": torch.ones(2, dtype=torch.bfloat16)}
+    out = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+        out.append({f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)})
+    a, b = out
+    assert sorted(a) == sorted(arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in a) <= bench.DUMP_BYTES
+    assert a["loss"].dtype == a["mask"].dtype == a["half"].dtype == np.float32 and a["idx"].dtype == np.float64
+    np.testing.assert_array_equal(a["mask"], arrays["mask"].numpy())
+    big = a["big"]
+    assert big.dtype == np.float64 and 0 < big.size < 20_000_000 and np.all(np.diff(big) > 0)
+    np.testing.assert_array_equal(big, b["big"])

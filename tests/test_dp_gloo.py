@@ -18,6 +18,12 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _cpu_ranks(monkeypatch):
+    """The spawned workers are CPU ranks over gloo on any machine: where a GPU is visible, init_from_env would put every
+    rank on it.  The workers inherit an environment that hides the devices, as on a machine without one."""
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "")
+
+
 def _worker(rank, world, port, out):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
@@ -42,7 +48,8 @@ def _worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
-def test_two_rank_gradient_mean(tmp_path):
+def test_two_rank_gradient_mean(tmp_path, monkeypatch):
+    _cpu_ranks(monkeypatch)
     port, out = _free_port(), str(tmp_path / "r")
     mp.spawn(_worker, args=(2, port, out), nprocs=2, join=True)
     res = [torch.load(out + f".{r}") for r in range(2)]
@@ -105,11 +112,12 @@ def _flat_worker(rank, world, port, out, overlap):
     dist.destroy_process_group()
 
 
-def test_flat_sgd_buckets_over_two_gloo_ranks(tmp_path):
+def test_flat_sgd_buckets_over_two_gloo_ranks(tmp_path, monkeypatch):
     """FlatSGD's data-parallel half (net_wrapper.py: reduce_gradients, the early all-reduce of the first group armed by
     arm_early_reduce, the `only=` range of an audio-only step) on 2 gloo ranks: every rank ends up with the MEAN of the
     per-shard gradients = the single-process gradient of the concatenated batch, for AV, AO and AV steps, with and without
     the overlapped early all-reduce; the groups outside an audio-only step's range are left untouched (zero)."""
+    _cpu_ranks(monkeypatch)
     sys.path.insert(0, ROOT)
     for overlap in (0, 1):
         port, out = _free_port(), str(tmp_path / f"f{overlap}")
@@ -207,11 +215,12 @@ def _reporting_worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
-def test_early_allreduce_with_reporting_nodes_over_two_gloo_ranks(tmp_path):
+def test_early_allreduce_with_reporting_nodes_over_two_gloo_ranks(tmp_path, monkeypatch):
     """FlatSGD.node_finished / _pending / _nodes_left with REPORTING nodes (attach_grad_sink: the networks' ParamGrads
     place gradients themselves and report): with one and with two U-Net nodes per step, one parameter of the first node
     handed back to autograd, the early all-reduce of the first group starts exactly once per step — after the LAST node
     and after the handed-back gradient was accumulated — and every rank's flat gradient equals the mean over the ranks."""
+    _cpu_ranks(monkeypatch)
     sys.path.insert(0, ROOT)
     port, out = _free_port(), str(tmp_path / "rep")
     mp.spawn(_reporting_worker, args=(2, port, out), nprocs=2, join=True)
