@@ -15,6 +15,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
+// The Winograd kernels load x / dY through buffer resources of num_records = 0xfffffff0 with 32-bit byte offsets.  A tensor of
+// `elems` floats whose resource base lies `shift` elements before its first element is addressable as a whole when the byte
+// offset of its last element, plus 4, stays within num_records; beyond it a valid element loads as 0 or wraps round.
+static inline bool buf32_fits(long long elems, long long shift) { return 4 * (elems + shift) <= 0xfffffff0LL; }
 // The descriptor with the batch its launch heuristics are planned for (avsep_conv_desc.plan_n, 0 = N): kernel-family,
 // tile-size and split-K DECISIONS are taken on this copy, grids and workspace sizes on the real batch.
 static inline avsep_conv_desc plan_desc(const avsep_conv_desc* d) {

@@ -429,7 +429,7 @@ bool wn_applicable(const avsep_conv_desc* d, int mode) {
     const int C1 = d->Cin - d->C0;
     if (d->C0 % WN_CK || (C1 != 0 && C1 != d->C0)) return false;
   }
-  if ((long long)d->N * (mode == 0 ? d->C0 : d->Cout) * d->H * d->W >= 0x3fffffffLL) return false;   // 32-bit BYTE offsets
+  if (!buf32_fits((long long)d->N * (mode == 0 ? d->C0 : d->Cout) * d->H * d->W, 0)) return false;   // x (or dY) from its own base
   const avsep_conv_desc e = plan_desc(d);
   const WnPlan p = wn_plan(&e, mode);
   return (long long)p.ptiles * p.gridM >= 128;      // at least half of the CUs busy (below that the split-K im2col path wins)

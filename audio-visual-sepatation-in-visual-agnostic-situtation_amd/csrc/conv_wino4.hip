@@ -241,7 +241,7 @@ __global__ __launch_bounds__(W4_THREADS) void wino4_kernel(W4Args a) {
     dst[pc] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(src1 ? rs_x1 : rs_x0, (int)p_off[sl], (int)soff, 0));
   };
   auto g_issue = [&](int kt_, int pc) __attribute__((always_inline)) { g_issue_to(praw, kt_, pc); };
-  auto s_store_from = [&](const float* src, int kt, int buf, int pc) __attribute__((always_inline)) {
+  auto lds_put_from = [&](const float* src, int kt, int buf, int pc) __attribute__((always_inline)) {
     const int sl = pc / CK, cc = pc % CK;
     float v = src[pc];
     if constexpr (!RAW) {
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(W4_THREADS) void wino4_kernel(W4Args a) {
     }
     (Pb + buf * P_FLOATS + cc * PS)[p_lds[sl]] = v;
   };
-  auto s_store = [&](int kt, int buf, int pc) __attribute__((always_inline)) { s_store_from(praw, kt, buf, pc); };
+  auto lds_put = [&](int kt, int buf, int pc) __attribute__((always_inline)) { lds_put_from(praw, kt, buf, pc); };
 
   // ---- stage T: thread (half = wave & 1, channel = 2 * (wave >> 1) + lk, tile = li) ----
   int t_src, t_dst;
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(W4_THREADS) void wino4_kernel(W4Args a) {
       if (m + RB < 36) bv[m + RB] = Vr[(((m + RB) % 9) * CK + 2 * ((m + RB) / 9)) * W4_NT];
       if ((m & 3) == 3) a_issue(kt1, m >> 2);
       if (m < NPC) {
-        s_store(kt2, buf, m);
+        lds_put(kt2, buf, m);
         g_issue(kt3, m);
       }
       if (m < 10) t_read(buf ^ 1, m);
@@ -360,11 +360,11 @@ __global__ __launch_bounds__(W4_THREADS) void wino4_kernel(W4Args a) {
 #pragma unroll
       for (int c = 0; c < 9; ++c) a_issue(0, c);
 #pragma unroll
-      for (int pc = 0; pc < NPC; ++pc) s_store_from(praw, 0, 0, pc);
+      for (int pc = 0; pc < NPC; ++pc) lds_put_from(praw, 0, 0, pc);
 #pragma unroll
       for (int pc = 0; pc < NPC; ++pc) g_issue_to(praw, min(2, nK - 1), pc);
 #pragma unroll
-      for (int pc = 0; pc < NPC; ++pc) s_store_from(praw1, min(1, nK - 1), 1, pc);
+      for (int pc = 0; pc < NPC; ++pc) lds_put_from(praw1, min(1, nK - 1), 1, pc);
     }
     lds_barrier();
 #pragma unroll
@@ -572,7 +572,7 @@ bool w4_applicable(const avsep_conv_desc* d, int mode) {
     const int C1 = d->Cin - d->C0;
     if (d->C0 % W4_CK || (C1 != 0 && C1 != d->C0)) return false;
   }
-  if ((long long)d->N * (mode == 0 ? d->C0 : d->Cout) * d->H * d->W >= 0x3fffffffLL) return false;   // 32-bit BYTE offsets
+  if (!buf32_fits((long long)d->N * (mode == 0 ? d->C0 : d->Cout) * d->H * d->W, 0)) return false;   // x (or dY) from its own base
   if ((long long)(cin / W4_CK) * cdiv(cout, W4_BM) * W4_U_FLOATS * 4 >= 0xffffffffLL) return false;
   const avsep_conv_desc e = plan_desc(d);
   const W4Plan p = w4_plan(&e, mode);

@@ -643,7 +643,9 @@ bool ww_applicable(const avsep_conv_desc* d) {
   const int C1 = d->Cin - d->C0;
   if (d->Cin % WW_B || d->C0 % WW_B || d->Cout < 48 || (C1 != 0 && C1 != d->C0)) return false;
   if (d->H >= 32768 || d->W >= 32768 || (long long)d->H * d->W >= (1 << 24)) return false;   // 24-bit offset arithmetic
-  if ((long long)d->N * (d->C0 > d->Cout ? d->C0 : d->Cout) * d->H * d->W >= 0x3fffffffLL) return false;   // 32-bit BYTE offsets of the buffer loads
+  // x's resource starts (W + 2) * PSTEP elements before the source (winow_kernel); dY's at dY
+  if (!buf32_fits((long long)d->N * d->C0 * d->H * d->W, (d->W + 2LL) * d->dil) ||
+      !buf32_fits((long long)d->N * d->Cout * d->H * d->W, 0)) return false;
   const avsep_conv_desc e = plan_desc(d);
   const WwPlan p = ww_plan(&e);
   return (long long)p.gridM * p.gridC * p.splits >= 128 && p.nchunks >= 8;
@@ -720,7 +722,9 @@ bool w4d_applicable(const avsep_conv_desc* d) {
   if (!(d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad == 1 && d->dil == 1) || d->up2x || d->C0 != d->Cin) return false;
   if ((d->H & 3) || (d->W & 3) || d->H < 8 || d->W < 8 || d->Ho * 2 != d->H || d->Wo * 2 != d->W) return false;
   if (d->Cin % WW_B || d->Cout < 48 || d->H >= 32768 || d->W >= 32768 || (long long)d->H * d->W >= (1 << 24)) return false;
-  if ((long long)d->N * (d->Cin > d->Cout ? d->Cin : d->Cout) * d->H * d->W >= 0x3fffffffLL) return false;
+  // x's resource starts W + 2 elements before x (wgrad4d_kernel); dY [N, Cout, H/2, W/2] at dY
+  if (!buf32_fits((long long)d->N * d->Cin * d->H * d->W, d->W + 2LL) ||
+      !buf32_fits((long long)d->N * d->Cout * d->Ho * d->Wo, 0)) return false;
   const avsep_conv_desc e = plan_desc(d);
   const WwPlan p = w4d_plan(&e);
   return p.cfg < 2 && (long long)p.gridM * p.gridC * p.splits >= 128 && p.nchunks >= 8;

@@ -543,7 +543,9 @@ bool x4_applicable(const avsep_conv_desc* d) {
   if (!(d->KH == 3 && d->KW == 3 && d->stride == 1 && (d->dil == 1 || d->dil == 2) && d->pad == d->dil) || d->up2x) return false;
   const int C1 = d->Cin - d->C0;
   if (d->Cin % X4_BCI || d->C0 % X4_BCI || d->Cout < 48 || (C1 != 0 && C1 != d->C0)) return false;
-  if ((long long)d->N * (d->C0 > d->Cout ? d->C0 : d->Cout) * d->H * d->W >= 0x3fffffffLL) return false;   // 32-bit BYTE offsets
+  // x's resource starts D * (W + 1) elements (2W + 2 for dilation 2) before the source (winow4_kernel); dY's at dY
+  if (!buf32_fits((long long)d->N * d->C0 * d->H * d->W, d->dil == 2 ? 2LL * d->W + 2 : d->W + 1LL) ||
+      !buf32_fits((long long)d->N * d->Cout * d->H * d->W, 0)) return false;
   const avsep_conv_desc e = plan_desc(d);
   X4Plan p;
   if (!x4_plan(&e, &p)) return false;
