@@ -12,3 +12,12 @@ from .net_wrapper import NetWrapper, create_optimizer, train_step, adjust_learni
 from .arguments import ArgParser                       # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # `separate` is imported on first use, not here: `python -m avsep_amd.separate` must find it un-imported (runpy refuses
+    # a module that the alias has already registered under the package's real name)
+    if name == "separate":
+        import importlib
+        return importlib.import_module(__name__ + ".separate")
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,174 @@
+// Long-form separation: windows of one recording's spectrogram in, cross-faded masks out (include/avsep.h).
+// Three HBM-bound gather / reduce kernels; time is the contiguous axis of every tensor and lanes run along it.
+// No atomics in this file: every sum has a fixed order.
+#include "common.h"
+#include "warp_coords.h"
+
+constexpr int LF_BLOCK = 256;
+constexpr int LF_ROWS = 8;   // output rows per workgroup of the two gather kernels: their set-up (warp_gy in float64, the
+                             // window search) is paid once per 8 x 256 outputs
+
+// ============================================================================
+// window prepare: warped magnitude + log of every window, read straight from the recording
+// ============================================================================
+// sample_bilin() on the window [Fin x W] that starts at column s of the [Fin x F] recording: columns outside the window
+// are grid_sample's zero padding (no eps), columns of the window past the recording's end are magnitude 0 (+ eps).
+__device__ __forceinline__ float sample_window(const float* __restrict__ p, const Bilin& b, int Fin, int F, int W, int s,
+                                               float eps) {
+  float v = 0.f;
+  const bool y0 = (unsigned)b.y0 < (unsigned)Fin, y1 = (unsigned)(b.y0 + 1) < (unsigned)Fin;
+  const bool x0 = (unsigned)b.x0 < (unsigned)W, x1 = (unsigned)(b.x0 + 1) < (unsigned)W;
+  const int c0 = s + b.x0, c1 = c0 + 1;
+  const bool in0 = (unsigned)c0 < (unsigned)F, in1 = (unsigned)c1 < (unsigned)F;
+  const float* r0 = p + (long long)b.y0 * F;
+  const float* r1 = r0 + F;
+  if (y0 && x0) v += ((in0 ? r0[c0] : 0.f) + eps) * b.wnw;
+  if (y0 && x1) v += ((in1 ? r0[c1] : 0.f) + eps) * b.wne;
+  if (y1 && x0) v += ((in0 ? r1[c0] : 0.f) + eps) * b.wsw;
+  if (y1 && x1) v += ((in1 ? r1[c1] : 0.f) + eps) * b.wse;
+  return v;
+}
+
+// grid (ceil(Fout / LF_ROWS), K), block over the window's frames
+__global__ __launch_bounds__(LF_BLOCK) void window_prepare_kernel(const float* __restrict__ mag, int Fin, int F,
+                                                                  const int* __restrict__ starts, int Fout, int W,
+                                                                  float* __restrict__ mag_w, float* __restrict__ log_w) {
+  const int f0 = blockIdx.x * LF_ROWS, k = blockIdx.y, rows = min(LF_ROWS, Fout - f0);
+  __shared__ float s_gy[LF_ROWS];
+  if (threadIdx.x < rows) s_gy[threadIdx.x] = warp_gy(f0 + threadIdx.x, Fout, 1);
+  __syncthreads();
+  const int s = starts[k];
+  for (int t = threadIdx.x; t < W; t += LF_BLOCK) {
+    const float gx = (float)linspace_pm1(t, W);
+    for (int r = 0; r < rows; ++r) {
+      Bilin bl = grid_bilin(gx, s_gy[r], Fin, W);
+      float v = sample_window(mag, bl, Fin, F, W, s, 1e-10f);
+      const long long o = ((long long)k * Fout + f0 + r) * W + t;
+      mag_w[o] = v;
+      log_w[o] = logf(v);
+    }
+  }
+}
+
+extern "C" int avsep_window_prepare(const float* mag, int32_t Fin, int32_t F, const int32_t* starts, int32_t K, int32_t Fout,
+                                    int32_t W, float* mag_w, float* log_mag_w, avsep_stream_t stream) {
+  if (!mag || !starts || !mag_w || !log_mag_w) return AVSEP_ERR_ARG;
+  if (Fin <= 0 || F <= 0 || K <= 0 || K > 65535 || Fout <= 0 || W <= 0) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(window_prepare_kernel, dim3(cdiv(Fout, LF_ROWS), K), dim3(LF_BLOCK), 0, (hipStream_t)stream, mag, Fin, F, starts, Fout,
+                     W, mag_w, log_mag_w);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+// ============================================================================
+// agreement of consecutive windows on the frames they share
+// ============================================================================
+// grid ((K-1) * N * N): one workgroup per (k, i, j).  Each thread adds its elements in index order, the wave and the
+// four wave totals are added in a fixed order: the same bits every run.
+__global__ __launch_bounds__(LF_BLOCK) void window_agreement_kernel(const float* __restrict__ masks,
+                                                                    const int* __restrict__ starts, int N, int Fout, int W,
+                                                                    double* __restrict__ D) {
+  const int j = blockIdx.x % N, i = (blockIdx.x / N) % N, k = blockIdx.x / (N * N);
+  const int d = starts[k + 1] - starts[k];
+  const int cw = d >= 0 ? W - d : 0;                       // shared columns
+  double acc = 0.0;
+  if (cw > 0) {
+    const float* a = masks + ((long long)k * N + i) * Fout * W + d;
+    const float* b = masks + ((long long)(k + 1) * N + j) * Fout * W;
+    const int total = Fout * cw;
+    for (int idx = threadIdx.x; idx < total; idx += LF_BLOCK) {
+      const int f = idx / cw, c = idx - f * cw;
+      acc += fabs((double)a[(long long)f * W + c] - (double)b[(long long)f * W + c]);
+    }
+  }
+  acc = wave_sum_d(acc);
+  __shared__ double s_part[LF_BLOCK / 64];
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = s_part[0];
+    for (int w = 1; w < LF_BLOCK / 64; ++w) t += s_part[w];
+    D[blockIdx.x] = t;
+  }
+}
+
+extern "C" int avsep_window_agreement(const float* masks, const int32_t* starts, int32_t K, int32_t N, int32_t Fout,
+                                      int32_t W, double* D, avsep_stream_t stream) {
+  if (!masks || !starts || !D) return AVSEP_ERR_ARG;
+  if (K < 2 || K > 65535 || N <= 0 || N > 64 || Fout <= 0 || W <= 0 || (long long)Fout * W > 0x7fffffffLL) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(window_agreement_kernel, dim3((unsigned)(K - 1) * N * N), dim3(LF_BLOCK), 0, (hipStream_t)stream, masks,
+                     starts, N, Fout, W, D);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+// ============================================================================
+// mask stitch: un-warp every covering window at (f, t), cross-fade, threshold, x magnitude
+// ============================================================================
+// grid (ceil(F / 256), ceil(Fin / LF_ROWS), N).  The windows that cover the block's 256 frames are a contiguous run
+// [k_lo, k_hi] of the ascending start table (two binary searches by one thread); a thread walks that run and keeps the
+// windows its own frame lies in, in ascending k.
+__global__ __launch_bounds__(LF_BLOCK) void mask_stitch_kernel(const float* __restrict__ masks, const int* __restrict__ starts,
+                                                               const int* __restrict__ perm, const float* __restrict__ mag,
+                                                               int K, int N, int Fout, int W, int Fin, int F, int binary,
+                                                               float thres, float* __restrict__ out,
+                                                               float* __restrict__ mask_out) {
+  const int t0 = blockIdx.x * LF_BLOCK, f0 = blockIdx.y * LF_ROWS, n = blockIdx.z, rows = min(LF_ROWS, Fin - f0);
+  __shared__ float s_gy[LF_ROWS];
+  __shared__ int s_lo, s_hi;
+  if (threadIdx.x < rows) s_gy[threadIdx.x] = warp_gy(f0 + threadIdx.x, Fin, 0);
+  if (threadIdx.x == LF_BLOCK - 1) {
+    const int t1 = min(t0 + LF_BLOCK, F) - 1;
+    int lo = 0, hi = K;                                    // first k with starts[k] + W > t0
+    while (lo < hi) {
+      int m = (lo + hi) >> 1;
+      if (starts[m] + W > t0) hi = m; else lo = m + 1;
+    }
+    s_lo = lo;
+    hi = K;                                                // first k with starts[k] > t1
+    while (lo < hi) {
+      int m = (lo + hi) >> 1;
+      if (starts[m] > t1) hi = m; else lo = m + 1;
+    }
+    s_hi = lo - 1;
+  }
+  __syncthreads();
+  const int t = t0 + threadIdx.x;
+  if (t >= F) return;
+  const int k_lo = s_lo, k_hi = s_hi;
+  for (int r = 0; r < rows; ++r) {
+    const float gy = s_gy[r];
+    float acc = 0.f, wsum = 0.f, first = 0.f;
+    int cnt = 0;
+    for (int k = k_lo; k <= k_hi; ++k) {
+      const int j = t - starts[k];
+      if ((unsigned)j >= (unsigned)W) continue;
+      const int src = perm[k * N + n];
+      if ((unsigned)src >= (unsigned)N) continue;
+      Bilin bl = grid_bilin((float)linspace_pm1(j, W), gy, Fout, W);
+      const float v = sample_bilin(masks + ((long long)k * N + src) * Fout * W, bl, Fout, W, 0.f);
+      const float w = (float)min(j + 1, W - j);
+      if (cnt == 0) first = v;
+      acc += w * v;
+      wsum += w;
+      ++cnt;
+    }
+    const float M = cnt == 1 ? first : (cnt ? acc / wsum : 0.f);
+    const int f = f0 + r;
+    const long long o = ((long long)n * Fin + f) * F + t;
+    out[o] = mag[(long long)f * F + t] * (binary ? (M > thres ? 1.f : 0.f) : M);
+    if (mask_out) mask_out[o] = M;
+  }
+}
+
+extern "C" int avsep_mask_stitch(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
+                                 int32_t N, int32_t Fout, int32_t W, int32_t Fin, int32_t F, int32_t binary, float thres,
+                                 float* out, float* mask_out, avsep_stream_t stream) {
+  if (!masks || !starts || !perm || !mag || !out) return AVSEP_ERR_ARG;
+  if (K <= 0 || K > 65535 || N <= 0 || N > 65535 || Fout <= 0 || W <= 0 || Fin <= 0 || Fin > 65535 || F <= 0)
+    return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(mask_stitch_kernel, dim3(cdiv(F, LF_BLOCK), cdiv(Fin, LF_ROWS), N), dim3(LF_BLOCK), 0, (hipStream_t)stream, masks,
+                     starts, perm, mag, K, N, Fout, W, Fin, F, binary, thres, out, mask_out);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}

@@ -707,6 +707,41 @@ def warp(x, hout, wout, warp_flag):
     return y
 
 
+def window_prepare(mag, starts, fout=256, width=256):
+    """mag [Fin,F] (one recording), starts int32 [K] on the device -> warped magnitude and its log, [K,1,fout,width] each:
+    per window what ``prepare`` / inference.NetWrapper.prepare_inferdata make of mag[:, s:s+width] (zero past F)."""
+    lib.require_gpu(mag)
+    Fin, F = mag.shape
+    Kw = starts.numel()
+    mix_w, logm = _f32((Kw, 1, fout, width), mag), _f32((Kw, 1, fout, width), mag)
+    call("avsep_window_prepare", ptr(mag), Fin, F, ptr(starts), Kw, fout, width, ptr(mix_w), ptr(logm))
+    return mix_w, logm
+
+
+def window_agreement(masks, starts):
+    """masks [K,N,Fout,W], starts int32 [K] -> float64 [K-1,N,N]: L1 distance of source i of window k and source j of
+    window k+1 over the frames both windows cover (bit-identical from run to run)."""
+    lib.require_gpu(masks)
+    Kw, N, Fo, W = masks.shape
+    D = torch.empty((max(Kw - 1, 0), N, N), dtype=torch.float64, device=masks.device)
+    if Kw > 1:
+        call("avsep_window_agreement", ptr(masks), ptr(starts), Kw, N, Fo, W, ptr(D))
+    return D
+
+
+def mask_stitch(masks, starts, perm, mag, binary, thres, want_mask=False):
+    """masks [K,N,Fout,W], starts int32 [K], perm int32 [K,N], mag [Fin,F] -> per-source magnitude [N,Fin,F] (and the blended
+    linear-frequency mask [N,Fin,F] with want_mask): un-warp, triangular cross-fade, threshold, x mag in one pass."""
+    lib.require_gpu(masks)
+    Kw, N, Fo, W = masks.shape
+    Fin, F = mag.shape
+    out = _f32((N, Fin, F), mag)
+    lin = _f32((N, Fin, F), mag) if want_mask else None
+    call("avsep_mask_stitch", ptr(masks), ptr(starts), ptr(perm), ptr(mag), Kw, N, Fo, W, Fin, F, int(bool(binary)),
+         float(thres), ptr(out), ptr(lin))
+    return out, lin
+
+
 def sgd_momentum_(p, g, buf, lr, momentum, weight_decay, grad_scale, first):
     call("avsep_sgd_momentum", ptr(p), ptr(g), ptr(buf), p.numel(), float(lr), float(momentum),
          float(weight_decay), float(grad_scale), int(first))

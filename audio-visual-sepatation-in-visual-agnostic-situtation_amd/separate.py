@@ -1,0 +1,236 @@
+"""Separate a recording of any length (the reference stops at one 65 535-sample tile: SURVEY.md §5.7; its glue for
+one tile is main.py:205-246 / inference.py:433-475).
+
+The recording gets ONE STFT.  Its spectrogram is cut into overlapping windows of 256 frames (``plan_windows``), all
+windows are warped straight out of the recording (``avsep_window_prepare``) and go through the eval-mode U-Net as a
+batch.  The warped masks are un-warped, cross-faded with a triangular weight on the recording's linear-frequency grid
+and multiplied with the mixture magnitude in one kernel (``avsep_mask_stitch``); ONE iSTFT per source with the whole
+recording's phase gives the waveforms.  Masks, not waveforms, are stitched: a per-chunk iSTFT has its own centre padding
+and window-sum-square normalisation at both ends, the grid_sample warp damps every tile's edge columns, and neither
+shows up when the blend happens before a single inverse transform.  A recording of one tile reduces to
+``evaluate.reconstruct``.
+
+Without frames the model has no fixed source order (permutation-invariant training plus a random swap per sample), so
+for ``use_vis=False`` the swap draw is pinned to "no swap" and consecutive windows are aligned on the frames they share
+(``avsep_window_agreement`` + ``align_permutations``) before blending.
+
+CLI: ``python -m avsep_amd.separate --wav mix.wav --frames a.npy b.npy --id <experiment> --out dir`` (flag set of
+arguments.py; 16-bit PCM WAV at ``--audRate``, no resampling).
+"""
+import itertools
+import os
+import wave
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from . import lib
+from .lib import AvsepError
+from .models import activate
+
+WIDTH = 256        # frames per window: the tile the network is trained on
+FOUT = 256         # log-frequency bins of the warped tile (inference.py:48-51)
+
+
+def plan_windows(F, stride, width=WIDTH):
+    """Start frames of the windows over F frames: 0, stride, 2*stride, ... while a window ends before F, then one last
+    window right-aligned at F - width.  One window [0] when F <= width.  Strictly ascending."""
+    F, stride, width = int(F), int(stride), int(width)
+    if F < 1 or width < 1 or not 1 <= stride <= width:
+        raise ValueError(f"plan_windows needs F >= 1 and 1 <= stride <= width, got F={F} stride={stride} width={width}")
+    starts, s = [], 0
+    while s + width < F:
+        starts.append(s)
+        s += stride
+    starts.append(max(0, F - width))
+    return starts
+
+
+def align_permutations(D):
+    """D [K-1,N,N] (``kernels.window_agreement``, any device) -> int32 [K,N] on the CPU: row k lists, per output source,
+    the channel of window k that carries it.  Window 0 is the identity; window k+1 takes the permutation p of its
+    channels with the least sum_n D[k, perm[k][n], p[n]] (all N! candidates in itertools.permutations order, the first
+    wins a tie — as PitWrapper does)."""
+    D = torch.as_tensor(D).detach().cpu().double()
+    if D.dim() != 3 or D.shape[1] != D.shape[2]:
+        raise ValueError(f"align_permutations takes [K-1,N,N], got {tuple(D.shape)}")
+    N = D.shape[1]
+    if not 1 <= N <= 3:
+        raise ValueError("align_permutations enumerates N! candidates: N <= 3")
+    cands = list(itertools.permutations(range(N)))
+    perms = [list(range(N))]
+    for k in range(D.shape[0]):
+        cur, best, best_cost = perms[-1], None, None
+        for p in cands:
+            cost = sum(D[k, cur[n], p[n]].item() for n in range(N))
+            if best is None or cost < best_cost:
+                best, best_cost = p, cost
+        perms.append(list(best))
+    return torch.tensor(perms, dtype=torch.int32)
+
+
+def _visual_features(net_frame, frames, args, Kw, batch):
+    """One feature tensor per source: [1,...] for a frame shared by all windows, [K,...] for one frame per window."""
+    feats = []
+    for n, fr in enumerate(frames):
+        if fr.dim() != 4 or fr.shape[0] not in (1, Kw):
+            raise AvsepError(f"frames[{n}] must be [1,3,H,W] or [{Kw},3,H,W] (one per window), got {tuple(fr.shape)}")
+        lib.require_gpu(fr)
+        parts = [activate(net_frame.forward(fr[i:i + batch].float().contiguous(), pool=args.not_pool_vis), args.img_activation)
+                 for i in range(0, fr.shape[0], batch)]
+        feats.append(parts[0] if len(parts) == 1 else torch.cat(parts, 0))
+    return feats
+
+
+def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False):
+    """Separate one recording ``wav`` [L] (on the GPU, L >= args.stft_frame; several recordings: one call each).
+
+    nets: (net_sound, net_frame), both in eval() — train-mode BatchNorm over the windows of one recording is never what
+    the caller wants, and raises AvsepError.  frames: list of N tensors, each [1,3,H,W] (one frame for the whole
+    recording: its feature map is computed once and broadcast over the windows) or [K,3,H,W] (one frame per window,
+    K = len(plan_windows(F, stride_frames))); ignored for use_vis=False.  Activations and ``pool`` as in
+    inference.NetWrapper.forward_av.  ``fusion_type == 'MixVis'`` and the duet form (a one-element frames list) are not
+    provided: NotImplementedError.
+
+    Returns {"wavs": [N, hop*(F-1)] clamped to [-1,1], "starts": list, "perms": int32 [K,N] (CPU)}; with return_masks
+    also "masks" [K,N,256,256] (warped, per window, network channel order) and "lin_masks" [N,Fin,F] (blended).
+    """
+    net_sound, net_frame = nets
+    lib.require_gpu(wav)
+    if wav.dim() != 1 or wav.numel() < args.stft_frame:
+        raise AvsepError(f"separate_long takes one recording [L] with L >= stft_frame, got {tuple(wav.shape)}")
+    if net_sound.training or (use_vis and net_frame.training):
+        raise AvsepError("separate_long needs the nets in eval(): call .eval() on both before separating")
+    if use_vis:
+        if args.fusion_type == "MixVis":
+            raise NotImplementedError("long-form separation does not provide the MixVis fusion")
+        if len(frames) == 1 and args.num_mix != 1:
+            raise NotImplementedError("long-form separation does not provide the duet form (one shared frame list)")
+        if len(frames) != args.num_mix:
+            raise AvsepError(f"separate_long needs one frame tensor per source ({args.num_mix}), got {len(frames)}")
+    N, dev = args.num_mix, wav.device
+    with torch.no_grad():
+        plan = K.Stft(dev, args.stft_frame, args.stft_hop, getattr(args, "stft_pad_mode", "reflect"))
+        mag, phase = plan.stft(wav.float().contiguous()[None])
+        mag, phase = mag[0], phase[0]                                    # [Fin, F]
+        starts = plan_windows(mag.shape[1], stride_frames, WIDTH)
+        Kw = len(starts)
+        starts_t = torch.tensor(starts, dtype=torch.int32, device=dev)
+        _, logm = K.window_prepare(mag, starts_t, FOUT, WIDTH)
+        masks = torch.empty((Kw, N, FOUT, WIDTH), dtype=torch.float32, device=dev)
+        if use_vis:
+            feats = _visual_features(net_frame, frames, args, Kw, batch)
+            for i in range(0, Kw, batch):
+                b = min(batch, Kw - i)
+                vs = [(f.expand(b, *f.shape[1:]) if f.shape[0] == 1 else f[i:i + b]).contiguous() for f in feats]
+                feat, _ = net_sound(logm[i:i + b], vs)
+                for n in range(N):
+                    masks[i:i + b, n] = activate(feat[:, n].unsqueeze(1), args.output_activation)[:, 0]
+            perms = torch.arange(N, dtype=torch.int32).repeat(Kw, 1)
+        else:
+            pinned = net_sound.ao_draws
+            try:
+                for i in range(0, Kw, batch):
+                    b = min(batch, Kw - i)
+                    # "no swap" for every window: a bool coin for two sources, permutation index 0 for more
+                    net_sound.ao_draws = torch.zeros(b, dtype=torch.bool if N == 2 else torch.int64)
+                    feat, _ = net_sound(logm[i:i + b], None)
+                    if feat.shape[1] != N:
+                        raise AvsepError(f"net_sound gives {feat.shape[1]} channels for num_mix={N}")
+                    masks[i:i + b] = activate(feat, args.output_activation)
+            finally:
+                net_sound.ao_draws = pinned
+            perms = align_permutations(K.window_agreement(masks, starts_t))
+        binary = bool(args.binary_mask)
+        mags, lin = K.mask_stitch(masks, starts_t, perms.to(dev), mag, binary, getattr(args, "mask_thres", 0.5), return_masks)
+        wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous()).clamp_(-1.0, 1.0)
+    out = {"wavs": wavs, "starts": starts, "perms": perms}
+    if return_masks:
+        out.update(masks=masks, lin_masks=lin)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 16-bit PCM WAV through the standard library, and the command line
+# ---------------------------------------------------------------------------------------------------------------------
+def read_wav(path):
+    """-> (float32 mono waveform in [-1, 1), sample rate).  16-bit PCM only; channels are averaged."""
+    with wave.open(path, "rb") as w:
+        if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+            raise AvsepError(f"{path}: only uncompressed 16-bit PCM WAV is read (sample width {w.getsampwidth()} bytes)")
+        rate, ch = w.getframerate(), w.getnchannels()
+        data = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.float32) / 32768.0
+    if ch > 1:
+        data = data.reshape(-1, ch).mean(1)
+    return data, rate
+
+
+def write_wav(path, data, rate):
+    """float waveform in [-1, 1] -> mono 16-bit PCM (x * 32768 rounded, +1.0 clips to 32767: read_wav's inverse)."""
+    pcm = np.clip(np.round(np.asarray(data, dtype=np.float64) * 32768.0), -32768, 32767).astype("<i2")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(rate))
+        w.writeframes(pcm.tobytes())
+
+
+def build_parser():
+    from .arguments import ArgParser
+    ap = ArgParser()
+    ap.add_train_arguments()
+    ap.add_other_arguments()
+    p = ap.parser
+    p.description = "Separate a WAV of any length with a trained checkpoint (windowed inference, stitched masks)."
+    p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at --audRate")
+    p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]")
+    p.add_argument("--out", default="separated", help="output directory (source<n>.wav)")
+    p.add_argument("--audio_only", action="store_true", help="no frames: audio-only branch with aligned windows")
+    p.add_argument("--window_stride", type=int, default=128, help="STFT frames between window starts (<= 256)")
+    p.add_argument("--window_batch", type=int, default=16, help="windows per U-Net pass")
+    p.add_argument("--latest", action="store_true", help="load *_latest.pth instead of *_best.pth")
+    return p
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if not args.audio_only and len(args.frames) != args.num_mix:
+        raise SystemExit(f"--frames needs {args.num_mix} files (one per source), or pass --audio_only")
+    return args
+
+
+def cli(argv=None):
+    from . import checkpoint as ckpt
+    from .models import ModelBuilder
+    args = parse_args(argv)
+    data, rate = read_wav(args.wav)
+    if rate != args.audRate:
+        raise SystemExit(f"{args.wav} is sampled at {rate} Hz, the model at {args.audRate} Hz: resample it first")
+    if not torch.cuda.is_available():
+        raise AvsepError("separation runs on an MI355X; there is no CPU fallback")
+    dev = torch.device("cuda", 0)
+    args.ckpt = os.path.join(args.ckpt, args.id)
+    if not args.weights_sound:
+        args.weights_sound, args.weights_frame = ckpt.resume_paths(args, best=not args.latest)
+    builder = ModelBuilder()
+    net_frame = builder.build_frame(arch=args.arch_frame, fc_dim=args.vis_channels, pool_type=args.img_pool,
+                                    weights=args.weights_frame)
+    net_sound = builder.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, weights=args.weights_sound,
+                                    fusion_type=args.fusion_type, att_type=args.att_type)
+    nets = (net_sound.to(dev).eval(), net_frame.to(dev).eval())
+    frames = []
+    for path in args.frames:
+        fr = torch.from_numpy(np.load(path)).float()
+        frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
+    out = separate_long(nets, torch.from_numpy(data).to(dev), frames, args, use_vis=not args.audio_only,
+                        stride_frames=args.window_stride, batch=args.window_batch)
+    os.makedirs(args.out, exist_ok=True)
+    for n, w in enumerate(out["wavs"].cpu().numpy()):
+        write_wav(os.path.join(args.out, f"source{n}.wav"), w, rate)
+    print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav")
+    return out
+
+
+if __name__ == "__main__":
+    cli()

@@ -413,6 +413,34 @@ int avsep_sdr_sums(const float* est, const float* ref, int32_t R, int32_t L, int
                    int64_t ref_stride, double* sums, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Long-form separation (csrc/longform.hip): one recording of F STFT frames is cut into K windows of W frames whose start
+ * frames `starts` [K] (int32, strictly ascending, >= 0) overlap; the windows go through the network as one batch and their
+ * masks are blended back on the recording's linear-frequency grid.  The reference only ever processes one W = 256 tile.
+ * mag: [Fin, F] whole-recording magnitude; masks: [K, N, Fout, W] warped per-window masks.  K, Fin, N <= 65535.
+ * ------------------------------------------------------------------------- */
+/* The network input of every window without materialising the [Fin, W] slices: per window k what inference.py:433-475
+ * (+1e-10, grid_sample on warpgrid(.., Fout, W, warp=True) of utils.py:12-26, log) computes from mag[:, s_k : s_k + W];
+ * frames past F read as 0 (then +1e-10).  mag_w, log_mag_w: [K, 1, Fout, W]. */
+int avsep_window_prepare(const float* mag, int32_t Fin, int32_t F, const int32_t* starts, int32_t K, int32_t Fout,
+                         int32_t W, float* mag_w, float* log_mag_w, avsep_stream_t stream);
+/* How well the sources of consecutive windows agree where the windows overlap (the audio-only branch has no fixed source
+ * order): D[k,i,j] = sum_f sum_c |m[k,i,f,c+d_k] - m[k+1,j,f,c]|, d_k = s[k+1] - s[k], c in [0, W - d_k); 0 when they
+ * do not overlap.  D: float64 [K-1, N, N], K >= 2.  One workgroup per entry, fixed summation order, no atomics: the
+ * result is bit-identical from run to run (the host takes an argmin over it). */
+int avsep_window_agreement(const float* masks, const int32_t* starts, int32_t K, int32_t N, int32_t Fout, int32_t W,
+                           double* D, avsep_stream_t stream);
+/* Cross-faded masks x mixture magnitude (main.py:205-246 for a recording of any length):
+ *   M[n,f,t] = sum_k w(t-s_k) * unwarp(m[k, perm[k,n]])(f, t-s_k) / sum_k w(t-s_k)   over windows with 0 <= t-s_k < W,
+ *   w(j) = min(j+1, W-j);   out[n,f,t] = mag[f,t] * (binary ? (M > thres) : M)      (threshold after blending).
+ * unwarp = grid_sample on warpgrid(.., Fin, W, warp=False) (utils.py:12-26), per window, time axis resampled too, as
+ * avsep_warp(.., warp=0) does.  A frame covered by ONE window gets that window's un-warped mask unchanged, so a one-tile
+ * recording reproduces avsep_warp + threshold + multiply bit for bit.  perm: int32 [K, N], entries in [0, N) (others
+ * contribute nothing).  out: [N, Fin, F]; mask_out (optional, may be null): the blended M, [N, Fin, F]. */
+int avsep_mask_stitch(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
+                      int32_t N, int32_t Fout, int32_t W, int32_t Fin, int32_t F, int32_t binary, float thres,
+                      float* out, float* mask_out, avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
  * that are accumulated into, exactly as for the fp32 NCHW entry points of the same names below.

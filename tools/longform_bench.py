@@ -1,0 +1,218 @@
+"""Long-form separation on cuda:0: a recording of --seconds (default 600 s at 11 025 Hz, L = 6 615 000) through
+separate_long with the full-size model (train_MUSIC flags: unet7 + resnet18dilated, fp32), stride 128, batch 16.
+
+Prints (1) seconds of audio separated per second of wall time, audio-visual and audio-only, with the split between
+STFT, window prepare, visual trunk, U-Net, agreement (+ host alignment), stitch and iSTFT — each stage of the real
+separate_long call wrapped in device synchronisations; (2) avsep_window_prepare and avsep_mask_stitch alone: time,
+algorithmic bytes, bytes/s against the 8 TB/s HBM peak, and the same result composed from the older entry points
+(gathered slices + K.warp + log; K.warp(.., 0) on every window + a torch cross-fade), outputs compared.
+Every number is a median over --reps runs after warm-up; the last line is one JSON object.
+Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import avsep_amd as P  # noqa: E402
+from avsep_amd import separate as S  # noqa: E402
+
+HBM_PEAK = 8.0e12
+
+
+def median_ms(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return statistics.median(out)
+
+
+class StageClock:
+    """Wraps the stage functions separate_long calls; every wrapped call is bracketed by device synchronisations."""
+
+    def __init__(self):
+        self.ms = {}
+        self._undo = []
+
+    def wrap(self, owner, attr, stage):
+        fn = getattr(owner, attr)
+
+        def timed(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn(*a, **kw)
+            torch.cuda.synchronize()
+            self.ms[stage] = self.ms.get(stage, 0.0) + (time.perf_counter() - t0) * 1e3
+            return r
+        had = attr in vars(owner)
+        self._undo.append((owner, attr, fn, had))
+        setattr(owner, attr, timed)
+
+    def restore(self):
+        for owner, attr, fn, had in reversed(self._undo):
+            if had:
+                setattr(owner, attr, fn)
+            else:
+                delattr(owner, attr)
+        self._undo = []
+
+
+def staged_run(nets, wav, frames, args, use_vis, stride, batch):
+    K = P.kernels
+    clk = StageClock()
+    clk.wrap(K.Stft, "stft", "stft")
+    clk.wrap(K.Stft, "istft", "istft")
+    clk.wrap(K, "window_prepare", "window_prepare")
+    clk.wrap(K, "window_agreement", "agreement")
+    clk.wrap(S, "align_permutations", "agreement")
+    clk.wrap(K, "mask_stitch", "stitch")
+    clk.wrap(nets[0], "forward", "unet")
+    clk.wrap(nets[1], "forward", "visual_trunk")
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch)
+        torch.cuda.synchronize()
+        total = (time.perf_counter() - t0) * 1e3
+    finally:
+        clk.restore()
+    clk.ms["other"] = total - sum(clk.ms.values())
+    clk.ms["total"] = total
+    return clk.ms
+
+
+def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps):
+    """Median wall time of the unwrapped call, and the median per-stage split of wrapped calls."""
+    def once():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    once()                                                               # warm-up: code objects, conv plans
+    wall = statistics.median(once() for _ in range(reps))
+    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch) for _ in range(reps)]
+    split = {k: statistics.median(s.get(k, 0.0) for s in splits) for k in splits[0]}
+    return wall, split
+
+
+def composed_prepare(mag, starts_t, width=256):
+    """The older entry points: gather the K slices (zero past the end), +1e-10, K.warp, log."""
+    Fin, F = mag.shape
+    padded = torch.cat([mag, mag.new_zeros(Fin, width)], 1)
+    idx = starts_t.long()[:, None] + torch.arange(width, device=mag.device)[None]       # [K,W]
+    slices = padded[:, idx].permute(1, 0, 2).unsqueeze(1)                                # [K,1,Fin,W]
+    w = P.kernels.warp((slices + 1e-10).contiguous(), 256, width, 1)
+    return w, torch.log(w)
+
+
+def composed_stitch(masks, starts_t, perm, mag, binary, thres, width=256):
+    """The older entry points: K.warp(.., 0) on every (window, source), triangular weights, one index_add_ per tensor,
+    divide, threshold, multiply.  (Recordings of at least one window: every window lies inside the recording.)"""
+    Kw, N, Fo, W = masks.shape
+    Fin, F = mag.shape
+    picked = torch.gather(masks, 1, perm.long()[:, :, None, None].expand(-1, -1, Fo, W))
+    lin = P.kernels.warp(picked.reshape(Kw * N, 1, Fo, W), Fin, W, 0).reshape(Kw, N, Fin, W)
+    j = torch.arange(W, device=mag.device)
+    tri = torch.minimum(j + 1, W - j).float()
+    idx = (starts_t.long()[:, None] + j[None]).reshape(-1)
+    acc = torch.zeros(N, Fin, F, device=mag.device)
+    acc.index_add_(2, idx, (lin * tri).permute(1, 2, 0, 3).reshape(N, Fin, Kw * W))
+    wsum = torch.zeros(F, device=mag.device).index_add_(0, idx, tri.repeat(Kw))
+    M = acc / wsum
+    return mag * ((M > thres).float() if binary else M), M
+
+
+def kernel_rows(mag, starts_t, masks, perm, args, reps):
+    K = P.kernels
+    Fin, F = mag.shape
+    Kw, N, Fo, W = masks.shape
+    rows = {}
+    # window prepare
+    a = K.window_prepare(mag, starts_t)
+    b = composed_prepare(mag, starts_t)
+    bytes_prep = 4 * (Fin * F + 2 * Kw * Fo * W)
+    ms_f = median_ms(lambda: K.window_prepare(mag, starts_t), reps)
+    ms_c = median_ms(lambda: composed_prepare(mag, starts_t), reps)
+    rows["window_prepare"] = {"fused_ms": ms_f, "composed_ms": ms_c, "algorithmic_bytes": bytes_prep,
+                              "fused_bytes_per_s": bytes_prep / (ms_f * 1e-3), "share_of_hbm_peak": bytes_prep / (ms_f * 1e-3) / HBM_PEAK,
+                              "max_abs_diff_vs_composed": max((a[0] - b[0]).abs().max().item(), (a[1] - b[1]).abs().max().item())}
+    # mask stitch (binary masks as the flagship configuration has them; without the optional mask output)
+    binary, thres = bool(args.binary_mask), args.mask_thres
+    a = K.mask_stitch(masks, starts_t, perm, mag, False, thres, want_mask=True)
+    b = composed_stitch(masks, starts_t, perm, mag, False, thres)
+    bytes_st = 4 * (Kw * N * Fo * W + Fin * F + N * Fin * F) + 4 * (Kw + Kw * N)
+    ms_f = median_ms(lambda: K.mask_stitch(masks, starts_t, perm, mag, binary, thres), reps)
+    ms_c = median_ms(lambda: composed_stitch(masks, starts_t, perm, mag, binary, thres), reps)
+    rows["mask_stitch"] = {"fused_ms": ms_f, "composed_ms": ms_c, "algorithmic_bytes": bytes_st,
+                           "fused_bytes_per_s": bytes_st / (ms_f * 1e-3), "share_of_hbm_peak": bytes_st / (ms_f * 1e-3) / HBM_PEAK,
+                           "max_abs_diff_vs_composed": (a[1] - b[1]).abs().max().item()}
+    # agreement: reads both windows' shared halves for every (k, i, j)
+    ms_a = median_ms(lambda: K.window_agreement(masks, starts_t), reps)
+    rows["window_agreement"] = {"fused_ms": ms_a}
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=600.0)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--stride", type=int, default=128)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--frame-size", type=int, default=224)
+    o = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("longform_bench measures on an MI355X; there is nothing to report without one")
+    dev = torch.device("cuda", 0)
+    args = P.arguments.train_music_args()
+    args.stft_pad_mode = "reflect"
+    torch.manual_seed(0)
+    mb = P.ModelBuilder()
+    snd = mb.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, fusion_type=args.fusion_type, att_type=args.att_type)
+    frm = mb.build_frame(arch=args.arch_frame, fc_dim=args.vis_channels, pool_type=args.img_pool)
+    nets = (snd.to(dev).eval(), frm.to(dev).eval())
+    L = int(round(o.seconds * args.audRate))
+    wav = (torch.rand(L, device=dev) * 2 - 1) * 0.3
+    frames = [torch.randn(1, 3, o.frame_size, o.frame_size, device=dev) for _ in range(args.num_mix)]
+    audio_s = L / args.audRate
+    result = {"seconds": audio_s, "samples": L, "stride_frames": o.stride, "batch": o.batch, "model": f"{args.arch_sound}+{args.arch_frame}",
+              "precision": P.kernels.get_precision() if hasattr(P.kernels, "get_precision") else "f32"}
+    for name, use_vis in (("av", True), ("ao", False)):
+        wall, split = whole_runs(nets, wav, frames, args, use_vis, o.stride, o.batch, o.reps)
+        result[name] = {"wall_ms": wall, "audio_seconds_per_second": audio_s / (wall * 1e-3), "split_ms": split}
+        print(f"{name.upper()}: {wall:9.1f} ms for {audio_s:.0f} s of audio = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
+        for k, v in split.items():
+            print(f"    {k:16s} {v:9.2f} ms", flush=True)
+    with torch.no_grad():
+        mag = P.kernels.Stft(dev, args.stft_frame, args.stft_hop, "reflect").stft(wav[None], want_phase=False)[0][0].contiguous()
+        starts = S.plan_windows(mag.shape[1], o.stride)
+        starts_t = torch.tensor(starts, dtype=torch.int32, device=dev)
+        masks = torch.rand(len(starts), args.num_mix, 256, 256, device=dev)
+        perm = torch.arange(args.num_mix, dtype=torch.int32, device=dev).repeat(len(starts), 1)
+        result["frames"], result["windows"] = mag.shape[1], len(starts)
+        result["kernels"] = kernel_rows(mag, starts_t, masks, perm, args, o.kernel_reps)
+    for k, r in result["kernels"].items():
+        if "composed_ms" in r:
+            print(f"{k}: fused {r['fused_ms']:.3f} ms ({r['fused_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
+                  f"{100 * r['share_of_hbm_peak']:.0f}% of 8 TB/s), composed {r['composed_ms']:.3f} ms "
+                  f"({r['composed_ms'] / r['fused_ms']:.1f} x), max |diff| {r['max_abs_diff_vs_composed']:.2e}", flush=True)
+        else:
+            print(f"{k}: {r['fused_ms']:.3f} ms", flush=True)
+    print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
