@@ -15,9 +15,9 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # `separate` is imported on first use, not here: `python -m avsep_amd.separate` must find it un-imported (runpy refuses
-    # a module that the alias has already registered under the package's real name)
-    if name == "separate":
+    # `separate` and `localise` are imported on first use, not here: `python -m avsep_amd.separate` / `.localise` must find
+    # the module un-imported (runpy refuses one that the alias has already registered under the package's real name)
+    if name in ("separate", "localise"):
         import importlib
-        return importlib.import_module(__name__ + ".separate")
+        return importlib.import_module(__name__ + "." + name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -742,6 +742,43 @@ def mask_stitch(masks, starts, perm, mag, binary, thres, want_mask=False):
     return out, lin
 
 
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
+
+
+def localise_maps(x, win, vs, att):
+    """x [K,D,Fq,Tq] bottleneck of K windows, win int32 [T] on the device, vs: C tensors [T,Dc,h,w] (duet: the same tensor
+    twice), att 'cos' | 'sig' -> maps [T,C,h,w], best int32 [T], scores [T,C!]: the CoLoc maps of every frame in one launch."""
+    lib.require_gpu(x)
+    Kw, D = x.shape[:2]
+    T, Dc, h, w = vs[0].shape
+    Cn = len(vs)
+    if any(tuple(v.shape) != (T, Dc, h, w) for v in vs) or Cn not in (2, 3) or Dc != D // Cn or win.numel() != T:
+        raise lib.AvsepError(f"localise_maps: {Cn} visual inputs {[tuple(v.shape) for v in vs]} against a bottleneck of {D} "
+                             f"channels and {win.numel()} window indices")
+    maps = _f32((T, Cn, h, w), x)
+    best = torch.empty((T,), dtype=torch.int32, device=x.device)
+    scores = _f32((T, 2 if Cn == 2 else 6), x)
+    call("avsep_localise_maps", ptr(x), ptr(win), _ptr_array(vs), T, Kw, Cn, D, x.shape[2] * x.shape[3], h * w,
+         {"cos": 0, "sig": 1}[att], ptr(maps), ptr(best), ptr(scores))
+    return maps, best, scores
+
+
+def heatmap_overlay(maps, frames, table, alpha256):
+    """maps [T,C,h,w] fp32, frames: C tensors [T,3,H,W] fp32 normalised (duet: the same tensor), table uint8 [256,3] on the
+    device, alpha256 in [0,256] -> uint8 [C,T,H,W,3] RGB: colour-mapped, resized, blended over the frames in one launch."""
+    lib.require_gpu(maps)
+    T, Cn, h, w = maps.shape
+    H, W = frames[0].shape[-2:]
+    if len(frames) != Cn or any(tuple(f.shape) != (T, 3, H, W) or f.dtype != torch.float32 for f in frames) \
+            or tuple(table.shape) != (256, 3) or table.dtype != torch.uint8:
+        raise lib.AvsepError(f"heatmap_overlay: maps {tuple(maps.shape)} need {Cn} float32 frame tensors [{T},3,H,W] and a uint8 "
+                             f"[256,3] table, got {[tuple(f.shape) for f in frames]} and {tuple(table.shape)}")
+    out = torch.empty((Cn, T, H, W, 3), dtype=torch.uint8, device=maps.device)
+    call("avsep_heatmap_overlay", ptr(maps), _ptr_array(frames), ptr(table), T, Cn, h, w, H, W, int(alpha256), ptr(out))
+    return out
+
+
 def sgd_momentum_(p, g, buf, lr, momentum, weight_decay, grad_scale, first):
     call("avsep_sgd_momentum", ptr(p), ptr(g), ptr(buf), p.numel(), float(lr), float(momentum),
          float(weight_decay), float(grad_scale), int(first))

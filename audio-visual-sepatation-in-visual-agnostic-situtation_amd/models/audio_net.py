@@ -157,6 +157,19 @@ class Unet(nn.Module):
         fa, ma, aa, fb, mb, ab = _UnetPairFn.apply(self, len(v_a), x.contiguous().float(), *vs, *self.param_list())
         return (fa, (ma, aa)), (fb, (mb, ab))
 
+    def bottleneck(self, x, batch=16):
+        """Encoder only, with the running BatchNorm statistics: x [K,1,F,T] -> the innermost down conv's output [K,D,Fq,Tq]
+        fp32, the tensor the fusion reads — in chunks of `batch`, no decoder, no autograd.  What localisation needs
+        (localise.py): the similarity maps depend on nothing past this point."""
+        lib.require_gpu(x)
+        if self.extra_size is not None:
+            raise NotImplementedError("the SoP++ variant has no fusion at its bottleneck")
+        with torch.no_grad():
+            _release_deferred(self)
+            parts = [K.to_f32(_encode(self, x[i:i + batch].contiguous().float(), training=False)["yd"][-1])
+                     for i in range(0, x.shape[0], batch)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
     def forward(self, x, v=None):
         lib.require_gpu(x)
         B = x.shape[0]

@@ -441,6 +441,36 @@ int avsep_mask_stitch(const float* masks, const int32_t* starts, const int32_t* 
                       float* out, float* mask_out, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Sound-source localisation over a clip (csrc/localise.hip): T video frames against the K windows of one recording.
+ * ------------------------------------------------------------------------- */
+/* The CoLoc similarity maps of every frame in one launch (replaces one whole forward pass per video frame,
+ * inference.py:537-578 calling inference.py:29-160; the maps themselves are fusion_net.py:35-64).
+ * x: [K, D, FT] fp32 bottleneck of the K windows; win: int32 [T], the window of frame t (values outside [0, K) are clamped);
+ * v: C pointers to [T, Dc, HW] fp32 visual feature maps, Dc = D / C (duet: the same pointer twice); att: 0 cos / 1 sig.
+ * Per frame, with k = win[t]: a_i = max over FT of x[k, i*Dc : (i+1)*Dc] (the first C*Dc channels), m[i][c] = att(a_i, v_c[t])
+ * exactly as avsep_fusion_n_av_fwd, score_p = sum_c max_hw m[perm_p[c]][c] over the C! permutations in itertools order,
+ * best = the FIRST maximum.  maps: [T, C, HW], maps[t, c] = m[perm_best[c]][c]; best: int32 [T]; scores: [T, C!].
+ * C in {2, 3}.  The C*C maps of a frame live in LDS: an HW that does not fit is AVSEP_ERR_ARG. */
+int avsep_localise_maps(const float* x, const int32_t* win, const float* const* v, int32_t T, int32_t K, int32_t C, int32_t D,
+                        int32_t FT, int32_t HW, int32_t att, float* maps, int32_t* best, float* scores, avsep_stream_t stream);
+/* Heat maps blended over the frames on the device (replaces the per-frame host round trip inference.py:509-534:
+ * normalise, cv2.resize, cv2.applyColorMap, weighted add).  maps: [T*C, h, w] fp32, map m belongs to frame m / C and source
+ * m % C; frames: C pointers to [T, 3, H, W] fp32 ImageNet-normalised RGB (duet: the same pointer); table: 256 x 3 uint8 RGB
+ * colours on the device; alpha256 in [0, 256].  out: uint8 [C, T, H, W, 3] RGB.  Defined so that integer and fp32 arithmetic
+ * in this exact order reproduces it bit for bit:
+ *   1. q = (uint8) trunc((255.0f * (m - mn)) / (mx - mn)) per cell, mn / mx = the map's min / max, fp32 round-to-nearest with
+ *      IEEE division and no fused multiply-add; mx == mn: q = 0.
+ *   2. resize h x w -> H x W, half-pixel centres, replicated border: num = (2X+1)*w - W, x0 = floor(num / 2W),
+ *      cx1 = ((num - x0*2W)*2048 + W) / (2W), cx0 = 2048 - cx1, x0 and x0 + 1 clamped to [0, w-1]; the same in y;
+ *      level = (q00*cx0*cy0 + q01*cx1*cy0 + q10*cx0*cy1 + q11*cx1*cy1 + 2^21) >> 22.
+ *   3. colour = table[level].
+ *   4. frame pixel p = clamp(floor((x*std + mean)*255 + 0.5), 0, 255), mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225).
+ *   5. out = (colour*alpha256 + p*(256 - alpha256) + 128) >> 8.
+ * h, w, H, W <= 65535; the map, the table and H + W resize entries live in LDS (64 KiB), else AVSEP_ERR_ARG. */
+int avsep_heatmap_overlay(const float* maps, const float* const* frames, const uint8_t* table, int32_t T, int32_t C, int32_t h,
+                          int32_t w, int32_t H, int32_t W, int32_t alpha256, uint8_t* out, avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
  * that are accumulated into, exactly as for the fp32 NCHW entry points of the same names below.
