@@ -742,6 +742,32 @@ def mask_stitch(masks, starts, perm, mag, binary, thres, want_mask=False):
     return out, lin
 
 
+def resample_poly(x, filt, up, down, in_ch=0, out_s16=False):
+    """Rational polyphase resampling (avsep_resample_poly, include/avsep.h).  x: f32 [B,L] (in_ch = 0) or interleaved int16
+    [L,in_ch] straight from a WAV file (one recording, down-mixed to mono while it is staged); filt: the f32 polyphase table
+    [T, up] of resample.filter_table on x's device -> f32 (or, with out_s16, int16) [B, ceil(L*up/down)]."""
+    lib.require_gpu(x)
+    lib.require_gpu(filt)
+    up, down, in_ch = int(up), int(down), int(in_ch)
+    if in_ch:
+        if x.dtype != torch.int16 or x.dim() != 2 or x.shape[1] != in_ch:
+            raise lib.AvsepError(f"resample_poly: in_ch={in_ch} takes interleaved int16 [L,{in_ch}], got {x.dtype} {tuple(x.shape)}")
+        B, L = 1, x.shape[0]
+    else:
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise lib.AvsepError(f"resample_poly takes float32 [B,L], got {x.dtype} {tuple(x.shape)}")
+        B, L = x.shape
+    if up < 1 or down < 1:
+        raise lib.AvsepError(f"resample_poly: up={up} down={down}")
+    T = -(-(20 * max(up, down) + 1) // up)
+    if filt.dtype != torch.float32 or tuple(filt.shape) != (T, up) or filt.device != x.device:
+        raise lib.AvsepError(f"resample_poly: the table of {up}/{down} is float32 [{T},{up}] on {x.device}, got "
+                             f"{filt.dtype} {tuple(filt.shape)} on {filt.device}")
+    y = torch.empty((B, -(-L * up // down)), dtype=torch.int16 if out_s16 else torch.float32, device=x.device)
+    call("avsep_resample_poly", ptr(x), ptr(filt), B, L, up, down, in_ch, int(bool(out_s16)), ptr(y))
+    return y
+
+
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 

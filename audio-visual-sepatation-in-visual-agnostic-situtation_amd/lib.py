@@ -85,6 +85,7 @@ SIGNATURES = {
     "avsep_mask_stitch": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "avsep_localise_maps": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avsep_heatmap_overlay": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_poly": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

@@ -25,7 +25,7 @@ from . import kernels as K
 from . import lib
 from .lib import AvsepError
 from .models import activate
-from .separate import FOUT, WIDTH, plan_windows, read_wav
+from .separate import FOUT, WIDTH, plan_windows, read_wav, read_wav_pcm, wav_rate
 
 
 def jet_table():
@@ -132,7 +132,7 @@ def build_parser():
     ap.add_other_arguments()
     p = ap.parser
     p.description = "Heat maps of where each source sounds, per video frame, from a trained checkpoint."
-    p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at --audRate")
+    p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at any sample rate (resampled to --audRate on the GPU)")
     p.add_argument("--frames", nargs="+", required=True,
                    help="one .npy [T,3,H,W] (normalised floats) per source; ONE file with --num_mix 2 is a duet")
     p.add_argument("--fps", type=float, required=True, help="video frames per second of the .npy stacks")
@@ -165,12 +165,20 @@ def cli(argv=None):
     from . import checkpoint as ckpt
     from .models import ModelBuilder
     args = parse_args(argv)
-    data, rate = read_wav(args.wav)
+    from . import resample as R
+    rate = wav_rate(args.wav)
     if rate != args.audRate:
-        raise SystemExit(f"{args.wav} is sampled at {rate} Hz, the model at {args.audRate} Hz: resample it first")
+        try:
+            R.check_rates(rate, args.audRate)
+        except AvsepError as e:
+            raise SystemExit(f"{args.wav}: {e}")
     if not torch.cuda.is_available():
         raise AvsepError("localisation runs on an MI355X; there is no CPU fallback")
     dev = torch.device("cuda", 0)
+    if rate == args.audRate:
+        wav = torch.from_numpy(read_wav(args.wav)[0]).to(dev)
+    else:                                            # frame times are in seconds: only the input side needs the model's rate
+        wav = R.resample_pcm(torch.from_numpy(read_wav_pcm(args.wav)[0]).to(dev), rate, args.audRate)
     args.ckpt = os.path.join(args.ckpt, args.id)
     if not args.weights_sound:
         args.weights_sound, args.weights_frame = ckpt.resume_paths(args, best=not args.latest)
@@ -182,7 +190,7 @@ def cli(argv=None):
     nets = (net_sound.to(dev).eval(), net_frame.to(dev).eval())
     frames = [torch.from_numpy(np.load(path)).float().to(dev) for path in args.frames]
     times = args.frame_offset + torch.arange(frames[0].shape[0], dtype=torch.float64) / args.fps
-    out = localise(nets, torch.from_numpy(data).to(dev), frames, times, args, stride_frames=args.window_stride,
+    out = localise(nets, wav, frames, times, args, stride_frames=args.window_stride,
                    batch=args.window_batch, alpha=args.alpha)
     os.makedirs(args.out, exist_ok=True)
     np.save(os.path.join(args.out, "maps.npy"), out["maps"].cpu().numpy())

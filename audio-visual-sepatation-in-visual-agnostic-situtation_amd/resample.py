@@ -1,0 +1,111 @@
+"""Sample-rate conversion on the GPU: WAV files at any rate in, sources at the file's own rate out.
+
+A rational polyphase FIR resampler with the filter ``scipy.signal.resample_poly`` uses by default (the training loader's
+choice, dataset.read_wav_segment, which stays on the CPU for its GPU-free workers).  The filter is designed here in
+float64 with NumPy alone, rounded once to f32 and handed to ``avsep_resample_poly`` (include/avsep.h, csrc/resample.hip) as
+a polyphase table cached per (up, down, device).  The kernel also reads interleaved 16-bit PCM directly (down-mix and
+conversion fused into its staging) and writes 16-bit PCM directly, so a long recording never exists as an f32 copy at the
+file's rate on the host.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from . import lib
+from .lib import AvsepError
+
+MAX_RATIO = 1280       # largest up / down after reduction: 8 ... 96 kHz to and from 11 025 Hz (441/1280, 147/1280)
+MAX_CHANNELS = 256
+
+_tables = {}
+
+
+def rational(rate_in, rate_out):
+    """-> (up, down), the reduced ratio rate_out / rate_in.  Rates are positive integers (Hz)."""
+    if int(rate_in) != rate_in or int(rate_out) != rate_out or rate_in < 1 or rate_out < 1:
+        raise ValueError(f"sample rates are positive integers, got {rate_in!r} and {rate_out!r}")
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    g = math.gcd(rate_in, rate_out)
+    return rate_out // g, rate_in // g
+
+
+def check_rates(rate_in, rate_out):
+    """rational(), refusing a ratio the kernel does not take: AvsepError that names both rates."""
+    up, down = rational(rate_in, rate_out)
+    if max(up, down) > MAX_RATIO:
+        raise AvsepError(f"{rate_in} Hz -> {rate_out} Hz reduces to {up}/{down}: the resampler takes ratios whose terms are "
+                         f"at most {MAX_RATIO} (8, 16, 22.05, 32, 44.1, 48, 88.2 and 96 kHz to and from 11 025 Hz)")
+    return up, down
+
+
+def design_filter(up, down):
+    """float64 [20*max(up,down)+1]: up * firwin(M, 1/m, window=('kaiser', 5.0)), the filter of scipy.signal.resample_poly."""
+    m = max(int(up), int(down))
+    half = 10 * m
+    M = 2 * half + 1
+    w = np.sinc((np.arange(M, dtype=np.float64) - half) / m) / m * np.kaiser(M, 5.0)
+    return w / w.sum() * int(up)
+
+
+def out_length(L, up, down):
+    """ceil(L * up / down)."""
+    return -(-int(L) * int(up) // int(down))
+
+
+def filter_table(up, down, device):
+    """The f32 polyphase table [T, up] of include/avsep.h on ``device``, T = ceil(M / up): column t holds the phase of the
+    outputs j = t (mod up), ho[i][t] = h[(t*down + half) % up + i*up], zero past the filter's end.  Built once per
+    (up, down, device).  For up = down = 1 the filter is the exact
+    unit impulse (sinc vanishes at the non-zero integers; the 1e-17 residue of sin(k*pi) in float64 is dropped), so that equal
+    rates give the input's own bits."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(up), int(down), str(device))
+    t = _tables.get(key)
+    if t is None:
+        up, down = key[:2]
+        h = design_filter(up, down)
+        if up == 1 and down == 1:
+            h = (np.arange(h.size) == h.size // 2).astype(np.float64)
+        T = -(-h.size // up)
+        full = np.zeros(T * up, dtype=np.float64)
+        full[:h.size] = h
+        phase = (np.arange(up, dtype=np.int64) * down + (h.size - 1) // 2) % up
+        ho = np.ascontiguousarray(full.reshape(T, up)[:, phase]).astype(np.float32)
+        t = _tables[key] = torch.from_numpy(ho).to(device)
+    return t
+
+
+def _check_length(L, up, down):
+    if L < 1 or L >= 2 ** 31 or out_length(L, up, down) >= 2 ** 31:
+        raise AvsepError(f"resampling takes 1 <= L and L, ceil(L*{up}/{down}) < 2^31 samples, got L={L}")
+
+
+def resample(x, rate_in, rate_out, out_s16=False):
+    """x: f32 [L] or [B,L] on the GPU -> the same rows at rate_out, f32 or (out_s16) int16 = clip(rint(y * 32768)).
+    Equal rates return x itself for f32."""
+    lib.require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() not in (1, 2):
+        raise AvsepError(f"resample takes a float32 waveform [L] or [B,L], got {x.dtype} {tuple(x.shape)}")
+    up, down = check_rates(rate_in, rate_out)
+    if up == down and not out_s16:
+        return x
+    _check_length(x.shape[-1], up, down)
+    rows = x.contiguous() if x.dim() == 2 else x.contiguous()[None]
+    y = K.resample_poly(rows, filter_table(up, down, x.device), up, down, 0, out_s16)
+    return y if x.dim() == 2 else y[0]
+
+
+def resample_pcm(pcm, rate_in, rate_out):
+    """pcm: interleaved int16 [L,C] on the GPU (a WAV file's frames) -> f32 mono [Lout] at rate_out: the channels' mean over
+    32768, resampled, in one kernel.  Equal rates go through the same kernel with the unit-impulse filter: the converted mono
+    signal, bit for bit separate.read_wav's array."""
+    lib.require_gpu(pcm)
+    if pcm.dtype != torch.int16 or pcm.dim() != 2 or not 1 <= pcm.shape[1] <= MAX_CHANNELS:
+        raise AvsepError(f"resample_pcm takes interleaved int16 [L,C] with 1 <= C <= {MAX_CHANNELS}, got {pcm.dtype} {tuple(pcm.shape)}")
+    up, down = check_rates(rate_in, rate_out)
+    _check_length(pcm.shape[0], up, down)
+    return K.resample_poly(pcm.contiguous(), filter_table(up, down, pcm.device), up, down, pcm.shape[1], False)[0]

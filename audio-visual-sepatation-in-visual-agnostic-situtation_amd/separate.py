@@ -15,7 +15,8 @@ for ``use_vis=False`` the swap draw is pinned to "no swap" and consecutive windo
 (``avsep_window_agreement`` + ``align_permutations``) before blending.
 
 CLI: ``python -m avsep_amd.separate --wav mix.wav --frames a.npy b.npy --id <experiment> --out dir`` (flag set of
-arguments.py; 16-bit PCM WAV at ``--audRate``, no resampling).
+arguments.py; 16-bit PCM WAV at any rate: a file that is not at ``--audRate`` is resampled on the GPU, resample.py, and
+the sources are written at the file's rate unless ``--out_rate model``).
 """
 import itertools
 import os
@@ -176,6 +177,34 @@ def write_wav(path, data, rate):
         w.writeframes(pcm.tobytes())
 
 
+def wav_rate(path):
+    """The sample rate in the file's header."""
+    with wave.open(path, "rb") as w:
+        return w.getframerate()
+
+
+def read_wav_pcm(path):
+    """-> (int16 [L, C] frames exactly as they lie in the file, sample rate).  16-bit PCM only; nothing is converted."""
+    with wave.open(path, "rb") as w:
+        if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+            raise AvsepError(f"{path}: only uncompressed 16-bit PCM WAV is read (sample width {w.getsampwidth()} bytes)")
+        rate, ch = w.getframerate(), w.getnchannels()
+        data = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)      # a writable copy in native order
+    return data.reshape(-1, ch), rate
+
+
+def write_wav_pcm(path, pcm, rate):
+    """int16 mono [L] -> 16-bit PCM WAV, sample for sample."""
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16 or pcm.ndim != 1:
+        raise AvsepError(f"write_wav_pcm takes int16 mono [L], got {pcm.dtype} {pcm.shape}")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(rate))
+        w.writeframes(pcm.astype("<i2", copy=False).tobytes())
+
+
 def build_parser():
     from .arguments import ArgParser
     ap = ArgParser()
@@ -183,7 +212,9 @@ def build_parser():
     ap.add_other_arguments()
     p = ap.parser
     p.description = "Separate a WAV of any length with a trained checkpoint (windowed inference, stitched masks)."
-    p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at --audRate")
+    p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at any sample rate (resampled to --audRate on the GPU)")
+    p.add_argument("--out_rate", choices=("file", "model"), default="file",
+                   help="rate of the written sources: the input file's own (default) or the model's --audRate")
     p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]")
     p.add_argument("--out", default="separated", help="output directory (source<n>.wav)")
     p.add_argument("--audio_only", action="store_true", help="no frames: audio-only branch with aligned windows")
@@ -204,12 +235,20 @@ def cli(argv=None):
     from . import checkpoint as ckpt
     from .models import ModelBuilder
     args = parse_args(argv)
-    data, rate = read_wav(args.wav)
+    from . import resample as R
+    rate = wav_rate(args.wav)
     if rate != args.audRate:
-        raise SystemExit(f"{args.wav} is sampled at {rate} Hz, the model at {args.audRate} Hz: resample it first")
+        try:
+            R.check_rates(rate, args.audRate)
+        except AvsepError as e:
+            raise SystemExit(f"{args.wav}: {e}")
     if not torch.cuda.is_available():
         raise AvsepError("separation runs on an MI355X; there is no CPU fallback")
     dev = torch.device("cuda", 0)
+    if rate == args.audRate:
+        wav = torch.from_numpy(read_wav(args.wav)[0]).to(dev)
+    else:                                            # the raw frames go up; down-mix, conversion and filter are one kernel
+        wav = R.resample_pcm(torch.from_numpy(read_wav_pcm(args.wav)[0]).to(dev), rate, args.audRate)
     args.ckpt = os.path.join(args.ckpt, args.id)
     if not args.weights_sound:
         args.weights_sound, args.weights_frame = ckpt.resume_paths(args, best=not args.latest)
@@ -223,11 +262,15 @@ def cli(argv=None):
     for path in args.frames:
         fr = torch.from_numpy(np.load(path)).float()
         frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
-    out = separate_long(nets, torch.from_numpy(data).to(dev), frames, args, use_vis=not args.audio_only,
+    out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
                         stride_frames=args.window_stride, batch=args.window_batch)
     os.makedirs(args.out, exist_ok=True)
-    for n, w in enumerate(out["wavs"].cpu().numpy()):
-        write_wav(os.path.join(args.out, f"source{n}.wav"), w, rate)
+    if rate != args.audRate and args.out_rate == "file":
+        for n, w in enumerate(R.resample(out["wavs"], args.audRate, rate, out_s16=True).cpu().numpy()):
+            write_wav_pcm(os.path.join(args.out, f"source{n}.wav"), w, rate)
+    else:
+        for n, w in enumerate(out["wavs"].cpu().numpy()):
+            write_wav(os.path.join(args.out, f"source{n}.wav"), w, args.audRate)
     print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav")
     return out
 

@@ -471,6 +471,33 @@ int avsep_heatmap_overlay(const float* maps, const float* const* frames, const u
                           int32_t w, int32_t H, int32_t W, int32_t alpha256, uint8_t* out, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Sample-rate conversion (csrc/resample.hip): a rational polyphase FIR resampler, so that a WAV file at any rate goes in
+ * and the separated sources come out at the file's own rate.  up = rate_out / g, down = rate_in / g, g = gcd; both in
+ * [1, 1280] (8 ... 96 kHz to and from 11 025 Hz; the worst cases are 441/1280 and 147/1280).
+ * Filter (the caller builds it in float64 and rounds it ONCE to f32): m = max(up, down), half = 10*m, M = 2*half + 1,
+ *   h[i] = up * w[i] / sum(w),  w[i] = (1/m) * sinc((i - half) / m) * kaiser(M, beta = 5.0)[i],   sinc(t) = sin(pi t)/(pi t),
+ * which is up * scipy.signal.firwin(M, 1/m, window=('kaiser', 5.0)): scipy.signal.resample_poly's default filter.
+ * It is passed as the polyphase table ho: f32 [T, up], T = ceil(M / up), with its columns in OUTPUT order, so that the
+ * threads of consecutive outputs read consecutive floats: column t holds the phase of every output j = t (mod up),
+ *   p(t) = (t*down + half) mod up,   ho[i][t] = h[p(t) + i*up] where p(t) + i*up < M, else 0.
+ * Result, per row r (rows never see each other; samples outside a row are zero: resample_poly's padtype='constant'):
+ *   Lout = ceil(L * up / down),   y[r, j] = sum_n x[r, n] * h[j*down - n*up + half]   over 0 <= n < L, filter index in [0, M).
+ * Arithmetic: with pos = j*down + half (64-bit), p = pos mod up, n0 = pos div up:
+ *   acc = 0;  for i = 0 .. T-1 (in this order):  acc = fma(x[r, n0 - i], f32(h[p + i*up]), acc)   (one f32 rounding per tap),
+ * a sample outside [0, L) is 0 and the last tap takes no sample when p + (T-1)*up >= M.  The order depends on (up, down, j)
+ * only: not on B, the launch geometry or the run; there are no atomics.  A row gives the same bits alone, inside a batch
+ * and on a second call.
+ * Input:  in_ch = 0: x is f32 [B, L].  in_ch = C in [1, 256]: x is interleaved int16 [L, C] as it lies in a WAV file (B must
+ *   be 1); the sample is the exact integer sum of the C channels divided (IEEE f32 division) by C * 32768, converted while
+ *   the tile is staged: no f32 copy of the file exists.
+ * Output: out_s16 = 0: y is f32 [B, Lout].  out_s16 = 1: y is int16 [B, Lout] = clip(rint(v * 32768), -32768, 32767) of
+ *   exactly the f32 value v the other mode stores (round half to even; v * 32768 is exact).
+ * 1 <= L, Lout < 2^31, B <= 65535; anything else is AVSEP_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------- */
+int avsep_resample_poly(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down, int32_t in_ch,
+                        int32_t out_s16, void* y, avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
  * that are accumulated into, exactly as for the fp32 NCHW entry points of the same names below.
