@@ -105,9 +105,50 @@ extern "C" int avsep_window_agreement(const float* masks, const int32_t* starts,
 // ============================================================================
 // mask stitch: un-warp every covering window at (f, t), cross-fade, threshold, x magnitude
 // ============================================================================
-// grid (ceil(F / 256), ceil(Fin / LF_ROWS), N).  The windows that cover the block's 256 frames are a contiguous run
-// [k_lo, k_hi] of the ascending start table (two binary searches by one thread); a thread walks that run and keeps the
-// windows its own frame lies in, in ascending k.
+// The windows that cover a block's 256 frames [t0, t0 + 256) are a contiguous run [lo, hi] of the ascending start table:
+// two binary searches.
+__device__ __forceinline__ void stitch_window_run(const int* __restrict__ starts, int K, int W, int t0, int F, int& lo_out,
+                                                  int& hi_out) {
+  const int t1 = min(t0 + LF_BLOCK, F) - 1;
+  int lo = 0, hi = K;                                      // first k with starts[k] + W > t0
+  while (lo < hi) {
+    int m = (lo + hi) >> 1;
+    if (starts[m] + W > t0) hi = m; else lo = m + 1;
+  }
+  lo_out = lo;
+  hi = K;                                                  // first k with starts[k] > t1
+  while (lo < hi) {
+    int m = (lo + hi) >> 1;
+    if (starts[m] > t1) hi = m; else lo = m + 1;
+  }
+  hi_out = lo - 1;
+}
+
+// The blended mask M of source n at frame t and the output row whose warp coordinate is gy: walks the run [k_lo, k_hi] and
+// keeps the windows the frame lies in, in ascending k.  The one body of both stitch kernels: they cannot disagree on M.
+__device__ __forceinline__ float stitch_point(const float* __restrict__ masks, const int* __restrict__ starts,
+                                              const int* __restrict__ perm, int k_lo, int k_hi, int N, int n, int Fout, int W,
+                                              int t, float gy) {
+  float acc = 0.f, wsum = 0.f, first = 0.f;
+  int cnt = 0;
+  for (int k = k_lo; k <= k_hi; ++k) {
+    const int j = t - starts[k];
+    if ((unsigned)j >= (unsigned)W) continue;
+    const int src = perm[k * N + n];
+    if ((unsigned)src >= (unsigned)N) continue;
+    Bilin bl = grid_bilin((float)linspace_pm1(j, W), gy, Fout, W);
+    const float v = sample_bilin(masks + ((long long)k * N + src) * Fout * W, bl, Fout, W, 0.f);
+    const float w = (float)min(j + 1, W - j);
+    if (cnt == 0) first = v;
+    acc += w * v;
+    wsum += w;
+    ++cnt;
+  }
+  return cnt == 1 ? first : (cnt ? acc / wsum : 0.f);
+}
+
+// grid (ceil(F / 256), ceil(Fin / LF_ROWS), N); one thread searches the window run, a thread then owns one frame of
+// LF_ROWS rows.
 __global__ __launch_bounds__(LF_BLOCK) void mask_stitch_kernel(const float* __restrict__ masks, const int* __restrict__ starts,
                                                                const int* __restrict__ perm, const float* __restrict__ mag,
                                                                int K, int N, int Fout, int W, int Fin, int F, int binary,
@@ -117,43 +158,13 @@ __global__ __launch_bounds__(LF_BLOCK) void mask_stitch_kernel(const float* __re
   __shared__ float s_gy[LF_ROWS];
   __shared__ int s_lo, s_hi;
   if (threadIdx.x < rows) s_gy[threadIdx.x] = warp_gy(f0 + threadIdx.x, Fin, 0);
-  if (threadIdx.x == LF_BLOCK - 1) {
-    const int t1 = min(t0 + LF_BLOCK, F) - 1;
-    int lo = 0, hi = K;                                    // first k with starts[k] + W > t0
-    while (lo < hi) {
-      int m = (lo + hi) >> 1;
-      if (starts[m] + W > t0) hi = m; else lo = m + 1;
-    }
-    s_lo = lo;
-    hi = K;                                                // first k with starts[k] > t1
-    while (lo < hi) {
-      int m = (lo + hi) >> 1;
-      if (starts[m] > t1) hi = m; else lo = m + 1;
-    }
-    s_hi = lo - 1;
-  }
+  if (threadIdx.x == LF_BLOCK - 1) stitch_window_run(starts, K, W, t0, F, s_lo, s_hi);
   __syncthreads();
   const int t = t0 + threadIdx.x;
   if (t >= F) return;
   const int k_lo = s_lo, k_hi = s_hi;
   for (int r = 0; r < rows; ++r) {
-    const float gy = s_gy[r];
-    float acc = 0.f, wsum = 0.f, first = 0.f;
-    int cnt = 0;
-    for (int k = k_lo; k <= k_hi; ++k) {
-      const int j = t - starts[k];
-      if ((unsigned)j >= (unsigned)W) continue;
-      const int src = perm[k * N + n];
-      if ((unsigned)src >= (unsigned)N) continue;
-      Bilin bl = grid_bilin((float)linspace_pm1(j, W), gy, Fout, W);
-      const float v = sample_bilin(masks + ((long long)k * N + src) * Fout * W, bl, Fout, W, 0.f);
-      const float w = (float)min(j + 1, W - j);
-      if (cnt == 0) first = v;
-      acc += w * v;
-      wsum += w;
-      ++cnt;
-    }
-    const float M = cnt == 1 ? first : (cnt ? acc / wsum : 0.f);
+    const float M = stitch_point(masks, starts, perm, k_lo, k_hi, N, n, Fout, W, t, s_gy[r]);
     const int f = f0 + r;
     const long long o = ((long long)n * Fin + f) * F + t;
     out[o] = mag[(long long)f * F + t] * (binary ? (M > thres ? 1.f : 0.f) : M);
@@ -169,6 +180,48 @@ extern "C" int avsep_mask_stitch(const float* masks, const int32_t* starts, cons
     return AVSEP_ERR_ARG;
   hipLaunchKernelGGL(mask_stitch_kernel, dim3(cdiv(F, LF_BLOCK), cdiv(Fin, LF_ROWS), N), dim3(LF_BLOCK), 0, (hipStream_t)stream, masks,
                      starts, perm, mag, K, N, Fout, W, Fin, F, binary, thres, out, mask_out);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+// The same grid for a recording of C channels: M is blended once per point (the gather through L2 is what the kernel's time
+// goes to) and multiplied into the C magnitudes.  Rows of [N, C, Fin, F] pass 2^31 elements on a multi-hour recording: every
+// offset is formed in 64 bits.
+__global__ __launch_bounds__(LF_BLOCK) void mask_stitch_channels_kernel(const float* __restrict__ masks,
+                                                                        const int* __restrict__ starts,
+                                                                        const int* __restrict__ perm,
+                                                                        const float* __restrict__ mag, int K, int N, int Fout,
+                                                                        int W, int C, int Fin, int F, int binary, float thres,
+                                                                        float* __restrict__ out, float* __restrict__ mask_out) {
+  const int t0 = blockIdx.x * LF_BLOCK, f0 = blockIdx.y * LF_ROWS, n = blockIdx.z, rows = min(LF_ROWS, Fin - f0);
+  __shared__ float s_gy[LF_ROWS];
+  __shared__ int s_lo, s_hi;
+  if (threadIdx.x < rows) s_gy[threadIdx.x] = warp_gy(f0 + threadIdx.x, Fin, 0);
+  if (threadIdx.x == LF_BLOCK - 1) stitch_window_run(starts, K, W, t0, F, s_lo, s_hi);
+  __syncthreads();
+  const int t = t0 + threadIdx.x;
+  if (t >= F) return;
+  const int k_lo = s_lo, k_hi = s_hi;
+  const long long plane = (long long)Fin * F;
+  for (int r = 0; r < rows; ++r) {
+    const float M = stitch_point(masks, starts, perm, k_lo, k_hi, N, n, Fout, W, t, s_gy[r]);
+    const float m = binary ? (M > thres ? 1.f : 0.f) : M;
+    const long long ft = (long long)(f0 + r) * F + t;
+    float* __restrict__ o = out + (long long)n * C * plane + ft;
+    for (int c = 0; c < C; ++c) o[c * plane] = mag[c * plane + ft] * m;
+    if (mask_out) mask_out[(long long)n * plane + ft] = M;
+  }
+}
+
+extern "C" int avsep_mask_stitch_channels(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag,
+                                          int32_t K, int32_t N, int32_t Fout, int32_t W, int32_t C, int32_t Fin, int32_t F,
+                                          int32_t binary, float thres, float* out, float* mask_out, avsep_stream_t stream) {
+  if (!masks || !starts || !perm || !mag || !out) return AVSEP_ERR_ARG;
+  if (K <= 0 || K > 65535 || N <= 0 || N > 65535 || Fout <= 0 || W <= 0 || C <= 0 || C > 65535 || Fin <= 0 || Fin > 65535 ||
+      F <= 0)
+    return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(mask_stitch_channels_kernel, dim3(cdiv(F, LF_BLOCK), cdiv(Fin, LF_ROWS), N), dim3(LF_BLOCK), 0,
+                     (hipStream_t)stream, masks, starts, perm, mag, K, N, Fout, W, C, Fin, F, binary, thres, out, mask_out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }

@@ -5,6 +5,9 @@
 // t0, t0 + S, t0 + 2S, ... of the tile: they share their phase, so each coefficient is loaded once (lanes on consecutive
 // columns of the table: coalesced) and used RS_R times.
 // No atomics: every output is one sequential f32 fused-multiply-add chain whose order depends on (up, down, j) only.
+// Two more kernels keep a file's channels apart with the same tiles and the same chains (rs_chains): resample_split_kernel
+// gives the down-mix and every channel of interleaved PCM in one pass, resample_join_kernel turns C rows back into
+// interleaved PCM and writes whole frames.
 #include "common.h"
 
 constexpr int RS_BLOCK = 256;
@@ -13,13 +16,20 @@ constexpr int RS_SPAN = 12288;     // floats of staged input a tile may touch (4
 constexpr int RS_MAX_S = 2048;
 constexpr int RS_MAX_RATIO = 1280;
 constexpr int RS_MAX_CH = 256;     // |sum of the channels| <= 256 * 32768 = 2^23: exact in f32, as is the divisor
+constexpr int RS_LDS = RS_SPAN + RS_SPAN / 32 + 1;   // slots of the staging array
+constexpr int RS_KEEP_CH = 8;      // channels split and join keep apart (7.1)
+constexpr int RJ_SPAN = 8704;      // join: staged floats of all C rows together (34 KiB + padding, beside a 16 KiB output tile;
+                                   // eight rows of a 1/1 tile still fit)
+constexpr int RJ_LDS = RJ_SPAN + RJ_SPAN / 32 + 1;
 
-// Sample n of a row; zero outside it.  in_ch >= 1: interleaved int16 [L, in_ch], the exact integer sum of the channels
-// over in_ch * 32768 with a correctly rounded division (separate.read_wav's value for one and two channels).
-__device__ __forceinline__ float rs_sample(const void* __restrict__ x, long long n, long long L, int in_ch) {
+// Sample n of a row; zero outside it.  in_ch >= 1: interleaved int16 [L, in_ch]; ch < 0 is the exact integer sum of the
+// channels over in_ch * 32768 with a correctly rounded division (separate.read_wav's value for one and two channels),
+// ch >= 0 is channel ch over 32768 (exact).
+__device__ __forceinline__ float rs_sample(const void* __restrict__ x, long long n, long long L, int in_ch, int ch) {
   if ((unsigned long long)n >= (unsigned long long)L) return 0.f;
   if (in_ch == 0) return ((const float*)x)[n];
   const int16_t* s = (const int16_t*)x + n * in_ch;
+  if (ch >= 0) return (float)s[ch] * (1.f / 32768.f);
   int sum = 0;
   for (int c = 0; c < in_ch; ++c) sum += s[c];
   return __fdiv_rn((float)sum, (float)(in_ch * 32768));
@@ -29,104 +39,259 @@ __device__ __forceinline__ float rs_sample(const void* __restrict__ x, long long
 // fall on 32 different banks instead of 16, 8 or 4.
 __device__ __forceinline__ int rs_slot(int s) { return s + (s >> 5); }
 
-// grid (ceil(Lout / (RS_R * S)), B).  Output j = j0 + dj sits at filter position pos = j * down + half = pos0 + dj * down:
-// phase p = pos mod up, newest input n = pos div up, taps i = 0 .. T-1 pair x[n - i] with h[p + i * up] = ho[i][dj mod up]
-// (j0 is a multiple of up, so the phase of dj is the phase of column dj mod up of the table).
+__device__ __forceinline__ int16_t rs_s16(float v) { return (int16_t)(int)fminf(fmaxf(rintf(v * 32768.f), -32768.f), 32767.f); }
+
+// A workgroup's tile: the RS_R * S outputs from j0 on.  Output j = j0 + dj sits at filter position
+// pos = j * down + half = pos0 + dj * down: phase p = pos mod up, newest input n = pos div up, taps i = 0 .. T-1 pair x[n - i]
+// with h[p + i * up] = ho[i][dj mod up] (j0 is a multiple of up, so the phase of dj is the phase of column dj mod up of the table).
 // pos0 is split once per workgroup in 64 bits (j * down passes 2^31 on a ten-minute file); dj * down < 2^24 stays 32-bit.
-// STAGED: the samples [n_lo, n_lo + span) of the tile are in LDS.  Otherwise (a ratio whose tile does not fit) every tap
-// reads global memory: the same values in the same order, so the mode never shows in the result.
+struct RsTile {
+  long long j0, n_lo;     // first output; oldest sample of the tile's first output
+  int r0, nout, span;     // pos0 mod up; outputs inside the row; samples [n_lo, n_lo + span) the tile touches
+};
+
+__device__ __forceinline__ RsTile rs_tile(int up, int down, int half, int T, int S, int Lout) {
+  RsTile t;
+  t.j0 = (long long)blockIdx.x * (RS_R * S);
+  const long long pos0 = t.j0 * down + half;
+  const long long q0 = pos0 / up;
+  t.r0 = (int)(pos0 - q0 * up);
+  t.nout = (int)min((long long)(RS_R * S), (long long)Lout - t.j0);
+  t.n_lo = q0 - (T - 1);
+  t.span = (t.r0 + (t.nout - 1) * down) / up + T;            // <= the staging array: checked by the host for a full tile
+  return t;
+}
+
+// The accumulation chains of a thread's RS_R outputs t0, t0 + S, ... of one row: the only arithmetic of this file, shared
+// by every kernel.  STAGED: the samples [n_lo, n_lo + span) of the row are in s_x.  Otherwise (a ratio whose tile does not
+// fit) every tap reads global memory: the same values in the same order, so the mode never shows in the result.
+// Outputs past the row's end compute on whatever the tile holds and are not stored by the callers; their reads stay inside
+// s_x (the host sized it for a full tile) or inside the row (rs_sample checks).
+template <bool STAGED>
+__device__ __forceinline__ void rs_chains(const float* s_x, const void* __restrict__ xr, long long n_lo, int L, int in_ch, int ch,
+                                          const float* __restrict__ ho, int up, int down, int M, int T, int S, int r0, int t0,
+                                          float acc[RS_R]) {
+  const int step = S / up * down;                            // input samples between a thread's outputs: S * down / up
+  const int v = r0 + t0 * down, dq = v / up, p = v - dq * up;
+  const float* __restrict__ h = ho + t0 % up;
+  int top[RS_R];                                             // newest sample of output r, relative to n_lo
+#pragma unroll
+  for (int r = 0; r < RS_R; ++r) {
+    top[r] = dq + r * step + T - 1;
+    acc[r] = 0.f;
+  }
+#define RS_X(r, i) (STAGED ? s_x[rs_slot(top[r] - (i))] : rs_sample(xr, n_lo + top[r] - (i), L, in_ch, ch))
+#pragma unroll 4
+  for (int i = 0; i < T - 1; ++i) {
+    const float c = h[i * up];
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) acc[r] = fmaf(RS_X(r, i), c, acc[r]);
+  }
+  // only the last tap can fall off the filter's end (p + (T-1) * up >= M): it then takes no sample at all
+  const float c = h[(T - 1) * up];
+  const bool last = p + (T - 1) * up < M;
+#pragma unroll
+  for (int r = 0; r < RS_R; ++r) acc[r] = fmaf(last ? RS_X(r, T - 1) : 0.f, c, acc[r]);
+#undef RS_X
+}
+
+// grid (ceil(Lout / (RS_R * S)), B).
 template <bool STAGED>
 __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const void* __restrict__ x, const float* __restrict__ ho, int up,
                                                                  int down, int half, int M, int T, int S, int L, int Lout,
                                                                  int in_ch, int out_s16, void* __restrict__ y) {
-  __shared__ float s_x[STAGED ? RS_SPAN + RS_SPAN / 32 + 1 : 1];
+  __shared__ float s_x[STAGED ? RS_LDS : 1];
   const int row = blockIdx.y;
-  const long long j0 = (long long)blockIdx.x * (RS_R * S);
-  const long long pos0 = j0 * down + half;
-  const long long q0 = pos0 / up;
-  const int r0 = (int)(pos0 - q0 * up);
-  const int nout = (int)min((long long)(RS_R * S), (long long)Lout - j0);
+  const RsTile tl = rs_tile(up, down, half, T, S, Lout);
   const void* xr = in_ch ? x : (const void*)((const float*)x + (long long)row * L);
-  const long long n_lo = q0 - (T - 1);                       // oldest sample of the tile's first output
   if (STAGED) {
-    const int span = (r0 + (nout - 1) * down) / up + T;      // <= RS_SPAN: checked by the host for a full tile
-    for (int s = threadIdx.x; s < span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(xr, n_lo + s, L, in_ch);
+    for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(xr, tl.n_lo + s, L, in_ch, -1);
     __syncthreads();
   }
-  const int step = S / up * down;                            // input samples between a thread's outputs: S * down / up
   for (int t0 = threadIdx.x; t0 < S; t0 += RS_BLOCK) {
-    if (t0 >= nout) break;                                   // none of this thread's outputs lies inside the row
-    const int v = r0 + t0 * down, dq = v / up, p = v - dq * up;
-    const float* __restrict__ h = ho + t0 % up;
-    // a thread's outputs past the row's end compute on whatever the tile holds and are not stored; their reads stay
-    // inside s_x (the host sized it for a full tile) or inside the row (rs_sample checks)
-    int top[RS_R];                                           // newest sample of output r, relative to n_lo
+    if (t0 >= tl.nout) break;                                // none of this thread's outputs lies inside the row
     float acc[RS_R];
-#pragma unroll
-    for (int r = 0; r < RS_R; ++r) {
-      top[r] = dq + r * step + T - 1;
-      acc[r] = 0.f;
-    }
-#define RS_X(r, i) (STAGED ? s_x[rs_slot(top[r] - (i))] : rs_sample(xr, n_lo + top[r] - (i), L, in_ch))
-#pragma unroll 4
-    for (int i = 0; i < T - 1; ++i) {
-      const float c = h[i * up];
-#pragma unroll
-      for (int r = 0; r < RS_R; ++r) acc[r] = fmaf(RS_X(r, i), c, acc[r]);
-    }
-    // only the last tap can fall off the filter's end (p + (T-1) * up >= M): it then takes no sample at all
-    const float c = h[(T - 1) * up];
-    const bool last = p + (T - 1) * up < M;
-#pragma unroll
-    for (int r = 0; r < RS_R; ++r) acc[r] = fmaf(last ? RS_X(r, T - 1) : 0.f, c, acc[r]);
-#undef RS_X
+    rs_chains<STAGED>(s_x, xr, tl.n_lo, L, in_ch, -1, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
     for (int r = 0; r < RS_R; ++r) {
       const int dj = t0 + r * S;
-      if (dj >= nout) break;
-      const long long o = (long long)row * Lout + j0 + dj;
+      if (dj >= tl.nout) break;
+      const long long o = (long long)row * Lout + tl.j0 + dj;
       if (out_s16)
-        ((int16_t*)y)[o] = (int16_t)(int)fminf(fmaxf(rintf(acc[r] * 32768.f), -32768.f), 32767.f);
+        ((int16_t*)y)[o] = rs_s16(acc[r]);
       else
         ((float*)y)[o] = acc[r];
     }
   }
 }
 
+// grid (ceil(Lout / (RS_R * S))).  Interleaved int16 [L, C] -> f32 [1 + C, Lout]: the workgroup makes its tile of every row
+// in turn, row 0 from the down-mix and row 1 + c from channel c, so the file is fetched from HBM once (the later rows find
+// the tile's frames in L2) and no de-interleaved copy of it exists.
+template <bool STAGED>
+__global__ __launch_bounds__(RS_BLOCK) void resample_split_kernel(const int16_t* __restrict__ x, const float* __restrict__ ho,
+                                                                  int up, int down, int half, int M, int T, int S, int L,
+                                                                  int Lout, int C, float* __restrict__ y) {
+  __shared__ float s_x[STAGED ? RS_LDS : 1];
+  const RsTile tl = rs_tile(up, down, half, T, S, Lout);
+  for (int row = 0; row <= C; ++row) {
+    const int ch = row - 1;                                  // -1: the down-mix
+    if (STAGED) {
+      if (row) __syncthreads();                              // the previous row's chains have read s_x
+      for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(x, tl.n_lo + s, L, C, ch);
+      __syncthreads();
+    }
+    for (int t0 = threadIdx.x; t0 < S; t0 += RS_BLOCK) {
+      if (t0 >= tl.nout) break;
+      float acc[RS_R];
+      rs_chains<STAGED>(s_x, x, tl.n_lo, L, C, ch, ho, up, down, M, T, S, tl.r0, t0, acc);
+#pragma unroll
+      for (int r = 0; r < RS_R; ++r) {
+        const int dj = t0 + r * S;
+        if (dj >= tl.nout) break;
+        y[(long long)row * Lout + tl.j0 + dj] = acc[r];
+      }
+    }
+  }
+}
+
+// grid (ceil(Lout / (RS_R * S))).  f32 [C, L] -> interleaved int16 [Lout, C].  A pass of the workgroup makes RS_R runs of
+// RS_BLOCK consecutive frames; it computes them for every channel into the LDS tile s_o, laid out as the file is
+// ([run][frame][channel]), and then stores each run as one contiguous stretch of RS_BLOCK * C samples, lanes on consecutive
+// 4-byte words (2-byte samples where the run starts on an odd sample): no store with a stride of 2C bytes.  The C rows of the
+// input tile are staged side by side, `pitch` slots apart.
+template <bool STAGED>
+__global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __restrict__ x, const float* __restrict__ ho, int up,
+                                                                 int down, int half, int M, int T, int S, int L, int Lout,
+                                                                 int C, int pitch, int16_t* __restrict__ y) {
+  __shared__ float s_x[STAGED ? RJ_LDS : 1];
+  __shared__ __align__(4) int16_t s_o[RS_R * RS_BLOCK * RS_KEEP_CH];
+  const RsTile tl = rs_tile(up, down, half, T, S, Lout);
+  if (STAGED) {
+    for (int c = 0; c < C; ++c)
+      for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK)
+        s_x[c * pitch + rs_slot(s)] = rs_sample(x + (long long)c * L, tl.n_lo + s, L, 0, -1);
+    __syncthreads();
+  }
+  const bool words = ((size_t)y & 3) == 0;
+  for (int tb = 0; tb < S && tb < tl.nout; tb += RS_BLOCK) {   // the same for every thread: the loop holds barriers
+    const int t0 = tb + threadIdx.x;
+    if (t0 < S && t0 < tl.nout) {
+      for (int c = 0; c < C; ++c) {
+        float acc[RS_R];
+        rs_chains<STAGED>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, ho, up, down, M, T, S, tl.r0, t0, acc);
+#pragma unroll
+        for (int r = 0; r < RS_R; ++r) s_o[(r * RS_BLOCK + threadIdx.x) * C + c] = rs_s16(acc[r]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) {
+      const int first = tb + r * S;                            // the run's first frame, relative to j0
+      if (first >= tl.nout) break;
+      const int cnt = min(min(RS_BLOCK, S - tb), tl.nout - first) * C;      // samples of the run
+      const long long e0 = (tl.j0 + first) * C;
+      const int16_t* src = s_o + r * RS_BLOCK * C;
+      if (words && !(e0 & 1)) {
+        for (int i = threadIdx.x; i < (cnt >> 1); i += RS_BLOCK) ((uint32_t*)(y + e0))[i] = ((const uint32_t*)src)[i];
+        if ((cnt & 1) && threadIdx.x == 0) y[e0 + cnt - 1] = src[cnt - 1];
+      } else {
+        for (int i = threadIdx.x; i < cnt; i += RS_BLOCK) y[e0 + i] = src[i];
+      }
+    }
+    __syncthreads();                                           // s_o is free for the next pass
+  }
+}
+
 // Outputs between a thread's RS_R outputs: a multiple of `up`, at least one pass of the workgroup, chosen for the fewest idle
-// lanes in the last pass among the sizes whose tile of RS_R * S outputs fits the LDS span (0: none does).
-static int rs_stride(int up, int down, int T) {
+// lanes in the last pass among the sizes whose tile of RS_R * S outputs fits the staging array: `rows` rows of the tile's
+// input side by side in `slots` slots (0: none does).
+static int rs_stride(int up, int down, int T, int rows, int slots) {
   int best = 0;
   double best_fill = 0.0;
   for (int S = up; S <= RS_MAX_S; S += up) {
     if (S < RS_BLOCK) continue;
     const long long span = ((long long)(up - 1) + ((long long)RS_R * S - 1) * down) / up + T;
-    if (span > RS_SPAN) break;
+    if ((span + span / 32 + 1) * rows > slots) break;
     const double fill = (double)S / roundup(S, RS_BLOCK);
     if (fill > best_fill + 1e-9) best = S, best_fill = fill;
   }
   return best;
 }
 
+// What the three entry points derive from (up, down): the filter's geometry and the tile.
+struct RsPlan {
+  int half, M, T, S, pitch;   // pitch: slots per staged row of a full tile
+  bool staged;
+  unsigned tiles;
+};
+
+static RsPlan rs_plan(int up, int down, long long lout, int rows, int slots) {
+  RsPlan p;
+  const int m = up > down ? up : down;
+  p.half = 10 * m, p.M = 2 * p.half + 1;
+  p.T = (p.M + up - 1) / up;
+  p.S = rs_stride(up, down, p.T, rows, slots);
+  p.staged = p.S > 0;
+  if (!p.staged) p.S = roundup(RS_BLOCK, up);
+  const long long span = ((long long)(up - 1) + ((long long)RS_R * p.S - 1) * down) / up + p.T;
+  p.pitch = p.staged ? (int)(span + span / 32 + 1) : 0;
+  p.tiles = (unsigned)cdiv(lout, (long long)RS_R * p.S);
+  return p;
+}
+
+static bool rs_ratio_ok(int up, int down, int L, long long* lout) {
+  if (up < 1 || up > RS_MAX_RATIO || down < 1 || down > RS_MAX_RATIO || L < 1) return false;
+  *lout = ((long long)L * up + down - 1) / down;
+  return *lout <= 0x7fffffffLL;
+}
+
 extern "C" int avsep_resample_poly(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down,
                                    int32_t in_ch, int32_t out_s16, void* y, avsep_stream_t stream) {
   if (!x || !ho || !y) return AVSEP_ERR_ARG;
-  if (up < 1 || up > RS_MAX_RATIO || down < 1 || down > RS_MAX_RATIO || L < 1 || B < 1 || B > 65535) return AVSEP_ERR_ARG;
+  long long lout;
+  if (!rs_ratio_ok(up, down, L, &lout) || B < 1 || B > 65535) return AVSEP_ERR_ARG;
   if (in_ch < 0 || in_ch > RS_MAX_CH || (in_ch >= 1 && B != 1) || (out_s16 != 0 && out_s16 != 1)) return AVSEP_ERR_ARG;
-  const long long lout = ((long long)L * up + down - 1) / down;
-  if (lout > 0x7fffffffLL) return AVSEP_ERR_ARG;
-  const int m = up > down ? up : down, half = 10 * m, M = 2 * half + 1;
-  const int T = (M + up - 1) / up;
-  int S = rs_stride(up, down, T);
-  const bool staged = S > 0;
-  if (!staged) S = roundup(RS_BLOCK, up);
-  const dim3 grid(cdiv(lout, (long long)RS_R * S), B);
-  if (staged)
-    hipLaunchKernelGGL(resample_poly_kernel<true>, grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, half, M, T, S,
-                       L, (int)lout, in_ch, out_s16, y);
+  const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
+  const dim3 grid(p.tiles, B);
+  if (p.staged)
+    hipLaunchKernelGGL(resample_poly_kernel<true>, grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half, p.M, p.T,
+                       p.S, L, (int)lout, in_ch, out_s16, y);
   else
-    hipLaunchKernelGGL(resample_poly_kernel<false>, grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, half, M, T, S,
-                       L, (int)lout, in_ch, out_s16, y);
+    hipLaunchKernelGGL(resample_poly_kernel<false>, grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half, p.M, p.T,
+                       p.S, L, (int)lout, in_ch, out_s16, y);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_resample_split(const int16_t* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, float* y,
+                                    avsep_stream_t stream) {
+  if (!x || !ho || !y) return AVSEP_ERR_ARG;
+  long long lout;
+  if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH) return AVSEP_ERR_ARG;
+  const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
+  if (p.staged)
+    hipLaunchKernelGGL(resample_split_kernel<true>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, C, y);
+  else
+    hipLaunchKernelGGL(resample_split_kernel<false>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, C, y);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int16_t* y,
+                                   avsep_stream_t stream) {
+  if (!x || !ho || !y) return AVSEP_ERR_ARG;
+  long long lout;
+  if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH) return AVSEP_ERR_ARG;
+  const RsPlan p = rs_plan(up, down, lout, C, RJ_LDS);
+  if (p.staged)
+    hipLaunchKernelGGL(resample_join_kernel<true>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, C, p.pitch, y);
+  else
+    hipLaunchKernelGGL(resample_join_kernel<false>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, C, p.pitch, y);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }

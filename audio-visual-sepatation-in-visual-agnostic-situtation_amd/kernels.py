@@ -742,6 +742,64 @@ def mask_stitch(masks, starts, perm, mag, binary, thres, want_mask=False):
     return out, lin
 
 
+def mask_stitch_channels(masks, starts, perm, mag_c, binary, thres, want_mask=False):
+    """mask_stitch for a recording that keeps its channels: mag_c [C,Fin,F] -> per-source, per-channel magnitude [N,C,Fin,F]
+    (and the blended mask [N,Fin,F] with want_mask).  The mask at (n, f, t) is blended once and multiplied into the C
+    magnitudes; out[:, c] has the bits of mask_stitch(.., mag_c[c])."""
+    lib.require_gpu(masks)
+    Kw, N, Fo, W = masks.shape
+    Cc, Fin, F = mag_c.shape
+    out = _f32((N, Cc, Fin, F), mag_c)
+    lin = _f32((N, Fin, F), mag_c) if want_mask else None
+    call("avsep_mask_stitch_channels", ptr(masks), ptr(starts), ptr(perm), ptr(mag_c), Kw, N, Fo, W, Cc, Fin, F,
+         int(bool(binary)), float(thres), ptr(out), ptr(lin))
+    return out, lin
+
+
+RESAMPLE_MAX_KEPT_CHANNELS = 8     # avsep_resample_split / _join: up to 7.1
+
+
+def _resample_table_check(what, filt, up, down, device):
+    if up < 1 or down < 1:
+        raise lib.AvsepError(f"{what}: up={up} down={down}")
+    T = -(-(20 * max(up, down) + 1) // up)
+    if filt.dtype != torch.float32 or tuple(filt.shape) != (T, up) or filt.device != device:
+        raise lib.AvsepError(f"{what}: the table of {up}/{down} is float32 [{T},{up}] on {device}, got "
+                             f"{filt.dtype} {tuple(filt.shape)} on {filt.device}")
+
+
+def resample_split(pcm, filt, up, down):
+    """avsep_resample_split (include/avsep.h): interleaved int16 [L,C], 1 <= C <= 8 -> f32 [1+C, ceil(L*up/down)]: row 0 the
+    down-mix resample_poly(.., in_ch=C) gives, row 1+c channel c over 32768 through the same filter.  filt as resample_poly."""
+    if pcm.dtype != torch.int16 or pcm.dim() != 2 or not 1 <= pcm.shape[1] <= RESAMPLE_MAX_KEPT_CHANNELS:
+        raise lib.AvsepError(f"resample_split takes interleaved int16 [L,C] with 1 <= C <= {RESAMPLE_MAX_KEPT_CHANNELS}, got "
+                             f"{pcm.dtype} {tuple(pcm.shape)}")
+    lib.require_gpu(pcm)
+    lib.require_gpu(filt)
+    up, down = int(up), int(down)
+    _resample_table_check("resample_split", filt, up, down, pcm.device)
+    L, Cc = pcm.shape
+    y = torch.empty((1 + Cc, -(-L * up // down)), dtype=torch.float32, device=pcm.device)
+    call("avsep_resample_split", ptr(pcm), ptr(filt), L, Cc, up, down, ptr(y))
+    return y
+
+
+def resample_join(x, filt, up, down):
+    """avsep_resample_join (include/avsep.h): f32 [C,L], 1 <= C <= 8 -> interleaved int16 [ceil(L*up/down), C], each value
+    clip(rint(v * 32768)) of what resample_poly computes for row c (its out_s16 value).  filt as resample_poly."""
+    if x.dtype != torch.float32 or x.dim() != 2 or not 1 <= x.shape[0] <= RESAMPLE_MAX_KEPT_CHANNELS:
+        raise lib.AvsepError(f"resample_join takes float32 [C,L] with 1 <= C <= {RESAMPLE_MAX_KEPT_CHANNELS}, got "
+                             f"{x.dtype} {tuple(x.shape)}")
+    lib.require_gpu(x)
+    lib.require_gpu(filt)
+    up, down = int(up), int(down)
+    _resample_table_check("resample_join", filt, up, down, x.device)
+    Cc, L = x.shape
+    y = torch.empty((-(-L * up // down), Cc), dtype=torch.int16, device=x.device)
+    call("avsep_resample_join", ptr(x), ptr(filt), Cc, L, up, down, ptr(y))
+    return y
+
+
 def resample_poly(x, filt, up, down, in_ch=0, out_s16=False):
     """Rational polyphase resampling (avsep_resample_poly, include/avsep.h).  x: f32 [B,L] (in_ch = 0) or interleaved int16
     [L,in_ch] straight from a WAV file (one recording, down-mixed to mono while it is staged); filt: the f32 polyphase table

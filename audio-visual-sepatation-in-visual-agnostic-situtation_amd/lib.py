@@ -83,9 +83,12 @@ SIGNATURES = {
     "avsep_window_prepare": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "avsep_window_agreement": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "avsep_mask_stitch": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "avsep_mask_stitch_channels": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "avsep_localise_maps": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avsep_heatmap_overlay": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_resample_poly": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_split": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_join": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

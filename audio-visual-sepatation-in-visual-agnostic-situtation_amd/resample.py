@@ -18,6 +18,7 @@ from .lib import AvsepError
 
 MAX_RATIO = 1280       # largest up / down after reduction: 8 ... 96 kHz to and from 11 025 Hz (441/1280, 147/1280)
 MAX_CHANNELS = 256
+MAX_KEPT_CHANNELS = K.RESAMPLE_MAX_KEPT_CHANNELS      # split_pcm / join_pcm: up to 7.1
 
 _tables = {}
 
@@ -109,3 +110,31 @@ def resample_pcm(pcm, rate_in, rate_out):
     up, down = check_rates(rate_in, rate_out)
     _check_length(pcm.shape[0], up, down)
     return K.resample_poly(pcm.contiguous(), filter_table(up, down, pcm.device), up, down, pcm.shape[1], False)[0]
+
+
+def split_pcm(pcm, rate_in, rate_out):
+    """pcm: interleaved int16 [L,C] on the GPU, 1 <= C <= 8 -> f32 [1+C, Lout] at rate_out in one kernel: row 0 is
+    resample_pcm's down-mix (the network's input), row 1+c is channel c over 32768 through the same filter.  Equal rates go
+    through the kernel with the unit-impulse filter: the converted samples, bit for bit."""
+    if pcm.dtype != torch.int16 or pcm.dim() != 2:
+        raise AvsepError(f"split_pcm takes interleaved int16 [L,C], got {pcm.dtype} {tuple(pcm.shape)}")
+    if not 1 <= pcm.shape[1] <= MAX_KEPT_CHANNELS:
+        raise AvsepError(f"split_pcm keeps 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {pcm.shape[1]}")
+    up, down = check_rates(rate_in, rate_out)
+    _check_length(pcm.shape[0], up, down)
+    lib.require_gpu(pcm)
+    return K.resample_split(pcm.contiguous(), filter_table(up, down, pcm.device), up, down)
+
+
+def join_pcm(x, rate_in, rate_out):
+    """x: f32 [C,L] on the GPU, 1 <= C <= 8 -> interleaved int16 [Lout,C] at rate_out, a WAV file's frames, in one kernel:
+    column c is resample(x[c], .., out_s16=True).  Equal rates go through the kernel with the unit-impulse filter: only the
+    rounding clip(rint(x * 32768))."""
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise AvsepError(f"join_pcm takes float32 [C,L], got {x.dtype} {tuple(x.shape)}")
+    if not 1 <= x.shape[0] <= MAX_KEPT_CHANNELS:
+        raise AvsepError(f"join_pcm writes 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {x.shape[0]}")
+    up, down = check_rates(rate_in, rate_out)
+    _check_length(x.shape[1], up, down)
+    lib.require_gpu(x)
+    return K.resample_join(x.contiguous(), filter_table(up, down, x.device), up, down)

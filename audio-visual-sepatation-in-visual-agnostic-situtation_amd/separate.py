@@ -17,6 +17,10 @@ for ``use_vis=False`` the swap draw is pinned to "no swap" and consecutive windo
 CLI: ``python -m avsep_amd.separate --wav mix.wav --frames a.npy b.npy --id <experiment> --out dir`` (flag set of
 arguments.py; 16-bit PCM WAV at any rate: a file that is not at ``--audRate`` is resampled on the GPU, resample.py, and
 the sources are written at the file's rate unless ``--out_rate model``).
+
+The model is trained on mono and always sees the down-mix.  With ``channels`` (``--channels keep``) the one blended mask is
+also applied to each channel's own magnitude (``avsep_mask_stitch_channels``) and inverted with that channel's own phase,
+so a stereo file gives stereo sources.
 """
 import itertools
 import os
@@ -84,7 +88,7 @@ def _visual_features(net_frame, frames, args, Kw, batch):
     return feats
 
 
-def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False):
+def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None):
     """Separate one recording ``wav`` [L] (on the GPU, L >= args.stft_frame; several recordings: one call each).
 
     nets: (net_sound, net_frame), both in eval() — train-mode BatchNorm over the windows of one recording is never what
@@ -96,11 +100,21 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
 
     Returns {"wavs": [N, hop*(F-1)] clamped to [-1,1], "starts": list, "perms": int32 [K,N] (CPU)}; with return_masks
     also "masks" [K,N,256,256] (warped, per window, network channel order) and "lin_masks" [N,Fin,F] (blended).
+
+    channels: f32 [C, L] on wav's device, the recording's channels (``wav`` stays the network's input; nothing on the way
+    to the masks changes).  The blended mask of every source is then also multiplied into each channel's magnitude and
+    inverted with that channel's phase: the result gains "channel_wavs" [N, C, hop*(F-1)], clamped to [-1,1].
     """
     net_sound, net_frame = nets
     lib.require_gpu(wav)
     if wav.dim() != 1 or wav.numel() < args.stft_frame:
         raise AvsepError(f"separate_long takes one recording [L] with L >= stft_frame, got {tuple(wav.shape)}")
+    if channels is not None:
+        if not torch.is_tensor(channels) or channels.dtype != torch.float32 or channels.dim() != 2 or channels.shape[0] < 1 \
+                or channels.shape[1] != wav.numel() or channels.device != wav.device:
+            what = f"{channels.dtype} {tuple(channels.shape)} on {channels.device}" if torch.is_tensor(channels) else type(channels).__name__
+            raise AvsepError(f"separate_long takes channels as float32 [C,{wav.numel()}] on {wav.device} (the recording's "
+                             f"channels, as long as wav), got {what}")
     if net_sound.training or (use_vis and net_frame.training):
         raise AvsepError("separate_long needs the nets in eval(): call .eval() on both before separating")
     if use_vis:
@@ -146,7 +160,16 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
         binary = bool(args.binary_mask)
         mags, lin = K.mask_stitch(masks, starts_t, perms.to(dev), mag, binary, getattr(args, "mask_thres", 0.5), return_masks)
         wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous()).clamp_(-1.0, 1.0)
+        if channels is not None:                                         # the same masks on every channel's own STFT
+            mag_c, phase_c = plan.stft(channels.contiguous())
+            Cc, Fin, Fr = mag_c.shape
+            mags_c, _ = K.mask_stitch_channels(masks, starts_t, perms.to(dev), mag_c, binary, getattr(args, "mask_thres", 0.5))
+            channel_wavs = plan.istft(mags_c.reshape(N * Cc, Fin, Fr),
+                                      phase_c[None].expand(N, -1, -1, -1).reshape(N * Cc, Fin, Fr).contiguous())
+            channel_wavs = channel_wavs.clamp_(-1.0, 1.0).reshape(N, Cc, -1)
     out = {"wavs": wavs, "starts": starts, "perms": perms}
+    if channels is not None:
+        out["channel_wavs"] = channel_wavs
     if return_masks:
         out.update(masks=masks, lin_masks=lin)
     return out
@@ -205,6 +228,18 @@ def write_wav_pcm(path, pcm, rate):
         w.writeframes(pcm.astype("<i2", copy=False).tobytes())
 
 
+def write_wav_pcm_channels(path, pcm, rate):
+    """int16 [L, C] frames -> 16-bit PCM WAV with C channels, sample for sample (read_wav_pcm's inverse)."""
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16 or pcm.ndim != 2 or pcm.shape[1] < 1:
+        raise AvsepError(f"write_wav_pcm_channels takes int16 frames [L,C], got {pcm.dtype} {pcm.shape}")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(pcm.shape[1])
+        w.setsampwidth(2)
+        w.setframerate(int(rate))
+        w.writeframes(np.ascontiguousarray(pcm).astype("<i2", copy=False).tobytes())
+
+
 def build_parser():
     from .arguments import ArgParser
     ap = ArgParser()
@@ -215,6 +250,9 @@ def build_parser():
     p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at any sample rate (resampled to --audRate on the GPU)")
     p.add_argument("--out_rate", choices=("file", "model"), default="file",
                    help="rate of the written sources: the input file's own (default) or the model's --audRate")
+    p.add_argument("--channels", choices=("mix", "keep"), default="mix",
+                   help="mix: the sources are mono (default); keep: every source is written with the file's channels "
+                        "(the model still hears the down-mix; its masks go onto each channel)")
     p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]")
     p.add_argument("--out", default="separated", help="output directory (source<n>.wav)")
     p.add_argument("--audio_only", action="store_true", help="no frames: audio-only branch with aligned windows")
@@ -237,6 +275,7 @@ def cli(argv=None):
     args = parse_args(argv)
     from . import resample as R
     rate = wav_rate(args.wav)
+    keep = args.channels == "keep"
     if rate != args.audRate:
         try:
             R.check_rates(rate, args.audRate)
@@ -245,7 +284,14 @@ def cli(argv=None):
     if not torch.cuda.is_available():
         raise AvsepError("separation runs on an MI355X; there is no CPU fallback")
     dev = torch.device("cuda", 0)
-    if rate == args.audRate:
+    channels = None
+    if keep:                                         # one kernel: the down-mix for the network and every channel beside it
+        pcm = read_wav_pcm(args.wav)[0]
+        if pcm.shape[1] > R.MAX_KEPT_CHANNELS:
+            raise SystemExit(f"{args.wav}: --channels keep takes files of up to {R.MAX_KEPT_CHANNELS} channels, this one has {pcm.shape[1]}")
+        rows = R.split_pcm(torch.from_numpy(pcm).to(dev), rate, args.audRate)
+        wav, channels = rows[0], rows[1:]
+    elif rate == args.audRate:
         wav = torch.from_numpy(read_wav(args.wav)[0]).to(dev)
     else:                                            # the raw frames go up; down-mix, conversion and filter are one kernel
         wav = R.resample_pcm(torch.from_numpy(read_wav_pcm(args.wav)[0]).to(dev), rate, args.audRate)
@@ -263,15 +309,20 @@ def cli(argv=None):
         fr = torch.from_numpy(np.load(path)).float()
         frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
     out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
-                        stride_frames=args.window_stride, batch=args.window_batch)
+                        stride_frames=args.window_stride, batch=args.window_batch, channels=channels)
     os.makedirs(args.out, exist_ok=True)
-    if rate != args.audRate and args.out_rate == "file":
+    if keep:
+        out_rate = rate if args.out_rate == "file" else args.audRate
+        for n, cw in enumerate(out["channel_wavs"]):
+            write_wav_pcm_channels(os.path.join(args.out, f"source{n}.wav"), R.join_pcm(cw, args.audRate, out_rate).cpu().numpy(), out_rate)
+    elif rate != args.audRate and args.out_rate == "file":
         for n, w in enumerate(R.resample(out["wavs"], args.audRate, rate, out_s16=True).cpu().numpy()):
             write_wav_pcm(os.path.join(args.out, f"source{n}.wav"), w, rate)
     else:
         for n, w in enumerate(out["wavs"].cpu().numpy()):
             write_wav(os.path.join(args.out, f"source{n}.wav"), w, args.audRate)
-    print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav")
+    kept = f", {channels.shape[0]} channel{'s' if channels.shape[0] != 1 else ''} each" if keep else ""
+    print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav{kept}")
     return out
 
 

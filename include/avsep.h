@@ -439,6 +439,16 @@ int avsep_window_agreement(const float* masks, const int32_t* starts, int32_t K,
 int avsep_mask_stitch(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
                       int32_t N, int32_t Fout, int32_t W, int32_t Fin, int32_t F, int32_t binary, float thres,
                       float* out, float* mask_out, avsep_stream_t stream);
+/* avsep_mask_stitch for a recording that keeps its C channels (the model hears their down-mix; its masks are functions of
+ * (source, bin, frame) only): mag is [C, Fin, F], one magnitude per channel, and
+ *   out[n,c,f,t] = mag[c,f,t] * (binary ? (M[n,f,t] > thres) : M[n,f,t]),
+ * with M blended once per (n, f, t) by the code avsep_mask_stitch runs: out[:, c] and mask_out are bit for bit what
+ * avsep_mask_stitch gives for mag[c].  out: [N, C, Fin, F], the layout avsep_istft takes as N*C rows; mask_out (optional, may
+ * be null): [N, Fin, F].  C <= 65535; offsets are formed in 64 bits ([N, C, Fin, F] passes 2^31 elements on a multi-hour
+ * recording). */
+int avsep_mask_stitch_channels(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
+                               int32_t N, int32_t Fout, int32_t W, int32_t C, int32_t Fin, int32_t F, int32_t binary,
+                               float thres, float* out, float* mask_out, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Sound-source localisation over a clip (csrc/localise.hip): T video frames against the K windows of one recording.
@@ -496,6 +506,19 @@ int avsep_heatmap_overlay(const float* maps, const float* const* frames, const u
  * ------------------------------------------------------------------------- */
 int avsep_resample_poly(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down, int32_t in_ch,
                         int32_t out_s16, void* y, avsep_stream_t stream);
+/* The two ends of a pipeline that keeps a file's channels apart, 1 <= C <= 8 (up to 7.1); filter table, limits and the
+ * per-output arithmetic are avsep_resample_poly's (one chain per output, its order a function of (up, down, j) only), so
+ * every value below is bit for bit the value avsep_resample_poly gives for the same row.
+ * avsep_resample_split: x is interleaved int16 [L, C]; y is f32 [1 + C, Lout].  Row 0 is the down-mix, what
+ *   avsep_resample_poly(in_ch = C) gives; row 1 + c is channel c over 32768 (exact), what avsep_resample_poly(in_ch = 0)
+ *   gives for that channel as an f32 row.  One pass over the file: no de-interleaved copy of it exists.
+ * avsep_resample_join: x is f32 [C, L]; y is interleaved int16 [Lout, C], y[j, c] = clip(rint(v * 32768), -32768, 32767) of
+ *   the value v avsep_resample_poly gives row c (its out_s16 output, transposed).  A workgroup makes all C channels of its
+ *   frames and stores them as whole frames, contiguously. */
+int avsep_resample_split(const int16_t* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, float* y,
+                         avsep_stream_t stream);
+int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int16_t* y,
+                        avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.

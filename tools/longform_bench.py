@@ -6,8 +6,12 @@ STFT, window prepare, visual trunk, U-Net, agreement (+ host alignment), stitch 
 separate_long call wrapped in device synchronisations; (2) avsep_window_prepare and avsep_mask_stitch alone: time,
 algorithmic bytes, bytes/s against the 8 TB/s HBM peak, and the same result composed from the older entry points
 (gathered slices + K.warp + log; K.warp(.., 0) on every window + a torch cross-fade), outputs compared.
+With --channels C (C >= 1) also (3) the audio-visual call with the recording's C channels kept (separate_long(channels=...)):
+wall time and stage split, the stages of the channel path (second STFT, stitch_channels, iSTFT over N*C rows) next to the
+mono ones; and avsep_mask_stitch_channels alone against C launches of avsep_mask_stitch on the same magnitudes, outputs
+compared bit for bit.
 Every number is a median over --reps runs after warm-up; the last line is one JSON object.
-Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20]"""
+Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20] [--channels C]"""
 import argparse
 import json
 import os
@@ -47,14 +51,19 @@ class StageClock:
         self._undo = []
 
     def wrap(self, owner, attr, stage):
+        """stage: a name, or a list of names for the first, second, ... call (the last one for every later call)."""
         fn = getattr(owner, attr)
+        names = [stage] if isinstance(stage, str) else list(stage)
+        calls = [0]
 
         def timed(*a, **kw):
+            name = names[min(calls[0], len(names) - 1)]
+            calls[0] += 1
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             r = fn(*a, **kw)
             torch.cuda.synchronize()
-            self.ms[stage] = self.ms.get(stage, 0.0) + (time.perf_counter() - t0) * 1e3
+            self.ms[name] = self.ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
             return r
         had = attr in vars(owner)
         self._undo.append((owner, attr, fn, had))
@@ -69,11 +78,13 @@ class StageClock:
         self._undo = []
 
 
-def staged_run(nets, wav, frames, args, use_vis, stride, batch):
+def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None):
     K = P.kernels
     clk = StageClock()
-    clk.wrap(K.Stft, "stft", "stft")
-    clk.wrap(K.Stft, "istft", "istft")
+    # with channels the second call of each transform is the channel path's: C rows in, N*C rows out
+    clk.wrap(K.Stft, "stft", "stft" if channels is None else ["stft", "stft_channels"])
+    clk.wrap(K.Stft, "istft", "istft" if channels is None else ["istft", "istft_channels"])
+    clk.wrap(K, "mask_stitch_channels", "stitch_channels")
     clk.wrap(K, "window_prepare", "window_prepare")
     clk.wrap(K, "window_agreement", "agreement")
     clk.wrap(S, "align_permutations", "agreement")
@@ -83,7 +94,7 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch):
     try:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels)
         torch.cuda.synchronize()
         total = (time.perf_counter() - t0) * 1e3
     finally:
@@ -93,17 +104,17 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch):
     return clk.ms
 
 
-def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps):
+def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps, channels=None):
     """Median wall time of the unwrapped call, and the median per-stage split of wrapped calls."""
     def once():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3
     once()                                                               # warm-up: code objects, conv plans
     wall = statistics.median(once() for _ in range(reps))
-    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch) for _ in range(reps)]
+    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch, channels) for _ in range(reps)]
     split = {k: statistics.median(s.get(k, 0.0) for s in splits) for k in splits[0]}
     return wall, split
 
@@ -165,6 +176,28 @@ def kernel_rows(mag, starts_t, masks, perm, args, reps):
     return rows
 
 
+def channel_stitch_row(mag_c, starts_t, masks, perm, args, reps):
+    """avsep_mask_stitch_channels on mag_c [C,Fin,F] against C launches of avsep_mask_stitch (stacked: what the caller would
+    have to do for the [N,C,Fin,F] layout one iSTFT takes; and the launches alone, without the stack)."""
+    K = P.kernels
+    Cc, Fin, F = mag_c.shape
+    Kw, N, Fo, W = masks.shape
+    binary, thres = bool(args.binary_mask), args.mask_thres
+    rows = [mag_c[c].contiguous() for c in range(Cc)]
+
+    def launches():
+        return [K.mask_stitch(masks, starts_t, perm, m, binary, thres)[0] for m in rows]
+    a = K.mask_stitch_channels(masks, starts_t, perm, mag_c, binary, thres)[0]
+    same = bool(torch.equal(a, torch.stack(launches(), 1)))
+    nbytes = 4 * (Kw * N * Fo * W + Cc * Fin * F + N * Cc * Fin * F) + 4 * (Kw + Kw * N)
+    ms_f = median_ms(lambda: K.mask_stitch_channels(masks, starts_t, perm, mag_c, binary, thres), reps)
+    ms_l = median_ms(launches, reps)
+    ms_s = median_ms(lambda: torch.stack(launches(), 1), reps)
+    return {"channels": Cc, "fused_ms": ms_f, "launches_ms": ms_l, "launches_stacked_ms": ms_s, "algorithmic_bytes": nbytes,
+            "fused_bytes_per_s": nbytes / (ms_f * 1e-3), "share_of_hbm_peak": nbytes / (ms_f * 1e-3) / HBM_PEAK,
+            "launches_over_fused": ms_l / ms_f, "bit_identical_to_launches": same}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=600.0)
@@ -173,6 +206,7 @@ def main():
     ap.add_argument("--stride", type=int, default=128)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--frame-size", type=int, default=224)
+    ap.add_argument("--channels", type=int, default=0, help="also measure the call that keeps C channels (0: skip)")
     o = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("longform_bench measures on an MI355X; there is nothing to report without one")
@@ -196,6 +230,15 @@ def main():
         print(f"{name.upper()}: {wall:9.1f} ms for {audio_s:.0f} s of audio = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
         for k, v in split.items():
             print(f"    {k:16s} {v:9.2f} ms", flush=True)
+    if o.channels > 0:
+        gains = torch.linspace(1.0, 0.5, o.channels, device=dev)[:, None]
+        ch = (wav[None] * gains).contiguous()                             # C channels of the recording, as long as wav
+        wall, split = whole_runs(nets, wav, frames, args, True, o.stride, o.batch, o.reps, channels=ch)
+        result["av_channels"] = {"channels": o.channels, "wall_ms": wall, "audio_seconds_per_second": audio_s / (wall * 1e-3),
+                                 "split_ms": split}
+        print(f"AV, {o.channels} channels kept: {wall:9.1f} ms = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
+        for k, v in split.items():
+            print(f"    {k:16s} {v:9.2f} ms", flush=True)
     with torch.no_grad():
         mag = P.kernels.Stft(dev, args.stft_frame, args.stft_hop, "reflect").stft(wav[None], want_phase=False)[0][0].contiguous()
         starts = S.plan_windows(mag.shape[1], o.stride)
@@ -204,7 +247,16 @@ def main():
         perm = torch.arange(args.num_mix, dtype=torch.int32, device=dev).repeat(len(starts), 1)
         result["frames"], result["windows"] = mag.shape[1], len(starts)
         result["kernels"] = kernel_rows(mag, starts_t, masks, perm, args, o.kernel_reps)
+        if o.channels > 0:
+            mag_c = (mag[None] * gains[:, :, None]).contiguous()
+            r = result["kernels"]["mask_stitch_channels"] = channel_stitch_row(mag_c, starts_t, masks, perm, args, o.kernel_reps)
+            print(f"mask_stitch_channels C={o.channels}: {r['fused_ms']:.3f} ms ({r['fused_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
+                  f"{100 * r['share_of_hbm_peak']:.0f}% of 8 TB/s); {o.channels} launches of mask_stitch {r['launches_ms']:.3f} ms "
+                  f"({r['launches_over_fused']:.2f} x; stacked to [N,C,Fin,F] {r['launches_stacked_ms']:.3f} ms); "
+                  f"bit-identical {r['bit_identical_to_launches']}", flush=True)
     for k, r in result["kernels"].items():
+        if k == "mask_stitch_channels":
+            continue
         if "composed_ms" in r:
             print(f"{k}: fused {r['fused_ms']:.3f} ms ({r['fused_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
                   f"{100 * r['share_of_hbm_peak']:.0f}% of 8 TB/s), composed {r['composed_ms']:.3f} ms "

@@ -10,6 +10,11 @@ Prints and writes to --out (default profiles/resample_bench.json):
 (3) the `separate` command line's stages on a ten-minute 48 kHz mono file with the full-size model (train_MUSIC flags:
     unet7 + resnet18dilated, fp32): read, upload, resample in, separate_long, resample out, download, write — each
     bracketed by device synchronisations, median of --cli-reps — and the share of the wall time each resample takes.
+(4) the two ends of `--channels keep` on a 48 kHz stereo file: avsep_resample_split (PCM -> down-mix + 2 channels at 11 025)
+    and avsep_resample_join (2 channels at 11 025 -> 48 kHz interleaved int16), each against the same result composed from
+    the older entry points on the device — resample_pcm for the down-mix, a de-interleave to f32 rows and one batched
+    resample for the channels; resample(out_s16) and a transpose back to interleaved frames — outputs compared bit for bit,
+    in the same process, alternating.
 The last line is one JSON object.
 Usage: python tools/resample_bench.py [--seconds 600] [--reps 20] [--cpu-reps 3] [--cli-reps 3] [--out FILE]"""
 import argparse
@@ -92,6 +97,39 @@ def kernel_cases(seconds, dev, reps, cpu_reps):
     return cases
 
 
+def channel_cases(seconds, dev, reps, rate=48000, channels=2):
+    """split and join against their compositions from resample_pcm / resample and torch copies."""
+    rng = np.random.default_rng(2)
+    pcm = torch.from_numpy(rng.integers(-20000, 20000, size=(int(seconds * rate), channels)).astype(np.int16)).to(dev)
+    x = torch.from_numpy((rng.random((channels, int(seconds * MODEL_RATE)), dtype=np.float32) * 2 - 1) * 0.5).to(dev)
+
+    def split_composed():
+        rows = (pcm.t().contiguous().float() / 32768.0)                                   # de-interleave: [C, L] f32
+        return torch.cat([RS.resample_pcm(pcm, rate, MODEL_RATE)[None], RS.resample(rows, rate, MODEL_RATE)])
+
+    def join_composed():
+        return RS.resample(x, MODEL_RATE, rate, out_s16=True).t().contiguous()
+    out = {}
+    for name, fused, composed, src in (("split_pcm_stereo_48000_to_11025", lambda: RS.split_pcm(pcm, rate, MODEL_RATE), split_composed, pcm),
+                                       ("join_stereo_11025_to_48000_s16", lambda: RS.join_pcm(x, MODEL_RATE, rate), join_composed, x)):
+        a, b = fused(), composed()
+        up, down = RS.rational(rate, MODEL_RATE) if src is pcm else RS.rational(MODEL_RATE, rate)
+        nbytes = src.numel() * src.element_size() + a.numel() * a.element_size() + RS.filter_table(up, down, dev).numel() * 4
+        ms_f, ms_c = [], []
+        for _ in range(3):                                                            # alternate the two variants
+            ms_f.append(median_ms(fused, reps))
+            ms_c.append(median_ms(composed, reps))
+        ms_f, ms_c = statistics.median(ms_f), statistics.median(ms_c)
+        out[name] = {"up": up, "down": down, "channels": channels, "kernel_ms": ms_f, "composed_ms": ms_c,
+                     "composed_over_kernel": ms_c / ms_f, "algorithmic_bytes": nbytes, "bytes_per_s": nbytes / (ms_f * 1e-3),
+                     "share_of_hbm_peak": nbytes / (ms_f * 1e-3) / HBM_PEAK, "bit_identical_to_composed": bool(torch.equal(a, b))}
+        c = out[name]
+        print(f"{name}: {up}/{down}, kernel {ms_f:.3f} ms ({c['bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
+              f"{100 * c['share_of_hbm_peak']:.1f}% of 8 TB/s), composed {ms_c:.3f} ms ({ms_c / ms_f:.2f} x), "
+              f"bit-identical {c['bit_identical_to_composed']}", flush=True)
+    return out
+
+
 def cli_stages(seconds, dev, reps, frame_size=224):
     """The stages of separate.cli on a 48 kHz mono file, timed one by one (each ends in a device synchronise)."""
     args = P.arguments.train_music_args()
@@ -148,6 +186,7 @@ def main():
     dev = torch.device("cuda", 0)
     result = {"seconds": o.seconds, "kernel_reps": o.reps, "cpu_reps": o.cpu_reps, "cpu_threads": torch.get_num_threads(),
               "kernels": kernel_cases(o.seconds, dev, o.reps, o.cpu_reps),
+              "channels": channel_cases(o.seconds, dev, o.reps),
               "separate_cli": cli_stages(o.seconds, dev, o.cli_reps),
               "command": "python tools/resample_bench.py"}
     with open(o.out, "w") as f:
