@@ -11,6 +11,7 @@
 //   stem tail            max-pool 3x3/s2 over relu(bn(y0)) and its fused backward  vision_net.py:111-117
 //   space-to-depth of the frames straight into a one-block B16 image
 #include "common.h"
+#include "conv_families.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 

@@ -11,8 +11,8 @@
 // Both operands are staged global -> registers -> LDS (K-major, double buffered, one barrier
 // per K-tile); each wave owns a (BM/WM)x(BN/WN) block of 32x32 MFMA tiles.
 #include "common.h"
+#include "conv_families.h"
 #include <stdio.h>
-#include <string.h>
 
 enum { M_FWD = 0, M_DGRAD = 1, M_WGRAD = 2 };
 
@@ -580,85 +580,6 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const float* __restric
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// direct.hip: VALU kernels for convolutions with <= 4 output channels (3x3, stride 1)
-bool smallco_applicable(const avsep_conv_desc* d);
-int smallco_fwd(const avsep_conv_desc* d, const float* wp, int wp_ld, const float* bias, float* y, hipStream_t st);
-size_t smallco_wgrad_workspace_floats(const avsep_conv_desc* d);
-int smallco_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* dbias, float* ws, hipStream_t st);
-bool head_applicable(const avsep_conv_desc* d);
-int head_fwd(const avsep_conv_desc* d, const float* wp, int wp_ld, const float* bias, float* y, float* ws, hipStream_t st);
-size_t head_fwd_workspace_floats(const avsep_conv_desc* d);
-size_t head_dgrad_workspace_floats(const avsep_conv_desc* d);
-size_t head_wgrad_workspace_floats(const avsep_conv_desc* d);
-int head_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* dbias, float* ws, hipStream_t st);
-int head_dgrad(const avsep_conv_desc* d, const float* w, const float* dy, float* g0, float* g1, const float* mean1,
-               const float* invstd1, double* bstats1, int acc0, float* ws, hipStream_t st);
-bool smallci_applicable(const avsep_conv_desc* d);
-int smallci_dgrad(const avsep_conv_desc* d, const float* w_oihw, const float* dy, float* dx, hipStream_t st);
-// conv_wino.hip: Winograd F(2x2, 3x3) form of the 3x3 / stride 1 / 'same' convs (forward and dgrad), fp32
-// conv_wino4.hip: Winograd F(4x4, 3x3) for the maps that tile by 4 (asked before F(2x2, 3x3))
-bool w4_applicable(const avsep_conv_desc* d, int mode);
-size_t w4_packed_floats(const avsep_conv_desc* d, int mode);
-int w4_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st);
-int w4_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* y, double* stats, hipStream_t st);
-int w4_dgrad(const avsep_conv_desc* d, const float* up, const float* dy, float* dx, const avsep_act_bwd* e, hipStream_t st);
-void w4_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap);
-bool wn_applicable(const avsep_conv_desc* d, int mode);
-size_t wn_packed_floats(const avsep_conv_desc* d, int mode);
-int wn_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st);
-int wn_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* y, double* stats, hipStream_t st);
-int wn_dgrad(const avsep_conv_desc* d, const float* up, const float* dy, float* dx, hipStream_t st);
-// conv3x3.hip: LDS-halo-patch kernel for 3x3 / stride 1 / pad 1 (forward, and dgrad through flipped weights)
-bool c3_applicable(const avsep_conv_desc* d, int mode);
-size_t c3_packed_floats(const avsep_conv_desc* d, int mode);
-int c3_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st);
-int c3_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, hipStream_t st);
-int c3_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, hipStream_t st);
-bool w3_applicable(const avsep_conv_desc* d);
-// wgrad_wino.hip: Winograd form of the 3x3 / stride 1 weight gradient, fp32
-// wgrad_wino4.hip: Winograd F(4x4, 3x3) weight gradient (asked before the F(2x2) form)
-bool x4_applicable(const avsep_conv_desc* d);
-size_t x4_workspace_floats(const avsep_conv_desc* d);
-int x4_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st);
-void x4_variant(const avsep_conv_desc* d, char* buf, size_t cap);
-bool ww_applicable(const avsep_conv_desc* d);
-size_t ww_workspace_floats(const avsep_conv_desc* d);
-int ww_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st);
-bool w4d_applicable(const avsep_conv_desc* d);      // 4x4 / stride 2 on the same skeleton (direct form)
-size_t w4d_workspace_floats(const avsep_conv_desc* d);
-int w4d_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st);
-bool c4_applicable(const avsep_conv_desc* d, int mode);
-size_t c4_packed_floats(const avsep_conv_desc* d, int mode);
-int c4_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st);
-int c4_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, hipStream_t st);
-int c4_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, hipStream_t st);
-// conv_misc.hip: 3x3/s2 and 1x1 convolutions of the visual trunk on the halo-patch kernel (fp32)
-bool cm_applicable(const avsep_conv_desc* d, int mode);
-size_t cm_packed_floats(const avsep_conv_desc* d, int mode);
-int cm_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st);
-int cm_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, hipStream_t st);
-int cm_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, hipStream_t st);
-size_t w3_workspace_floats(const avsep_conv_desc* d);
-// conv_bf16.hip: bf16-operand halo-patch kernels (desc.prec == AVSEP_PREC_BF16)
-bool bf_applicable(const avsep_conv_desc* d, int mode);
-size_t bf_workspace_bytes(const avsep_conv_desc* d, int mode);
-size_t bf_packed_floats(const avsep_conv_desc* d, int mode);
-int bf_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st);
-int bf_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, void* ws, size_t ws_bytes,
-           hipStream_t st);
-int bf_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, void* ws, size_t ws_bytes, hipStream_t st);
-bool bf_out_b16(const avsep_conv_desc* d, int mode);
-// wgrad_b16.hip: bf16 weight gradient over B16 images (transposed LDS reads)
-bool wbn_applicable(const avsep_conv_desc* d);
-size_t wbn_workspace_floats(const avsep_conv_desc* d);
-int wbn_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st);
-void wbn_variant(const avsep_conv_desc* d, char* buf, size_t cap);
-int b16_channel_sum(const void* x, int N, int C, int HW, double* acc, float* out, hipStream_t st);   // b16.hip
-int w3_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st);
-// wgrad_smallci.hip
-bool scw_applicable(const avsep_conv_desc* d);
-size_t scw_workspace_floats(const avsep_conv_desc* d);
-int scw_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st);
 static int check_desc(const avsep_conv_desc* d, bool fwd_only = false) {
   if (!d || !d->x0) return AVSEP_ERR_ARG;
   if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->H <= 0 || d->W <= 0) return AVSEP_ERR_ARG;
@@ -691,61 +612,34 @@ static CArgs make_args(const avsep_conv_desc* d) {
   return a;
 }
 
+// split-K combines, shared with the other conv files
+int splitk_combine(const float* ws, long long slab, int S, const avsep_conv_desc* d, const float* bias, float* y, double* stats,
+                   hipStream_t st) {
+  int chunks = min(cdiv(1024, d->Cout), d->N);
+  if (chunks < 1) chunks = 1;
+  hipLaunchKernelGGL(splitk_combine_kernel, dim3(d->Cout, chunks), dim3(256), 0, st, ws, slab, S, d->N, d->Cout, d->Ho * d->Wo,
+                     bias, y, stats);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+int reduce_slabs_strided(const float* ws, float* out, long long n, int S, long long stride, hipStream_t st) {
+  return launch_reduce_slabs(ws, out, n, S, stride, st);
+}
+int reduce_slabs(const float* ws, float* out, long long n, int S, hipStream_t st) { return launch_reduce_slabs(ws, out, n, S, n, st); }
+
+// ---------------------------------------------------------------------------
+// the im2col family (igemm): serves every descriptor, so it closes each route table
+// ---------------------------------------------------------------------------
 static inline int packed_rows(const avsep_conv_desc* d, int mode) {
   return mode == 0 ? roundup(d->Cin * d->KH * d->KW, 32) : roundup(d->KH * d->KW * d->Cout, 32);
 }
-static inline int packed_ld(const avsep_conv_desc* d, int mode) { return roundup(mode == 0 ? d->Cout : d->Cin, 128); }
-
-static bool wgrad_takes_b16(const avsep_conv_desc* d) {
-  return !smallco_applicable(d) && !head_applicable(d) && wbn_applicable(d);
-}
-extern "C" int avsep_conv_io_formats(const avsep_conv_desc* d, int32_t mode, int32_t* in_fmt, int32_t* out_b16) {
-  if (!in_fmt || !out_b16 || mode < 0 || mode > 2) return AVSEP_ERR_ARG;
-  int rc = check_desc(d, mode == 0);
-  if (rc) return rc;
-  *in_fmt = AVSEP_FMT_F32;
-  *out_b16 = 0;
-  if (mode == 0) {
-    if (!smallco_applicable(d) && !head_applicable(d) && bf_applicable(d, 0)) { *in_fmt = AVSEP_FMT_B16; *out_b16 = bf_out_b16(d, 0); }
-  } else if (mode == 1) {
-    if (!smallci_applicable(d) && !head_applicable(d) && bf_applicable(d, 1)) { *in_fmt = AVSEP_FMT_B16; *out_b16 = bf_out_b16(d, 1); }
-  } else if (wgrad_takes_b16(d)) {
-    *in_fmt = AVSEP_FMT_B16;
-  }
-  return AVSEP_OK;
-}
-
-extern "C" size_t avsep_conv_packed_floats(const avsep_conv_desc* d, int mode) {
-  if (!d || (mode != 0 && mode != 1)) return 0;
-  if (mode == 1 && smallci_applicable(d)) return (size_t)d->Cout * d->Cin * d->KH * d->KW;   // OIHW as is
-  if (bf_applicable(d, mode)) return bf_packed_floats(d, mode);
-  if (w4_applicable(d, mode)) return w4_packed_floats(d, mode);
-  if (wn_applicable(d, mode)) return wn_packed_floats(d, mode);
-  if (c3_applicable(d, mode)) return c3_packed_floats(d, mode);
-  if (c4_applicable(d, mode)) return c4_packed_floats(d, mode);
-  if (cm_applicable(d, mode)) return cm_packed_floats(d, mode);
-  return (size_t)packed_rows(d, mode) * packed_ld(d, mode);
-}
-
-extern "C" int avsep_conv_pack_weights(const avsep_conv_desc* d, const float* w, float* packed, int mode,
-                                       avsep_stream_t stream) {
-  if (!d || !w || !packed || (mode != 0 && mode != 1)) return AVSEP_ERR_ARG;
-  if (mode == 1 && smallci_applicable(d)) {
-    if (hipMemcpyAsync(packed, w, (size_t)d->Cout * d->Cin * d->KH * d->KW * sizeof(float), hipMemcpyDeviceToDevice,
-                       (hipStream_t)stream) != hipSuccess)
-      return AVSEP_ERR_LAUNCH;
-    return AVSEP_OK;
-  }
-  if (bf_applicable(d, mode)) return bf_pack(d, w, packed, mode, (hipStream_t)stream);
-  if (w4_applicable(d, mode)) return w4_pack(d, w, packed, mode, (hipStream_t)stream);
-  if (wn_applicable(d, mode)) return wn_pack(d, w, packed, mode, (hipStream_t)stream);
-  if (c3_applicable(d, mode)) return c3_pack(d, w, packed, mode, (hipStream_t)stream);
-  if (c4_applicable(d, mode)) return c4_pack(d, w, packed, mode, (hipStream_t)stream);
-  if (cm_applicable(d, mode)) return cm_pack(d, w, packed, mode, (hipStream_t)stream);
-  int rows = packed_rows(d, mode), ld = packed_ld(d, mode);
+static bool igemm_applicable(const avsep_conv_desc*, int) { return true; }
+static size_t igemm_packed_floats(const avsep_conv_desc* d, int mode) { return (size_t)packed_rows(d, mode) * igemm_packed_ld(d, mode); }
+static int igemm_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st) {
+  int rows = packed_rows(d, mode), ld = igemm_packed_ld(d, mode);
   long long total = (long long)rows * ld;
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, packed,
-                     d->Cout, d->Cin, d->KH, d->KW, rows, ld, mode);
+  hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w, packed, d->Cout, d->Cin, d->KH, d->KW,
+                     rows, ld, mode);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -770,10 +664,6 @@ static SplitPlan splitk_plan(long long tiles, int K) {
   if (p.splits < 2) { p.splits = 1; p.kts = 0; }
   return p;
 }
-static bool fwd_uses_igemm(const avsep_conv_desc* d, const double* stats) {
-  return !((!stats && (smallco_applicable(d) || head_applicable(d))) || bf_applicable(d, 0) || w4_applicable(d, 0) || wn_applicable(d, 0) ||
-           c3_applicable(d, 0) || c4_applicable(d, 0) || cm_applicable(d, 0));
-}
 // the im2col kernel's tile size and split-K are decided on the planned batch (plan_desc), like every launch heuristic
 static bool fwd_big(const avsep_conv_desc* d) { return use_big(d->Cout, (long long)plan_batch(d) * d->Ho * d->Wo); }
 static bool dgrad_big(const avsep_conv_desc* d) {
@@ -794,69 +684,50 @@ static SplitPlan dgrad_split(const avsep_conv_desc* d) {
   int taps = cdiv(d->KH, s) * cdiv(d->KW, s);               // taps of the fullest parity class
   return splitk_plan(tiles, taps * d->Cout);
 }
-
-// split-K combines, shared with conv_bf16.hip
-int splitk_combine(const float* ws, long long slab, int S, const avsep_conv_desc* d, const float* bias, float* y, double* stats,
-                   hipStream_t st) {
-  int chunks = min(cdiv(1024, d->Cout), d->N);
-  if (chunks < 1) chunks = 1;
-  hipLaunchKernelGGL(splitk_combine_kernel, dim3(d->Cout, chunks), dim3(256), 0, st, ws, slab, S, d->N, d->Cout, d->Ho * d->Wo,
-                     bias, y, stats);
-  AVSEP_LAUNCH_CHECK();
-  return AVSEP_OK;
-}
-int reduce_slabs_strided(const float* ws, float* out, long long n, int S, long long stride, hipStream_t st) {
-  return launch_reduce_slabs(ws, out, n, S, stride, st);
-}
-int reduce_slabs(const float* ws, float* out, long long n, int S, hipStream_t st) { return launch_reduce_slabs(ws, out, n, S, n, st); }
-
-static size_t fwd_workspace_no_head(const avsep_conv_desc* d) {
-  if (!check_desc(d, true) && bf_applicable(d, 0)) return bf_workspace_bytes(d, 0);
-  if (check_desc(d, true) || !fwd_uses_igemm(d, (const double*)1)) return 0;
-  SplitPlan p = fwd_split(d);
-  return p.splits > 1 ? (size_t)p.splits * d->N * d->Cout * d->Ho * d->Wo * sizeof(float) : 0;
-}
-extern "C" size_t avsep_conv2d_fwd_workspace_bytes(const avsep_conv_desc* d) {
-  size_t need = fwd_workspace_no_head(d);
-  if (!check_desc(d, true) && head_applicable(d)) {      // the head kernels serve the call without statistics: cover both
-    const size_t h = head_fwd_workspace_floats(d) * sizeof(float);
-    if (h > need) need = h;
-  }
-  return need;
-}
-extern "C" size_t avsep_conv2d_dgrad_workspace_bytes(const avsep_conv_desc* d) {
-  if (!check_desc(d) && !smallci_applicable(d) && bf_applicable(d, 1)) return bf_workspace_bytes(d, 1);
-  if (check_desc(d) || bf_applicable(d, 1) || w4_applicable(d, 1) || wn_applicable(d, 1) || c3_applicable(d, 1) || smallci_applicable(d) || c4_applicable(d, 1) ||
-      cm_applicable(d, 1))
-    return 0;
-  SplitPlan p = dgrad_split(d);
-  return p.splits > 1 ? (size_t)p.splits * d->N * d->Cin * d->H * d->W * sizeof(float) : 0;
+struct WgradPlan {
+  bool big;
+  int splits, chunk, tiles;
+};
+static WgradPlan wgrad_plan(const avsep_conv_desc* d) {
+  WgradPlan p;
+  int M = d->Cout, Kc = d->Cin * d->KH * d->KW;
+  long long P = (long long)d->N * d->Ho * d->Wo;
+  p.big = M > 64 && Kc > 64;
+  int bm = p.big ? 128 : 64;
+  p.tiles = cdiv(M, bm) * cdiv(Kc, bm);
+  int want = cdiv(1024, p.tiles);                       // aim for ~1024 workgroups
+  long long maxs = (P + 255) / 256;                      // at least 256 pixels per split
+  int splits = (int)((want < maxs) ? want : maxs);
+  if (splits < 1) splits = 1;
+  long long chunk = (P + splits - 1) / splits;
+  chunk = (chunk + 31) / 32 * 32;
+  p.chunk = (int)chunk;
+  p.splits = (int)((P + chunk - 1) / chunk);
+  return p;
 }
 
-extern "C" int avsep_conv2d_fwd(const avsep_conv_desc* d, const float* w_packed, const float* bias, float* y,
-                                double* stats, void* workspace, size_t workspace_bytes, avsep_stream_t stream) {
-  int rc = check_desc(d, true);
-  if (rc) return rc;
-  if (!w_packed || !y) return AVSEP_ERR_ARG;
-  if (!stats && smallco_applicable(d)) return smallco_fwd(d, w_packed, packed_ld(d, 0), bias, y, (hipStream_t)stream);
-  if (!stats && head_applicable(d)) {
-    if (!workspace || workspace_bytes < head_fwd_workspace_floats(d) * sizeof(float)) return AVSEP_ERR_WORKSPACE;
-    return head_fwd(d, w_packed, packed_ld(d, 0), bias, y, (float*)workspace, (hipStream_t)stream);
-  }
-  if (bf_applicable(d, 0)) return bf_fwd(d, w_packed, bias, y, stats, workspace, workspace_bytes, (hipStream_t)stream);
-  if (w4_applicable(d, 0)) return w4_fwd(d, w_packed, bias, y, stats, (hipStream_t)stream);
-  if (wn_applicable(d, 0)) return wn_fwd(d, w_packed, bias, y, stats, (hipStream_t)stream);
-  if (c3_applicable(d, 0)) return c3_fwd(d, w_packed, bias, y, stats, (hipStream_t)stream);
-  if (c4_applicable(d, 0)) return c4_fwd(d, w_packed, bias, y, stats, (hipStream_t)stream);
-  if (cm_applicable(d, 0)) return cm_fwd(d, w_packed, bias, y, stats, (hipStream_t)stream);
+static size_t igemm_workspace_bytes(const avsep_conv_desc* d, int mode) {   // the split-K slabs
+  const int S = mode == 0 ? fwd_split(d).splits : mode == 1 ? dgrad_split(d).splits : wgrad_plan(d).splits;
+  if (S <= 1) return 0;
+  if (mode == 0) return (size_t)S * d->N * d->Cout * d->Ho * d->Wo * sizeof(float);
+  if (mode == 1) return (size_t)S * d->N * d->Cin * d->H * d->W * sizeof(float);
+  return (size_t)S * d->Cout * d->Cin * d->KH * d->KW * sizeof(float);
+}
+static void igemm_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap) {
+  if (mode == 0) snprintf(buf, cap, "BM%d,split%d", fwd_big(d) ? 128 : 64, fwd_split(d).splits);
+  else if (mode == 1) snprintf(buf, cap, "BM%d,split%d", dgrad_big(d) ? 128 : 64, dgrad_split(d).splits);
+}
+
+static int igemm_fwd(const avsep_conv_desc* d, const float* w_packed, const float* bias, float* y, double* stats, void* workspace,
+                     size_t workspace_bytes, hipStream_t st) {
   CArgs a = make_args(d);
-  a.wp = w_packed; a.wp_ld = packed_ld(d, 0); a.out = y; a.bias = bias; a.stats = stats;
+  a.wp = w_packed; a.wp_ld = igemm_packed_ld(d, 0); a.out = y; a.bias = bias; a.stats = stats;
   a.M = d->Cout; a.K = d->Cin * d->KH * d->KW;
   long long ncols = (long long)d->N * d->Ho * d->Wo;
   if (ncols > 0x7fffffffLL) return AVSEP_ERR_ARG;
   a.Ncols = (int)ncols;
-  hipStream_t st = (hipStream_t)stream;
   SplitPlan sp = fwd_split(d);
+  // too little workspace: unsplit.  Asked of the size the caller was told (both routes of the descriptor), not of this family's
   if (sp.splits > 1 && (!workspace || workspace_bytes < avsep_conv2d_fwd_workspace_bytes(d))) sp = SplitPlan{1, 0};
   if (sp.splits > 1) {
     a.kts = sp.kts;
@@ -873,39 +744,21 @@ extern "C" int avsep_conv2d_fwd(const avsep_conv_desc* d, const float* w_packed,
     else hipLaunchKernelGGL((igemm_kernel<M_FWD, 64, 64, 16, 2, 2, false>), dim3(a.gridM * cdiv(ncols, 64), sp.splits), dim3(256), 0, st, a);
   }
   AVSEP_LAUNCH_CHECK();
-  if (sp.splits > 1) {
-    int chunks = min(cdiv(1024, d->Cout), d->N);
-    if (chunks < 1) chunks = 1;
-    hipLaunchKernelGGL(splitk_combine_kernel, dim3(d->Cout, chunks), dim3(256), 0, st, (const float*)workspace, a.slab,
-                       sp.splits, d->N, d->Cout, d->Ho * d->Wo, bias, y, stats);
-    AVSEP_LAUNCH_CHECK();
-  }
-  return AVSEP_OK;
+  return sp.splits > 1 ? splitk_combine((const float*)workspace, a.slab, sp.splits, d, bias, y, stats, st) : AVSEP_OK;
 }
 
-extern "C" int avsep_conv2d_dgrad(const avsep_conv_desc* d, const float* w_packed_dgrad, const float* dy, float* dx,
-                                  void* workspace, size_t workspace_bytes, avsep_stream_t stream) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!w_packed_dgrad || !dy || !dx) return AVSEP_ERR_ARG;
-  if (smallci_applicable(d)) return smallci_dgrad(d, w_packed_dgrad, dy, dx, (hipStream_t)stream);
-  if (bf_applicable(d, 1)) return bf_dgrad(d, w_packed_dgrad, dy, dx, workspace, workspace_bytes, (hipStream_t)stream);
-  if (w4_applicable(d, 1)) return w4_dgrad(d, w_packed_dgrad, dy, dx, nullptr, (hipStream_t)stream);
-  if (wn_applicable(d, 1)) return wn_dgrad(d, w_packed_dgrad, dy, dx, (hipStream_t)stream);
-  if (c3_applicable(d, 1)) return c3_dgrad(d, w_packed_dgrad, dy, dx, (hipStream_t)stream);
-  if (c4_applicable(d, 1)) return c4_dgrad(d, w_packed_dgrad, dy, dx, (hipStream_t)stream);
-  if (cm_applicable(d, 1)) return cm_dgrad(d, w_packed_dgrad, dy, dx, (hipStream_t)stream);
+static int igemm_dgrad(const avsep_conv_desc* d, const float* w_packed_dgrad, const float* dy, float* dx, const avsep_act_bwd*,
+                       void* workspace, size_t workspace_bytes, hipStream_t st) {
   CArgs a = make_args(d);
-  a.wp = w_packed_dgrad; a.wp_ld = packed_ld(d, 1); a.dy = dy; a.out = dx;
+  a.wp = w_packed_dgrad; a.wp_ld = igemm_packed_ld(d, 1); a.dy = dy; a.out = dx;
   a.M = d->Cin;
   const int s = d->stride;
   if (s != 1 && s != 2 && s != 4) return AVSEP_ERR_ARG;
   a.lstride = s == 1 ? 0 : (s == 2 ? 1 : 2);
   long long ncols = (long long)d->N * cdiv(d->H, s) * cdiv(d->W, s);  // largest parity class
   if ((long long)d->N * d->H * d->W > 0x7fffffffLL) return AVSEP_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
   SplitPlan sp = dgrad_split(d);
-  if (sp.splits > 1 && (!workspace || workspace_bytes < avsep_conv2d_dgrad_workspace_bytes(d))) sp = SplitPlan{1, 0};
+  if (sp.splits > 1 && (!workspace || workspace_bytes < igemm_workspace_bytes(d, 1))) sp = SplitPlan{1, 0};
   if (sp.splits > 1) {
     a.kts = sp.kts;
     a.slab = (long long)d->N * d->Cin * d->H * d->W;
@@ -929,105 +782,15 @@ extern "C" int avsep_conv2d_dgrad(const avsep_conv_desc* d, const float* w_packe
   return AVSEP_OK;
 }
 
-struct WgradPlan {
-  bool big;
-  int splits, chunk, tiles;
-};
-static WgradPlan wgrad_plan(const avsep_conv_desc* d) {
-  WgradPlan p;
-  int M = d->Cout, Kc = d->Cin * d->KH * d->KW;
-  long long P = (long long)d->N * d->Ho * d->Wo;
-  p.big = M > 64 && Kc > 64;
-  int bm = p.big ? 128 : 64;
-  p.tiles = cdiv(M, bm) * cdiv(Kc, bm);
-  int want = cdiv(1024, p.tiles);                       // aim for ~1024 workgroups
-  long long maxs = (P + 255) / 256;                      // at least 256 pixels per split
-  int splits = (int)((want < maxs) ? want : maxs);
-  if (splits < 1) splits = 1;
-  long long chunk = (P + splits - 1) / splits;
-  chunk = (chunk + 31) / 32 * 32;
-  p.chunk = (int)chunk;
-  p.splits = (int)((P + chunk - 1) / chunk);
-  return p;
-}
-
-// the data gradient through the activation in front of the conv's input (include/avsep.h): in the F(4x4) Winograd kernel's
-// epilogue, else as the two launches it stands for
-static bool dgrad_act_fused(const avsep_conv_desc* d) {
-  return !smallci_applicable(d) && !bf_applicable(d, 1) && w4_applicable(d, 1);
-}
-extern "C" int32_t avsep_conv2d_dgrad_act_fused(const avsep_conv_desc* d) { return (!check_desc(d) && dgrad_act_fused(d)) ? 1 : 0; }
-extern "C" int avsep_conv2d_dgrad_act(const avsep_conv_desc* d, const float* w_packed_dgrad, const float* dy,
-                                      const avsep_act_bwd* e, float* dx, void* workspace, size_t workspace_bytes,
-                                      avsep_stream_t stream) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!w_packed_dgrad || !dy || !dx || !e || !e->y) return AVSEP_ERR_ARG;
-  if (d->dxfmt != AVSEP_FMT_F32) return AVSEP_ERR_ARG;
-  if ((e->scale == nullptr) != (e->shift == nullptr) || (e->res_scale == nullptr) != (e->res_shift == nullptr) ||
-      (e->res_scale && !e->residual) || (e->bstats && (!e->mean || !e->invstd)))
-    return AVSEP_ERR_ARG;
-  if (e->act != AVSEP_ACT_NONE && e->act != AVSEP_ACT_RELU && e->act != AVSEP_ACT_LRELU02) return AVSEP_ERR_ARG;
-  if (dgrad_act_fused(d)) return w4_dgrad(d, w_packed_dgrad, dy, dx, e, (hipStream_t)stream);
-  rc = avsep_conv2d_dgrad(d, w_packed_dgrad, dy, dx, workspace, workspace_bytes, stream);
-  if (rc) return rc;
-  return avsep_affine_act_bwd(dx, e->dz2, e->y, e->scale, e->shift, e->residual, e->res_scale, e->res_shift, e->add, e->mean,
-                              e->invstd, e->act, d->N, d->Cin, d->H * d->W, dx, e->bstats, stream);
-}
-
-extern "C" size_t avsep_conv2d_wgrad_workspace_bytes(const avsep_conv_desc* d) {
-  if (check_desc(d)) return 0;
-  if (smallco_applicable(d)) return smallco_wgrad_workspace_floats(d) * sizeof(float);
-  if (head_applicable(d)) return head_wgrad_workspace_floats(d) * sizeof(float);
-  if (wbn_applicable(d)) return wbn_workspace_floats(d) * sizeof(float) + (size_t)2 * d->Cout * sizeof(double);
-  if (x4_applicable(d)) return x4_workspace_floats(d) * sizeof(float);
-  if (ww_applicable(d)) return ww_workspace_floats(d) * sizeof(float);
-  if (w4d_applicable(d)) return w4d_workspace_floats(d) * sizeof(float);
-  if (w3_applicable(d)) return w3_workspace_floats(d) * sizeof(float);
-  if (scw_applicable(d)) return scw_workspace_floats(d) * sizeof(float);
+static int igemm_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float*, float* ws, hipStream_t st) {
   WgradPlan p = wgrad_plan(d);
-  if (p.splits <= 1) return 0;
-  return (size_t)p.splits * d->Cout * d->Cin * d->KH * d->KW * sizeof(float);
-}
-
-extern "C" int avsep_conv2d_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* dbias, void* workspace,
-                                  size_t workspace_bytes, avsep_stream_t stream) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!dy || !dw) return AVSEP_ERR_ARG;
-  WgradPlan p = wgrad_plan(d);
-  size_t need = avsep_conv2d_wgrad_workspace_bytes(d);
-  if (need > workspace_bytes || (need && !workspace)) return AVSEP_ERR_WORKSPACE;
-  if (smallco_applicable(d)) return smallco_wgrad(d, dy, dw, dbias, (float*)workspace, (hipStream_t)stream);
-  if (head_applicable(d)) return head_wgrad(d, dy, dw, dbias, (float*)workspace, (hipStream_t)stream);
-  if (wbn_applicable(d)) {
-    int rcw = wbn_wgrad(d, dy, dw, (float*)workspace, (hipStream_t)stream);
-    if (rcw || !dbias) return rcw;
-    double* acc = reinterpret_cast<double*>((float*)workspace + wbn_workspace_floats(d));   // behind the slabs (8-byte aligned: slab sizes are multiples of 64*64)
-    return b16_channel_sum(dy, d->N, d->Cout, d->Ho * d->Wo, acc, dbias, (hipStream_t)stream);
-  }
-  if (x4_applicable(d) || ww_applicable(d) || w4d_applicable(d) || w3_applicable(d) || scw_applicable(d)) {
-    int rc3 = x4_applicable(d) ? x4_wgrad(d, dy, dw, (float*)workspace, (hipStream_t)stream)
-              : ww_applicable(d) ? ww_wgrad(d, dy, dw, (float*)workspace, (hipStream_t)stream)
-              : w4d_applicable(d) ? w4d_wgrad(d, dy, dw, (float*)workspace, (hipStream_t)stream)
-              : w3_applicable(d) ? w3_wgrad(d, dy, dw, (float*)workspace, (hipStream_t)stream)
-                                 : scw_wgrad(d, dy, dw, (float*)workspace, (hipStream_t)stream);
-    if (rc3) return rc3;
-    if (dbias) {
-      hipLaunchKernelGGL(channel_sum_kernel, dim3(d->Cout), dim3(256), 0, (hipStream_t)stream, dy, d->N, d->Cout,
-                         d->Ho * d->Wo, dbias);
-      AVSEP_LAUNCH_CHECK();
-    }
-    return AVSEP_OK;
-  }
   CArgs a = make_args(d);
   a.dy = dy;
   a.M = d->Cout; a.Ncols = d->Cin * d->KH * d->KW; a.K = 0;
   long long P = (long long)d->N * d->Ho * d->Wo;
   if (P > 0x7fffffffLL) return AVSEP_ERR_ARG;
   a.P = (int)P; a.chunk = p.chunk;
-  a.out = (p.splits > 1) ? (float*)workspace : dw;
-  hipStream_t st = (hipStream_t)stream;
+  a.out = (p.splits > 1) ? ws : dw;
   if (p.big) {
     a.gridM = cdiv(a.M, 128);
     if (d->up2x) hipLaunchKernelGGL((igemm_kernel<M_WGRAD, 128, 128, 32, 2, 2, true>), dim3(a.gridM * cdiv(a.Ncols, 128), p.splits), dim3(256), 0, st, a);
@@ -1040,69 +803,193 @@ extern "C" int avsep_conv2d_wgrad(const avsep_conv_desc* d, const float* dy, flo
   AVSEP_LAUNCH_CHECK();
   if (p.splits > 1) {
     long long n = (long long)a.M * a.Ncols;
-    hipLaunchKernelGGL(reduce_slabs_kernel<64>, dim3(cdiv(n, 64)), dim3(256), 0, st, (const float*)workspace, dw, n, p.splits, n);
-    AVSEP_LAUNCH_CHECK();
-  }
-  if (dbias) {
-    hipLaunchKernelGGL(channel_sum_kernel, dim3(d->Cout), dim3(256), 0, st, dy, d->N, d->Cout, d->Ho * d->Wo, dbias);
+    hipLaunchKernelGGL(reduce_slabs_kernel<64>, dim3(cdiv(n, 64)), dim3(256), 0, st, (const float*)ws, dw, n, p.splits, n);
     AVSEP_LAUNCH_CHECK();
   }
   return AVSEP_OK;
 }
 
-extern "C" const char* avsep_conv_kernel_name(const avsep_conv_desc* d, int32_t mode, int32_t with_stats) {
-  if (check_desc(d, mode == 0)) return "invalid";
-  if (mode == 0) {
-    if (!with_stats && smallco_applicable(d)) return "smallco_fwd";
-    if (!with_stats && head_applicable(d)) return "head_fwd_kernel";
-    if (bf_applicable(d, 0)) return "convbf_kernel";
-    if (w4_applicable(d, 0)) return "wino4_kernel";
-    if (wn_applicable(d, 0)) return "wino_kernel";
-    if (c3_applicable(d, 0) || c4_applicable(d, 0) || cm_applicable(d, 0)) return "conv3x3_kernel";
-    return "igemm_kernel<fwd>";
-  }
-  if (mode == 1) {
-    if (head_applicable(d)) return "head_dgrad_kernel";
-    if (smallci_applicable(d)) return "smallci_dgrad";
-    if (bf_applicable(d, 1)) return "convbf_kernel";
-    if (w4_applicable(d, 1)) return "wino4_kernel";
-    if (wn_applicable(d, 1)) return "wino_kernel";
-    if (c3_applicable(d, 1) || c4_applicable(d, 1) || cm_applicable(d, 1)) return "conv3x3_kernel";
-    return "igemm_kernel<dgrad>";
-  }
-  if (smallco_applicable(d)) return "smallco_wgrad";
-  if (head_applicable(d)) return "head_wgrad_kernel";
-  if (wbn_applicable(d)) return "wgradb_kernel";
-  if (x4_applicable(d)) return "winow4_kernel";
-  if (ww_applicable(d)) return "winow_kernel";
-  if (w4d_applicable(d)) return "wgrad4d_kernel";
-  if (w3_applicable(d)) return "wgrad3x3_kernel";
-  if (scw_applicable(d)) return "smallci_wgrad_kernel";
-  return "igemm_kernel<wgrad>";
+// ---------------------------------------------------------------------------
+// routes: which family serves a call.  The three tables below are the ONLY place where the order of the families exists:
+// the first applicable entry of the mode's table launches the call, and every query about the call (formats, packed image,
+// workspace, name, variant) reads the slots of that same entry.
+// ---------------------------------------------------------------------------
+enum ConvFamily { /* forward, data gradient: */ SMALLCO, HEAD, SMALLCI, BF, W4, WN, C3, C4, CM, IGEMM,
+                  /* weight gradient:        */ G_SMALLCO, G_HEAD, G_WBN, G_X4, G_WW, G_W4D, G_W3, G_SCW, G_IGEMM };
+struct ConvEntry {
+  ConvFamily fam, image;     // image: the family whose packed weight image the launch reads
+  bool stats_free;           // serves forward calls without BatchNorm statistics only
+  const char* name;
+  conv_applicable_fn* applicable;
+  conv_workspace_fn* workspace;
+  conv_variant_fn* variant;
+  conv_packed_floats_fn* packed_floats;
+  conv_pack_fn* pack;
+  conv_fwd_fn* fwd;          // the launch slot: the one of the table's mode is set
+  conv_dgrad_fn* dgrad;
+  conv_wgrad_fn* wgrad;
+};
+// slots a family leaves empty
+#define NO_WORKSPACE(p) static size_t p##_workspace_bytes(const avsep_conv_desc*, int) { return 0; }
+#define NO_VARIANT(p) static void p##_variant(const avsep_conv_desc*, int, char*, size_t) {}
+NO_WORKSPACE(smallci) NO_WORKSPACE(w4) NO_WORKSPACE(wn) NO_WORKSPACE(c3) NO_WORKSPACE(c4) NO_WORKSPACE(cm)
+NO_VARIANT(smallco) NO_VARIANT(head) NO_VARIANT(smallci) NO_VARIANT(wn) NO_VARIANT(ww) NO_VARIANT(w4d) NO_VARIANT(w3) NO_VARIANT(scw)
+// an entry takes every slot from ONE prefix
+#define SLOTS(p) p##_applicable, p##_workspace_bytes, p##_variant
+#define FWD(F, p, name) {F, F, false, name, SLOTS(p), p##_packed_floats, p##_pack, p##_fwd, nullptr, nullptr}
+// the few-output-channel forward kernels read the im2col family's [k][Cout] image and leave statistics to the other route
+#define FWD_STATS_FREE(F, p, name) {F, IGEMM, true, name, SLOTS(p), nullptr, nullptr, p##_fwd, nullptr, nullptr}
+#define DGRAD(F, p, name) {F, F, false, name, SLOTS(p), p##_packed_floats, p##_pack, nullptr, p##_dgrad, nullptr}
+#define WGRAD(F, p, name) {F, F, false, name, SLOTS(p), nullptr, nullptr, nullptr, nullptr, p##_wgrad}
+static const ConvEntry FWD_TABLE[] = {
+    FWD_STATS_FREE(SMALLCO, smallco, "smallco_fwd"), FWD_STATS_FREE(HEAD, head, "head_fwd_kernel"),
+    FWD(BF, bf, "convbf_kernel"), FWD(W4, w4, "wino4_kernel"), FWD(WN, wn, "wino_kernel"), FWD(C3, c3, "conv3x3_kernel"),
+    FWD(C4, c4, "conv3x3_kernel"), FWD(CM, cm, "conv3x3_kernel"), FWD(IGEMM, igemm, "igemm_kernel<fwd>")};
+static const ConvEntry DGRAD_TABLE[] = {
+    DGRAD(SMALLCI, smallci, "smallci_dgrad"), DGRAD(BF, bf, "convbf_kernel"), DGRAD(W4, w4, "wino4_kernel"),
+    DGRAD(WN, wn, "wino_kernel"), DGRAD(C3, c3, "conv3x3_kernel"), DGRAD(C4, c4, "conv3x3_kernel"),
+    DGRAD(CM, cm, "conv3x3_kernel"), DGRAD(IGEMM, igemm, "igemm_kernel<dgrad>")};
+static const ConvEntry WGRAD_TABLE[] = {
+    WGRAD(G_SMALLCO, smallco, "smallco_wgrad"), WGRAD(G_HEAD, head, "head_wgrad_kernel"), WGRAD(G_WBN, wbn, "wgradb_kernel"),
+    WGRAD(G_X4, x4, "winow4_kernel"), WGRAD(G_WW, ww, "winow_kernel"), WGRAD(G_W4D, w4d, "wgrad4d_kernel"),
+    WGRAD(G_W3, w3, "wgrad3x3_kernel"), WGRAD(G_SCW, scw, "smallci_wgrad_kernel"), WGRAD(G_IGEMM, igemm, "igemm_kernel<wgrad>")};
+
+struct ConvRoute { const ConvEntry* run; const ConvEntry* pack; };   // the entry that launches; the entry whose weight image it reads
+// The route of a call of `mode` over a valid descriptor.  A forward descriptor has two routes, with and without statistics,
+// and ONE packed weight image: AVSEP_ERR_ARG if the two would not read the same image.
+static int conv_route(const avsep_conv_desc* d, int mode, bool with_stats, ConvRoute* r) {
+  const ConvEntry* table = mode == 0 ? FWD_TABLE : mode == 1 ? DGRAD_TABLE : WGRAD_TABLE;
+  const ConvEntry* e = table;
+  while (!e->applicable(d, mode)) ++e;          // ends at the im2col entry at the latest
+  const ConvEntry* s = e;                        // the same walk past the entries that take no statistics
+  while (s->stats_free) do ++s; while (!s->applicable(d, mode));
+  if (s->image != e->image) return AVSEP_ERR_ARG;
+  r->run = with_stats ? s : e;
+  for (r->pack = table; r->pack->fam != r->run->image;) ++r->pack;
+  return AVSEP_OK;
 }
 
-void bf_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap);      // conv_bf16.hip
-void c3_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap);      // conv3x3.hip
-void c4_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap);
-void cm_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap);      // conv_misc.hip
+extern "C" int avsep_conv_io_formats(const avsep_conv_desc* d, int32_t mode, int32_t* in_fmt, int32_t* out_b16) {
+  if (!in_fmt || !out_b16 || mode < 0 || mode > 2) return AVSEP_ERR_ARG;
+  int rc = check_desc(d, mode == 0);
+  ConvRoute r;
+  if (rc || (rc = conv_route(d, mode, false, &r))) return rc;
+  *in_fmt = (r.run->fam == BF || r.run->fam == G_WBN) ? AVSEP_FMT_B16 : AVSEP_FMT_F32;
+  *out_b16 = r.run->fam == BF ? bf_out_b16(d, mode) : 0;
+  return AVSEP_OK;
+}
 
+extern "C" size_t avsep_conv_packed_floats(const avsep_conv_desc* d, int mode) {
+  ConvRoute r;
+  if (!d || (mode != 0 && mode != 1) || conv_route(d, mode, true, &r)) return 0;
+  return r.pack->packed_floats(d, mode);
+}
+
+extern "C" int avsep_conv_pack_weights(const avsep_conv_desc* d, const float* w, float* packed, int mode,
+                                       avsep_stream_t stream) {
+  if (!d || !w || !packed || (mode != 0 && mode != 1)) return AVSEP_ERR_ARG;
+  ConvRoute r;
+  int rc = conv_route(d, mode, true, &r);
+  return rc ? rc : r.pack->pack(d, w, packed, mode, (hipStream_t)stream);
+}
+
+// the workspace of the run entry of a call; 0 for a descriptor no call accepts
+static size_t route_workspace(const avsep_conv_desc* d, int mode, bool with_stats) {
+  ConvRoute r;
+  return (check_desc(d, mode == 0) || conv_route(d, mode, with_stats, &r)) ? 0 : r.run->workspace(d, mode);
+}
+extern "C" size_t avsep_conv2d_fwd_workspace_bytes(const avsep_conv_desc* d) {   // covers both routes of the descriptor
+  return max(route_workspace(d, 0, true), route_workspace(d, 0, false));
+}
+extern "C" size_t avsep_conv2d_dgrad_workspace_bytes(const avsep_conv_desc* d) { return route_workspace(d, 1, false); }
+extern "C" size_t avsep_conv2d_wgrad_workspace_bytes(const avsep_conv_desc* d) { return route_workspace(d, 2, false); }
+
+extern "C" int avsep_conv2d_fwd(const avsep_conv_desc* d, const float* w_packed, const float* bias, float* y,
+                                double* stats, void* workspace, size_t workspace_bytes, avsep_stream_t stream) {
+  int rc = check_desc(d, true);
+  if (rc) return rc;
+  if (!w_packed || !y) return AVSEP_ERR_ARG;
+  ConvRoute r;
+  if ((rc = conv_route(d, 0, stats != nullptr, &r))) return rc;
+  return r.run->fwd(d, w_packed, bias, y, stats, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int avsep_conv2d_dgrad(const avsep_conv_desc* d, const float* w_packed_dgrad, const float* dy, float* dx,
+                                  void* workspace, size_t workspace_bytes, avsep_stream_t stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  if (!w_packed_dgrad || !dy || !dx) return AVSEP_ERR_ARG;
+  ConvRoute r;
+  if ((rc = conv_route(d, 1, false, &r))) return rc;
+  return r.run->dgrad(d, w_packed_dgrad, dy, dx, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// the data gradient through the activation in front of the conv's input (include/avsep.h): in the F(4x4) Winograd kernel's
+// epilogue, else as the two launches it stands for
+extern "C" int32_t avsep_conv2d_dgrad_act_fused(const avsep_conv_desc* d) {
+  ConvRoute r;
+  return (!check_desc(d) && !conv_route(d, 1, false, &r) && r.run->fam == W4) ? 1 : 0;
+}
+extern "C" int avsep_conv2d_dgrad_act(const avsep_conv_desc* d, const float* w_packed_dgrad, const float* dy,
+                                      const avsep_act_bwd* e, float* dx, void* workspace, size_t workspace_bytes,
+                                      avsep_stream_t stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  if (!w_packed_dgrad || !dy || !dx || !e || !e->y) return AVSEP_ERR_ARG;
+  if (d->dxfmt != AVSEP_FMT_F32) return AVSEP_ERR_ARG;
+  if ((e->scale == nullptr) != (e->shift == nullptr) || (e->res_scale == nullptr) != (e->res_shift == nullptr) ||
+      (e->res_scale && !e->residual) || (e->bstats && (!e->mean || !e->invstd)))
+    return AVSEP_ERR_ARG;
+  if (e->act != AVSEP_ACT_NONE && e->act != AVSEP_ACT_RELU && e->act != AVSEP_ACT_LRELU02) return AVSEP_ERR_ARG;
+  ConvRoute r;
+  if ((rc = conv_route(d, 1, false, &r))) return rc;
+  if (r.run->fam == W4) return r.run->dgrad(d, w_packed_dgrad, dy, dx, e, workspace, workspace_bytes, (hipStream_t)stream);
+  rc = avsep_conv2d_dgrad(d, w_packed_dgrad, dy, dx, workspace, workspace_bytes, stream);
+  if (rc) return rc;
+  return avsep_affine_act_bwd(dx, e->dz2, e->y, e->scale, e->shift, e->residual, e->res_scale, e->res_shift, e->add, e->mean,
+                              e->invstd, e->act, d->N, d->Cin, d->H * d->W, dx, e->bstats, stream);
+}
+
+extern "C" int avsep_conv2d_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* dbias, void* workspace,
+                                  size_t workspace_bytes, avsep_stream_t stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  if (!dy || !dw) return AVSEP_ERR_ARG;
+  ConvRoute r;
+  if ((rc = conv_route(d, 2, false, &r))) return rc;
+  const ConvFamily fam = r.run->fam;
+  const size_t need = r.run->workspace(d, 2);
+  if (need > workspace_bytes || (need && !workspace)) return AVSEP_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  rc = r.run->wgrad(d, dy, dw, dbias, (float*)workspace, st);
+  if (rc || !dbias || fam == G_SMALLCO || fam == G_HEAD) return rc;   // those two sum dbias themselves
+  if (fam == G_WBN)   // dy is a B16 image; the accumulators are the last 2 * Cout doubles of the family's workspace
+    return b16_channel_sum(dy, d->N, d->Cout, d->Ho * d->Wo, (double*)((char*)workspace + need) - 2 * d->Cout, dbias, st);
+  hipLaunchKernelGGL(channel_sum_kernel, dim3(d->Cout), dim3(256), 0, st, dy, d->N, d->Cout, d->Ho * d->Wo, dbias);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+// the name a call is reported under, and its entry (null where no slot of the tables stands behind the name)
+static const char* reported_name(const avsep_conv_desc* d, int mode, bool with_stats, const ConvEntry** run) {
+  ConvRoute r;
+  *run = nullptr;
+  if (check_desc(d, mode == 0) || conv_route(d, mode, with_stats, &r)) return "invalid";
+  // a head descriptor's data gradient is the separate entry point avsep_conv2d_dgrad_up2x; callers read its kernel's name here
+  if (mode == 1 && head_applicable(d, mode)) return "head_dgrad_kernel";
+  *run = r.run;
+  return r.run->name;
+}
+extern "C" const char* avsep_conv_kernel_name(const avsep_conv_desc* d, int32_t mode, int32_t with_stats) {
+  const ConvEntry* run;
+  return reported_name(d, mode, with_stats != 0, &run);
+}
 extern "C" int avsep_conv_kernel_variant(const avsep_conv_desc* d, int32_t mode, int32_t with_stats, char* buf, size_t cap) {
   if (!buf || cap < 8) return AVSEP_ERR_ARG;
-  const char* fam = avsep_conv_kernel_name(d, mode, with_stats);
+  const ConvEntry* run;
+  const char* fam = reported_name(d, mode, with_stats != 0, &run);
   char tail[64] = "";
-  if (!strcmp(fam, "convbf_kernel")) bf_variant(d, mode, tail, sizeof(tail));
-  else if (!strcmp(fam, "wgradb_kernel")) wbn_variant(d, tail, sizeof(tail));
-  else if (!strcmp(fam, "wino4_kernel")) w4_variant(d, mode, tail, sizeof(tail));
-  else if (!strcmp(fam, "winow4_kernel")) x4_variant(d, tail, sizeof(tail));
-  else if (!strcmp(fam, "conv3x3_kernel")) {
-    if (c3_applicable(d, mode)) c3_variant(d, mode, tail, sizeof(tail));
-    else if (c4_applicable(d, mode)) c4_variant(d, mode, tail, sizeof(tail));
-    else cm_variant(d, mode, tail, sizeof(tail));
-  } else if (!strcmp(fam, "igemm_kernel<fwd>")) {
-    snprintf(tail, sizeof(tail), "BM%d,split%d", fwd_big(d) ? 128 : 64, fwd_split(d).splits);
-  } else if (!strcmp(fam, "igemm_kernel<dgrad>")) {
-    snprintf(tail, sizeof(tail), "BM%d,split%d", dgrad_big(d) ? 128 : 64, dgrad_split(d).splits);
-  }
+  if (run) run->variant(d, mode, tail, sizeof(tail));
   snprintf(buf, cap, tail[0] ? "%s:%s" : "%s", fam, tail);
   return AVSEP_OK;
 }
@@ -1112,10 +999,10 @@ extern "C" int avsep_conv_kernel_variant(const avsep_conv_desc* d, int32_t mode,
 // the two low-res sources
 // ---------------------------------------------------------------------------
 extern "C" int32_t avsep_conv2d_head_applicable(const avsep_conv_desc* d) {
-  return (check_desc(d) == AVSEP_OK && head_applicable(d)) ? 1 : 0;
+  return (check_desc(d) == AVSEP_OK && head_applicable(d, 1)) ? 1 : 0;
 }
 extern "C" size_t avsep_conv2d_dgrad_up2x_workspace_bytes(const avsep_conv_desc* d) {
-  return (check_desc(d) == AVSEP_OK && head_applicable(d)) ? head_dgrad_workspace_floats(d) * sizeof(float) : 0;
+  return (check_desc(d) == AVSEP_OK && head_applicable(d, 1)) ? head_dgrad_workspace_floats(d) * sizeof(float) : 0;
 }
 extern "C" int avsep_conv2d_dgrad_up2x(const avsep_conv_desc* d, const float* w, const float* dy, float* g0, float* g1,
                                        const float* mean1, const float* invstd1, double* bstats1, int32_t acc0,
@@ -1124,7 +1011,7 @@ extern "C" int avsep_conv2d_dgrad_up2x(const avsep_conv_desc* d, const float* w,
   if (rc) return rc;
   if (!w || !dy || (!g0 && !g1)) return AVSEP_ERR_ARG;
   if (bstats1 && (!mean1 || !invstd1 || !g1)) return AVSEP_ERR_ARG;
-  if (!head_applicable(d)) return AVSEP_ERR_ARG;   // unsupported geometry: use avsep_conv2d_dgrad + avsep_relu_up2x_bwd
+  if (!head_applicable(d, 1)) return AVSEP_ERR_ARG;   // unsupported geometry: use avsep_conv2d_dgrad + avsep_relu_up2x_bwd
   if (!workspace || workspace_bytes < head_dgrad_workspace_floats(d) * sizeof(float)) return AVSEP_ERR_WORKSPACE;
   return head_dgrad(d, w, dy, g0, g1, mean1, invstd1, bstats1, acc0, (float*)workspace, (hipStream_t)stream);
 }

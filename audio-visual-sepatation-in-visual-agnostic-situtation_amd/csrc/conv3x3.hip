@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include "halo_kernel.h"
+#include "conv_families.h"
 
 // weight packing for this path.  Rows r = ((cpair*9 + tap)*2 + parity), column = output channel.
 //   mode 0 (forward): in-channel ci = 2*cpair+parity, value w[co][ci][tap],          column co
@@ -37,8 +38,6 @@ __global__ void c3_pack_kernel(const float* __restrict__ w, float* __restrict__ 
 // ---------------------------------------------------------------------------
 // forward: needs Cin % 4 == 0 and the source split on a chunk boundary; dgrad: Cout % 4 == 0
 // conv_flat.hip: flat-pixel tiles for the small square maps of the visual trunk
-int c3_flat_width(int H, int W, int dil);
-int c3_flat_launch(C3Args& a, int dil, hipStream_t st);
 static bool c3_flat_enabled(int algo) { return !(algo & AVSEP_ALGO_NO_FLAT); }
 static bool c3_flat(const avsep_conv_desc* d) {
   return !d->up2x && d->C0 == d->Cin && c3_flat_width(d->H, d->W, d->dil) > 0 && (long long)d->N * d->H * d->W < 0x7fffffffLL &&
@@ -113,7 +112,8 @@ void c4_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap) {
   else c3_variant_text(d->Cin, d->H / 2, d->W / 2, plan_batch(d), false, false, buf, cap);     // each of the 4 parity classes
 }
 
-int c3_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, hipStream_t st) {
+int c3_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, void*, size_t,
+           hipStream_t st) {
   C3Args a{};
   a.N = d->N; a.planN = d->plan_n; a.algo = d->algo; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
   a.C0 = d->C0; a.C1 = d->Cin - d->C0; a.act0 = d->act0; a.act1 = d->act1; a.up2x = d->up2x;
@@ -126,7 +126,8 @@ int c3_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* 
 }
 
 // dX[N,Cin,H,W] = conv3x3(dY[N,Cout,H,W], flipped/transposed weights)
-int c3_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, hipStream_t st) {
+int c3_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, const avsep_act_bwd*, void*, size_t,
+             hipStream_t st) {
   C3Args a{};
   a.N = d->N; a.planN = d->plan_n; a.algo = d->algo; a.Cin = d->Cout; a.H = d->H; a.W = d->W; a.Cout = d->Cin;
   a.C0 = d->Cout; a.C1 = 0; a.Hs = d->H; a.Ws = d->W;
@@ -201,7 +202,8 @@ static int c4_launch(C3Args& a, hipStream_t st) {
   return AVSEP_OK;
 }
 
-int c4_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, hipStream_t st) {
+int c4_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, void*, size_t,
+           hipStream_t st) {
   C3Args a{};
   a.N = d->N; a.planN = d->plan_n; a.algo = d->algo; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
   a.C0 = d->C0; a.C1 = d->Cin - d->C0; a.act0 = d->act0; a.act1 = d->act1; a.up2x = 0;
@@ -213,7 +215,8 @@ int c4_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* 
 }
 
 // dX[N,Cin,H,W] from dY[N,Cout,Ho,Wo]: four 2x2-tap stride-1 convs over dY, one per input-pixel parity class
-int c4_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, hipStream_t st) {
+int c4_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, const avsep_act_bwd*, void*, size_t,
+             hipStream_t st) {
   const int ld = roundup(d->Cin, 128);
   for (int cls = 0; cls < 4; ++cls) {
     const int ph = cls >> 1, pw = cls & 1;
@@ -518,7 +521,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_kernel(W3Args a) {
     }
 }
 
-bool w3_applicable(const avsep_conv_desc* d) {
+bool w3_applicable(const avsep_conv_desc* d, int) {
   if (d->KH == 3 && d->KW == 3 && d->stride == 2 && d->dil == 1 && d->pad == 1)       // ResNet layer2.0 / layer3.0 conv1
     return !d->up2x && d->C0 == d->Cin && (d->H & 1) == 0 && (d->W & 1) == 0 && d->Wo >= 12 && (d->Wo & 1) == 0 && d->Cout > 4 &&
            d->Cin >= 32 && d->N <= 65535 && (long long)(d->Cout > d->Cin ? d->Cout : d->Cin) * d->H * d->W < 0x7fffffffLL;
@@ -548,9 +551,9 @@ static W3Plan w3_plan(const avsep_conv_desc* d) {
   p.splits = (int)((tiles + p.tps - 1) / p.tps);
   return p;
 }
-size_t w3_workspace_floats(const avsep_conv_desc* d) {
+size_t w3_workspace_bytes(const avsep_conv_desc* d, int) {
   W3Plan p = w3_plan(d);
-  return p.splits > 1 ? (size_t)p.splits * d->Cout * d->Cin * 9 : 0;
+  return p.splits > 1 ? (size_t)p.splits * d->Cout * d->Cin * 9 * sizeof(float) : 0;
 }
 // dw[cc][tap] = sum_z ws[z][tap][cc], cc = co*Cin + ci: coalesced plane reads, 36 contiguous bytes written per (co, ci).
 // Block = 4 split groups x 64 values of cc: a thread sums every 4th slab, the four partial sums meet in LDS in a fixed
@@ -585,7 +588,7 @@ int w3_reduce(const float* ws, float* dw, long long P, int splits, hipStream_t s
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
-int w3_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st) {
+int w3_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float*, float* ws, hipStream_t st) {
   W3Plan p = w3_plan(d);
   W3Args a{};
   a.N = d->N; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.Ho = d->Ho; a.Wo = d->Wo;

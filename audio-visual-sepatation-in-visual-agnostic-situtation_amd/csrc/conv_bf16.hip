@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "halo_bf16.h"
+#include "conv_families.h"
 #include "res_bf16.h"
 
 // mode 0: forward  M = Cout, k-channel = ci, value w[m][c][tap]
@@ -121,7 +122,6 @@ static long long bf_flat_wgs(int M, long long P) {
   return (long long)f.gm * cdiv(P, f.big ? 256 : 128);
 }
 
-size_t bf_workspace_bytes(const avsep_conv_desc* d, int mode);
 bool bf_applicable(const avsep_conv_desc* d, int mode) {
   if (d->prec != AVSEP_PREC_BF16 || !bf_enabled(d)) return false;
   const int cls = bf_class(d);
@@ -310,10 +310,6 @@ static int bf3_launch(C3Args& a, int dil, void* ws, size_t ws_bytes, int* splits
   if (bf_res_ok(3, 3, a.Cin, a.Cout, a.W, dil, false)) return bf_launch_res<3, 3, 4>(a, st);
   return dil == 1 ? bf_launch_rect<3, 3, 1, 1>(a, st) : bf_launch_rect<3, 3, 1, 2>(a, st);
 }
-int splitk_combine(const float* ws, long long slab, int S, const avsep_conv_desc* d, const float* bias, float* y, double* stats,
-                   hipStream_t st);                                                   // conv.hip
-int reduce_slabs(const float* ws, float* out, long long n, int S, hipStream_t st);   // conv.hip
-
 int bf_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, void* ws, size_t ws_bytes,
            hipStream_t st) {
   C3Args a{};
@@ -339,7 +335,8 @@ int bf_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* 
   }
 }
 
-int bf_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, void* ws, size_t ws_bytes, hipStream_t st) {
+int bf_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, const avsep_act_bwd*, void* ws, size_t ws_bytes,
+             hipStream_t st) {
   if (d->dyfmt != AVSEP_FMT_B16) return AVSEP_ERR_ARG;
   const int out16 = d->dxfmt == AVSEP_FMT_B16;
   if (out16 && (d->Cin % 16 != 0 || !bf_out_b16(d, 1))) return AVSEP_ERR_ARG;

@@ -4,6 +4,7 @@
 // A rectangular 8x16 tile covers a 14x14 (and a 28x28) map at 77 %, a 4x32 tile a 56x56 map at 87.5 %; the flat tile's
 // 128 MFMA columns are 128 consecutive pixels of (n, h, w), so only the last tile of the batch is partial.
 #include "halo_kernel.h"
+#include "conv_families.h"
 
 // FW if (W, dil) has a flat instantiation, else 0.  Geometry requirements are checked by the caller (c3_applicable).
 int c3_flat_width(int H, int W, int dil) {

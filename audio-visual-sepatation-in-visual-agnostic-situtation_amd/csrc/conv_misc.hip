@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "halo_kernel.h"
+#include "conv_families.h"
 
 static inline bool cm_enabled(const avsep_conv_desc* d) { return !(d->algo & AVSEP_ALGO_NO_MISC_PATCH); }
 static int cm_class(const avsep_conv_desc* d) {
@@ -90,14 +91,14 @@ static int cm_launch(C3Args& a, hipStream_t st) {
   return AVSEP_OK;
 }
 
-void c3_variant_text(int M, int Ho, int Wo, long long planN, bool flat, bool quantise, char* buf, size_t cap);   // conv3x3.hip
 void cm_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap) {
   if (mode == 0) c3_variant_text(d->Cout, d->Ho, d->Wo, plan_batch(d), false, false, buf, cap);
   else if (cm_class(d) == 1) c3_variant_text(d->Cin, d->Ho, d->Wo, plan_batch(d), false, false, buf, cap);
   else c3_variant_text(d->Cin, d->H / 2, d->W / 2, plan_batch(d), false, false, buf, cap);
 }
 
-int cm_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, hipStream_t st) {
+int cm_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double* stats, void*, size_t,
+           hipStream_t st) {
   C3Args a{};
   a.N = d->N; a.planN = d->plan_n; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
   a.C0 = d->C0; a.C1 = d->Cin - d->C0; a.act0 = d->act0; a.act1 = d->act1; a.up2x = 0;
@@ -110,7 +111,8 @@ int cm_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* 
   return d->stride == 1 ? cm_launch<1, 1, 1, 16>(a, st) : cm_launch<1, 1, 2, 16>(a, st);
 }
 
-int cm_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, hipStream_t st) {
+int cm_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, const avsep_act_bwd*, void*, size_t,
+             hipStream_t st) {
   const int ld = roundup(d->Cin, 128);
   C3Args a{};
   a.N = d->N; a.planN = d->plan_n; a.Cin = d->Cout; a.H = d->Ho; a.W = d->Wo; a.Cout = d->Cin;       // the conv runs over dY

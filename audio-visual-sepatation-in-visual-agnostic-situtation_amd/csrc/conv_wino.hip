@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_families.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -471,7 +472,8 @@ static int wn_launch(WArgs& a, const avsep_conv_desc* d, int mode, bool raw, hip
   return AVSEP_OK;
 }
 
-int wn_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* y, double* stats, hipStream_t st) {
+int wn_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* y, double* stats, void*, size_t,
+           hipStream_t st) {
   WArgs a{};
   a.N = d->N; a.C0 = d->C0; a.C1 = d->Cin - d->C0; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
   a.act0 = d->act0; a.act1 = d->act1;
@@ -482,7 +484,8 @@ int wn_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* 
 }
 
 // dX[N,Cin,H,W] = conv3x3(dY[N,Cout,H,W], flipped / transposed weights); the identity holds for any dilation with pad == dil
-int wn_dgrad(const avsep_conv_desc* d, const float* up, const float* dy, float* dx, hipStream_t st) {
+int wn_dgrad(const avsep_conv_desc* d, const float* up, const float* dy, float* dx, const avsep_act_bwd*, void*, size_t,
+             hipStream_t st) {
   WArgs a{};
   a.N = d->N; a.C0 = d->Cout; a.C1 = 0; a.Cin = d->Cout; a.H = d->H; a.W = d->W; a.Cout = d->Cin;
   a.x0 = dy; a.up = up; a.out = dx;

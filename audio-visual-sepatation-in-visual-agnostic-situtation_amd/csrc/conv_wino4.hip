@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_families.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -628,7 +629,8 @@ static int w4_launch(W4Args& a, const avsep_conv_desc* d, int mode, bool raw, hi
   return AVSEP_OK;
 }
 
-int w4_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* y, double* stats, hipStream_t st) {
+int w4_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* y, double* stats, void*, size_t,
+           hipStream_t st) {
   W4Args a{};
   a.N = d->N; a.C0 = d->C0; a.C1 = d->Cin - d->C0; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
   a.act0 = d->act0; a.act1 = d->act1;
@@ -639,7 +641,8 @@ int w4_fwd(const avsep_conv_desc* d, const float* up, const float* bias, float* 
 }
 
 // dX[N,Cin,H,W] = conv3x3(dY[N,Cout,H,W], flipped / transposed weights)
-int w4_dgrad(const avsep_conv_desc* d, const float* up, const float* dy, float* dx, const avsep_act_bwd* e, hipStream_t st) {
+int w4_dgrad(const avsep_conv_desc* d, const float* up, const float* dy, float* dx, const avsep_act_bwd* e, void*, size_t,
+             hipStream_t st) {
   W4Args a{};
   a.N = d->N; a.C0 = d->Cout; a.C1 = 0; a.Cin = d->Cout; a.H = d->H; a.W = d->W; a.Cout = d->Cin;
   a.x0 = dy; a.up = up; a.out = dx;

@@ -4,6 +4,7 @@
 // halo patch (coalesced rows), the few output channels live in registers, and the weights are read
 // through the scalar unit (wave-uniform addresses).  gfx950, wave64.
 #include "common.h"
+#include "conv_families.h"
 
 #define SC_MAXCO 4
 
@@ -298,10 +299,18 @@ __global__ __launch_bounds__(256) void k4s2_smallci_dgrad_kernel(const float* __
 // ---------------------------------------------------------------------------
 // host dispatch (called from conv.hip)
 // ---------------------------------------------------------------------------
-bool smallci_applicable(const avsep_conv_desc* d) {
+bool smallci_applicable(const avsep_conv_desc* d, int) {
   return d->Cin <= 4 && d->dil == 1 && !d->up2x && d->H <= 65535 && d->N <= 65535;
 }
-int smallci_dgrad(const avsep_conv_desc* d, const float* w_oihw, const float* dy, float* dx, hipStream_t st) {
+// the "packed" image of this family is the OIHW weight as is
+size_t smallci_packed_floats(const avsep_conv_desc* d, int) { return (size_t)d->Cout * d->Cin * d->KH * d->KW; }
+int smallci_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, hipStream_t st) {
+  if (hipMemcpyAsync(packed, w, smallci_packed_floats(d, mode) * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return AVSEP_ERR_LAUNCH;
+  return AVSEP_OK;
+}
+int smallci_dgrad(const avsep_conv_desc* d, const float* w_oihw, const float* dy, float* dx, const avsep_act_bwd*, void*, size_t,
+                  hipStream_t st) {
   if (d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad == 1 && (d->W & 7) == 0 && (d->H & 1) == 0) {
     dim3 g2(cdiv(d->W / 8, 32), cdiv(d->H / 2, 8), d->N);
     switch (d->Cin) {
@@ -328,12 +337,13 @@ int smallci_dgrad(const avsep_conv_desc* d, const float* w_oihw, const float* dy
   return AVSEP_OK;
 }
 
-bool smallco_applicable(const avsep_conv_desc* d) {
+bool smallco_applicable(const avsep_conv_desc* d, int) {
   return d->Cout <= SC_MAXCO && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dil == 1 && !d->up2x &&
          d->C0 == d->Cin && !d->scale0 && d->act0 == AVSEP_ACT_NONE && d->W <= G_WMAX && (d->W & 15) == 0 && d->N <= 65535;
 }
 
-int smallco_fwd(const avsep_conv_desc* d, const float* wp, int wp_ld, const float* bias, float* y, hipStream_t st) {
+int smallco_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double*, void*, size_t, hipStream_t st) {
+  const int wp_ld = igemm_packed_ld(d, 0);
   dim3 grid(cdiv(d->W, F_TW), cdiv(d->H, F_TH), d->N);
   switch (d->Cout) {
     case 1: hipLaunchKernelGGL(smallco_fwd_kernel<1>, grid, dim3(256), 0, st, d->x0, wp, wp_ld, bias, y, d->Cin, d->H, d->W); break;
@@ -345,8 +355,8 @@ int smallco_fwd(const avsep_conv_desc* d, const float* wp, int wp_ld, const floa
   return AVSEP_OK;
 }
 
-size_t smallco_wgrad_workspace_floats(const avsep_conv_desc* d) {
-  return (size_t)d->N * G_STRIPS * d->Cout * d->Cin * 9 + (size_t)d->N * d->Cout;
+size_t smallco_workspace_bytes(const avsep_conv_desc* d, int mode) {   // the weight gradient's partial sums
+  return mode == 2 ? ((size_t)d->N * G_STRIPS * d->Cout * d->Cin * 9 + (size_t)d->N * d->Cout) * sizeof(float) : 0;
 }
 
 int smallco_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* dbias, float* ws, hipStream_t st) {

@@ -14,6 +14,7 @@
 // HBM pass over the low-res sources.
 #include <stdlib.h>
 #include "common.h"
+#include "conv_families.h"
 
 struct HeadArgs {
   const float *x0, *x1, *sc0, *sh0, *sc1, *sh1;
@@ -455,10 +456,8 @@ __global__ __launch_bounds__(256) void head_wgrad_kernel(HeadArgs a, int KT, con
 // ---------------------------------------------------------------------------------------------------------------
 // host side (called from conv.hip)
 // ---------------------------------------------------------------------------------------------------------------
-int reduce_slabs_strided(const float* ws, float* out, long long n, int S, long long stride, hipStream_t st);   // conv.hip
-
 #define HD_MAXCO 4
-bool head_applicable(const avsep_conv_desc* d) {
+bool head_applicable(const avsep_conv_desc* d, int) {
   return d->up2x && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dil == 1 && d->Cout <= HD_MAXCO &&
          d->act0 == AVSEP_ACT_RELU && (d->C0 == d->Cin || d->act1 == AVSEP_ACT_RELU) && (d->W & 3) == 0 && (d->H & 3) == 0 &&
          d->Cin <= 256 && d->N <= 65535 && d->H / 4 <= 65535 &&
@@ -475,10 +474,13 @@ static HeadArgs head_args(const avsep_conv_desc* d) {
 static inline size_t head_planes_floats(const avsep_conv_desc* d) {       // T or S: [N][9*Cout][Hl][Wl]
   return (size_t)d->N * 9 * d->Cout * (d->H / 2) * (d->W / 2);
 }
-size_t head_fwd_workspace_floats(const avsep_conv_desc* d) { return head_planes_floats(d); }
 size_t head_dgrad_workspace_floats(const avsep_conv_desc* d) { return head_planes_floats(d); }
 
-int head_fwd(const avsep_conv_desc* d, const float* wp, int wp_ld, const float* bias, float* y, float* ws, hipStream_t st) {
+int head_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* y, double*, void* workspace, size_t ws_bytes,
+             hipStream_t st) {
+  if (!workspace || ws_bytes < head_workspace_bytes(d, 0)) return AVSEP_ERR_WORKSPACE;
+  float* ws = (float*)workspace;
+  const int wp_ld = igemm_packed_ld(d, 0);
   HeadArgs a = head_args(d);
   const long long HWl = (long long)a.Hl * a.Wl;
   const int KT = 9 * d->Cout, MT = (KT + 31) / 32, KS = (d->Cin + 15) / 16 * 8;
@@ -528,10 +530,12 @@ static int head_wgrad_segments(const avsep_conv_desc* d) {
   while (seg < 64 && waves * seg < 2048 && HWl / (2 * seg) >= 512) seg *= 2;
   return seg;
 }
-size_t head_wgrad_workspace_floats(const avsep_conv_desc* d) {
+size_t head_workspace_bytes(const avsep_conv_desc* d, int mode) {
+  if (mode == 0) return head_planes_floats(d) * sizeof(float);
+  if (mode != 2) return 0;
   const long long HWl = (long long)(d->H / 2) * (d->W / 2);
   const int SEG = head_wgrad_segments(d);
-  return head_planes_floats(d) + (size_t)d->N * SEG * d->Cout * d->Cin * 9 + (size_t)d->N * cdiv(HWl, 256) * d->Cout;
+  return (head_planes_floats(d) + (size_t)d->N * SEG * d->Cout * d->Cin * 9 + (size_t)d->N * cdiv(HWl, 256) * d->Cout) * sizeof(float);
 }
 int head_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* dbias, float* ws, hipStream_t st) {
   HeadArgs a = head_args(d);

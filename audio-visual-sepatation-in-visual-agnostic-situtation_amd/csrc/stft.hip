@@ -2,6 +2,7 @@
 // 1-D convolution of the padded waveform with the windowed DFT basis: a [2*bins x n_fft] x
 // [n_fft x frames] GEMM per row on the f32 MFMA (conv.hip), fused pad / magnitude-phase kernels.
 #include "common.h"
+#include "conv_families.h"
 
 static inline int bins_of(int n_fft) { return n_fft / 2 + 1; }
 
@@ -128,8 +129,6 @@ __global__ __launch_bounds__(256) void stft_magphase_kernel(const float* __restr
   }
 }
 
-int c1x4_stft_fwd(const float* xt, const float* wp, float* out, int R, int NH, int hop, int cout, int frames,
-                  hipStream_t st);   // conv3x3.hip
 
 // the 1x4-conv form needs n_fft <= 4 hops (librosa's default 1022/256 does), whole channel pairs and room for a tile
 static bool stft_fast(int R, int L, int n_fft, int hop) {

@@ -22,6 +22,7 @@
 // apart mod 256; stride 2: 32 B apart mod 64).
 #include <type_traits>
 #include "common.h"
+#include "conv_families.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -371,7 +372,7 @@ static int wbn_class(const avsep_conv_desc* d) {
   return 0;
 }
 static inline bool wbn_enabled(const avsep_conv_desc* d) { return !(d->algo & AVSEP_ALGO_NO_BF16_KERNELS); }
-bool wbn_applicable(const avsep_conv_desc* d) {
+bool wbn_applicable(const avsep_conv_desc* d, int) {
   if (!wbn_enabled(d) || !wbn_class(d)) return false;
   if (d->Cin % 16 || d->Cout % 16 || d->Cin < 16 || d->Cout < 16) return false;
   if (d->Wo < 8 || d->Ho < 4 || d->N > 65535) return false;
@@ -405,11 +406,12 @@ static WbPlan wbn_plan(const avsep_conv_desc* d) {
   p.splits = cdiv(p.chunks, p.per_split);
   return p;
 }
-size_t wbn_workspace_floats(const avsep_conv_desc* d) {
+// the slabs (sizes are multiples of 64*64 floats, so what follows is 8-byte aligned), then b16_channel_sum's accumulators
+size_t wbn_workspace_bytes(const avsep_conv_desc* d, int) {
   const WbPlan p = wbn_plan(d);
-  return (size_t)p.splits * d->KH * d->KW * p.CoutP * p.CinP;
+  return (size_t)p.splits * d->KH * d->KW * p.CoutP * p.CinP * sizeof(float) + (size_t)2 * d->Cout * sizeof(double);
 }
-void wbn_variant(const avsep_conv_desc* d, char* buf, size_t cap) {
+void wbn_variant(const avsep_conv_desc* d, int, char* buf, size_t cap) {
   const WbPlan p = wbn_plan(d);
   snprintf(buf, cap, "%dx%d,split%d", p.th, p.tw, p.plan_splits);
 }
@@ -429,7 +431,7 @@ static int wbn_launch(WbArgs& a, const WbPlan& p, bool raw, hipStream_t st) {
   return AVSEP_OK;
 }
 
-int wbn_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st) {
+int wbn_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float*, float* ws, hipStream_t st) {
   if (d->xfmt != AVSEP_FMT_B16 || d->dyfmt != AVSEP_FMT_B16) return AVSEP_ERR_ARG;
   const WbPlan p = wbn_plan(d);
   WbArgs a{};

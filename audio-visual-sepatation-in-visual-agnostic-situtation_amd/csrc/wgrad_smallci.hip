@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_families.h"
 
 struct ScwArgs {
   const float* x;
@@ -136,7 +137,6 @@ __global__ __launch_bounds__(256, 2) void smallci_wgrad_kernel(ScwArgs a) {
   }
 }
 
-int reduce_slabs_strided(const float* ws, float* out, long long n, int S, long long stride, hipStream_t st);   // conv.hip
 
 // ---------------------------------------------------------------------------
 // host side (called from conv.hip)
@@ -160,16 +160,16 @@ static int scw_slabs(const avsep_conv_desc* d) {
   const int want = 2 * cu_count() / cdiv(d->Cout, 64);            // two workgroups per CU
   return (int)(tiles < want ? tiles : (want < 1 ? 1 : want));
 }
-bool scw_applicable(const avsep_conv_desc* d) {
+bool scw_applicable(const avsep_conv_desc* d, int) {
   if ((d->algo & AVSEP_ALGO_NO_SMALLCI_WGRAD) || !scw_class(d)) return false;
   if ((d->W & 3) || (d->Wo & 3) || d->Wo < 8 || d->Wo > 128 || d->W > 256) return false;      // register-staged rows: ND / NX pieces per thread
   if ((long long)d->N * d->Ho > 0x7fffffffLL || d->Cout > 65535 * 64) return false;
   return scw_smem(d) <= 72 * 1024;                                 // two workgroups per CU
 }
-size_t scw_workspace_floats(const avsep_conv_desc* d) {
-  return (size_t)scw_slabs(d) * cdiv(d->Cout, 64) * 64 * d->Cin * d->KH * d->KW;
+size_t scw_workspace_bytes(const avsep_conv_desc* d, int) {
+  return (size_t)scw_slabs(d) * cdiv(d->Cout, 64) * 64 * d->Cin * d->KH * d->KW * sizeof(float);
 }
-int scw_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st) {
+int scw_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float*, float* ws, hipStream_t st) {
   ScwArgs a{};
   a.x = d->x0; a.dy = dy; a.part = ws;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.Ho = d->Ho; a.Wo = d->Wo;

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_families.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -590,7 +591,6 @@ __global__ __launch_bounds__(WW_THREADS) void wgrad4d_kernel(W4dArgs a) {
 // ---------------------------------------------------------------------------
 // host side (called from conv.hip)
 // ---------------------------------------------------------------------------
-int w3_reduce(const float* ws, float* dw, long long P, int splits, hipStream_t st);      // conv3x3.hip
 
 struct WwCfg { int gh, gw, g; };     // pixels per group, groups per chunk
 static const WwCfg WW_CFGS[4] = {{4, 16, 1}, {8, 8, 1}, {2, 16, 2}, {4, 8, 1}};     // [3]: dilation 2 (4x8 sub-pixels x both column parities)
@@ -635,7 +635,7 @@ static WwPlan ww_plan(const avsep_conv_desc* d) {
   return p;
 }
 
-bool ww_applicable(const avsep_conv_desc* d) {
+bool ww_applicable(const avsep_conv_desc* d, int) {
   const bool off = (d->algo & (AVSEP_ALGO_NO_WINOGRAD | AVSEP_ALGO_NO_WINOGRAD_WGRAD)) != 0;
   if (off || d->prec != AVSEP_PREC_F32) return false;
   if (!(d->KH == 3 && d->KW == 3 && d->stride == 1 && (d->dil == 1 || d->dil == 2) && d->pad == d->dil) || d->up2x) return false;
@@ -650,9 +650,9 @@ bool ww_applicable(const avsep_conv_desc* d) {
   const WwPlan p = ww_plan(&e);
   return (long long)p.gridM * p.gridC * p.splits >= 128 && p.nchunks >= 8;
 }
-size_t ww_workspace_floats(const avsep_conv_desc* d) {
+size_t ww_workspace_bytes(const avsep_conv_desc* d, int) {
   const WwPlan p = ww_plan(d);
-  return (size_t)p.splits * 9 * d->Cout * d->Cin;
+  return (size_t)p.splits * 9 * d->Cout * d->Cin * sizeof(float);
 }
 
 template <bool SUB, bool RAW>
@@ -668,7 +668,7 @@ static void ww_launch_cfg(const WwArgs& a, int cfg, dim3 grid, hipStream_t st) {
   }
 }
 
-int ww_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st) {
+int ww_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float*, float* ws, hipStream_t st) {
   const WwPlan p = ww_plan(d);
   WwArgs a{};
   a.N = d->N; a.C0 = d->C0; a.C1 = d->Cin - d->C0; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
@@ -714,7 +714,7 @@ static WwPlan w4d_plan(const avsep_conv_desc* d) {
   e.dil = 1;
   return ww_plan(&e);
 }
-bool w4d_applicable(const avsep_conv_desc* d) {
+bool w4d_applicable(const avsep_conv_desc* d, int) {
   const bool off = (d->algo & (AVSEP_ALGO_NO_WINOGRAD | AVSEP_ALGO_NO_WINOGRAD_WGRAD)) != 0;
   // (bf16 descriptors too: conv.hip asks the bf16 kernel first, and the maps it does not take — 8 / 4 wide at the deep
   // U-Net levels — are better off here in fp32 than on the im2col kernel: 0.31 against 0.60 ms at 512 -> 512 @ 16x16)
@@ -729,11 +729,11 @@ bool w4d_applicable(const avsep_conv_desc* d) {
   const WwPlan p = w4d_plan(&e);
   return p.cfg < 2 && (long long)p.gridM * p.gridC * p.splits >= 128 && p.nchunks >= 8;
 }
-size_t w4d_workspace_floats(const avsep_conv_desc* d) {
+size_t w4d_workspace_bytes(const avsep_conv_desc* d, int) {
   const WwPlan p = w4d_plan(d);
-  return (size_t)p.splits * 16 * d->Cout * d->Cin;
+  return (size_t)p.splits * 16 * d->Cout * d->Cin * sizeof(float);
 }
-int w4d_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st) {
+int w4d_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float*, float* ws, hipStream_t st) {
   const WwPlan p = w4d_plan(d);
   W4dArgs a{};
   a.N = d->N; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.Ho = d->Ho; a.Wo = d->Wo;

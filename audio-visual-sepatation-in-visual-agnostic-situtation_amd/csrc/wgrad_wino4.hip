@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_families.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -507,7 +508,6 @@ __global__ __launch_bounds__(X4_THREADS) void winow4_kernel(X4Args a) {
 // ---------------------------------------------------------------------------
 // host side (called from conv.hip)
 // ---------------------------------------------------------------------------
-int w3_reduce(const float* ws, float* dw, long long P, int splits, hipStream_t st);      // conv3x3.hip
 
 struct X4Plan { int ryn, rxn, nkt, kps, splits, gridM, gridC, dil, Hs, Ws, gen; };
 constexpr double X4_MIN_FILL = 0.7;             // pixels of the map / pixels of its 8x8 regions: below it the F(2x2) form wins
@@ -538,7 +538,7 @@ static bool x4_plan(const avsep_conv_desc* d, X4Plan* out) {
   return true;
 }
 
-bool x4_applicable(const avsep_conv_desc* d) {
+bool x4_applicable(const avsep_conv_desc* d, int) {
   if ((d->algo & (AVSEP_ALGO_NO_WINOGRAD | AVSEP_ALGO_NO_WINOGRAD_WGRAD | AVSEP_ALGO_NO_WINOGRAD4)) || d->prec != AVSEP_PREC_F32) return false;
   if (!(d->KH == 3 && d->KW == 3 && d->stride == 1 && (d->dil == 1 || d->dil == 2) && d->pad == d->dil) || d->up2x) return false;
   const int C1 = d->Cin - d->C0;
@@ -553,19 +553,19 @@ bool x4_applicable(const avsep_conv_desc* d) {
   if (!x4_plan(d, &q)) return false;
   return (long long)p.gridM * p.gridC * p.splits >= 128 && p.nkt >= 8;
 }
-size_t x4_workspace_floats(const avsep_conv_desc* d) {
+size_t x4_workspace_bytes(const avsep_conv_desc* d, int) {
   X4Plan p;
   if (!x4_plan(d, &p)) return 0;
-  return (size_t)p.splits * 9 * d->Cout * d->Cin;
+  return (size_t)p.splits * 9 * d->Cout * d->Cin * sizeof(float);
 }
-void x4_variant(const avsep_conv_desc* d, char* buf, size_t cap) {
+void x4_variant(const avsep_conv_desc* d, int, char* buf, size_t cap) {
   X4Plan p;
   const avsep_conv_desc e = plan_desc(d);
   if (!x4_plan(&e, &p)) { snprintf(buf, cap, "?"); return; }
   snprintf(buf, cap, "8x8%s,split%d", p.gen == 3 ? "p,dil2" : p.gen == 2 ? "e" : p.gen == 1 ? "g" : "", p.splits);
 }
 
-int x4_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float* ws, hipStream_t st) {
+int x4_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, float*, float* ws, hipStream_t st) {
   X4Plan p;
   if (!x4_plan(d, &p)) return AVSEP_ERR_ARG;
   X4Args a{};

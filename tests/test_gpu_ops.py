@@ -133,6 +133,23 @@ for _c in _rows_after((64, 64, 32, 32, 80, 4, 2, 1, 1), 3):
     EXPECT_FAMILY[_c] = {"wgrad": "wgrad4d_kernel"}
 for _c in _rows_after((3, 3, 32, 64, 72, 7, 2, 3, 1), 3) + [(2, 1, 32, 48, 24, 4, 2, 1, 1)]:
     EXPECT_FAMILY[_c] = {"wgrad": "smallci_wgrad_kernel"}
+# the routes no row exists for in particular, pinned on rows that take them: the halo-patch kernel in its three host forms
+# (3x3 / stride 1, 4x4 / stride 2, the trunk's 3x3 / stride 2 and 1x1), its weight gradient, the im2col kernel without and
+# with split-K, and the few-channel direct kernels ("fwd:nostats" is the forward call that asks for no statistics)
+_HALO = {"fwd": "conv3x3_kernel", "dgrad": "conv3x3_kernel"}
+_IM2COL = {"fwd": "igemm_kernel<fwd>", "dgrad": "igemm_kernel<dgrad>", "wgrad": "igemm_kernel<wgrad>"}
+for _c, _f in [((2, 64, 12, 40, 136, 3, 1, 1, 1), dict(_HALO, wgrad="wgrad3x3_kernel")),
+               ((3, 32, 34, 32, 64, 4, 2, 1, 1), dict(_HALO, wgrad="igemm_kernel<wgrad>")),
+               ((3, 32, 56, 56, 48, 3, 2, 1, 1), dict(_HALO, wgrad="wgrad3x3_kernel")),
+               ((3, 64, 14, 14, 144, 1, 1, 0, 1), dict(_HALO, wgrad="igemm_kernel<wgrad>")),
+               ((2, 64, 16, 16, 128, 4, 2, 1, 1), _IM2COL),
+               ((8, 512, 4, 4, 512, 4, 2, 1, 1), _IM2COL),
+               ((1, 20, 12, 16, 2, 3, 1, 1, 1), {"fwd": "igemm_kernel<fwd>", "fwd:nostats": "smallco_fwd", "wgrad": "smallco_wgrad"}),
+               ((2, 37, 21, 144, 2, 3, 1, 1, 1), {"fwd:nostats": "smallco_fwd", "wgrad": "smallco_wgrad"}),
+               ((2, 1, 32, 48, 24, 4, 2, 1, 1), {"dgrad": "smallci_dgrad"}),
+               ((2, 3, 30, 30, 64, 7, 2, 3, 1), {"dgrad": "smallci_dgrad"})]:
+    assert _c in CONV_CASES
+    EXPECT_FAMILY.setdefault(_c, {}).update(_f)
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -157,8 +174,9 @@ def _conv_case(dev, K, case):
     y_ref.backward(dy)
     xd, wd, bd, dyd = x.to(dev), w.to(dev), b.to(dev), dy.to(dev)
     cv = K.Conv(xd, Cout, k, s, p, d)
-    for mode, fam in EXPECT_FAMILY.get(case, {}).items():
-        assert cv.kernel_name(mode) == fam, (case, mode, cv.kernel_variant(mode))
+    for key, fam in EXPECT_FAMILY.get(case, {}).items():
+        mode, _, flag = key.partition(":")
+        assert cv.kernel_name(mode, with_stats=flag != "nostats") == fam, (case, key, cv.kernel_variant(mode, flag != "nostats"))
     st = K.zeros_stats(Cout, xd)
     y = cv.fwd(cv.pack(wd, 0), bd, st)
     assert_close(y, y_ref, 2e-5, "fwd")
