@@ -756,6 +756,68 @@ def mask_stitch_channels(masks, starts, perm, mag_c, binary, thres, want_mask=Fa
     return out, lin
 
 
+MWF_MAX_CHANNELS = 8     # avsep_mwf_*: C and N up to 8
+MWF_MAX_SOURCES = 8
+
+
+def _mwf_check(what, ymag, yph):
+    lib.require_gpu(ymag)
+    lib.require_gpu(yph)
+    if ymag.dim() != 4 or ymag.dtype != torch.float32 or yph.dtype != torch.float32 or yph.device != ymag.device \
+            or tuple(yph.shape) not in (tuple(ymag.shape), tuple(ymag.shape[1:])):
+        raise lib.AvsepError(f"{what} takes ymag f32 [N,C,Fin,F] and yph [C,Fin,F] (shared by the sources) or [N,C,Fin,F], got "
+                             f"{ymag.dtype} {tuple(ymag.shape)} and {yph.dtype} {tuple(yph.shape)}")
+    N, Cc, Fin, F = ymag.shape
+    if not (1 <= N <= MWF_MAX_SOURCES and 1 <= Cc <= MWF_MAX_CHANNELS and Fin >= 1 and F >= 1):
+        raise lib.AvsepError(f"{what}: 1 <= N <= {MWF_MAX_SOURCES}, 1 <= C <= {MWF_MAX_CHANNELS}, Fin, F >= 1; got {tuple(ymag.shape)}")
+    return N, Cc, Fin, F
+
+
+def _mwf_cov(ymag, yph):
+    """-> f32 [N, Fin, C, C, 2]"""
+    N, Cc, Fin, F = ymag.shape
+    nbytes = lib.load().avsep_mwf_workspace_bytes(N, Cc, Fin, F)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=ymag.device)
+    cov = _f32((N, Fin, Cc, Cc, 2), ymag)
+    call("avsep_mwf_cov", ptr(ymag), ptr(yph), int(yph.dim() == 4), N, Cc, Fin, F, ptr(cov), ptr(ws), nbytes)
+    return cov
+
+
+def _mwf_apply(xmag, xph, ymag, cov, reg):
+    N, Cc, Fin, F = ymag.shape
+    out_mag, out_ph = _f32((N, Cc, Fin, F), ymag), _f32((N, Cc, Fin, F), ymag)
+    call("avsep_mwf_apply", ptr(xmag), ptr(xph), ptr(ymag), ptr(cov), N, Cc, Fin, F, reg, ptr(out_mag), ptr(out_ph))
+    return out_mag, out_ph
+
+
+def mwf_cov(ymag, yph):
+    """Spatial covariance of every source per bin row: ymag [N,C,Fin,F], yph [C,Fin,F] (one phase for all sources) or
+    [N,C,Fin,F] -> complex64 [N,Fin,C,C], R_n[f] = sum_t Y Y^H / max(sum_t mean_c |Y|^2, FLT_MIN) (trace C, or 0 for a source
+    that is silent in the row).  Fixed summation order: the same bits on every call."""
+    _mwf_check("mwf_cov", ymag, yph)
+    return torch.view_as_complex(_mwf_cov(ymag.contiguous(), yph.contiguous()))
+
+
+def mwf(xmag, xph, ymag, yph, iterations=1, reg=1e-3):
+    """Multichannel Wiener filter (include/avsep.h): xmag, xph [C,Fin,F] the channels' STFT, ymag [N,C,Fin,F] the source
+    images' magnitudes (mask_stitch_channels), yph their phase, [C,Fin,F] shared or [N,C,Fin,F] -> (mag, phase), both
+    [N,C,Fin,F], after ``iterations`` passes (each pass re-estimates the covariances from the previous pass's output).
+    ``reg`` is relative to each bin's power: the sources sum to X / (1 + ~reg)."""
+    N, Cc, Fin, F = _mwf_check("mwf", ymag, yph)
+    lib.require_gpu(xmag)
+    lib.require_gpu(xph)
+    for name, t in (("xmag", xmag), ("xph", xph)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (Cc, Fin, F) or t.device != ymag.device:
+            raise lib.AvsepError(f"mwf takes {name} f32 [{Cc},{Fin},{F}] on {ymag.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    iterations, reg = int(iterations), float(reg)
+    if iterations < 1 or not reg >= 0.0:
+        raise lib.AvsepError(f"mwf needs iterations >= 1 and reg >= 0, got {iterations} and {reg}")
+    xmag, xph, mag, ph = xmag.contiguous(), xph.contiguous(), ymag.contiguous(), yph.contiguous()
+    for _ in range(iterations):
+        mag, ph = _mwf_apply(xmag, xph, mag, _mwf_cov(mag, ph), reg)
+    return mag, ph
+
+
 RESAMPLE_MAX_KEPT_CHANNELS = 8     # avsep_resample_split / _join: up to 7.1
 
 

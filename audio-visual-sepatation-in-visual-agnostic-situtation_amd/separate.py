@@ -20,7 +20,9 @@ the sources are written at the file's rate unless ``--out_rate model``).
 
 The model is trained on mono and always sees the down-mix.  With ``channels`` (``--channels keep``) the one blended mask is
 also applied to each channel's own magnitude (``avsep_mask_stitch_channels``) and inverted with that channel's own phase,
-so a stereo file gives stereo sources.
+so a stereo file gives stereo sources.  ``wiener=k`` (``--wiener k``) then runs k passes of a multichannel Wiener filter
+(``kernels.mwf``) over those source images: the masked channels give every source a spatial covariance per bin, and each
+time-frequency bin of the mixture is filtered again with them, so a source keeps its own place in the stereo image.
 """
 import itertools
 import os
@@ -35,6 +37,7 @@ from .lib import AvsepError
 from .models import activate
 
 WIDTH = 256        # frames per window: the tile the network is trained on
+MAX_WIENER = 8     # passes of the multichannel Wiener filter a call may ask for
 FOUT = 256         # log-frequency bins of the warped tile (inference.py:48-51)
 
 
@@ -88,7 +91,8 @@ def _visual_features(net_frame, frames, args, Kw, batch):
     return feats
 
 
-def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None):
+def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None,
+                  wiener=0):
     """Separate one recording ``wav`` [L] (on the GPU, L >= args.stft_frame; several recordings: one call each).
 
     nets: (net_sound, net_frame), both in eval() — train-mode BatchNorm over the windows of one recording is never what
@@ -104,8 +108,20 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
     channels: f32 [C, L] on wav's device, the recording's channels (``wav`` stays the network's input; nothing on the way
     to the masks changes).  The blended mask of every source is then also multiplied into each channel's magnitude and
     inverted with that channel's phase: the result gains "channel_wavs" [N, C, hop*(F-1)], clamped to [-1,1].
+
+    wiener: int in 0 ... 8, passes of the multichannel Wiener filter (``kernels.mwf``, relative regulariser 1e-3) over the
+    masked channels before their iSTFT; needs ``channels`` (C = 1 gives the single-channel Wiener gain).  0 is the path
+    above, bit for bit.  With wiener >= 1 the channel stitch uses the SOFT mask whatever ``args.binary_mask`` says: the
+    filter weighs every source by the power its mask leaves it, and a thresholded mask has thrown that posterior away.
+    Each source then gets its own phase (one iSTFT over N*C rows), and the sources of a bin sum to the mixture over
+    1 + ~1e-3, not to the mixture exactly.  The covariances are one per bin row for the whole recording (time-invariant).
+    "wavs", "perms", "masks" and "lin_masks" do not depend on ``wiener``.
     """
     net_sound, net_frame = nets
+    if isinstance(wiener, bool) or not isinstance(wiener, int) or not 0 <= wiener <= MAX_WIENER:
+        raise AvsepError(f"separate_long takes wiener as an int in 0 ... {MAX_WIENER} (passes of the multichannel Wiener filter), got {wiener!r}")
+    if wiener and channels is None:
+        raise AvsepError("separate_long(wiener=...) filters the recording's channels: pass channels= as well")
     lib.require_gpu(wav)
     if wav.dim() != 1 or wav.numel() < args.stft_frame:
         raise AvsepError(f"separate_long takes one recording [L] with L >= stft_frame, got {tuple(wav.shape)}")
@@ -163,9 +179,14 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
         if channels is not None:                                         # the same masks on every channel's own STFT
             mag_c, phase_c = plan.stft(channels.contiguous())
             Cc, Fin, Fr = mag_c.shape
-            mags_c, _ = K.mask_stitch_channels(masks, starts_t, perms.to(dev), mag_c, binary, getattr(args, "mask_thres", 0.5))
-            channel_wavs = plan.istft(mags_c.reshape(N * Cc, Fin, Fr),
-                                      phase_c[None].expand(N, -1, -1, -1).reshape(N * Cc, Fin, Fr).contiguous())
+            mags_c, _ = K.mask_stitch_channels(masks, starts_t, perms.to(dev), mag_c, binary and not wiener,
+                                               getattr(args, "mask_thres", 0.5))
+            if wiener:                                                   # soft source images in, one phase per source out
+                mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener)
+                phases_c = phases_c.reshape(N * Cc, Fin, Fr)
+            else:
+                phases_c = phase_c[None].expand(N, -1, -1, -1).reshape(N * Cc, Fin, Fr).contiguous()
+            channel_wavs = plan.istft(mags_c.reshape(N * Cc, Fin, Fr), phases_c)
             channel_wavs = channel_wavs.clamp_(-1.0, 1.0).reshape(N, Cc, -1)
     out = {"wavs": wavs, "starts": starts, "perms": perms}
     if channels is not None:
@@ -253,6 +274,9 @@ def build_parser():
     p.add_argument("--channels", choices=("mix", "keep"), default="mix",
                    help="mix: the sources are mono (default); keep: every source is written with the file's channels "
                         "(the model still hears the down-mix; its masks go onto each channel)")
+    p.add_argument("--wiener", type=int, default=0, metavar="K",
+                   help="with --channels keep: K passes (0 ... 8) of a multichannel Wiener filter over the masked channels, "
+                        "so every source keeps its own place in the stereo image (0, the default: the mask on every channel)")
     p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]")
     p.add_argument("--out", default="separated", help="output directory (source<n>.wav)")
     p.add_argument("--audio_only", action="store_true", help="no frames: audio-only branch with aligned windows")
@@ -266,6 +290,10 @@ def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     if not args.audio_only and len(args.frames) != args.num_mix:
         raise SystemExit(f"--frames needs {args.num_mix} files (one per source), or pass --audio_only")
+    if not 0 <= args.wiener <= MAX_WIENER:
+        raise SystemExit(f"--wiener takes 0 ... {MAX_WIENER} passes, got {args.wiener}")
+    if args.wiener and args.channels != "keep":
+        raise SystemExit("--wiener filters the file's channels: it needs --channels keep")
     return args
 
 
@@ -309,7 +337,7 @@ def cli(argv=None):
         fr = torch.from_numpy(np.load(path)).float()
         frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
     out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
-                        stride_frames=args.window_stride, batch=args.window_batch, channels=channels)
+                        stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener)
     os.makedirs(args.out, exist_ok=True)
     if keep:
         out_rate = rate if args.out_rate == "file" else args.audRate
@@ -322,6 +350,8 @@ def cli(argv=None):
         for n, w in enumerate(out["wavs"].cpu().numpy()):
             write_wav(os.path.join(args.out, f"source{n}.wav"), w, args.audRate)
     kept = f", {channels.shape[0]} channel{'s' if channels.shape[0] != 1 else ''} each" if keep else ""
+    if args.wiener:
+        kept += f", multichannel Wiener filter x{args.wiener}"
     print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav{kept}")
     return out
 

@@ -451,6 +451,32 @@ int avsep_mask_stitch_channels(const float* masks, const int32_t* starts, const 
                                float thres, float* out, float* mask_out, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Multichannel Wiener filter over the stitched source images (csrc/mwf.hip): what turns N masked copies of a C-channel
+ * recording into N sources with their own place in the spatial image.  X[c,f,t] = xmag * exp(i xph) is the channels' STFT
+ * [C, Fin, F]; Y_n[c,f,t] = ymag * exp(i yph) the current source images [N, C, Fin, F].  One pass, all in fp32:
+ *   1. v_n[f,t] = (1/C) sum_c ymag[n,c,f,t]^2
+ *   2. R_n[f]   = (sum_t Y_n[:,f,t] Y_n[:,f,t]^H) / max(sum_t v_n[f,t], FLT_MIN)     C x C Hermitian; a silent source: R_n = 0
+ *   3. S[f,t]   = sum_n v_n[f,t] R_n[f] + (reg * tr(sum_n v_n R_n) / C + FLT_MIN) I
+ *   4. S z = X[:,f,t]                                  one Cholesky solve per bin, shared by the sources
+ *   5. Y_n'[:,f,t] = v_n[f,t] R_n[f] z                 (exactly 0 where v_n = 0), stored as magnitude and atan2 phase (0 at 0)
+ * The regulariser is relative to the bin's own power (a dual-mono file gives a rank-1 S at every level): the sources of a
+ * pass sum to X / (1 + about reg), not to X.  1 <= N <= 8, 1 <= C <= 8, Fin <= 65535, F <= 2^31 - 1 - 4096; every offset into
+ * [N, C, Fin, F] is formed in 64 bits.  No atomics: every sum has a fixed order that depends on F alone (threads walk chunks of
+ * 2048 frames), so a second call gives the same bits.
+ * avsep_mwf_cov:   steps 1-2.  yph is [N, C, Fin, F] when phase_per_source != 0, else [C, Fin, F] shared by the sources (the
+ *   first pass: masked magnitudes on the mixture's phase).  cov: f32 [N, Fin, C, C, 2], the full R_n as (re, im), diagonal
+ *   imaginary parts exactly 0, upper triangle the exact conjugate of the lower.  ws: avsep_mwf_workspace_bytes(N, C, Fin, F).
+ * avsep_mwf_apply: steps 3-5 from cov; out_mag / out_phase [N, C, Fin, F], the layout avsep_istft takes as N*C rows; they must
+ *   not alias ymag.  reg >= 0 (0 is only safe where S has full rank).
+ * Anything outside these limits, a null pointer or a workspace that is too small is AVSEP_ERR_ARG before any launch (the
+ * workspace query returns 0). */
+size_t avsep_mwf_workspace_bytes(int32_t N, int32_t C, int32_t Fin, int32_t F);
+int avsep_mwf_cov(const float* ymag, const float* yph, int32_t phase_per_source, int32_t N, int32_t C, int32_t Fin, int32_t F,
+                  float* cov, float* ws, size_t ws_bytes, avsep_stream_t stream);
+int avsep_mwf_apply(const float* xmag, const float* xph, const float* ymag, const float* cov, int32_t N, int32_t C, int32_t Fin,
+                    int32_t F, float reg, float* out_mag, float* out_phase, avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Sound-source localisation over a clip (csrc/localise.hip): T video frames against the K windows of one recording.
  * ------------------------------------------------------------------------- */
 /* The CoLoc similarity maps of every frame in one launch (replaces one whole forward pass per video frame,

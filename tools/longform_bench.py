@@ -10,8 +10,12 @@ With --channels C (C >= 1) also (3) the audio-visual call with the recording's C
 wall time and stage split, the stages of the channel path (second STFT, stitch_channels, iSTFT over N*C rows) next to the
 mono ones; and avsep_mask_stitch_channels alone against C launches of avsep_mask_stitch on the same magnitudes, outputs
 compared bit for bit.
+With --wiener K as well (4) that call runs K passes of the multichannel Wiener filter (separate_long(wiener=K)): the stage
+split gains mwf_cov and mwf_apply; and kernels.mwf alone (one pass on the soft source images of the C channels) against the
+same result composed on the device from torch ops (torch.polar, einsum, torch.linalg.solve on complex64), the two timed in
+alternation: time, algorithmic bytes, share of the HBM peak, outputs compared as complex numbers.
 Every number is a median over --reps runs after warm-up; the last line is one JSON object.
-Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20] [--channels C]"""
+Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20] [--channels C [--wiener K]]"""
 import argparse
 import json
 import os
@@ -41,6 +45,24 @@ def median_ms(fn, reps, warmup=3):
         torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1))
     return statistics.median(out)
+
+
+def alternating_median_ms(fns, reps, warmup=2):
+    """Medians of several functions timed in alternation (a, b, a, b, ...) with device events, after warm-up of each."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    out = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[i].append(e0.elapsed_time(e1))
+    return [statistics.median(o) for o in out]
 
 
 class StageClock:
@@ -78,13 +100,15 @@ class StageClock:
         self._undo = []
 
 
-def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None):
+def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, wiener=0):
     K = P.kernels
     clk = StageClock()
     # with channels the second call of each transform is the channel path's: C rows in, N*C rows out
     clk.wrap(K.Stft, "stft", "stft" if channels is None else ["stft", "stft_channels"])
     clk.wrap(K.Stft, "istft", "istft" if channels is None else ["istft", "istft_channels"])
     clk.wrap(K, "mask_stitch_channels", "stitch_channels")
+    clk.wrap(K, "_mwf_cov", "mwf_cov")
+    clk.wrap(K, "_mwf_apply", "mwf_apply")
     clk.wrap(K, "window_prepare", "window_prepare")
     clk.wrap(K, "window_agreement", "agreement")
     clk.wrap(S, "align_permutations", "agreement")
@@ -94,7 +118,7 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None):
     try:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener)
         torch.cuda.synchronize()
         total = (time.perf_counter() - t0) * 1e3
     finally:
@@ -104,17 +128,17 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None):
     return clk.ms
 
 
-def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps, channels=None):
+def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps, channels=None, wiener=0):
     """Median wall time of the unwrapped call, and the median per-stage split of wrapped calls."""
     def once():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3
     once()                                                               # warm-up: code objects, conv plans
     wall = statistics.median(once() for _ in range(reps))
-    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch, channels) for _ in range(reps)]
+    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch, channels, wiener) for _ in range(reps)]
     split = {k: statistics.median(s.get(k, 0.0) for s in splits) for k in splits[0]}
     return wall, split
 
@@ -198,6 +222,43 @@ def channel_stitch_row(mag_c, starts_t, masks, perm, args, reps):
             "launches_over_fused": ms_l / ms_f, "bit_identical_to_launches": same}
 
 
+FLT_MIN = 1.1754943508222875e-38
+
+
+def composed_mwf(xmag, xph, ymag, yph, reg=1e-3):
+    """One pass of the filter from torch ops on the device (complex64): the five steps of include/avsep.h as they stand."""
+    X = torch.polar(xmag, xph)                                                          # [C,Fin,F]
+    Y = torch.polar(ymag, yph.expand_as(ymag).contiguous())                             # [N,C,Fin,F]
+    Cc = X.shape[0]
+    v = (ymag * ymag).sum(1) / Cc                                                       # [N,Fin,F]
+    R = torch.einsum("ncft,ndft->nfcd", Y, Y.conj()) / v.sum(-1).clamp_min(FLT_MIN)[:, :, None, None]
+    Sm = torch.einsum("nft,nfcd->ftcd", v.to(R.dtype), R)
+    lam = reg * torch.diagonal(Sm, dim1=-2, dim2=-1).real.sum(-1) / Cc + FLT_MIN
+    Sm = Sm + lam[:, :, None, None] * torch.eye(Cc, device=X.device, dtype=R.dtype)
+    z = torch.linalg.solve(Sm, X.permute(1, 2, 0).contiguous())                         # [Fin,F,C]
+    Wn = torch.einsum("nfcd,ftd->ncft", R, z) * v[:, None]
+    return Wn.abs(), Wn.angle()
+
+
+def mwf_row(mag_c, phase_c, masks_lin, reps):
+    """kernels.mwf (one pass) on the soft source images masks_lin [N,Fin,F] x mag_c [C,Fin,F] against composed_mwf."""
+    K = P.kernels
+    Cc, Fin, F = mag_c.shape
+    N = masks_lin.shape[0]
+    ymag = (masks_lin[:, None] * mag_c[None]).contiguous()
+    a = torch.polar(*K.mwf(mag_c, phase_c, ymag, phase_c))
+    b = torch.polar(*composed_mwf(mag_c, phase_c, ymag, phase_c))
+    diff = ((a - b).abs().max() / b.abs().max()).item()
+    del a, b
+    # cov reads ymag and the shared phase; apply reads X (magnitude, phase) and ymag, and writes magnitude and phase
+    nbytes = 4 * Fin * F * (N * Cc + Cc + 2 * Cc + N * Cc + 2 * N * Cc)
+    ms_f, ms_c = alternating_median_ms([lambda: K.mwf(mag_c, phase_c, ymag, phase_c),
+                                        lambda: composed_mwf(mag_c, phase_c, ymag, phase_c)], reps)
+    return {"channels": Cc, "sources": N, "fused_ms": ms_f, "composed_ms": ms_c, "algorithmic_bytes": nbytes,
+            "fused_bytes_per_s": nbytes / (ms_f * 1e-3), "share_of_hbm_peak": nbytes / (ms_f * 1e-3) / HBM_PEAK,
+            "composed_over_fused": ms_c / ms_f, "max_rel_diff_vs_composed": diff}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=600.0)
@@ -207,7 +268,11 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--frame-size", type=int, default=224)
     ap.add_argument("--channels", type=int, default=0, help="also measure the call that keeps C channels (0: skip)")
+    ap.add_argument("--wiener", type=int, default=0, help="with --channels: also K passes of the multichannel Wiener filter (0: skip)")
+    ap.add_argument("--mwf-reps", type=int, default=5, help="timed repetitions of the mwf row (the composition is slow)")
     o = ap.parse_args()
+    if o.wiener and o.channels < 1:
+        raise SystemExit("--wiener measures the channel path: pass --channels C as well")
     if not torch.cuda.is_available():
         raise SystemExit("longform_bench measures on an MI355X; there is nothing to report without one")
     dev = torch.device("cuda", 0)
@@ -239,6 +304,13 @@ def main():
         print(f"AV, {o.channels} channels kept: {wall:9.1f} ms = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
         for k, v in split.items():
             print(f"    {k:16s} {v:9.2f} ms", flush=True)
+        if o.wiener:
+            wall, split = whole_runs(nets, wav, frames, args, True, o.stride, o.batch, o.reps, channels=ch, wiener=o.wiener)
+            result["av_channels_wiener"] = {"channels": o.channels, "wiener": o.wiener, "wall_ms": wall,
+                                            "audio_seconds_per_second": audio_s / (wall * 1e-3), "split_ms": split}
+            print(f"AV, {o.channels} channels kept, Wiener x{o.wiener}: {wall:9.1f} ms = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
+            for k, v in split.items():
+                print(f"    {k:16s} {v:9.2f} ms", flush=True)
     with torch.no_grad():
         mag = P.kernels.Stft(dev, args.stft_frame, args.stft_hop, "reflect").stft(wav[None], want_phase=False)[0][0].contiguous()
         starts = S.plan_windows(mag.shape[1], o.stride)
@@ -254,8 +326,16 @@ def main():
                   f"{100 * r['share_of_hbm_peak']:.0f}% of 8 TB/s); {o.channels} launches of mask_stitch {r['launches_ms']:.3f} ms "
                   f"({r['launches_over_fused']:.2f} x; stacked to [N,C,Fin,F] {r['launches_stacked_ms']:.3f} ms); "
                   f"bit-identical {r['bit_identical_to_launches']}", flush=True)
+        if o.wiener:
+            lin = torch.rand(args.num_mix, mag.shape[0], mag.shape[1], device=dev)
+            ph_c = (torch.rand(o.channels, mag.shape[0], mag.shape[1], device=dev) * 2 - 1) * 3.14159
+            mag_r = (mag[None] * (0.5 + torch.rand(o.channels, mag.shape[0], mag.shape[1], device=dev))).contiguous()
+            r = result["kernels"]["mwf"] = mwf_row(mag_r, ph_c, lin, o.mwf_reps)
+            print(f"mwf C={o.channels} N={args.num_mix}, one pass: {r['fused_ms']:.3f} ms ({r['fused_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
+                  f"{100 * r['share_of_hbm_peak']:.0f}% of 8 TB/s); composed from torch ops {r['composed_ms']:.3f} ms "
+                  f"({r['composed_over_fused']:.1f} x); max |diff| / max |ref| {r['max_rel_diff_vs_composed']:.2e}", flush=True)
     for k, r in result["kernels"].items():
-        if k == "mask_stitch_channels":
+        if k in ("mask_stitch_channels", "mwf"):
             continue
         if "composed_ms" in r:
             print(f"{k}: fused {r['fused_ms']:.3f} ms ({r['fused_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
