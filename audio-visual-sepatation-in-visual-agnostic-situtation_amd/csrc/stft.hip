@@ -3,6 +3,7 @@
 // [n_fft x frames] GEMM per row on the f32 MFMA (conv.hip), fused pad / magnitude-phase kernels.
 #include "common.h"
 #include "conv_families.h"
+#include "stft_parts.h"
 
 static inline int bins_of(int n_fft) { return n_fft / 2 + 1; }
 
@@ -143,6 +144,46 @@ extern "C" size_t avsep_stft_workspace_bytes(int32_t R, int32_t L, int32_t n_fft
   return ((size_t)R * (L + n_fft) + spec) * sizeof(float);
 }
 
+// ---- the parts misi.hip calls as well (stft_parts.h) ----
+bool stft_fast_path(int R, int L, int n_fft, int hop) { return stft_fast(R, L, n_fft, hop); }
+
+// wp: [hop * 4][roundup(2 * bins, 128)], the operand c1x4_stft_fwd reads
+int stft_repack_basis(const float* basis, int n_fft, int hop, float* wp, hipStream_t st) {
+  const int ld = roundup(2 * bins_of(n_fft), 128);
+  hipLaunchKernelGGL(stft_basis_repack_kernel, dim3(cdiv((long long)hop * 4 * ld, 256)), dim3(256), 0, st, basis, n_fft, hop,
+                     4, ld, wp);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+// Pad and multiply with the basis.  Fast path: `basis` is the repacked one, stage holds [hop][R][frames + 3], spec comes out
+// co-major [2*bins][R][frames].  Otherwise: `basis` is the plan's, stage holds [R][L + n_fft], spec is [R][2*bins][frames].
+int stft_pad_gemm(const float* wav, int R, int L, int n_fft, int hop, int reflect, const float* basis, float* stage, float* spec,
+                  hipStream_t st) {
+  const int pad = n_fft / 2, Lp = L + 2 * pad, bins = bins_of(n_fft), frames = 1 + L / hop;
+  if (stft_fast(R, L, n_fft, hop)) {
+    const int NH = frames + 3;
+    hipLaunchKernelGGL(stft_pad_t_kernel, dim3(cdiv(NH, 32), R), dim3(256), (size_t)32 * (hop + 1) * sizeof(float), st, wav, L,
+                       pad, reflect, hop, R, NH, stage);
+    AVSEP_LAUNCH_CHECK();
+    return c1x4_stft_fwd(stage, basis, spec, R, NH, hop, 2 * bins, frames, st);
+  }
+  hipLaunchKernelGGL(stft_pad_kernel, dim3(min(cdiv(Lp, 256), 1024), R), dim3(256), 0, st, wav, L, pad, reflect, stage);
+  AVSEP_LAUNCH_CHECK();
+  avsep_conv_desc d{};
+  d.N = R; d.Cin = 1; d.H = 1; d.W = Lp; d.Cout = 2 * bins; d.Ho = 1; d.Wo = frames;
+  d.KH = 1; d.KW = n_fft; d.stride = hop; d.pad = 0; d.dil = 1; d.C0 = 1; d.x0 = stage;
+  return avsep_conv2d_fwd(&d, basis, nullptr, spec, nullptr, nullptr, 0, (avsep_stream_t)st);
+}
+
+// td [R][n_fft][frames] = inverse basis x spec [R][2*bins][frames] (a 1x1 conv)
+int istft_gemm(const float* spec, int R, int n_fft, int frames, const float* inv_basis, float* td, hipStream_t st) {
+  avsep_conv_desc d{};
+  d.N = R; d.Cin = 2 * bins_of(n_fft); d.H = 1; d.W = frames; d.Cout = n_fft; d.Ho = 1; d.Wo = frames;
+  d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0; d.dil = 1; d.C0 = d.Cin; d.x0 = spec;
+  return avsep_conv2d_fwd(&d, inv_basis, nullptr, td, nullptr, nullptr, 0, (avsep_stream_t)st);
+}
+
 extern "C" int avsep_stft_mag(const float* wav, int32_t R, int32_t L, int32_t n_fft, int32_t hop, int32_t reflect,
                               const float* basis, float* mag, float* phase, void* workspace, size_t workspace_bytes,
                               avsep_stream_t stream) {
@@ -151,37 +192,24 @@ extern "C" int avsep_stft_mag(const float* wav, int32_t R, int32_t L, int32_t n_
   if (!workspace || workspace_bytes < avsep_stft_workspace_bytes(R, L, n_fft, hop)) return AVSEP_ERR_WORKSPACE;
   const int pad = n_fft / 2, Lp = L + 2 * pad, bins = bins_of(n_fft), frames = 1 + L / hop;
   hipStream_t st = (hipStream_t)stream;
-  if (stft_fast(R, L, n_fft, hop)) {
-    const int NH = frames + 3, ld = roundup(2 * bins, 128);
-    float* xt = (float*)workspace;
-    float* wp = xt + (size_t)hop * R * NH;
-    float* spec = wp + (size_t)hop * 4 * ld;
-    hipLaunchKernelGGL(stft_pad_t_kernel, dim3(cdiv(NH, 32), R), dim3(256), (size_t)32 * (hop + 1) * sizeof(float), st, wav, L,
-                       pad, reflect, hop, R, NH, xt);
-    AVSEP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(stft_basis_repack_kernel, dim3(cdiv((long long)hop * 4 * ld, 256)), dim3(256), 0, st, basis, n_fft, hop,
-                       4, ld, wp);
-    AVSEP_LAUNCH_CHECK();
-    int rc = c1x4_stft_fwd(xt, wp, spec, R, NH, hop, 2 * bins, frames, st);
+  const bool fast = stft_fast(R, L, n_fft, hop);
+  float* stage = (float*)workspace;                        // xt | padded
+  const float* b = basis;
+  float* spec;
+  if (fast) {
+    float* wp = stage + (size_t)hop * R * (frames + 3);
+    spec = wp + (size_t)hop * 4 * roundup(2 * bins, 128);
+    int rc = stft_repack_basis(basis, n_fft, hop, wp, st);
     if (rc) return rc;
-    long long n = (long long)bins * frames;
-    hipLaunchKernelGGL(stft_magphase_kernel, dim3((int)min((n + 255) / 256, (long long)1024), R), dim3(256), 0, st, spec, bins,
-                       frames, R, 1, mag, phase);
-    AVSEP_LAUNCH_CHECK();
-    return AVSEP_OK;
+    b = wp;
+  } else {
+    spec = stage + (size_t)R * Lp;
   }
-  float* padded = (float*)workspace;
-  float* spec = padded + (size_t)R * Lp;
-  hipLaunchKernelGGL(stft_pad_kernel, dim3(min(cdiv(Lp, 256), 1024), R), dim3(256), 0, st, wav, L, pad, reflect, padded);
-  AVSEP_LAUNCH_CHECK();
-  avsep_conv_desc d{};
-  d.N = R; d.Cin = 1; d.H = 1; d.W = Lp; d.Cout = 2 * bins; d.Ho = 1; d.Wo = frames;
-  d.KH = 1; d.KW = n_fft; d.stride = hop; d.pad = 0; d.dil = 1; d.C0 = 1; d.x0 = padded;
-  int rc = avsep_conv2d_fwd(&d, basis, nullptr, spec, nullptr, nullptr, 0, stream);
+  int rc = stft_pad_gemm(wav, R, L, n_fft, hop, reflect, b, stage, spec, st);
   if (rc) return rc;
   long long n = (long long)bins * frames;
   hipLaunchKernelGGL(stft_magphase_kernel, dim3((int)min((n + 255) / 256, (long long)1024), R), dim3(256), 0, st, spec, bins,
-                     frames, R, 0, mag, phase);
+                     frames, R, fast ? 1 : 0, mag, phase);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -238,10 +266,7 @@ extern "C" int avsep_istft(const float* mag, const float* phase, int32_t R, int3
   hipLaunchKernelGGL(istft_spec_kernel, dim3((int)min((n + 255) / 256, (long long)1024), R), dim3(256), 0, st, mag, phase, n,
                      spec);
   AVSEP_LAUNCH_CHECK();
-  avsep_conv_desc d{};
-  d.N = R; d.Cin = 2 * bins; d.H = 1; d.W = frames; d.Cout = n_fft; d.Ho = 1; d.Wo = frames;
-  d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0; d.dil = 1; d.C0 = 2 * bins; d.x0 = spec;
-  int rc = avsep_conv2d_fwd(&d, inv_basis, nullptr, td, nullptr, nullptr, 0, stream);
+  int rc = istft_gemm(spec, R, n_fft, frames, inv_basis, td, st);
   if (rc) return rc;
   hipLaunchKernelGGL(istft_ola_kernel, dim3(min(cdiv(out_len, 256), 1024), R), dim3(256), 0, st, td, n_fft, hop, frames,
                      out_len, wav);

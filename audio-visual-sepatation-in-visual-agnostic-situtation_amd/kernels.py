@@ -1010,6 +1010,10 @@ def maxpool_bn_relu_bwd_apply(g, idx, y, bnrow, pqr, g2=None, out_f32=False):
     return dy
 
 
+MISI_MAX_SOURCES = 8      # avsep_misi: N and G up to 8
+MISI_MAX_GROUPS = 8
+
+
 class Stft:
     """librosa-style STFT/iSTFT plan (bases built once on the device)."""
 
@@ -1042,3 +1046,37 @@ class Stft:
         call("avsep_istft", ptr(mag), ptr(phase), R, self.n_fft, self.hop, frames, ptr(self.inv_basis), ptr(wav),
              out_len, ptr(ws), nbytes)
         return wav
+
+    def misi(self, mix, mag, phase, iterations, want_phase=False):
+        """Mixture-consistent phase iterations (include/avsep.h, csrc/misi.hip): mix [G,out_len] the mixtures, mag
+        [N,G,bins,F] the stems' target magnitudes (row (n, g) belongs to mixture g), phase the start phase, [G,bins,F]
+        shared by the sources or [N,G,bins,F]; out_len = hop * (F - 1).  -> wav [N,G,out_len] after ``iterations`` passes
+        (the plain iSTFT of the last spectrum: the stems are not forced to sum to the mixture), and with want_phase also the
+        last phase [N,G,bins,F].  One call enqueues every pass; a second call gives the same bits."""
+        for t in (mix, mag, phase):
+            lib.require_gpu(t)
+        bins = self.n_fft // 2 + 1
+        if mag.dim() != 4 or mag.dtype != torch.float32 or mag.shape[2] != bins:
+            raise lib.AvsepError(f"misi takes mag f32 [N,G,{bins},F], got {mag.dtype} {tuple(mag.shape)}")
+        N, G, _, F = mag.shape
+        if not (1 <= N <= MISI_MAX_SOURCES and 1 <= G <= MISI_MAX_GROUPS):
+            raise lib.AvsepError(f"misi: 1 <= N <= {MISI_MAX_SOURCES}, 1 <= G <= {MISI_MAX_GROUPS}; got {tuple(mag.shape)}")
+        out_len = self.hop * (F - 1)
+        if out_len <= self.n_fft // 2:
+            raise lib.AvsepError(f"misi needs hop * (F - 1) > n_fft / 2 samples, got F = {F} at {self.n_fft}/{self.hop}")
+        if phase.dtype != torch.float32 or phase.device != mag.device \
+                or tuple(phase.shape) not in (tuple(mag.shape), tuple(mag.shape[1:])):
+            raise lib.AvsepError(f"misi takes phase f32 [{G},{bins},{F}] (shared by the sources) or [{N},{G},{bins},{F}] on "
+                                 f"{mag.device}, got {phase.dtype} {tuple(phase.shape)} on {phase.device}")
+        if mix.dtype != torch.float32 or tuple(mix.shape) != (G, out_len) or mix.device != mag.device:
+            raise lib.AvsepError(f"misi takes mix f32 [{G},{out_len}] on {mag.device}, got {mix.dtype} {tuple(mix.shape)} on {mix.device}")
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+            raise lib.AvsepError(f"misi needs iterations as an int >= 1, got {iterations!r}")
+        mix, mag, phase = mix.contiguous(), mag.contiguous(), phase.contiguous()
+        nbytes = lib.load().avsep_misi_workspace_bytes(N, G, self.n_fft, self.hop, F)
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=mag.device)
+        wav = _f32((N, G, out_len), mag)
+        ph = _f32((N, G, bins, F), mag) if want_phase else None
+        call("avsep_misi", ptr(mix), ptr(mag), ptr(phase), int(phase.dim() == 4), N, G, self.n_fft, self.hop, F, self.reflect,
+             iterations, ptr(self.fwd_basis), ptr(self.inv_basis), ptr(wav), ptr(ph), ptr(ws), nbytes)
+        return (wav, ph) if want_phase else wav

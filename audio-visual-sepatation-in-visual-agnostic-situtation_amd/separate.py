@@ -23,6 +23,11 @@ also applied to each channel's own magnitude (``avsep_mask_stitch_channels``) an
 so a stereo file gives stereo sources.  ``wiener=k`` (``--wiener k``) then runs k passes of a multichannel Wiener filter
 (``kernels.mwf``) over those source images: the masked channels give every source a spatial covariance per bin, and each
 time-frequency bin of the mixture is filtered again with them, so a source keeps its own place in the stereo image.
+
+A masked magnitude on the mixture's phase is not the STFT of any signal.  ``phase_iters=k`` (``--phase_iters k``) runs k
+mixture-consistent phase iterations (MISI, ``kernels.Stft.misi``) in place of the one inverse transform: every stem gets a
+phase of its own under the magnitude it was given.  The gain grows with the quality of the magnitudes; thresholded
+(binary) masks gain nothing from it.
 """
 import itertools
 import os
@@ -38,6 +43,7 @@ from .models import activate
 
 WIDTH = 256        # frames per window: the tile the network is trained on
 MAX_WIENER = 8     # passes of the multichannel Wiener filter a call may ask for
+MAX_PHASE_ITERS = 32   # mixture-consistent phase iterations a call may ask for
 FOUT = 256         # log-frequency bins of the warped tile (inference.py:48-51)
 
 
@@ -92,7 +98,7 @@ def _visual_features(net_frame, frames, args, Kw, batch):
 
 
 def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None,
-                  wiener=0):
+                  wiener=0, phase_iters=0):
     """Separate one recording ``wav`` [L] (on the GPU, L >= args.stft_frame; several recordings: one call each).
 
     nets: (net_sound, net_frame), both in eval() — train-mode BatchNorm over the windows of one recording is never what
@@ -116,10 +122,19 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
     Each source then gets its own phase (one iSTFT over N*C rows), and the sources of a bin sum to the mixture over
     1 + ~1e-3, not to the mixture exactly.  The covariances are one per bin row for the whole recording (time-invariant).
     "wavs", "perms", "masks" and "lin_masks" do not depend on ``wiener``.
+
+    phase_iters: int in 0 ... 32, mixture-consistent phase iterations (``kernels.Stft.misi``) in place of the one inverse
+    transform.  0 is the path above, bit for bit.  With k >= 1 "wavs" are the stitched magnitudes after k passes against
+    ``wav[:hop*(F-1)]``, started from the mixture's phase; "channel_wavs" the channel magnitudes after k passes, every
+    channel's N stems against that channel, started from the channel's own phase or, with ``wiener``, from the filter's
+    magnitudes and per-source phases.  The stems are clamped as before and are not forced to sum to the mixture.
+    "perms", "masks" and "lin_masks" do not depend on it.
     """
     net_sound, net_frame = nets
     if isinstance(wiener, bool) or not isinstance(wiener, int) or not 0 <= wiener <= MAX_WIENER:
         raise AvsepError(f"separate_long takes wiener as an int in 0 ... {MAX_WIENER} (passes of the multichannel Wiener filter), got {wiener!r}")
+    if isinstance(phase_iters, bool) or not isinstance(phase_iters, int) or not 0 <= phase_iters <= MAX_PHASE_ITERS:
+        raise AvsepError(f"separate_long takes phase_iters as an int in 0 ... {MAX_PHASE_ITERS} (mixture-consistent phase iterations), got {phase_iters!r}")
     if wiener and channels is None:
         raise AvsepError("separate_long(wiener=...) filters the recording's channels: pass channels= as well")
     lib.require_gpu(wav)
@@ -175,19 +190,26 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
             perms = align_permutations(K.window_agreement(masks, starts_t))
         binary = bool(args.binary_mask)
         mags, lin = K.mask_stitch(masks, starts_t, perms.to(dev), mag, binary, getattr(args, "mask_thres", 0.5), return_masks)
-        wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous()).clamp_(-1.0, 1.0)
+        out_len = plan.hop * (mag.shape[1] - 1)
+        if phase_iters:
+            wavs = plan.misi(wav.float()[None, :out_len], mags[:, None], phase[None], phase_iters)[:, 0].clamp_(-1.0, 1.0)
+        else:
+            wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous()).clamp_(-1.0, 1.0)
         if channels is not None:                                         # the same masks on every channel's own STFT
             mag_c, phase_c = plan.stft(channels.contiguous())
             Cc, Fin, Fr = mag_c.shape
             mags_c, _ = K.mask_stitch_channels(masks, starts_t, perms.to(dev), mag_c, binary and not wiener,
                                                getattr(args, "mask_thres", 0.5))
+            phases_c = phase_c                                           # shared by the sources
             if wiener:                                                   # soft source images in, one phase per source out
                 mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener)
-                phases_c = phases_c.reshape(N * Cc, Fin, Fr)
+            if phase_iters:                                              # every channel is the mixture of its N stems
+                channel_wavs = plan.misi(channels[:, :out_len], mags_c, phases_c, phase_iters).clamp_(-1.0, 1.0)
             else:
-                phases_c = phase_c[None].expand(N, -1, -1, -1).reshape(N * Cc, Fin, Fr).contiguous()
-            channel_wavs = plan.istft(mags_c.reshape(N * Cc, Fin, Fr), phases_c)
-            channel_wavs = channel_wavs.clamp_(-1.0, 1.0).reshape(N, Cc, -1)
+                if not wiener:
+                    phases_c = phase_c[None].expand(N, -1, -1, -1).contiguous()
+                channel_wavs = plan.istft(mags_c.reshape(N * Cc, Fin, Fr), phases_c.reshape(N * Cc, Fin, Fr))
+                channel_wavs = channel_wavs.clamp_(-1.0, 1.0).reshape(N, Cc, -1)
     out = {"wavs": wavs, "starts": starts, "perms": perms}
     if channels is not None:
         out["channel_wavs"] = channel_wavs
@@ -277,6 +299,9 @@ def build_parser():
     p.add_argument("--wiener", type=int, default=0, metavar="K",
                    help="with --channels keep: K passes (0 ... 8) of a multichannel Wiener filter over the masked channels, "
                         "so every source keeps its own place in the stereo image (0, the default: the mask on every channel)")
+    p.add_argument("--phase_iters", type=int, default=0, metavar="K",
+                   help="K mixture-consistent phase iterations (0 ... 32) in place of the one inverse transform: every source "
+                        "gets a phase of its own (0, the default: the mixture's phase; no gain with --binary_mask 1)")
     p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]")
     p.add_argument("--out", default="separated", help="output directory (source<n>.wav)")
     p.add_argument("--audio_only", action="store_true", help="no frames: audio-only branch with aligned windows")
@@ -292,6 +317,8 @@ def parse_args(argv=None):
         raise SystemExit(f"--frames needs {args.num_mix} files (one per source), or pass --audio_only")
     if not 0 <= args.wiener <= MAX_WIENER:
         raise SystemExit(f"--wiener takes 0 ... {MAX_WIENER} passes, got {args.wiener}")
+    if not 0 <= args.phase_iters <= MAX_PHASE_ITERS:
+        raise SystemExit(f"--phase_iters takes 0 ... {MAX_PHASE_ITERS} passes, got {args.phase_iters}")
     if args.wiener and args.channels != "keep":
         raise SystemExit("--wiener filters the file's channels: it needs --channels keep")
     return args
@@ -337,7 +364,8 @@ def cli(argv=None):
         fr = torch.from_numpy(np.load(path)).float()
         frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
     out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
-                        stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener)
+                        stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener,
+                        phase_iters=args.phase_iters)
     os.makedirs(args.out, exist_ok=True)
     if keep:
         out_rate = rate if args.out_rate == "file" else args.audRate
@@ -352,6 +380,8 @@ def cli(argv=None):
     kept = f", {channels.shape[0]} channel{'s' if channels.shape[0] != 1 else ''} each" if keep else ""
     if args.wiener:
         kept += f", multichannel Wiener filter x{args.wiener}"
+    if args.phase_iters:
+        kept += f", phase iterations x{args.phase_iters}"
     print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav{kept}")
     return out
 

@@ -477,6 +477,31 @@ int avsep_mwf_apply(const float* xmag, const float* xph, const float* ymag, cons
                     int32_t F, float reg, float* out_mag, float* out_phase, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Mixture-consistent phase iterations (csrc/misi.hip; MISI, Gunawan & Sen 2010): give every stem of a mixture a phase of its
+ * own.  R = N * G rows: N sources, G groups; a group is the set of N rows that sum to one mixture (G = 1 for mono stems,
+ * G = C for channel stems).  mix [G, out_len] with out_len = hop * (frames - 1); mag [N, G, bins, frames] the target
+ * magnitudes A; phase the start phase, [G, bins, frames] shared by the sources or, with phase_per_source != 0,
+ * [N, G, bins, frames].  iSTFT / STFT below are avsep_istft (synthesis window in the basis, window-sum-square normalisation,
+ * centre trim, length out_len) and avsep_stft_mag's transform (reflect or zero padding, `frames` frames).  In fp32:
+ *   1. s_n = iSTFT(A_n * exp(i phase))
+ *   2. for k = 1 ... iterations:
+ *        e  = mix - sum_n s_n                  (n ascending)
+ *        Z_n = STFT(s_n + e / N)
+ *        s_n = iSTFT(A_n * Z_n / |Z_n|)        (A_n * 1 where Z_n = 0, as atan2f(0, 0) = 0 gives)
+ *   3. wav_out [N, G, out_len] = s_n after the last pass: the plain iSTFT of the last spectrum (the stems are not forced to
+ *      sum to the mixture); phase_out (optional, may be null) [N, G, bins, frames] = atan2f of the last Z_n.
+ * fwd_basis / inv_basis: avsep_stft_basis(n_fft).  1 <= N <= 8, 1 <= G <= 8, iterations >= 1, out_len > n_fft / 2.  One call
+ * enqueues every pass on the stream: no host synchronisation, no allocation, no atomics; every sum has a fixed order, so a second
+ * call gives the same bits, and the groups are processed one by one, so a call with G groups gives the bits of G calls with
+ * one.  Every offset is formed in 64 bits.  A null pointer, a zero size or anything outside these limits is AVSEP_ERR_ARG
+ * before any launch (the workspace query returns 0); ws: avsep_misi_workspace_bytes bytes, else AVSEP_ERR_WORKSPACE. */
+size_t avsep_misi_workspace_bytes(int32_t N, int32_t G, int32_t n_fft, int32_t hop, int32_t frames);
+int avsep_misi(const float* mix, const float* mag, const float* phase, int32_t phase_per_source, int32_t N, int32_t G,
+               int32_t n_fft, int32_t hop, int32_t frames, int32_t reflect, int32_t iterations, const float* fwd_basis,
+               const float* inv_basis, float* wav_out, float* phase_out_or_null, void* ws, size_t ws_bytes,
+               avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Sound-source localisation over a clip (csrc/localise.hip): T video frames against the K windows of one recording.
  * ------------------------------------------------------------------------- */
 /* The CoLoc similarity maps of every frame in one launch (replaces one whole forward pass per video frame,

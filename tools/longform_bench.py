@@ -14,8 +14,14 @@ With --wiener K as well (4) that call runs K passes of the multichannel Wiener f
 split gains mwf_cov and mwf_apply; and kernels.mwf alone (one pass on the soft source images of the C channels) against the
 same result composed on the device from torch ops (torch.polar, einsum, torch.linalg.solve on complex64), the two timed in
 alternation: time, algorithmic bytes, share of the HBM peak, outputs compared as complex numbers.
+With --phase_iters K (5) the audio-visual call runs K mixture-consistent phase iterations (separate_long(phase_iters=K), with
+the channels and the Wiener passes of the options above when they are given): wall time, and the split gains misi (and
+misi_channels); and one kernels.Stft.misi call of K passes on the recording at N = 2, G = 1 and N = 2, G = 2 against the same
+result composed on the device from Stft.istft, torch arithmetic and Stft.stft, the two timed in alternation with device
+events; the two kernels the call adds (overlap-add + consistency, re-phase) are timed per launch from a profiler trace of
+one call: algorithmic bytes per pass and their share of the HBM peak.
 Every number is a median over --reps runs after warm-up; the last line is one JSON object.
-Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20] [--channels C [--wiener K]]"""
+Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20] [--channels C [--wiener K]] [--phase_iters K]"""
 import argparse
 import json
 import os
@@ -100,12 +106,13 @@ class StageClock:
         self._undo = []
 
 
-def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, wiener=0):
+def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, wiener=0, phase_iters=0):
     K = P.kernels
     clk = StageClock()
     # with channels the second call of each transform is the channel path's: C rows in, N*C rows out
     clk.wrap(K.Stft, "stft", "stft" if channels is None else ["stft", "stft_channels"])
     clk.wrap(K.Stft, "istft", "istft" if channels is None else ["istft", "istft_channels"])
+    clk.wrap(K.Stft, "misi", "misi" if channels is None else ["misi", "misi_channels"])
     clk.wrap(K, "mask_stitch_channels", "stitch_channels")
     clk.wrap(K, "_mwf_cov", "mwf_cov")
     clk.wrap(K, "_mwf_apply", "mwf_apply")
@@ -118,7 +125,7 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, w
     try:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener, phase_iters=phase_iters)
         torch.cuda.synchronize()
         total = (time.perf_counter() - t0) * 1e3
     finally:
@@ -128,17 +135,17 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, w
     return clk.ms
 
 
-def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps, channels=None, wiener=0):
+def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps, channels=None, wiener=0, phase_iters=0):
     """Median wall time of the unwrapped call, and the median per-stage split of wrapped calls."""
     def once():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener, phase_iters=phase_iters)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3
     once()                                                               # warm-up: code objects, conv plans
     wall = statistics.median(once() for _ in range(reps))
-    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch, channels, wiener) for _ in range(reps)]
+    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch, channels, wiener, phase_iters) for _ in range(reps)]
     split = {k: statistics.median(s.get(k, 0.0) for s in splits) for k in splits[0]}
     return wall, split
 
@@ -259,6 +266,70 @@ def mwf_row(mag_c, phase_c, masks_lin, reps):
             "composed_over_fused": ms_c / ms_f, "max_rel_diff_vs_composed": diff}
 
 
+def composed_misi(plan, mix, A, phase, passes):
+    """The passes from the older entry points: Stft.istft, torch arithmetic, Stft.stft (magnitude and angle written, the
+    magnitude thrown away, the angle read back through the inverse)."""
+    N, G, bins, F = A.shape
+    rows = A.reshape(N * G, bins, F)
+    s = plan.istft(rows, phase.expand(N, G, bins, F).reshape(N * G, bins, F).contiguous()).reshape(N, G, -1)
+    for _ in range(passes):
+        e = mix - s.sum(0)
+        _, ph = plan.stft((s + e / N).reshape(N * G, -1))
+        s = plan.istft(rows, ph).reshape(N, G, -1)
+    return s
+
+
+def misi_kernel_times(fn):
+    """Per-launch device time (ms) of the two kernels csrc/misi.hip adds, from a profiler trace of one call; None where the
+    trace does not name them."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        out = {}
+        for ev in prof.key_averages():
+            for name in ("misi_ola_kernel", "misi_rephase_kernel"):
+                if name in ev.key and ev.count:
+                    us = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+                    tot, cnt = out.get(name, (0.0, 0))
+                    out[name] = (tot + us, cnt + ev.count)
+        return {k: t / c * 1e-3 for k, (t, c) in out.items() if t > 0}
+    except Exception as e:                                                # a tool's extra: the rows above do not depend on it
+        print(f"profiler trace unavailable ({type(e).__name__}: {e}); per-kernel times not measured", flush=True)
+        return {}
+
+
+def misi_row(plan, wav, mag, phase, G, passes, reps):
+    """One Stft.misi call of ``passes`` passes for N = 2 stems of each of G mixtures as long as the recording, against
+    composed_misi; the two timed in alternation."""
+    N = 2
+    bins, F = mag.shape
+    out_len = plan.hop * (F - 1)
+    gains = torch.linspace(1.0, 0.5, G, device=wav.device)[:, None]
+    mix = (wav[None, :out_len] * gains).contiguous()
+    A = (torch.rand(N, 1, bins, F, device=wav.device) * (mag[None, None] * gains[None, :, :, None])).contiguous()
+    ph = phase[None].expand(G, -1, -1).contiguous()
+    a, b = plan.misi(mix, A, ph, passes), composed_misi(plan, mix, A, ph, passes)
+    diff = ((a - b).abs().max() / b.abs().max()).item()
+    del a, b
+    ms_f, ms_c = alternating_median_ms([lambda: plan.misi(mix, A, ph, passes), lambda: composed_misi(plan, mix, A, ph, passes)], reps)
+    R = N * G
+    # per pass: the overlap-add reads the inverse GEMM's output, the table and the mixture and writes the projected stems; the
+    # re-phase reads both planes of the forward GEMM's output and the magnitudes and writes the inverse GEMM's operand
+    bytes_ola = 4 * (R * plan.n_fft * F + out_len + G * out_len + R * out_len)
+    bytes_reph = 4 * R * bins * F * 5
+    per = misi_kernel_times(lambda: plan.misi(mix, A, ph, passes))
+    row = {"sources": N, "groups": G, "passes": passes, "fused_ms": ms_f, "composed_ms": ms_c, "composed_over_fused": ms_c / ms_f,
+           "fused_ms_per_pass": ms_f / passes, "max_rel_diff_vs_composed": diff,
+           "ola_algorithmic_bytes_per_pass": bytes_ola, "rephase_algorithmic_bytes_per_pass": bytes_reph}
+    for key, name, nb in (("ola", "misi_ola_kernel", bytes_ola), ("rephase", "misi_rephase_kernel", bytes_reph)):
+        if name in per:
+            row[f"{key}_ms"] = per[name]
+            row[f"{key}_share_of_hbm_peak"] = nb / (per[name] * 1e-3) / HBM_PEAK
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=600.0)
@@ -269,6 +340,7 @@ def main():
     ap.add_argument("--frame-size", type=int, default=224)
     ap.add_argument("--channels", type=int, default=0, help="also measure the call that keeps C channels (0: skip)")
     ap.add_argument("--wiener", type=int, default=0, help="with --channels: also K passes of the multichannel Wiener filter (0: skip)")
+    ap.add_argument("--phase_iters", type=int, default=0, help="also K mixture-consistent phase iterations: the call and Stft.misi alone (0: skip)")
     ap.add_argument("--mwf-reps", type=int, default=5, help="timed repetitions of the mwf row (the composition is slow)")
     o = ap.parse_args()
     if o.wiener and o.channels < 1:
@@ -311,8 +383,30 @@ def main():
             print(f"AV, {o.channels} channels kept, Wiener x{o.wiener}: {wall:9.1f} ms = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
             for k, v in split.items():
                 print(f"    {k:16s} {v:9.2f} ms", flush=True)
+    if o.phase_iters:
+        ch = (wav[None] * torch.linspace(1.0, 0.5, o.channels, device=dev)[:, None]).contiguous() if o.channels > 0 else None
+        wall, split = whole_runs(nets, wav, frames, args, True, o.stride, o.batch, o.reps, channels=ch, wiener=o.wiener,
+                                 phase_iters=o.phase_iters)
+        result["av_phase_iters"] = {"channels": o.channels, "wiener": o.wiener, "phase_iters": o.phase_iters, "wall_ms": wall,
+                                    "audio_seconds_per_second": audio_s / (wall * 1e-3), "split_ms": split}
+        print(f"AV, phase iterations x{o.phase_iters}" + (f", {o.channels} channels kept" if o.channels else "")
+              + (f", Wiener x{o.wiener}" if o.wiener else "") + f": {wall:9.1f} ms = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
+        for k, v in split.items():
+            print(f"    {k:16s} {v:9.2f} ms", flush=True)
+        del ch
     with torch.no_grad():
-        mag = P.kernels.Stft(dev, args.stft_frame, args.stft_hop, "reflect").stft(wav[None], want_phase=False)[0][0].contiguous()
+        plan = P.kernels.Stft(dev, args.stft_frame, args.stft_hop, "reflect")
+        if o.phase_iters:
+            m1, p1 = plan.stft(wav[None])
+            for G in (1, 2):
+                r = result.setdefault("misi", {})[f"N2_G{G}"] = misi_row(plan, wav, m1[0], p1[0], G, o.phase_iters, o.reps)
+                per = ", ".join(f"{k} {r[k + '_ms']:.3f} ms / launch ({100 * r[k + '_share_of_hbm_peak']:.0f}% of 8 TB/s on "
+                                f"{r[k + '_algorithmic_bytes_per_pass'] / 1e6:.0f} MB)" for k in ("ola", "rephase") if k + "_ms" in r)
+                print(f"misi N=2 G={G}, {o.phase_iters} passes: {r['fused_ms']:.3f} ms ({r['fused_ms_per_pass']:.3f} ms / pass); composed from "
+                      f"istft + torch + stft {r['composed_ms']:.3f} ms ({r['composed_over_fused']:.2f} x); max |diff| / max |ref| "
+                      f"{r['max_rel_diff_vs_composed']:.2e}" + (f"; {per}" if per else "; per-kernel times not measured"), flush=True)
+            del m1, p1
+        mag = plan.stft(wav[None], want_phase=False)[0][0].contiguous()
         starts = S.plan_windows(mag.shape[1], o.stride)
         starts_t = torch.tensor(starts, dtype=torch.int32, device=dev)
         masks = torch.rand(len(starts), args.num_mix, 256, 256, device=dev)
