@@ -8,6 +8,7 @@
 //   3. bss_project_kernel  the projection itself: sum_i conv(C_i, ref_i) over the L + flen - 1 output samples
 // The residual energies / log10 of the three ratios are a few elementwise torch ops on the host side (bss_eval.py).
 #include "common.h"
+#include "bss_lu.h"
 
 // ---- 1. correlations -------------------------------------------------------------------------------------------------------------
 // R[b][i][j][u], u = tau + flen - 1, tau in (-flen, flen):  sum_t ref_i[t + tau] * ref_j[t]
@@ -76,10 +77,6 @@ __global__ __launch_bounds__(1024) void bss_solve_kernel(const double* __restric
   double* const A = work + (long long)sys * M * M;
   double* const rowk = bs_smem;                     // [M]  row k of U during step k
   double* const x = bs_smem + M;                    // [nrhs][M]
-  __shared__ double red_v[16];
-  __shared__ int red_i[16];
-  __shared__ int s_piv;
-  __shared__ double s_pivval;
 
   // build A (column-major) and the right-hand sides
   for (int c = 0; c < M; ++c) {
@@ -96,90 +93,7 @@ __global__ __launch_bounds__(1024) void bss_solve_kernel(const double* __restric
     }
   __syncthreads();
 
-  bool singular = false;
-  for (int k = 0; k < M; ++k) {
-    // pivot search in column k
-    double best = -1.0;
-    int bi = k;
-    for (int r = tid; r < M; r += 1024)
-      if (r >= k) {
-        const double v = fabs(A[(long long)k * M + r]);
-        if (v > best) { best = v; bi = r; }
-      }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const double ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if ((tid & 63) == 0) { red_v[tid >> 6] = best; red_i[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      double bv = red_v[0];
-      int bx = red_i[0];
-      for (int w = 1; w < 16; ++w)
-        if (red_v[w] > bv || (red_v[w] == bv && red_i[w] < bx)) { bv = red_v[w]; bx = red_i[w]; }
-      s_piv = bx;
-      s_pivval = bv;
-    }
-    __syncthreads();
-    const int p = s_piv;
-    if (!(s_pivval > 0.0)) { singular = true; if (tid == 0) info[sys] = k + 1; break; }   // exactly singular (or NaN)
-    // swap rows k and p in every column and in the right-hand sides; stage row k of U
-    for (int c = tid; c < M; c += 1024) {
-      double vk = A[(long long)c * M + k];
-      if (p != k) {
-        const double vp = A[(long long)c * M + p];
-        A[(long long)c * M + p] = vk;
-        A[(long long)c * M + k] = vp;
-        vk = vp;
-      }
-      rowk[c] = vk;
-    }
-    if (p != k && tid < nrhs) {
-      const double t = x[tid * M + k];
-      x[tid * M + k] = x[tid * M + p];
-      x[tid * M + p] = t;
-    }
-    __syncthreads();
-    const double inv = 1.0 / rowk[k];
-    // column k of L, trailing update, and the forward substitution of the right-hand sides folded into the same sweep
-    for (int r = tid; r < M; r += 1024)
-      if (r > k) {
-        const double l = A[(long long)k * M + r] * inv;
-        A[(long long)k * M + r] = l;
-        // the sweep is latency-bound (an 8 MB matrix per system, one row element per column): 16 independent loads in flight
-        int c = k + 1;
-        for (; c + 16 <= M; c += 16) {
-          double v[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) v[u] = A[(long long)(c + u) * M + r];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) A[(long long)(c + u) * M + r] = fma(-l, rowk[c + u], v[u]);
-        }
-        for (; c < M; ++c) A[(long long)c * M + r] = fma(-l, rowk[c], A[(long long)c * M + r]);
-        for (int q = 0; q < nrhs; ++q) x[q * M + r] = fma(-l, x[q * M + k], x[q * M + r]);
-      }
-    __syncthreads();
-  }
-  if (singular) {
-    for (int q = 0; q < nrhs; ++q)
-      for (int r = tid; r < M; r += 1024) C[((long long)sys * M + r) * nrhs + q] = 0.0;
-    return;
-  }
-  if (tid == 0) info[sys] = 0;
-  // back substitution with U (the forward half was done on the fly)
-  for (int k = M - 1; k >= 0; --k) {
-    if (tid < nrhs) x[tid * M + k] /= A[(long long)k * M + k];
-    __syncthreads();
-    for (int r = tid; r < k; r += 1024) {
-      const double u = A[(long long)k * M + r];
-      for (int q = 0; q < nrhs; ++q) x[q * M + r] = fma(-u, x[q * M + k], x[q * M + r]);
-    }
-    __syncthreads();
-  }
-  for (int q = 0; q < nrhs; ++q)
-    for (int r = tid; r < M; r += 1024) C[((long long)sys * M + r) * nrhs + q] = x[q * M + r];
+  bss_lu_solve(A, M, nrhs, rowk, x, info + sys, C + (long long)sys * M * nrhs);
 }
 extern "C" size_t avsep_bss_solve_workspace_bytes(int32_t B, int32_t S, int32_t flen, int32_t mode) {
   if (B <= 0 || S <= 0 || flen <= 0) return 0;

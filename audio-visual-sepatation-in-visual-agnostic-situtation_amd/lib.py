@@ -129,6 +129,13 @@ SIGNATURES = {
     "avsep_bss_solve_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "avsep_bss_solve": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P]),
     "avsep_bss_project": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_bss_seg_corr_workspace_bytes": (_Z, [_I, _I, C.c_int64, _I]),
+    "avsep_bss_seg_corr": (C.c_int, [_P, _P, _I, C.c_int64, _I, _P, _I, C.c_int64, _P, _Z, _P, _P, _P]),
+    "avsep_bss_solve_groups_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "avsep_bss_solve_groups": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P]),
+    "avsep_bss_window_energies_workspace_bytes": (_Z, [_I, _I, C.c_int64]),
+    "avsep_bss_window_energies": (C.c_int, [_P, _P, _I, _I, C.c_int64, _I, _P, _I, C.c_int64, _P, _P, _P, _P, _I, C.c_int64,
+                                            _P, _Z, _P, _P]),
     "avsep_grid_unpack": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "avsep_bn_bwd_apply_to_b16": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "avsep_b16_bn_bwd_apply": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),

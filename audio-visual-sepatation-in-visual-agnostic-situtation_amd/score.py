@@ -1,0 +1,315 @@
+"""Score separated stems against their references: windowed image-form BSS-eval (SDR / ISR / SIR / SAR).
+
+    python -m avsep_amd.score --ref a.wav b.wav --est sep/source0.wav sep/source1.wav \
+        [--win 1.0 --hop 1.0 --filters track|window --flen 512 --json scores.json]
+
+The reference scores 6 s mono training batches with mir_eval's bss_eval_sources (main.py:260-266; bss_eval.py here).  Music
+stems are conventionally scored with the image form of the same decomposition (Vincent et al. 2006, `bss_decomp_mtifilt`):
+every estimate channel is projected, by least squares, on `flen` delayed copies of (a) the channels of its own true source
+and (b) the channels of all true sources; with rows q = source * C + channel, s = r_q zero-padded by flen - 1,
+
+    e_spat = p_own - s      e_interf = p_all - p_own      e_artif = e_q - p_all
+
+and, energies summed over the channels of a source and a sample range T,
+
+    SDR = 10 log10  sum s^2 / sum (e_q - s)^2             ISR = 10 log10  sum s^2 / sum e_spat^2
+    SIR = 10 log10  sum (s + e_spat)^2 / sum e_interf^2   SAR = 10 log10  sum p_all^2 / sum e_artif^2
+
+taken in short windows, the median over windows reported.  filters="track" fits one set of filters on the whole recording
+and scores every window (and the whole padded recording: "track") with it; filters="window" fits every window on its own
+(one full-length window at C = 1 is bss_eval_sources' SIR and SAR).  Everything is float64 on the GPU through three entry
+points of csrc/bss_windows.hip: lagged correlations read in place (no window is copied), the dense LU of bsseval.hip per
+(segment, source group), and the two FIR projections with their residual energies (no projected waveform is stored).
+Exactly singular Gram matrices (dual-mono: a mono file saved as stereo) take bss_eval.py's host least-squares path.
+"""
+import argparse
+import itertools
+import json
+import math
+
+import numpy as np
+import torch
+
+from . import lib
+from .lib import AvsepError, call, ptr
+
+MAX_ROWS = 8                 # P = S * C
+MAX_UNKNOWNS = 2048          # P * flen: the dense solver's size (one workgroup per system)
+TERMS = 7                    # s^2, (e-s)^2, e_spat^2, (s+e_spat)^2, e_interf^2, p_all^2, e_artif^2
+_BATCH_BYTES = 8 << 30       # workspace budget of one batch of windows in filters="window" (50 MB per window at 2048 unknowns)
+
+
+def plan_windows(L, win, hop):
+    """-> (window starts, window length): window w covers [w * hop, w * hop + win), w = 0 ... (L - win) // hop; a remainder
+    is dropped; a signal shorter than one window is one window, the whole signal."""
+    if win < 1 or hop < 1:
+        raise AvsepError(f"win and hop are positive sample counts, got win={win} hop={hop}")
+    if L < win:
+        return [0], L
+    return [w * hop for w in range((L - win) // hop + 1)], win
+
+
+def best_permutation(sdr_db):
+    """sdr_db[i][j]: plain track SDR (dB) of estimate i against reference j.  -> perm with perm[j] = the estimate scored
+    against reference j, the one with the largest mean; the lexicographically first on ties."""
+    S = len(sdr_db)
+    best, best_mean = None, None
+    for perm in itertools.permutations(range(S)):
+        m = sum(float(sdr_db[perm[j]][j]) for j in range(S)) / S
+        if best is None or m > best_mean:
+            best, best_mean = perm, m
+    return list(best)
+
+
+def check_limits(S, C, flen):
+    P = S * C
+    if S < 1 or C < 1:
+        raise AvsepError(f"score_stems needs at least one source and one channel (1 <= S), got S={S} C={C}")
+    if P > MAX_ROWS:
+        raise AvsepError(f"score_stems takes at most P = S * C <= {MAX_ROWS} rows, got {S} sources x {C} channels = {P}")
+    if flen < 1 or P * flen > MAX_UNKNOWNS:
+        raise AvsepError(f"score_stems solves at most P * flen <= {MAX_UNKNOWNS} unknowns (the dense solver's size), "
+                         f"got {P} rows x flen {flen} = {P * flen}")
+
+
+def _i64(vals, dev):
+    return torch.tensor(list(vals), dtype=torch.int64, device=dev)
+
+
+def seg_corr(refs, ests, flen, starts, n):
+    """refs, ests [P, L] float64; segments [starts[i], starts[i] + n).  -> R [nseg, P, P, 2 flen - 1], D [nseg, P(est), P(ref), flen]."""
+    Lb = lib.load()
+    P, L = refs.shape
+    dev, nseg = refs.device, len(starts)
+    nbytes = Lb.avsep_bss_seg_corr_workspace_bytes(nseg, P, n, flen)
+    ws = torch.empty((max(nbytes // 8, 1),), dtype=torch.float64, device=dev)
+    R = torch.empty((nseg, P, P, 2 * flen - 1), dtype=torch.float64, device=dev)
+    D = torch.empty((nseg, P, P, flen), dtype=torch.float64, device=dev)
+    seg = _i64(starts, dev)
+    call("avsep_bss_seg_corr", ptr(refs), ptr(ests), P, L, flen, ptr(seg), nseg, n, ptr(ws), nbytes, ptr(R), ptr(D))
+    return R, D
+
+
+def _gram(R, seg, rows, flen):
+    k = torch.arange(flen, device=R.device)
+    lag = (k[None, :] - k[:, None]) + flen - 1                              # [a, c] -> c - a + flen - 1
+    return torch.cat([torch.cat([R[seg, i, j][lag] for j in rows], 1) for i in rows], 0)
+
+
+def solve_groups(R, D, G, flen):
+    """The filters of every (segment, group of G rows): [nseg * P / G, G * flen, G]."""
+    Lb = lib.load()
+    nseg, P = R.shape[:2]
+    ng, M = P // G, G * flen
+    nbytes = Lb.avsep_bss_solve_groups_workspace_bytes(nseg, P, G, flen)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=R.device)
+    C = torch.empty((nseg * ng, M, G), dtype=torch.float64, device=R.device)
+    info = torch.empty((nseg * ng,), dtype=torch.int32, device=R.device)
+    call("avsep_bss_solve_groups", ptr(R), ptr(D), nseg, P, G, flen, ptr(ws), nbytes, ptr(C), ptr(info))
+    bad = info != 0
+    if G > 1:
+        # Two rows with the same samples (dual-mono) give two bit-identical block rows of the Gram matrix: exactly singular,
+        # but the LU only meets an exact zero when every multiplier x * (1 / x) rounds to 1, which it need not.  Found here.
+        g = torch.arange(ng, device=R.device)
+        Rg = R.reshape(nseg, ng, G, ng, G, -1)[:, g, :, g]                    # [ng, nseg, G(i), G(j), lags]: R[seg, gG+i, gG+j]
+        for i in range(G):
+            for k in range(i + 1, G):
+                bad |= (Rg[:, :, i] == Rg[:, :, k]).flatten(2).all(2).t().reshape(-1)
+    for s in bad.nonzero().flatten().tolist():        # exactly singular (dual-mono, a silent row): minimum-norm least squares
+        seg, base = s // ng, (s % ng) * G
+        rows = list(range(base, base + G))
+        A = _gram(R, seg, rows, flen).cpu()
+        rhs = D[seg, base:base + G, base:base + G].permute(1, 2, 0).reshape(M, G).cpu()
+        C[s] = torch.linalg.lstsq(A, rhs.contiguous(), driver="gelsd").solution.to(C.device)   # (gelsd: see bss_eval._solve)
+    return C
+
+
+def window_energies(refs, ests, C, flen, starts, n, C_all, C_own, range_seg, range_off, rlen):
+    """-> [nrange, S, 7]: the seven energy sums of every (range, source)."""
+    Lb = lib.load()
+    P, L = refs.shape
+    dev, nrange = refs.device, len(range_seg)
+    nbytes = Lb.avsep_bss_window_energies_workspace_bytes(nrange, P, rlen)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    sums = torch.empty((nrange, P // C, TERMS), dtype=torch.float64, device=dev)
+    # (the index arrays stay referenced until the launch is queued: a temporary's block would go to the next temporary)
+    seg, rseg, roff = _i64(starts, dev), torch.tensor(list(range_seg), dtype=torch.int32, device=dev), _i64(range_off, dev)
+    call("avsep_bss_window_energies", ptr(refs), ptr(ests), P, C, L, flen, ptr(seg), len(starts), n, ptr(C_all), ptr(C_own),
+         ptr(rseg), ptr(roff), nrange, rlen, ptr(ws), nbytes, ptr(sums))
+    return sums
+
+
+def _scores(sums, S):
+    """[..., S, 7] -> sdr, isr, sir, sar [...] in dB."""
+    db = lambda a, b: 10 * torch.log10(a / b)                              # noqa: E731
+    sdr, isr = db(sums[..., 0], sums[..., 1]), db(sums[..., 0], sums[..., 2])
+    sir = db(sums[..., 3], sums[..., 4]) if S > 1 else torch.full_like(sdr, math.inf)
+    return sdr, isr, sir, db(sums[..., 5], sums[..., 6])
+
+
+def _silent_windows(refs, ests, starts, wlen):
+    """[W] bool: some reference source or some estimate has exactly zero energy over all its channels inside the window."""
+    silent = torch.zeros((len(starts),), dtype=torch.bool, device=refs.device)
+    a = _i64(starts, refs.device)
+    for x in (refs, ests):
+        nz = ((x * x) != 0).any(1).to(torch.int64)                            # [S, L]
+        cs = torch.nn.functional.pad(nz.cumsum(1), (1, 0))
+        silent |= ((cs[:, a + wlen] - cs[:, a]) == 0).any(0)
+    return silent
+
+
+def _median(frames, S, name):
+    if name == "sir" and S == 1:
+        return torch.full((S,), math.inf, dtype=torch.float64, device=frames.device)
+    return torch.nanquantile(frames, 0.5, dim=1)          # the mean of the two middle windows when their count is even
+
+
+def score_stems(refs, ests, win, hop, filters="track", flen=512, permute=True):
+    """refs, ests: [S, C, L] (or [S, L]: C = 1) tensors on the GPU; win, hop in samples.  -> dict:
+    "perm" (perm[j] = the estimate scored against reference j), "sdr" / "isr" / "sir" / "sar" [S] (nanmedian over windows),
+    "frames" {the four names: [S, W]}, "window_starts", and with filters="track" "track" {the four names: [S]}.
+
+    With permute=True the estimates are matched to the references by the permutation with the largest mean track-level
+    PLAIN SDR, sum s_j^2 / sum (e_i - s_j)^2 over the whole recording (S^2 energy sums, no extra solve; the first
+    permutation in lexicographic order on ties).  This is deliberately simpler than mir_eval, which solves every
+    (estimate, reference) pair and takes the permutation with the largest mean SIR.
+    A window in which a reference source or an estimate is exactly silent is NaN for every source and metric."""
+    lib.require_gpu(refs)
+    lib.require_gpu(ests)
+    if filters not in ("track", "window"):
+        raise AvsepError(f"filters is 'track' or 'window', got {filters!r}")
+    if refs.dim() == 2:
+        refs = refs[:, None]
+    if ests.dim() == 2:
+        ests = ests[:, None]
+    if refs.dim() != 3 or refs.shape != ests.shape:
+        raise AvsepError(f"refs and ests are [S, C, L] of one shape, got {tuple(refs.shape)} and {tuple(ests.shape)}")
+    S, C, L = refs.shape
+    check_limits(S, C, flen)
+    if L < 1:
+        raise AvsepError("score_stems needs at least one sample")
+    starts, wlen = plan_windows(L, int(win), int(hop))
+    refs, ests = refs.double().contiguous(), ests.double().contiguous()
+    P, W, dev = S * C, len(starts), refs.device
+
+    perm = list(range(S))
+    if permute and S > 1:
+        es = (refs * refs).sum((1, 2))
+        plain = [[(10 * torch.log10(es[j] / ((ests[i] - refs[j]) ** 2).sum())).item() for j in range(S)] for i in range(S)]
+        perm = best_permutation(plain)
+        if perm != list(range(S)):
+            ests = ests[perm].contiguous()
+    rr, er = refs.reshape(P, L), ests.reshape(P, L)
+    silent = _silent_windows(refs, ests, starts, wlen)
+    out = {"perm": perm, "window_starts": list(starts)}
+    frames = torch.full((W, S, TERMS), math.nan, dtype=torch.float64, device=dev)
+
+    if filters == "track":
+        R, D = seg_corr(rr, er, flen, [0], L)
+        C_all, C_own = solve_groups(R, D, P, flen), solve_groups(R, D, C, flen)
+        frames = window_energies(rr, er, C, flen, [0], L, C_all, C_own, [0] * W, starts, wlen)
+        track = window_energies(rr, er, C, flen, [0], L, C_all, C_own, [0], [0], L + flen - 1)[0]
+        out["track"] = dict(zip(("sdr", "isr", "sir", "sar"), _scores(track, S)))
+    else:
+        live = [w for w, z in enumerate(silent.tolist()) if not z]                 # silent windows are not solved
+        per_seg = 8 * ((P * flen) ** 2 + S * (C * flen) ** 2) + lib.load().avsep_bss_seg_corr_workspace_bytes(1, P, wlen, flen)
+        nb = int(max(1, min(256, _BATCH_BYTES // per_seg)))
+        for b0 in range(0, len(live), nb):
+            ws = live[b0:b0 + nb]
+            seg = [starts[w] for w in ws]
+            R, D = seg_corr(rr, er, flen, seg, wlen)
+            C_all, C_own = solve_groups(R, D, P, flen), solve_groups(R, D, C, flen)
+            frames[ws] = window_energies(rr, er, C, flen, seg, wlen, C_all, C_own, range(len(ws)), [0] * len(ws), wlen + flen - 1)
+    frames[silent] = math.nan
+    names = ("sdr", "isr", "sir", "sar")
+    out["frames"] = {k: v.t().contiguous() for k, v in zip(names, _scores(frames, S))}      # [S, W]
+    if S == 1:
+        out["frames"]["sir"][:, silent] = math.nan
+    for k in names:
+        out[k] = _median(out["frames"][k], S, k)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the command line
+# ---------------------------------------------------------------------------------------------------------------------
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m avsep_amd.score",
+                                description="Score separated stems against their references: windowed SDR / ISR / SIR / SAR "
+                                            "(image-form BSS-eval, median over windows).")
+    p.add_argument("--ref", nargs="+", required=True, help="the true stems, one 16-bit PCM WAV per source")
+    p.add_argument("--est", nargs="+", required=True, help="the separated stems, as many files (matched to --ref by plain SDR)")
+    p.add_argument("--win", type=float, default=1.0, help="window length in seconds")
+    p.add_argument("--hop", type=float, default=1.0, help="seconds between window starts")
+    p.add_argument("--filters", choices=("track", "window"), default="track",
+                   help="track: one set of distortion filters for the recording (default); window: one per window")
+    p.add_argument("--flen", type=int, default=512, help="taps of the distortion filters")
+    p.add_argument("--json", default=None, help="write the scores (medians, per-window frames, track) to this file")
+    return p
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if len(args.ref) != len(args.est):
+        raise SystemExit(f"--ref names {len(args.ref)} files and --est {len(args.est)}: one estimate per reference")
+    if args.win <= 0 or args.hop <= 0:
+        raise SystemExit("--win and --hop are positive numbers of seconds")
+    return args
+
+
+def read_stems(ref_paths, est_paths):
+    """-> (refs, ests: float64 numpy [S, C, L] in [-1, 1), rate).  All files share one rate and one channel count (nothing is
+    resampled or down-mixed here); the lengths are trimmed to the shortest file."""
+    from .separate import read_wav_pcm
+    data = [read_wav_pcm(p) for p in list(ref_paths) + list(est_paths)]
+    paths = list(ref_paths) + list(est_paths)
+    rate, ch = data[0][1], data[0][0].shape[1]
+    for path, (pcm, r) in zip(paths, data):
+        if r != rate:
+            raise SystemExit(f"{path}: sample rate {r} Hz, but {paths[0]} has {rate} Hz: the scorer does not resample, "
+                             "bring the files to one rate first")
+        if pcm.shape[1] != ch:
+            raise SystemExit(f"{path}: {pcm.shape[1]} channel(s), but {paths[0]} has {ch}: all stems need one channel count")
+    L = min(pcm.shape[0] for pcm, _ in data)
+    if L < 1:
+        raise SystemExit("the shortest file is empty")
+    x = np.stack([pcm[:L].T.astype(np.float64) / 32768.0 for pcm, _ in data])                # [2 S, C, L]
+    return x[:len(ref_paths)], x[len(ref_paths):], rate
+
+
+def _jsonable(t):
+    """Strict JSON has no NaN / Infinity: a silent window is null, an infinite ratio the string "inf" / "-inf"."""
+    one = lambda v: None if math.isnan(v) else (v if math.isfinite(v) else str(v))      # noqa: E731
+    return [[one(v) for v in row] for row in t.tolist()] if t.dim() == 2 else [one(v) for v in t.tolist()]
+
+
+def cli(argv=None):
+    args = parse_args(argv)
+    refs, ests, rate = read_stems(args.ref, args.est)
+    try:
+        check_limits(refs.shape[0], refs.shape[1], args.flen)
+    except AvsepError as e:
+        raise SystemExit(str(e))
+    if not torch.cuda.is_available():
+        raise AvsepError("scoring runs on an MI355X; there is no CPU fallback")
+    dev = torch.device("cuda", 0)
+    win, hop = max(1, int(round(args.win * rate))), max(1, int(round(args.hop * rate)))
+    res = score_stems(torch.from_numpy(refs).to(dev), torch.from_numpy(ests).to(dev), win, hop, args.filters, args.flen)
+    names = ("sdr", "isr", "sir", "sar")
+    for j, path in enumerate(args.ref):
+        line = "  ".join(f"{k.upper()} {res[k][j].item():7.2f} dB" for k in names)
+        print(f"source {j} ({path} <- {args.est[res['perm'][j]]}): {line}")
+    if args.json:
+        doc = {"rate": rate, "win": win, "hop": hop, "filters": args.filters, "flen": args.flen, "perm": res["perm"],
+               "window_starts": res["window_starts"]}
+        doc.update({k: _jsonable(res[k]) for k in names})
+        doc["frames"] = {k: _jsonable(res["frames"][k]) for k in names}
+        if "track" in res:
+            doc["track"] = {k: _jsonable(res["track"][k]) for k in names}
+        with open(args.json, "w") as f:
+            json.dump(doc, f, allow_nan=False)
+    return res
+
+
+if __name__ == "__main__":
+    cli()

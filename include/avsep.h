@@ -648,6 +648,38 @@ int avsep_bss_solve(const double* R, const double* D, int32_t B, int32_t S, int3
 int avsep_bss_project(const double* refs, const double* C, int32_t B, int32_t S, int32_t E, int32_t L, int32_t flen, int32_t mode,
                       double* out, avsep_stream_t stream);
 
+/* ---- Windowed image-form BSS-eval: SDR / ISR / SIR / SAR over all channels of a source, in short windows (csrc/bss_windows.hip;
+ * avsep_amd/score.py).  The reference scores 6 s mono training batches only (asteroid -> mir_eval.separation.bss_eval_sources,
+ * main.py:260-266); this is the image form of the same decomposition (Vincent et al. 2006, bss_decomp_mtifilt) for whole recordings.
+ * float64 throughout.  refs, ests: [P][L], row p = source * C + channel, P = S * C <= 8.  A segment is the samples
+ * [seg_starts[s], seg_starts[s] + n) of every row, treated as zero outside itself; seg_starts [nseg] (int64, device memory), all
+ * segments of a call have the same length n; flen <= 512.
+ * avsep_bss_seg_corr:  R [nseg][P][P][2*flen-1]: R[..][tau + flen - 1] = sum_t r_p[t + tau] * r_q[t],
+ *                      D [nseg][P(estimate e)][P(reference p)][flen]: D[..][k] = sum_t r_p[t - k] * e_e[t]; the rows are read in
+ *                      place, no atomics: per-block partial sums in `workspace` are added in ascending order, so a segment's result
+ *                      is the same bits in every call that holds it.
+ * avsep_bss_solve_groups: the least-squares filters of the row groups g*G .. g*G+G-1 (G divides P; G = C: a source on its own
+ *                      channels, G = P: all sources), G*flen <= 2048 unknowns and G right-hand sides (the estimate rows of the
+ *                      group) per (segment, group): C [nseg * P/G][G*flen][G], info [nseg * P/G] as avsep_bss_solve (the same LU).
+ * avsep_bss_window_energies: range i = samples [range_off[i], range_off[i] + rlen) of segment range_seg[i], relative to the
+ *                      segment's start (range_seg int32 [nrange], range_off int64 [nrange], device memory; the projections live on
+ *                      [0, n + flen - 1)).  With C_all [nseg][P*flen][P] (G = P) and C_own [nseg * S][C*flen][C] (G = C) from
+ *                      avsep_bss_solve_groups, p_all / p_own the two FIR projections of row q, s = r_q, e = e_q:
+ *                      sums [nrange][S][7] = sum over the range and the source's channels of
+ *                      s^2, (e-s)^2, (p_own-s)^2, p_own^2, (p_all-p_own)^2, p_all^2, (e-p_all)^2.  No waveform is written; block
+ *                      partials in `workspace`, then an ordered sum. */
+size_t avsep_bss_seg_corr_workspace_bytes(int32_t nseg, int32_t P, int64_t n, int32_t flen);
+int avsep_bss_seg_corr(const double* refs, const double* ests, int32_t P, int64_t L, int32_t flen, const int64_t* seg_starts,
+                       int32_t nseg, int64_t n, double* workspace, size_t workspace_bytes, double* R, double* D, avsep_stream_t stream);
+size_t avsep_bss_solve_groups_workspace_bytes(int32_t nseg, int32_t P, int32_t G, int32_t flen);
+int avsep_bss_solve_groups(const double* R, const double* D, int32_t nseg, int32_t P, int32_t G, int32_t flen, double* workspace,
+                           size_t workspace_bytes, double* C, int32_t* info, avsep_stream_t stream);
+size_t avsep_bss_window_energies_workspace_bytes(int32_t nrange, int32_t P, int64_t rlen);
+int avsep_bss_window_energies(const double* refs, const double* ests, int32_t P, int32_t C, int64_t L, int32_t flen,
+                              const int64_t* seg_starts, int32_t nseg, int64_t n, const double* C_all, const double* C_own,
+                              const int32_t* range_seg, const int64_t* range_off, int32_t nrange, int64_t rlen, double* workspace,
+                              size_t workspace_bytes, double* sums, avsep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
