@@ -1,17 +1,18 @@
-// Windowed image-form BSS-eval (SDR / ISR / SIR / SAR over all channels of a source; Vincent et al. 2006, bss_decomp_mtifilt for
-// images; the reference scores with asteroid -> mir_eval, main.py:260-266, on 6 s mono batches only).  Float64 throughout.
+// BSS-eval, every form of it in this library: the windowed image form (SDR / ISR / SIR / SAR over all channels of a source; Vincent
+// et al. 2006, bss_decomp_mtifilt for images) and mir_eval's bss_eval_sources on 6 s mono training batches (what the reference
+// scores with, asteroid -> mir_eval, main.py:260-266: a batch [B, S, L] is S rows of B L samples, C = 1, sample b the segment
+// [b L, b L + L)).  Float64 throughout.
 // The rows are p = source * C + channel, P = S * C of them, each [L] samples.  A SEGMENT [a, a + n) is a stretch of the rows that
 // is treated as zero outside itself; all segments of one call have the same length n.
 //   1. bss_seg_corr_kernel + bss_seg_corr_reduce   lagged correlations of every segment, read in place from the [P, L] rows;
 //                                                  register-tiled (8 lags x 8 samples per thread), no atomics: per-block partials,
 //                                                  then a sum in ascending block order
 //   2. bss_solve_groups_kernel                     the least-squares filters of a group of G rows (G = C: own source, G = P: all
-//                                                  sources) by the LU of bss_lu.h, one workgroup per (segment, group)
-//   3. bss_win_energy_kernel + bss_win_energy_reduce  both FIR projections of a row and the seven residual energies of a sample
+//                                                  sources) by LU with partial pivoting, one workgroup per (segment, group)
+//   3. bss_win_energy_kernel + bss_win_energy_reduce  both FIR projections of a row and the eight residual energies of a sample
 //                                                  RANGE of its segment, in registers: no projected waveform is written out
 // Every offset into the rows is formed in 64 bits (ten minutes at 48 kHz are 2.9e7 samples per row).
 #include "common.h"
-#include "bss_lu.h"
 
 // LDS images whose readers sit 8 doubles apart (a thread owns 8 consecutive lags / outputs) get two pad doubles per 8: every
 // block of 8 stays contiguous and 16-byte aligned (ds_read_b128), and lane l reads byte 80 l + const, bank 4 (5 l mod 16): the
@@ -169,7 +170,105 @@ extern "C" int avsep_bss_seg_corr(const double* refs, const double* ests, int32_
 // ---- 2. the least-squares systems of row groups ------------------------------------------------------------------------------------
 // System seg * (P / G) + g: the rows g G .. g G + G - 1 of segment seg.  M = G * flen unknowns, G right-hand sides (the estimate
 // rows of the same group): A[(i,a)][(j,c)] = R[seg][gG+i][gG+j][c - a + flen - 1], right-hand side e: D[seg][gG+e][gG+i][a].
-// C [system][M][G].  The build differs from bss_solve_kernel in its indexing only; the solve is bss_lu.h's.
+// C [system][M][G].
+// bss_lu_solve: one workgroup of 1024 threads; the caller has built the M x M matrix A column-major in global memory (a thread owns
+// rows tid, tid + 1024, ...: every access to a column is coalesced) and the `nrhs` right-hand sides x [nrhs][M] in LDS, and has
+// synchronised.  LU with partial pivoting exactly as LAPACK getrf / numpy.linalg.solve (row swaps applied at once), then the two
+// triangular solves on the right-hand sides.  *info = k + 1 when the k-th pivot is exactly zero (the solution is written as zeros
+// and the caller falls back to minimum-norm least squares), else 0.  out: [M][nrhs].
+__device__ __forceinline__ void bss_lu_solve(double* __restrict__ A, int M, int nrhs, double* rowk, double* x, int* __restrict__ info,
+                                             double* __restrict__ out) {
+  const int tid = threadIdx.x;
+  __shared__ double red_v[16];
+  __shared__ int red_i[16];
+  __shared__ int s_piv;
+  __shared__ double s_pivval;
+  bool singular = false;
+  for (int k = 0; k < M; ++k) {
+    // pivot search in column k
+    double best = -1.0;
+    int bi = k;
+    for (int r = tid; r < M; r += 1024)
+      if (r >= k) {
+        const double v = fabs(A[(long long)k * M + r]);
+        if (v > best) { best = v; bi = r; }
+      }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const double ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if ((tid & 63) == 0) { red_v[tid >> 6] = best; red_i[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      double bv = red_v[0];
+      int bx = red_i[0];
+      for (int w = 1; w < 16; ++w)
+        if (red_v[w] > bv || (red_v[w] == bv && red_i[w] < bx)) { bv = red_v[w]; bx = red_i[w]; }
+      s_piv = bx;
+      s_pivval = bv;
+    }
+    __syncthreads();
+    const int p = s_piv;
+    if (!(s_pivval > 0.0)) { singular = true; if (tid == 0) *info = k + 1; break; }   // exactly singular (or NaN)
+    // swap rows k and p in every column and in the right-hand sides; stage row k of U
+    for (int c = tid; c < M; c += 1024) {
+      double vk = A[(long long)c * M + k];
+      if (p != k) {
+        const double vp = A[(long long)c * M + p];
+        A[(long long)c * M + p] = vk;
+        A[(long long)c * M + k] = vp;
+        vk = vp;
+      }
+      rowk[c] = vk;
+    }
+    if (p != k && tid < nrhs) {
+      const double t = x[tid * M + k];
+      x[tid * M + k] = x[tid * M + p];
+      x[tid * M + p] = t;
+    }
+    __syncthreads();
+    const double inv = 1.0 / rowk[k];
+    // column k of L, trailing update, and the forward substitution of the right-hand sides folded into the same sweep
+    for (int r = tid; r < M; r += 1024)
+      if (r > k) {
+        const double l = A[(long long)k * M + r] * inv;
+        A[(long long)k * M + r] = l;
+        // the sweep is latency-bound (an 8 MB matrix per system, one row element per column): 16 independent loads in flight
+        int c = k + 1;
+        for (; c + 16 <= M; c += 16) {
+          double v[16];
+#pragma unroll
+          for (int u = 0; u < 16; ++u) v[u] = A[(long long)(c + u) * M + r];
+#pragma unroll
+          for (int u = 0; u < 16; ++u) A[(long long)(c + u) * M + r] = fma(-l, rowk[c + u], v[u]);
+        }
+        for (; c < M; ++c) A[(long long)c * M + r] = fma(-l, rowk[c], A[(long long)c * M + r]);
+        for (int q = 0; q < nrhs; ++q) x[q * M + r] = fma(-l, x[q * M + k], x[q * M + r]);
+      }
+    __syncthreads();
+  }
+  if (singular) {
+    for (int q = 0; q < nrhs; ++q)
+      for (int r = tid; r < M; r += 1024) out[(long long)r * nrhs + q] = 0.0;
+    return;
+  }
+  if (tid == 0) *info = 0;
+  // back substitution with U (the forward half was done on the fly)
+  for (int k = M - 1; k >= 0; --k) {
+    if (tid < nrhs) x[tid * M + k] /= A[(long long)k * M + k];
+    __syncthreads();
+    for (int r = tid; r < k; r += 1024) {
+      const double u = A[(long long)k * M + r];
+      for (int q = 0; q < nrhs; ++q) x[q * M + r] = fma(-u, x[q * M + k], x[q * M + r]);
+    }
+    __syncthreads();
+  }
+  for (int q = 0; q < nrhs; ++q)
+    for (int r = tid; r < M; r += 1024) out[(long long)r * nrhs + q] = x[q * M + r];
+}
+
 __global__ __launch_bounds__(1024) void bss_solve_groups_kernel(const double* __restrict__ R, const double* __restrict__ D, int P, int G, int flen,
                                                                 double* __restrict__ work, double* __restrict__ C, int* __restrict__ info) {
   extern __shared__ double sg_smem[];
@@ -223,14 +322,15 @@ extern "C" int avsep_bss_solve_groups(const double* R, const double* D, int32_t 
 // [0, n + flen - 1), samples past that count as nothing).  For row q = j C + c of the range's segment and every sample t:
 //   p_all = sum_p sum_k C_all[seg][(p,k)][q] r_p[t - k]           C_all [nseg][P * flen][P]
 //   p_own = sum_i sum_k C_own[seg * S + j][(i,k)][c] r_{jC+i}[t - k]   C_own [nseg * S][C * flen][C]
-//   s = r_q[t], e = e_q[t] (zero from n on), and the seven squares
-//   0: s^2   1: (e - s)^2   2: (p_own - s)^2   3: p_own^2   4: (p_all - p_own)^2   5: p_all^2   6: (e - p_all)^2
+//   s = r_q[t], e = e_q[t] (zero from n on), and the eight squares, each summed on its own
+//   0: s^2   1: (e - s)^2   2: (p_own - s)^2   3: p_own^2   4: (p_all - p_own)^2   5: p_all^2   6: (e - p_all)^2   7: (e - p_own)^2
+// (the image form uses 0 .. 6; mir_eval's SDR, sum 3 / sum 7, counts e_interf + e_artif = e - p_own as the distortion)
 // grid (chunks of 1024 samples, P, ranges), 128 threads, a thread owns 8 consecutive samples.  The reference rows pass through
 // LDS one at a time (window of 1024 + flen8 - 1 samples, padded by pad8, and that row's taps); per 8 taps a thread reads 8 new
 // window values and 8 (16 on an own-source row) taps (a broadcast) for 64 (128) FMAs.  A block's sums (thread: ascending
 // samples; wave: butterfly; waves: ascending) go to its slot of `part`; the reduce pass adds a range's slots, strided over the 64
 // lanes of one wave in ascending order, then the butterfly: the order is a function of rlen alone.
-constexpr int EN_OUT = 1024, EN_T = 8, EN_THREADS = 128, EN_TERMS = 7;
+constexpr int EN_OUT = 1024, EN_T = 8, EN_THREADS = 128, EN_TERMS = 8;
 
 __global__ __launch_bounds__(EN_THREADS) void bss_win_energy_kernel(const double* __restrict__ refs, const double* __restrict__ ests, int P, int Cn,
                                                                     long long L, int flen, const long long* __restrict__ seg_starts, int nseg,
@@ -308,7 +408,7 @@ __global__ __launch_bounds__(EN_THREADS) void bss_win_energy_kernel(const double
     if (t >= 0 && t < t_end) {
       const bool in = t < n && ta >= 0 && ta < L;
       const double s = in ? refs[(long long)q * L + ta] : 0.0, e = in ? ests[(long long)q * L + ta] : 0.0;
-      const double d1 = e - s, d2 = po[i] - s, d4 = pa[i] - po[i], d6 = e - pa[i];
+      const double d1 = e - s, d2 = po[i] - s, d4 = pa[i] - po[i], d6 = e - pa[i], d7 = e - po[i];
       sum[0] = fma(s, s, sum[0]);
       sum[1] = fma(d1, d1, sum[1]);
       sum[2] = fma(d2, d2, sum[2]);
@@ -316,6 +416,7 @@ __global__ __launch_bounds__(EN_THREADS) void bss_win_energy_kernel(const double
       sum[4] = fma(d4, d4, sum[4]);
       sum[5] = fma(pa[i], pa[i], sum[5]);
       sum[6] = fma(d6, d6, sum[6]);
+      sum[7] = fma(d7, d7, sum[7]);
     }
   }
 #pragma unroll

@@ -17,10 +17,11 @@ and, energies summed over the channels of a source and a sample range T,
 
 taken in short windows, the median over windows reported.  filters="track" fits one set of filters on the whole recording
 and scores every window (and the whole padded recording: "track") with it; filters="window" fits every window on its own
-(one full-length window at C = 1 is bss_eval_sources' SIR and SAR).  Everything is float64 on the GPU through three entry
-points of csrc/bss_windows.hip: lagged correlations read in place (no window is copied), the dense LU of bsseval.hip per
-(segment, source group), and the two FIR projections with their residual energies (no projected waveform is stored).
-Exactly singular Gram matrices (dual-mono: a mono file saved as stereo) take bss_eval.py's host least-squares path.
+(one full-length window at C = 1 is bss_eval_sources' SIR and SAR, and runs the same code).  Everything is float64 on the GPU
+through the three entry points of csrc/bss_windows.hip, whose host layer is bss_eval.py: lagged correlations read in place (no
+window is copied), a dense LU per (segment, source group), and the two FIR projections with their residual energies (no
+projected waveform is stored); exactly singular Gram matrices (dual-mono: a mono file saved as stereo) take its host
+least-squares path.  Here: window planning, the permutation, silence, the medians and the command line.
 """
 import argparse
 import itertools
@@ -31,12 +32,9 @@ import numpy as np
 import torch
 
 from . import lib
-from .lib import AvsepError, call, ptr
-
-MAX_ROWS = 8                 # P = S * C
-MAX_UNKNOWNS = 2048          # P * flen: the dense solver's size (one workgroup per system)
-TERMS = 7                    # s^2, (e-s)^2, e_spat^2, (s+e_spat)^2, e_interf^2, p_all^2, e_artif^2
-_BATCH_BYTES = 8 << 30       # workspace budget of one batch of windows in filters="window" (50 MB per window at 2048 unknowns)
+from .bss_eval import (MAX_ROWS, MAX_UNKNOWNS, TERMS, _gram, _i64, check_limits, seg_corr, segment_energies,      # noqa: F401
+                       solve_groups, window_energies)
+from .lib import AvsepError
 
 
 def plan_windows(L, win, hop):
@@ -61,86 +59,8 @@ def best_permutation(sdr_db):
     return list(best)
 
 
-def check_limits(S, C, flen):
-    P = S * C
-    if S < 1 or C < 1:
-        raise AvsepError(f"score_stems needs at least one source and one channel (1 <= S), got S={S} C={C}")
-    if P > MAX_ROWS:
-        raise AvsepError(f"score_stems takes at most P = S * C <= {MAX_ROWS} rows, got {S} sources x {C} channels = {P}")
-    if flen < 1 or P * flen > MAX_UNKNOWNS:
-        raise AvsepError(f"score_stems solves at most P * flen <= {MAX_UNKNOWNS} unknowns (the dense solver's size), "
-                         f"got {P} rows x flen {flen} = {P * flen}")
-
-
-def _i64(vals, dev):
-    return torch.tensor(list(vals), dtype=torch.int64, device=dev)
-
-
-def seg_corr(refs, ests, flen, starts, n):
-    """refs, ests [P, L] float64; segments [starts[i], starts[i] + n).  -> R [nseg, P, P, 2 flen - 1], D [nseg, P(est), P(ref), flen]."""
-    Lb = lib.load()
-    P, L = refs.shape
-    dev, nseg = refs.device, len(starts)
-    nbytes = Lb.avsep_bss_seg_corr_workspace_bytes(nseg, P, n, flen)
-    ws = torch.empty((max(nbytes // 8, 1),), dtype=torch.float64, device=dev)
-    R = torch.empty((nseg, P, P, 2 * flen - 1), dtype=torch.float64, device=dev)
-    D = torch.empty((nseg, P, P, flen), dtype=torch.float64, device=dev)
-    seg = _i64(starts, dev)
-    call("avsep_bss_seg_corr", ptr(refs), ptr(ests), P, L, flen, ptr(seg), nseg, n, ptr(ws), nbytes, ptr(R), ptr(D))
-    return R, D
-
-
-def _gram(R, seg, rows, flen):
-    k = torch.arange(flen, device=R.device)
-    lag = (k[None, :] - k[:, None]) + flen - 1                              # [a, c] -> c - a + flen - 1
-    return torch.cat([torch.cat([R[seg, i, j][lag] for j in rows], 1) for i in rows], 0)
-
-
-def solve_groups(R, D, G, flen):
-    """The filters of every (segment, group of G rows): [nseg * P / G, G * flen, G]."""
-    Lb = lib.load()
-    nseg, P = R.shape[:2]
-    ng, M = P // G, G * flen
-    nbytes = Lb.avsep_bss_solve_groups_workspace_bytes(nseg, P, G, flen)
-    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=R.device)
-    C = torch.empty((nseg * ng, M, G), dtype=torch.float64, device=R.device)
-    info = torch.empty((nseg * ng,), dtype=torch.int32, device=R.device)
-    call("avsep_bss_solve_groups", ptr(R), ptr(D), nseg, P, G, flen, ptr(ws), nbytes, ptr(C), ptr(info))
-    bad = info != 0
-    if G > 1:
-        # Two rows with the same samples (dual-mono) give two bit-identical block rows of the Gram matrix: exactly singular,
-        # but the LU only meets an exact zero when every multiplier x * (1 / x) rounds to 1, which it need not.  Found here.
-        g = torch.arange(ng, device=R.device)
-        Rg = R.reshape(nseg, ng, G, ng, G, -1)[:, g, :, g]                    # [ng, nseg, G(i), G(j), lags]: R[seg, gG+i, gG+j]
-        for i in range(G):
-            for k in range(i + 1, G):
-                bad |= (Rg[:, :, i] == Rg[:, :, k]).flatten(2).all(2).t().reshape(-1)
-    for s in bad.nonzero().flatten().tolist():        # exactly singular (dual-mono, a silent row): minimum-norm least squares
-        seg, base = s // ng, (s % ng) * G
-        rows = list(range(base, base + G))
-        A = _gram(R, seg, rows, flen).cpu()
-        rhs = D[seg, base:base + G, base:base + G].permute(1, 2, 0).reshape(M, G).cpu()
-        C[s] = torch.linalg.lstsq(A, rhs.contiguous(), driver="gelsd").solution.to(C.device)   # (gelsd: see bss_eval._solve)
-    return C
-
-
-def window_energies(refs, ests, C, flen, starts, n, C_all, C_own, range_seg, range_off, rlen):
-    """-> [nrange, S, 7]: the seven energy sums of every (range, source)."""
-    Lb = lib.load()
-    P, L = refs.shape
-    dev, nrange = refs.device, len(range_seg)
-    nbytes = Lb.avsep_bss_window_energies_workspace_bytes(nrange, P, rlen)
-    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
-    sums = torch.empty((nrange, P // C, TERMS), dtype=torch.float64, device=dev)
-    # (the index arrays stay referenced until the launch is queued: a temporary's block would go to the next temporary)
-    seg, rseg, roff = _i64(starts, dev), torch.tensor(list(range_seg), dtype=torch.int32, device=dev), _i64(range_off, dev)
-    call("avsep_bss_window_energies", ptr(refs), ptr(ests), P, C, L, flen, ptr(seg), len(starts), n, ptr(C_all), ptr(C_own),
-         ptr(rseg), ptr(roff), nrange, rlen, ptr(ws), nbytes, ptr(sums))
-    return sums
-
-
 def _scores(sums, S):
-    """[..., S, 7] -> sdr, isr, sir, sar [...] in dB."""
+    """[..., S, 8] -> sdr, isr, sir, sar [...] in dB."""
     db = lambda a, b: 10 * torch.log10(a / b)                              # noqa: E731
     sdr, isr = db(sums[..., 0], sums[..., 1]), db(sums[..., 0], sums[..., 2])
     sir = db(sums[..., 3], sums[..., 4]) if S > 1 else torch.full_like(sdr, math.inf)
@@ -212,14 +132,8 @@ def score_stems(refs, ests, win, hop, filters="track", flen=512, permute=True):
         out["track"] = dict(zip(("sdr", "isr", "sir", "sar"), _scores(track, S)))
     else:
         live = [w for w, z in enumerate(silent.tolist()) if not z]                 # silent windows are not solved
-        per_seg = 8 * ((P * flen) ** 2 + S * (C * flen) ** 2) + lib.load().avsep_bss_seg_corr_workspace_bytes(1, P, wlen, flen)
-        nb = int(max(1, min(256, _BATCH_BYTES // per_seg)))
-        for b0 in range(0, len(live), nb):
-            ws = live[b0:b0 + nb]
-            seg = [starts[w] for w in ws]
-            R, D = seg_corr(rr, er, flen, seg, wlen)
-            C_all, C_own = solve_groups(R, D, P, flen), solve_groups(R, D, C, flen)
-            frames[ws] = window_energies(rr, er, C, flen, seg, wlen, C_all, C_own, range(len(ws)), [0] * len(ws), wlen + flen - 1)
+        if live:
+            frames[live] = segment_energies(rr, er, C, flen, [starts[w] for w in live], wlen)
     frames[silent] = math.nan
     names = ("sdr", "isr", "sir", "sar")
     out["frames"] = {k: v.t().contiguous() for k, v in zip(names, _scores(frames, S))}      # [S, W]

@@ -631,26 +631,10 @@ int avsep_b16_maxpool_bn_relu_bwd(const void* g, const void* g2, const void* idx
 /* avsep_space_to_depth2 written as a one-block B16 image [N][1][H/2+3][W/2+3][16] (4*C <= 16) */
 int avsep_b16_space_to_depth2(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, void* xs, avsep_stream_t stream);
 
-/* ---- BSS-eval SDR / SIR / SAR (eval path; replaces asteroid -> mir_eval.separation.bss_eval_sources, main.py:260-266) ----------
- * float64 throughout, as mir_eval.  refs [B][S][L], ests [B][E][L] (E == S in the reference's use), flen <= 512 delayed copies.
- * avsep_bss_corr:    R [B][S][S][2*flen-1]: R[..][tau + flen - 1] = sum_t ref_i[t + tau] * ref_j[t]  (the block-Toeplitz Gram matrix),
- *                    D [B][E][S][flen]:     D[..][k] = sum_t ref_i[t - k] * est_e[t]                 (the right-hand sides).
- * avsep_bss_solve:   least-squares filters by LU with partial pivoting (numpy.linalg.solve's algorithm), one workgroup per system.
- *                    mode 0: all sources, C [B][S*flen][E];  mode 1: own source only (E == S), C [B*S][flen][1].
- *                    info[system] = 0, or k + 1 when pivot k is exactly zero (a silent source): C is zero there and the caller
- *                    solves that system by minimum-norm least squares, as mir_eval does.  workspace: avsep_bss_solve_workspace_bytes.
- * avsep_bss_project: out [B][E][L + flen - 1] = sum_i conv(C_i, ref_i) (mode 0) or conv(C_e, ref_e) (mode 1). */
-int avsep_bss_corr(const double* refs, const double* ests, int32_t B, int32_t S, int32_t E, int32_t L, int32_t flen, double* R, double* D,
-                   avsep_stream_t stream);
-size_t avsep_bss_solve_workspace_bytes(int32_t B, int32_t S, int32_t flen, int32_t mode);
-int avsep_bss_solve(const double* R, const double* D, int32_t B, int32_t S, int32_t E, int32_t flen, int32_t mode, double* workspace,
-                    size_t workspace_bytes, double* C, int32_t* info, avsep_stream_t stream);
-int avsep_bss_project(const double* refs, const double* C, int32_t B, int32_t S, int32_t E, int32_t L, int32_t flen, int32_t mode,
-                      double* out, avsep_stream_t stream);
-
-/* ---- Windowed image-form BSS-eval: SDR / ISR / SIR / SAR over all channels of a source, in short windows (csrc/bss_windows.hip;
- * avsep_amd/score.py).  The reference scores 6 s mono training batches only (asteroid -> mir_eval.separation.bss_eval_sources,
- * main.py:260-266); this is the image form of the same decomposition (Vincent et al. 2006, bss_decomp_mtifilt) for whole recordings.
+/* ---- BSS-eval (csrc/bss_windows.hip; avsep_amd/bss_eval.py, avsep_amd/score.py): SDR / SIR / SAR of 6 s mono training batches (eval
+ * path; replaces asteroid -> mir_eval.separation.bss_eval_sources, main.py:260-266) and the image form of the same decomposition
+ * (Vincent et al. 2006, bss_decomp_mtifilt) for whole recordings: SDR / ISR / SIR / SAR over all channels of a source, in short
+ * windows.  A batch [B][S][L] is the rows [S][B*L], C = 1, sample b the segment [b*L, b*L + L).
  * float64 throughout.  refs, ests: [P][L], row p = source * C + channel, P = S * C <= 8.  A segment is the samples
  * [seg_starts[s], seg_starts[s] + n) of every row, treated as zero outside itself; seg_starts [nseg] (int64, device memory), all
  * segments of a call have the same length n; flen <= 512.
@@ -660,14 +644,16 @@ int avsep_bss_project(const double* refs, const double* C, int32_t B, int32_t S,
  *                      is the same bits in every call that holds it.
  * avsep_bss_solve_groups: the least-squares filters of the row groups g*G .. g*G+G-1 (G divides P; G = C: a source on its own
  *                      channels, G = P: all sources), G*flen <= 2048 unknowns and G right-hand sides (the estimate rows of the
- *                      group) per (segment, group): C [nseg * P/G][G*flen][G], info [nseg * P/G] as avsep_bss_solve (the same LU).
+ *                      group) per (segment, group), by LU with partial pivoting (numpy.linalg.solve's algorithm), one workgroup
+ *                      per system: C [nseg * P/G][G*flen][G]; info [nseg * P/G] = 0, or k + 1 when pivot k is exactly zero (a silent
+ *                      row): C is zero there and the caller solves that system by minimum-norm least squares, as mir_eval does.
  * avsep_bss_window_energies: range i = samples [range_off[i], range_off[i] + rlen) of segment range_seg[i], relative to the
  *                      segment's start (range_seg int32 [nrange], range_off int64 [nrange], device memory; the projections live on
  *                      [0, n + flen - 1)).  With C_all [nseg][P*flen][P] (G = P) and C_own [nseg * S][C*flen][C] (G = C) from
  *                      avsep_bss_solve_groups, p_all / p_own the two FIR projections of row q, s = r_q, e = e_q:
- *                      sums [nrange][S][7] = sum over the range and the source's channels of
- *                      s^2, (e-s)^2, (p_own-s)^2, p_own^2, (p_all-p_own)^2, p_all^2, (e-p_all)^2.  No waveform is written; block
- *                      partials in `workspace`, then an ordered sum. */
+ *                      sums [nrange][S][8] = sum over the range and the source's channels of
+ *                      s^2, (e-s)^2, (p_own-s)^2, p_own^2, (p_all-p_own)^2, p_all^2, (e-p_all)^2, (e-p_own)^2 (the last is the
+ *                      distortion of mir_eval's SDR).  No waveform is written; block partials in `workspace`, then an ordered sum. */
 size_t avsep_bss_seg_corr_workspace_bytes(int32_t nseg, int32_t P, int64_t n, int32_t flen);
 int avsep_bss_seg_corr(const double* refs, const double* ests, int32_t P, int64_t L, int32_t flen, const int64_t* seg_starts,
                        int32_t nseg, int64_t n, double* workspace, size_t workspace_bytes, double* R, double* D, avsep_stream_t stream);

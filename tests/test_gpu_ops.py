@@ -1117,12 +1117,13 @@ def test_bss_eval_vs_oracle(dev):
 
 @pytest.mark.parametrize("B,S,L,flen", [(3, 2, 20000, 512), (2, 3, 9000, 512), (2, 2, 3000, 64), (1, 1, 5000, 512)])
 def test_bss_eval_kernels_vs_oracle(dev, B, S, L, flen):
-    """csrc/bsseval.hip against the numpy restatement of mir_eval (oracle/bss_eval.py) on correlated mixtures: more samples,
-    three sources (a 1536 x 1536 system per sample), a short filter, a single source; and the pieces on their own — the
-    lagged correlations against numpy.correlate, the solved filters against numpy.linalg.solve on the same Gram matrix."""
+    """bss_eval_sources (csrc/bss_windows.hip on the batch-as-segments layout: S rows of B L samples, sample b the segment
+    [b L, b L + L)) against the numpy restatement of mir_eval (oracle/bss_eval.py) on correlated mixtures: more samples,
+    three sources (a 1536 x 1536 system per sample), a short filter, a single source; and the pieces on their own, for
+    sample 0 and the last sample (a wrong segment offset shows there) — the lagged correlations against numpy.correlate,
+    the solved filters against numpy.linalg.solve on the same Gram matrix."""
     from oracle import bss_eval as OB
     from avsep_amd import bss_eval as PB
-    P = _pkg()
     rs = np.random.RandomState(B * 100 + S * 10 + flen)
     s = rs.randn(B, S, L)
     s[:, :, 1:] += 0.6 * s[:, :, :-1]                                     # coloured sources: an ill-conditioned Gram matrix
@@ -1136,20 +1137,19 @@ def test_bss_eval_kernels_vs_oracle(dev, B, S, L, flen):
                 if np.isfinite(ref[j]) and ref[j] < 100:
                     assert abs(got[b, j].item() - ref[j]) < 1e-3, (name, b, j, got[b, j].item(), ref[j])
     # the pieces: correlations and one solved system
-    K = P.kernels
-    R = torch.empty((B, S, S, 2 * flen - 1), dtype=torch.float64, device=dev)
-    D = torch.empty((B, S, S, flen), dtype=torch.float64, device=dev)
-    rt, et = torch.from_numpy(s).to(dev), torch.from_numpy(ests).to(dev)
-    P.lib.call("avsep_bss_corr", K.ptr(rt), K.ptr(et), B, S, S, L, flen, K.ptr(R), K.ptr(D))
+    rt, et = (torch.from_numpy(x).to(dev).transpose(0, 1).reshape(S, B * L).contiguous() for x in (s, ests))
+    R, D = PB.seg_corr(rt, et, flen, [b * L for b in range(B)], L)
+    C = PB.solve_groups(R, D, S, flen)
+    assert R.shape == (B, S, S, 2 * flen - 1) and D.shape == (B, S, S, flen) and C.shape == (B, S * flen, S)
     i, j, e = 0, S - 1, S - 1
-    full = np.correlate(s[0, i], s[0, j], "full")                         # full[L - 1 + tau] = sum_t a[t + tau] * b[t]
-    assert_close(R[0, i, j], torch.from_numpy(full[L - 1 - (flen - 1):L - 1 + flen].copy()), 1e-11, "lagged correlations")
-    fe = np.correlate(ests[0, e], s[0, i], "full")                        # fe[L - 1 + k] = sum_t est[t + k] * ref[t] = sum_t ref[t - k] est[t]
-    assert_close(D[0, e, i], torch.from_numpy(fe[L - 1:L - 1 + flen].copy()), 1e-11, "right-hand sides")
-    C = PB._solve(R, D, B, S, S, flen, 0)
-    G = PB._gram(R, 0, list(range(S)), flen).cpu().numpy()
-    rhs = D[0].reshape(S, S * flen).t().cpu().numpy()
-    assert_close(C[0], torch.from_numpy(np.linalg.solve(G, rhs)), 1e-6, "filters vs numpy.linalg.solve on the same Gram matrix")
+    for b in sorted({0, B - 1}):
+        full = np.correlate(s[b, i], s[b, j], "full")                     # full[L - 1 + tau] = sum_t a[t + tau] * b[t]
+        assert_close(R[b, i, j], torch.from_numpy(full[L - 1 - (flen - 1):L - 1 + flen].copy()), 1e-11, f"lagged correlations, sample {b}")
+        fe = np.correlate(ests[b, e], s[b, i], "full")                    # fe[L - 1 + k] = sum_t est[t + k] * ref[t] = sum_t ref[t - k] est[t]
+        assert_close(D[b, e, i], torch.from_numpy(fe[L - 1:L - 1 + flen].copy()), 1e-11, f"right-hand sides, sample {b}")
+        G = PB._gram(R, b, list(range(S)), flen).cpu().numpy()
+        rhs = D[b].reshape(S, S * flen).t().cpu().numpy()
+        assert_close(C[b], torch.from_numpy(np.linalg.solve(G, rhs)), 1e-6, f"filters vs numpy.linalg.solve on the same Gram matrix, sample {b}")
 
 
 def test_bss_eval_silent_source_takes_the_least_squares_fallback(dev):

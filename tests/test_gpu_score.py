@@ -1,5 +1,6 @@
 """gpu: avsep_amd.score.score_stems and the three entry points of csrc/bss_windows.hip against the numpy restatement
-tests/score_ref.py (pinned on the CPU by test_score_host.py), against the merged mono scorer, and for determinism."""
+tests/score_ref.py (pinned on the CPU by test_score_host.py), the batch scorer bss_eval_sources on the same kernels against
+oracle/bss_eval.py, and both for determinism."""
 import json
 
 import numpy as np
@@ -126,17 +127,70 @@ def test_correlations_many_chunks_per_block(dev):
 
 @pytest.mark.parametrize("S,L,flen", [(2, 6000, 512), (3, 3000, 64)])
 def test_one_full_window_is_the_merged_mono_scorer(dev, S, L, flen):
-    """C = 1, filters="window", one full-length window: SIR and SAR of bss_eval.bss_eval_sources (1e-3 dB); SDR is the plain
-    ratio (1e-9 dB against torch float64)."""
+    """C = 1, filters="window", one full-length window: SIR and SAR of bss_eval.bss_eval_sources, which runs the same
+    kernels, so oracle/bss_eval.py on the CPU is the arbiter of both (1e-3 dB), and of bss_eval_sources' SDR; score_stems'
+    SDR is the plain ratio (1e-9 dB against torch float64)."""
     from avsep_amd import bss_eval as PB
+    from oracle import bss_eval as OB
     s, e = make_inputs(S, 1, L, 40 + S)
     st, et = torch.from_numpy(s).to(dev), torch.from_numpy(e).to(dev)
     got = _score().score_stems(st, et, L, L, "window", flen, permute=False)
-    _, sir, sar = PB.bss_eval_sources(st[:, 0][None], et[:, 0][None], flen)
+    sdr, sir, sar = PB.bss_eval_sources(st[:, 0][None], et[:, 0][None], flen)
+    osdr, osir, osar = (torch.from_numpy(np.asarray(x)).to(dev) for x in OB.bss_eval_sources(s[:, 0], e[:, 0], flen))
     assert got["frames"]["sir"].shape == (S, 1)
-    assert (got["sir"] - sir[0]).abs().max().item() < DB_TOL and (got["sar"] - sar[0]).abs().max().item() < DB_TOL, (got, sir, sar)
+    for name, ours, ref in (("score_stems sir", got["sir"], osir), ("score_stems sar", got["sar"], osar),
+                            ("bss_eval_sources sdr", sdr[0], osdr), ("bss_eval_sources sir", sir[0], osir),
+                            ("bss_eval_sources sar", sar[0], osar)):
+        assert torch.isfinite(ref).all() and (ref < 100).all(), (name, ref)
+        print(f"{name}: max |d| = {(ours - ref).abs().max().item():.3e} dB")
+        assert (ours - ref).abs().max().item() < DB_TOL, (name, ours, ref)
     plain = 10 * torch.log10((st ** 2).sum((1, 2)) / ((et - st) ** 2).sum((1, 2)))
     assert (got["sdr"] - plain).abs().max().item() < 1e-9
+
+
+_batch = {}
+
+
+def batch_inputs(dev):
+    """B = 3, S = 2, L = 3000 (not a multiple of the correlation kernel's 2048-sample chunk: samples 1 and 2 start inside a
+    chunk), flen = 64; make_inputs' recipe per sample."""
+    if not _batch:
+        pairs = [make_inputs(2, 1, 3000, 500 + b) for b in range(3)]
+        _batch["s"], _batch["e"] = (np.stack([p[k][:, 0] for p in pairs]) for k in (0, 1))
+    return torch.from_numpy(_batch["s"]).to(dev), torch.from_numpy(_batch["e"]).to(dev), 64
+
+
+def _same_triple(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def test_bss_eval_sources_two_calls_give_identical_bits(dev):
+    from avsep_amd import bss_eval as PB
+    st, et, flen = batch_inputs(dev)
+    a = PB.bss_eval_sources(st, et, flen)
+    assert all(x.shape == (3, 2) and torch.isfinite(x).all() for x in a)
+    assert _same_triple(a, PB.bss_eval_sources(st, et, flen))
+
+
+def test_bss_eval_sources_a_sample_alone_is_the_sample_in_the_batch(dev):
+    from avsep_amd import bss_eval as PB
+    st, et, flen = batch_inputs(dev)
+    a = PB.bss_eval_sources(st, et, flen)
+    for b in range(3):
+        one = PB.bss_eval_sources(st[b:b + 1], et[b:b + 1], flen)
+        assert _same_triple([x[b:b + 1] for x in a], one), b
+
+
+def test_bss_eval_sources_split_into_batches_is_the_unsplit_call(dev, monkeypatch):
+    from avsep_amd import bss_eval as PB
+    st, et, flen = batch_inputs(dev)
+    a = PB.bss_eval_sources(st, et, flen)
+    calls = []
+    seg_corr = PB.seg_corr
+    monkeypatch.setattr(PB, "seg_corr", lambda r, e, f, starts, n: calls.append(len(starts)) or seg_corr(r, e, f, starts, n))
+    monkeypatch.setattr(PB, "_BATCH_BYTES", 1)                # below one segment's workspace: one sample per batch
+    assert _same_triple(a, PB.bss_eval_sources(st, et, flen))
+    assert calls == [1, 1, 1], calls
 
 
 def _same_bits(a, b):
@@ -230,7 +284,9 @@ def test_one_source_and_limits(dev, monkeypatch):
 
     def no_launch(*a, **k):
         raise AssertionError("a kernel was launched")
-    monkeypatch.setattr(SC, "call", no_launch)
+    from avsep_amd import bss_eval as PB
+    assert not hasattr(SC, "call"), "score.py launches nothing itself: every launch goes through bss_eval.call"
+    monkeypatch.setattr(PB, "call", no_launch)
     z = torch.zeros((3, 2, 1000), device=dev)
     with pytest.raises(SC.AvsepError, match="P \\* flen <= 2048"):
         SC.score_stems(z, z, 500, 500, "track", 342)
@@ -238,6 +294,10 @@ def test_one_source_and_limits(dev, monkeypatch):
         SC.score_stems(torch.zeros((3, 3, 100), device=dev), torch.zeros((3, 3, 100), device=dev), 50, 50)
     with pytest.raises(SC.AvsepError):
         SC.score_stems(torch.zeros((2, 2, 100)), torch.zeros((2, 2, 100)), 50, 50)          # CPU tensors: no fallback
+    with pytest.raises(SC.AvsepError, match="<= 8 rows"):
+        PB.bss_eval_sources(torch.zeros((1, 9, 100), device=dev), torch.zeros((1, 9, 100), device=dev), 8)
+    with pytest.raises(SC.AvsepError, match="P \\* flen <= 2048"):
+        PB.bss_eval_sources(torch.zeros((2, 5, 1000), device=dev), torch.zeros((2, 5, 1000), device=dev))
 
 
 def test_cli_round_trip(dev, tmp_path, capsys):
