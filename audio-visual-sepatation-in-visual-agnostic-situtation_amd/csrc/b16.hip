@@ -12,6 +12,7 @@
 //   space-to-depth of the frames straight into a one-block B16 image
 #include "common.h"
 #include "conv_families.h"
+#include <string.h>
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -112,10 +113,14 @@ __global__ __launch_bounds__(256) void f32_bn_bwd_apply_to_b16_kernel(const floa
   }
 }
 static bool b16_dims_ok(int N, int C, long long HW);
+// the fp32 <-> B16 boundary kernels: a thread per position, grid-stride beyond 64 workgroups per (block, image)
+static GluePlan b16_convert_plan(int N, int C, int HW) {
+  return GluePlan{"position", dim3(min(cdiv(HW, 256), 64), C / 16, N)};
+}
 extern "C" int avsep_bn_bwd_apply_to_b16(const float* dz, const float* y, const float* pqr, int32_t N, int32_t C, int32_t HW, void* out,
                                          avsep_stream_t stream) {
   if (!dz || !y || !pqr || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(f32_bn_bwd_apply_to_b16_kernel, dim3(min(cdiv(HW, 256), 64), C / 16, N), dim3(256), 0, (hipStream_t)stream, dz, y,
+  hipLaunchKernelGGL(f32_bn_bwd_apply_to_b16_kernel, b16_convert_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, dz, y,
                      pqr, C, HW, (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -125,28 +130,27 @@ static bool b16_dims_ok(int N, int C, long long HW) {
 }
 extern "C" int avsep_f32_to_b16(const float* x, int32_t N, int32_t C, int32_t HW, void* out, avsep_stream_t stream) {
   if (!x || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(f32_to_b16_kernel, dim3(min(cdiv(HW, 256), 64), C / 16, N), dim3(256), 0, (hipStream_t)stream, x, C, HW,
+  hipLaunchKernelGGL(f32_to_b16_kernel, b16_convert_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, x, C, HW,
                      (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
 extern "C" int avsep_b16_to_f32(const void* x, int32_t N, int32_t C, int32_t HW, float* out, avsep_stream_t stream) {
   if (!x || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_to_f32_kernel, dim3(min(cdiv(HW, 256), 64), C / 16, N), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(b16_to_f32_kernel, b16_convert_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream,
                      (const u32x4*)x, C, HW, out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
 
 // ---- elementwise passes: grid (slot chunks, C/16, image slices) ---------------------------------------------------------------
-struct B16Grid { dim3 g; };
-static B16Grid b16_grid(int N, int C, long long HW) {
+static GluePlan b16_grid(int N, int C, long long HW) {
   const int gx = (int)min((HW * 2 + 255) / 256, (long long)32);
   int gz = N;
   const long long want = 4096;                        // enough workgroups for 256 CUs without one per image on big batches
   if ((long long)gx * (C / 16) * gz > want) gz = (int)max(1LL, want / ((long long)gx * (C / 16)));
   if (gz > N) gz = N;
-  return B16Grid{dim3(gx, C / 16, gz)};
+  return GluePlan{gz < N ? "slot,images" : "slot", dim3(gx, C / 16, gz)};
 }
 
 // z = act(scale*y + shift [+ res_scale*res + res_shift | + res])
@@ -180,7 +184,7 @@ extern "C" int avsep_b16_affine_act(const void* y, const float* scale, const flo
   if (!y || !z || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
   if ((scale == nullptr) != (shift == nullptr) || (res_scale == nullptr) != (res_shift == nullptr)) return AVSEP_ERR_ARG;
   if (act != AVSEP_ACT_NONE && act != AVSEP_ACT_RELU && act != AVSEP_ACT_LRELU02) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_affine_act_kernel, b16_grid(N, C, HW).g, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y, scale, shift,
+  hipLaunchKernelGGL(b16_affine_act_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y, scale, shift,
                      (const u32x4*)residual, res_scale, res_shift, act, N, C, HW, (u32x4*)z);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -237,7 +241,7 @@ extern "C" int avsep_b16_affine_act_bwd(const void* dz, const void* dz2, const v
   if ((scale == nullptr) != (shift == nullptr) || (res_scale == nullptr) != (res_shift == nullptr)) return AVSEP_ERR_ARG;
   if (bstats && (!mean || !invstd)) return AVSEP_ERR_ARG;
   if (act != AVSEP_ACT_NONE && act != AVSEP_ACT_RELU && act != AVSEP_ACT_LRELU02) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_affine_act_bwd_kernel, b16_grid(N, C, HW).g, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
+  hipLaunchKernelGGL(b16_affine_act_bwd_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
                      (const u32x4*)dz2, (const u32x4*)y, scale, shift, (const u32x4*)residual, res_scale, res_shift,
                      (const u32x4*)add, mean, invstd, act, N, C, HW, (u32x4*)out, bstats);
   AVSEP_LAUNCH_CHECK();
@@ -265,7 +269,7 @@ __global__ __launch_bounds__(256) void b16_bn_bwd_apply_kernel(const u32x4* __re
 extern "C" int avsep_b16_bn_bwd_apply(const void* dz, const void* y, const float* pqr, int32_t N, int32_t C, int32_t HW, void* out,
                                       avsep_stream_t stream) {
   if (!dz || !y || !pqr || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_bn_bwd_apply_kernel, b16_grid(N, C, HW).g, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
+  hipLaunchKernelGGL(b16_bn_bwd_apply_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
                      (const u32x4*)y, pqr, N, C, HW, (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -295,7 +299,7 @@ __global__ void b16_sum_finish_kernel(const double* acc, int C, float* out) {
 // acc: 2*C zeroed doubles of workspace
 int b16_channel_sum(const void* x, int N, int C, int HW, double* acc, float* out, hipStream_t st) {
   if (hipMemsetAsync(acc, 0, (size_t)2 * C * sizeof(double), st) != hipSuccess) return AVSEP_ERR_LAUNCH;
-  hipLaunchKernelGGL(b16_channel_sum_kernel, b16_grid(N, C, HW).g, dim3(256), 0, st, (const u32x4*)x, N, C, HW, acc);
+  hipLaunchKernelGGL(b16_channel_sum_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, st, (const u32x4*)x, N, C, HW, acc);
   hipLaunchKernelGGL(b16_sum_finish_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, acc, C, out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -349,7 +353,7 @@ extern "C" int avsep_b16_relu_up2x_fwd(const void* x0, const void* x1, const flo
     return AVSEP_ERR_ARG;
   if ((sc0 == nullptr) != (sh0 == nullptr) || (sc1 == nullptr) != (sh1 == nullptr)) return AVSEP_ERR_ARG;
   const float rh = H > 1 ? (float)(H - 1) / (float)(2 * H - 1) : 0.f, rw = W > 1 ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
-  hipLaunchKernelGGL(b16_relu_up2x_fwd_kernel, b16_grid(N, C0 + C1, 4LL * H * W).g, dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(b16_relu_up2x_fwd_kernel, b16_grid(N, C0 + C1, 4LL * H * W).grid, dim3(256), 0, (hipStream_t)stream,
                      (const u32x4*)x0, (const u32x4*)x1, sc0, sh0, sc1, sh1, N, C0, C1, H, W, rh, rw, (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -546,7 +550,7 @@ extern "C" int avsep_b16_maxpool3x3s2_fwd(const void* y, const float* scale, con
   if (!y || !z || H <= 0 || W <= 0 || !b16_dims_ok(N, C, (long long)H * W)) return AVSEP_ERR_ARG;
   if ((scale == nullptr) != (shift == nullptr)) return AVSEP_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(b16_maxpool_fwd_kernel, b16_grid(N, C, (long long)Ho * Wo).g, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y,
+  hipLaunchKernelGGL(b16_maxpool_fwd_kernel, b16_grid(N, C, (long long)Ho * Wo).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y,
                      scale, shift, act, N, C, H, W, Ho, Wo, (u32x4*)z, (uint2*)idx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -644,12 +648,12 @@ extern "C" int avsep_b16_maxpool_bn_relu_bwd(const void* g, const void* g2, cons
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   if (!dy) {                        // pass 1
     if (!bstats || !mean || !invstd) return AVSEP_ERR_ARG;
-    hipLaunchKernelGGL(b16_maxpool_bwd_stats_kernel, b16_grid(N, C, (long long)Ho * Wo).g, dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(b16_maxpool_bwd_stats_kernel, b16_grid(N, C, (long long)Ho * Wo).grid, dim3(256), 0, (hipStream_t)stream,
                        (const u32x4*)g, (const u32x4*)g2, (const uint2*)idx, (const u32x4*)y, scale, shift, mean, invstd, N, C, H, W,
                        Ho, Wo, bstats);
   } else {                          // pass 2
     if (!pqr) return AVSEP_ERR_ARG;
-    hipLaunchKernelGGL(b16_maxpool_bwd_apply_kernel, b16_grid(N, C, (long long)H * W).g, dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(b16_maxpool_bwd_apply_kernel, b16_grid(N, C, (long long)H * W).grid, dim3(256), 0, (hipStream_t)stream,
                        (const u32x4*)g, (const u32x4*)g2, (const uint2*)idx, (const u32x4*)y, scale, shift, pqr, N, C, H, W, Ho, Wo,
                        dy_f32 ? nullptr : (u32x4*)dy, dy_f32 ? (float*)dy : nullptr);
   }
@@ -683,10 +687,13 @@ __global__ __launch_bounds__(256) void b16_space_to_depth2_kernel(const float* _
     xs[i] = b16_pack8(v);
   }
 }
+static GluePlan b16_space_to_depth2_plan(long long total) {
+  return GluePlan{"flat", dim3((int)min((total + 255) / 256, (long long)262144))};
+}
 extern "C" int avsep_b16_space_to_depth2(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, void* xs, avsep_stream_t stream) {
   if (!x || !xs || N <= 0 || C <= 0 || 4 * C > 16 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return AVSEP_ERR_ARG;
   const long long total = (long long)N * (H / 2 + 3) * (W / 2 + 3) * 2;
-  hipLaunchKernelGGL(b16_space_to_depth2_kernel, dim3((int)min((total + 255) / 256, (long long)262144)), dim3(256), 0,
+  hipLaunchKernelGGL(b16_space_to_depth2_kernel, b16_space_to_depth2_plan(total).grid, dim3(256), 0,
                      (hipStream_t)stream, x, C, H, W, total, (u32x4*)xs);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -780,4 +787,25 @@ extern "C" int avsep_grid_unpack(const float* grid, int32_t N, int32_t C, int32_
                      PY, PX, HG, WG, out, (int)(ofmt == AVSEP_FMT_F32), stats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
+}
+
+// ---- launch plans of the launchers above, for avsep_glue_plan (ops.hip) ---------------------------------------------------------------
+bool b16_glue_plan(const char* op, int N, int C, int H, int W, int aux, GluePlan* out) {
+  (void)aux;
+  auto is = [&](const char* name) { return strcmp(op, name) == 0; };
+  const long long HW = (long long)H * W;
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  if (is("b16_space_to_depth2")) {
+    if (4 * C > 16 || (H & 1) || (W & 1)) return false;
+    *out = b16_space_to_depth2_plan((long long)N * (H / 2 + 3) * (W / 2 + 3) * 2);
+    return true;
+  }
+  if (!b16_dims_ok(N, C, HW)) return false;
+  if (is("f32_to_b16") || is("b16_to_f32") || is("bn_bwd_apply_to_b16")) *out = b16_convert_plan(N, C, (int)HW);
+  else if (is("b16_affine_act") || is("b16_affine_act_bwd") || is("b16_bn_bwd_apply") || is("b16_channel_sum") ||
+           is("b16_maxpool_bwd_apply"))
+    *out = b16_grid(N, C, HW);
+  else if (is("b16_maxpool_fwd") || is("b16_maxpool_bwd_stats")) *out = b16_grid(N, C, (long long)Ho * Wo);
+  else return false;
+  return true;
 }

@@ -15,6 +15,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
+// Launch plan of a glue kernel (ops.hip, b16.hip): the kernel form a launcher picks for a shape and its grid.  Every launcher
+// takes both from its *_plan function, and avsep_glue_plan reports the same answer on the host.
+struct GluePlan { const char* form; dim3 grid; };
+// b16.hip's share of avsep_glue_plan: false when `op` is none of its launchers or the shape is one its launcher refuses
+bool b16_glue_plan(const char* op, int N, int C, int H, int W, int aux, GluePlan* out);
 // The Winograd kernels load x / dY through buffer resources of num_records = 0xfffffff0 with 32-bit byte offsets.  A tensor of
 // `elems` floats whose resource base lies `shift` elements before its first element is addressable as a whole when the byte
 // offset of its last element, plus 4, stays within num_records; beyond it a valid element loads as 0 or wraps round.

@@ -3,6 +3,8 @@
 // gfx950 only.  See include/avsep.h for the contract of every entry point.
 #include "common.h"
 #include "warp_coords.h"
+#include <string.h>
+#include <stdio.h>
 
 // ============================================================================
 // BatchNorm pieces
@@ -37,13 +39,16 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
   }
 }
 
-extern "C" int avsep_channel_stats(const float* x, int32_t N, int32_t C, int32_t HW, double* stats,
-                                   avsep_stream_t stream) {
-  if (!x || !stats || N <= 0 || C <= 0 || HW <= 0) return AVSEP_ERR_ARG;
+static GluePlan channel_stats_plan(int N, int C, int HW) {
   long long total = (long long)N * HW;
   int chunks = (int)min((long long)cdiv(2048, C), (total + 4095) / 4096);
   if (chunks < 1) chunks = 1;
-  hipLaunchKernelGGL(channel_stats_kernel, dim3(C, chunks), dim3(256), 0, (hipStream_t)stream, x, N, C, HW, stats);
+  return GluePlan{"chunks", dim3(C, chunks)};
+}
+extern "C" int avsep_channel_stats(const float* x, int32_t N, int32_t C, int32_t HW, double* stats,
+                                   avsep_stream_t stream) {
+  if (!x || !stats || N <= 0 || C <= 0 || HW <= 0) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(channel_stats_kernel, channel_stats_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, x, N, C, HW, stats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -148,12 +153,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   }
 }
 
+// (the kernel itself takes the 16-byte form when HW % 4 == 0)
+static GluePlan bn_bwd_apply_plan(int N, int C, int HW) {
+  int gx = min(cdiv(HW, 1024), 64);
+  return GluePlan{(HW & 3) == 0 ? "vec4" : "scalar", dim3(gx, C, N)};
+}
 extern "C" int avsep_bn_bwd_apply(const float* dz, const float* y, const float* pqr, int32_t N, int32_t C, int32_t HW,
                                   float* dy, avsep_stream_t stream) {
   if (!dz || !y || !pqr || !dy || N <= 0 || C <= 0 || HW <= 0) return AVSEP_ERR_ARG;
   if (C > 65535 || N > 65535) return AVSEP_ERR_ARG;
-  int gx = min(cdiv(HW, 1024), 64);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(gx, C, N), dim3(256), 0, (hipStream_t)stream, dz, y, pqr, C, HW, dy);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, bn_bwd_apply_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, dz, y, pqr, C, HW, dy);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -190,13 +199,16 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
   }
 }
 
+static GluePlan affine_act_plan(int N, int C, int HW) {
+  int gx = min(cdiv(HW, (HW & 3) == 0 ? 1024 : 256), 64);
+  return GluePlan{(HW & 3) == 0 ? "vec4" : "scalar", dim3(gx, C, N)};
+}
 extern "C" int avsep_affine_act(const float* y, const float* scale, const float* shift, const float* residual,
                                 const float* res_scale, const float* res_shift, int32_t act, int32_t N, int32_t C,
                                 int32_t HW, float* z, avsep_stream_t stream) {
   if (!y || !z || N <= 0 || C <= 0 || HW <= 0 || C > 65535 || N > 65535) return AVSEP_ERR_ARG;
   if ((res_scale == nullptr) != (res_shift == nullptr)) return AVSEP_ERR_ARG;
-  int gx = min(cdiv(HW, (HW & 3) == 0 ? 1024 : 256), 64);
-  hipLaunchKernelGGL(affine_act_kernel, dim3(gx, C, N), dim3(256), 0, (hipStream_t)stream, y, scale, shift, residual,
+  hipLaunchKernelGGL(affine_act_kernel, affine_act_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, y, scale, shift, residual,
                      res_scale, res_shift, act, C, HW, z);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -259,6 +271,12 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const float* __rest
   }
 }
 
+static GluePlan affine_act_bwd_plan(int N, int C, int HW) {
+  long long total = (long long)N * HW;
+  int chunks = (int)min((long long)cdiv(2048, C), (total + 2047) / 2048);
+  if (chunks < 1) chunks = 1;
+  return GluePlan{(HW & 3) == 0 ? "v4" : "v1", dim3(C, chunks)};
+}
 extern "C" int avsep_affine_act_bwd(const float* dz, const float* dz2, const float* y, const float* scale, const float* shift,
                                     const float* residual, const float* res_scale, const float* res_shift,
                                     const float* add, const float* mean, const float* invstd, int32_t act, int32_t N,
@@ -267,13 +285,12 @@ extern "C" int avsep_affine_act_bwd(const float* dz, const float* dz2, const flo
   if (bstats && (!mean || !invstd)) return AVSEP_ERR_ARG;
   long long total = (long long)N * HW;
   if (total > 0x7fffffffLL) return AVSEP_ERR_ARG;
-  int chunks = (int)min((long long)cdiv(2048, C), (total + 2047) / 2048);
-  if (chunks < 1) chunks = 1;
-  if ((HW & 3) == 0)
-    hipLaunchKernelGGL(affine_act_bwd_kernel<4>, dim3(C, chunks), dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
+  const GluePlan pl = affine_act_bwd_plan(N, C, HW);
+  if (pl.form[1] == '4')
+    hipLaunchKernelGGL(affine_act_bwd_kernel<4>, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
                        residual, res_scale, res_shift, add, mean, invstd, act, N, C, HW, dz_pre, bstats);
   else
-    hipLaunchKernelGGL(affine_act_bwd_kernel<1>, dim3(C, chunks), dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
+    hipLaunchKernelGGL(affine_act_bwd_kernel<1>, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
                        residual, res_scale, res_shift, add, mean, invstd, act, N, C, HW, dz_pre, bstats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1011,19 +1028,26 @@ __global__ __launch_bounds__(256) void maxpool_fwd4_kernel(const float* __restri
   if (idx) *reinterpret_cast<int4*>(idx + o) = make_int4(bi[0], bi[1], bi[2], bi[3]);
 }
 
+static GluePlan maxpool_fwd_plan(long long NC, int H, int W) {
+  int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  if ((W & 7) == 0 && (H & 1) == 0 && NC <= 65535 && (long long)H * W < 0x7fffffffLL)
+    return GluePlan{"fwd4", dim3(cdiv(Ho * (Wo >> 2), 256), (unsigned)NC)};
+  long long total = NC * Ho * Wo;
+  return GluePlan{"generic", dim3((int)min((total + 255) / 256, (long long)65536))};
+}
 extern "C" int avsep_maxpool3x3s2_fwd(const float* x, const float* scale, const float* shift, int32_t act, int32_t C,
                                       int32_t NC, int32_t H, int32_t W, float* y, int32_t* idx, avsep_stream_t stream) {
   if (!x || !y || NC <= 0 || H <= 0 || W <= 0 || C <= 0 || NC % C) return AVSEP_ERR_ARG;
   if ((scale == nullptr) != (shift == nullptr)) return AVSEP_ERR_ARG;
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if ((W & 7) == 0 && (H & 1) == 0 && NC <= 65535 && (long long)H * W < 0x7fffffffLL) {
-    hipLaunchKernelGGL(maxpool_fwd4_kernel, dim3(cdiv(Ho * (Wo >> 2), 256), NC), dim3(256), 0, (hipStream_t)stream, x, scale, shift, act,
+  const GluePlan pl = maxpool_fwd_plan(NC, H, W);
+  if (pl.form[3] == '4') {
+    hipLaunchKernelGGL(maxpool_fwd4_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x, scale, shift, act,
                        C, H, W, Ho, Wo, y, idx);
     AVSEP_LAUNCH_CHECK();
     return AVSEP_OK;
   }
-  long long total = (long long)NC * Ho * Wo;
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3((int)min((total + 255) / 256, (long long)65536)), dim3(256), 0,
+  hipLaunchKernelGGL(maxpool_fwd_kernel, pl.grid, dim3(256), 0,
                      (hipStream_t)stream, x, scale, shift, act, C, NC, H, W, Ho, Wo, y, idx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1047,12 +1071,15 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
     dx[i] = s;
   }
 }
+static GluePlan maxpool_bwd_plan(long long NC, int H, int W) {
+  long long total = NC * H * W;
+  return GluePlan{"gather", dim3((int)min((total + 255) / 256, (long long)65536))};
+}
 extern "C" int avsep_maxpool3x3s2_bwd(const float* dy, const int32_t* idx, int32_t NC, int32_t H, int32_t W, float* dx,
                                       avsep_stream_t stream) {
   if (!dy || !idx || !dx || NC <= 0 || H <= 0 || W <= 0) return AVSEP_ERR_ARG;
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  long long total = (long long)NC * H * W;
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((int)min((total + 255) / 256, (long long)65536)), dim3(256), 0,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, maxpool_bwd_plan(NC, H, W).grid, dim3(256), 0,
                      (hipStream_t)stream, dy, idx, NC, H, W, Ho, Wo, dx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1083,13 +1110,17 @@ __global__ __launch_bounds__(256) void space_to_depth2_kernel(const float* __res
     }
   }
 }
+static GluePlan space_to_depth2_plan(int N, int H, int W, int Cp) {
+  const int per = (H / 2 + 3) * (W / 2 + 3), gx = (per + 255) / 256 < 16 ? (per + 255) / 256 : 16;
+  const int planes = N * Cp;
+  return GluePlan{"planes", dim3(gx, planes < 65535 ? planes : 65535)};
+}
 extern "C" int avsep_space_to_depth2(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t Cp, float* xs,
                                      avsep_stream_t stream) {
   if (!x || !xs || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Cp < 4 * C) return AVSEP_ERR_ARG;
   if ((long long)N * Cp > 0x7fffffffLL || (long long)H * W > 0x3fffffffLL) return AVSEP_ERR_ARG;
-  const int per = (H / 2 + 3) * (W / 2 + 3), gx = (per + 255) / 256 < 16 ? (per + 255) / 256 : 16;
   const int planes = N * Cp;
-  hipLaunchKernelGGL(space_to_depth2_kernel, dim3(gx, planes < 65535 ? planes : 65535), dim3(256), 0, (hipStream_t)stream, x, C, Cp,
+  hipLaunchKernelGGL(space_to_depth2_kernel, space_to_depth2_plan(N, H, W, Cp).grid, dim3(256), 0, (hipStream_t)stream, x, C, Cp,
                      H, W, planes, xs);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1230,13 +1261,26 @@ __global__ __launch_bounds__(256) void maxpool_bn_relu_bwd_apply1_kernel(const f
     dy[i] = fmaf(pqr[c], s, fmaf(pqr[C + c], yv, pqr[2 * C + c]));
   }
 }
+static GluePlan maxpool_bn_relu_bwd_stats_plan(int N, int C) { return GluePlan{"plane", dim3(C, N)}; }
+static GluePlan maxpool_bn_relu_bwd_apply_plan(int N, int C, int H, int W) {
+  const long long total = (long long)N * C * H * W;
+  if ((W & 3) == 0 && (long long)N * C <= 65535 && (long long)H * W < 0x7fffffffLL) {
+    const int per = H * (W / 4), gx = (per + 255) / 256 < 64 ? (per + 255) / 256 : 64;
+    return GluePlan{"apply4", dim3(gx, N * C)};
+  }
+  if ((W & 1) == 0 && (long long)N * C <= 65535 && (long long)H * W < 0x7fffffffLL) {
+    const int per = H * (W / 2), gx = (per + 255) / 256 < 64 ? (per + 255) / 256 : 64;
+    return GluePlan{"pair", dim3(gx, N * C)};
+  }
+  return GluePlan{"apply1", dim3((int)min((total + 255) / 256, (long long)262144))};
+}
 extern "C" int avsep_maxpool_bn_relu_bwd_stats(const float* g, const int32_t* idx, const float* y, const float* scale,
                                                const float* shift, const float* mean, const float* invstd, int32_t N, int32_t C,
                                                int32_t H, int32_t W, double* bstats, avsep_stream_t stream) {
   if (!g || !idx || !y || !scale || !shift || !mean || !invstd || !bstats) return AVSEP_ERR_ARG;
   if (N <= 0 || N > 65535 || C <= 0 || H <= 0 || W <= 0) return AVSEP_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(maxpool_bn_relu_bwd_stats_kernel, dim3(C, N), dim3(256), 0, (hipStream_t)stream, g, idx, y, scale, shift,
+  hipLaunchKernelGGL(maxpool_bn_relu_bwd_stats_kernel, maxpool_bn_relu_bwd_stats_plan(N, C).grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale, shift,
                      mean, invstd, C, H * W, Ho * Wo, bstats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1246,17 +1290,15 @@ extern "C" int avsep_maxpool_bn_relu_bwd_apply(const float* g, const int32_t* id
                                                float* dy, avsep_stream_t stream) {
   if (!g || !idx || !y || !scale || !shift || !pqr || !dy || N <= 0 || C <= 0 || H <= 0 || W <= 0) return AVSEP_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  const long long total = (long long)N * C * H * W;
-  if ((W & 3) == 0 && (long long)N * C <= 65535 && (long long)H * W < 0x7fffffffLL) {
-    const int per = H * (W / 4), gx = (per + 255) / 256 < 64 ? (per + 255) / 256 : 64;
-    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply4_kernel, dim3(gx, N * C), dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
+  const GluePlan pl = maxpool_bn_relu_bwd_apply_plan(N, C, H, W);
+  if (pl.form[0] == 'a' && pl.form[5] == '4') {
+    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply4_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
                        shift, pqr, C, H, W, Ho, Wo, dy);
-  } else if ((W & 1) == 0 && (long long)N * C <= 65535 && (long long)H * W < 0x7fffffffLL) {
-    const int per = H * (W / 2), gx = (per + 255) / 256 < 64 ? (per + 255) / 256 : 64;
-    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply_kernel, dim3(gx, N * C), dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
+  } else if (pl.form[0] == 'p') {
+    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
                        shift, pqr, C, H, W, Ho, Wo, dy);
   } else {
-    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply1_kernel, dim3((int)min((total + 255) / 256, (long long)262144)), dim3(256), 0,
+    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply1_kernel, pl.grid, dim3(256), 0,
                        (hipStream_t)stream, g, idx, y, scale, shift, pqr, C, N * C, H, W, Ho, Wo, dy);
   }
   AVSEP_LAUNCH_CHECK();
@@ -1273,11 +1315,14 @@ __global__ __launch_bounds__(256) void temporal_mean_fwd_kernel(const float* __r
     y[i] = s / (float)T;
   }
 }
+// one element per thread and pass, grid-stride beyond `cap` workgroups (temporal mean: 65536, SGD: 16384)
+static GluePlan flat_plan(long long total, long long cap) {
+  return GluePlan{"flat", dim3((int)min((total + 255) / 256, cap))};
+}
 extern "C" int avsep_temporal_mean_fwd(const float* x, int32_t B, int32_t T, int32_t CHW, float* y,
                                        avsep_stream_t stream) {
   if (!x || !y || B <= 0 || T <= 0 || CHW <= 0) return AVSEP_ERR_ARG;
-  long long total = (long long)B * CHW;
-  hipLaunchKernelGGL(temporal_mean_fwd_kernel, dim3((int)min((total + 255) / 256, (long long)65536)), dim3(256), 0,
+  hipLaunchKernelGGL(temporal_mean_fwd_kernel, flat_plan((long long)B * CHW, 65536).grid, dim3(256), 0,
                      (hipStream_t)stream, x, B, T, (long long)CHW, y);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1294,8 +1339,7 @@ __global__ __launch_bounds__(256) void temporal_mean_bwd_kernel(const float* __r
 extern "C" int avsep_temporal_mean_bwd(const float* dy, int32_t B, int32_t T, int32_t CHW, float* dx,
                                        avsep_stream_t stream) {
   if (!dy || !dx || B <= 0 || T <= 0 || CHW <= 0) return AVSEP_ERR_ARG;
-  long long total = (long long)B * T * CHW;
-  hipLaunchKernelGGL(temporal_mean_bwd_kernel, dim3((int)min((total + 255) / 256, (long long)65536)), dim3(256), 0,
+  hipLaunchKernelGGL(temporal_mean_bwd_kernel, flat_plan((long long)B * T * CHW, 65536).grid, dim3(256), 0,
                      (hipStream_t)stream, dy, B, T, (long long)CHW, dx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1315,7 +1359,7 @@ extern "C" int avsep_sgd_momentum(float* p, const float* g, float* buf, size_t n
                                   float weight_decay, float grad_scale, int32_t first, avsep_stream_t stream) {
   if (!p || !g || !buf) return AVSEP_ERR_ARG;
   if (n == 0) return AVSEP_OK;
-  hipLaunchKernelGGL(sgd_kernel, dim3((int)min((n + 255) / 256, (size_t)16384)), dim3(256), 0, (hipStream_t)stream, p, g, buf,
+  hipLaunchKernelGGL(sgd_kernel, flat_plan((long long)n, 16384).grid, dim3(256), 0, (hipStream_t)stream, p, g, buf,
                      n, lr, momentum, weight_decay, grad_scale, first);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1481,6 +1525,37 @@ extern "C" int avsep_sdr_sums(const float* est, const float* ref, int32_t R, int
   hipLaunchKernelGGL(sdr_sums_kernel, dim3(min(cdiv(L, 2048), 64), R), dim3(256), 0, (hipStream_t)stream, est, ref, L,
                      (long long)est_stride, (long long)ref_stride, sums);
   AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+// the launch plan of a glue launcher, from the function the launcher itself calls (include/avsep.h)
+extern "C" int avsep_glue_plan(const char* op, int32_t N, int32_t C, int32_t H, int32_t W, int32_t aux, char* form, size_t cap,
+                               int32_t grid[3]) {
+  if (!op || !form || !grid || cap < 32 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || aux < 0) return AVSEP_ERR_ARG;
+  const long long HWl = (long long)H * W, NC = (long long)N * C;
+  const int HW = (int)HWl;
+  const bool hw_ok = HWl <= 0x7fffffffLL, zgrid_ok = C <= 65535 && N <= 65535;
+  GluePlan p{nullptr, dim3(0, 0, 0)};
+  auto is = [&](const char* name) { return strcmp(op, name) == 0; };
+  if (is("channel_stats")) { if (hw_ok) p = channel_stats_plan(N, C, HW); }
+  else if (is("bn_bwd_apply")) { if (hw_ok && zgrid_ok) p = bn_bwd_apply_plan(N, C, HW); }
+  else if (is("affine_act")) { if (hw_ok && zgrid_ok) p = affine_act_plan(N, C, HW); }
+  else if (is("affine_act_bwd")) { if (hw_ok && N * HWl <= 0x7fffffffLL) p = affine_act_bwd_plan(N, C, HW); }
+  else if (is("maxpool_fwd")) { if (NC <= 0x7fffffffLL) p = maxpool_fwd_plan(NC, H, W); }
+  else if (is("maxpool_bwd")) { if (NC <= 0x7fffffffLL) p = maxpool_bwd_plan(NC, H, W); }
+  else if (is("maxpool_bn_relu_bwd_stats")) { if (N <= 65535) p = maxpool_bn_relu_bwd_stats_plan(N, C); }
+  else if (is("maxpool_bn_relu_bwd_apply")) p = maxpool_bn_relu_bwd_apply_plan(N, C, H, W);
+  else if (is("space_to_depth2")) {
+    if (!(H & 1) && !(W & 1) && aux >= 4 * (long long)C && (long long)N * aux <= 0x7fffffffLL && HWl <= 0x3fffffffLL)
+      p = space_to_depth2_plan(N, H, W, aux);
+  }
+  else if (is("temporal_mean_fwd")) { if (aux > 0 && C * HWl <= 0x7fffffffLL) p = flat_plan(N * (C * HWl), 65536); }
+  else if (is("temporal_mean_bwd")) { if (aux > 0 && C * HWl <= 0x7fffffffLL) p = flat_plan(N * (long long)aux * (C * HWl), 65536); }
+  else if (is("sgd")) p = flat_plan(NC * HWl, 16384);
+  else if (!b16_glue_plan(op, N, C, H, W, aux, &p)) return AVSEP_ERR_ARG;
+  if (!p.form) return AVSEP_ERR_ARG;
+  snprintf(form, cap, "%s", p.form);
+  grid[0] = (int32_t)p.grid.x; grid[1] = (int32_t)p.grid.y; grid[2] = (int32_t)p.grid.z;
   return AVSEP_OK;
 }
 

@@ -49,6 +49,7 @@ SIGNATURES = {
     "avsep_version": (C.c_int, []),
     "avsep_arch": (C.c_char_p, []),
     "avsep_strerror": (C.c_char_p, [C.c_int]),
+    "avsep_glue_plan": (C.c_int, [C.c_char_p, _I, _I, _I, _I, _I, C.c_char_p, _Z, C.POINTER(C.c_int32)]),
     "avsep_conv_packed_floats": (_Z, [_CD, C.c_int]),
     "avsep_conv_pack_weights": (C.c_int, [_CD, _P, _P, C.c_int, _P]),
     "avsep_conv_io_formats": (C.c_int, [_CD, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

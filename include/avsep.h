@@ -52,6 +52,20 @@ typedef void* avsep_stream_t;
 int avsep_version(void);
 const char* avsep_arch(void);          /* "gfx950" */
 const char* avsep_strerror(int code);
+/* The launch plan of a glue kernel (csrc/ops.hip, csrc/b16.hip): the kernel form and the grid (256-thread workgroups) its
+ * launcher chooses for a shape, from the very function the launcher calls.  Host only: no device is touched, no pointer
+ * but `op`, `form` and `grid` is read.  `op` and the meaning of (N, C, H, W, aux), HW = H * W wherever the entry point takes HW:
+ *   channel_stats, bn_bwd_apply, affine_act, affine_act_bwd, maxpool_bn_relu_bwd_stats, maxpool_bn_relu_bwd_apply,
+ *   f32_to_b16, b16_to_f32, bn_bwd_apply_to_b16, b16_affine_act, b16_affine_act_bwd, b16_bn_bwd_apply, b16_channel_sum,
+ *   b16_maxpool_fwd, b16_maxpool_bwd_stats, b16_maxpool_bwd_apply, b16_space_to_depth2      [N, C, H, W] as the entry point's
+ *   maxpool_fwd, maxpool_bwd        NC = N * C planes of H x W
+ *   space_to_depth2                 aux = Cp
+ *   temporal_mean_fwd, temporal_mean_bwd    B = N, T = aux, CHW = C * H * W
+ *   sgd                             n = N * C * H * W
+ * `form` (cap >= 32 bytes) receives the form's name, grid[3] the grid.  AVSEP_ERR_ARG for an unknown op or a shape the
+ * launcher refuses. */
+int avsep_glue_plan(const char* op, int32_t N, int32_t C, int32_t H, int32_t W, int32_t aux, char* form, size_t cap,
+                    int32_t grid[3]);
 
 /* ---------------------------------------------------------------------------
  * Convolution as implicit GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32).
