@@ -21,6 +21,7 @@ class _InnerProdFn(torch.autograd.Function):
         lib.require_gpu(snd)
         B, K = snd.shape[:2]
         HW = snd[0, 0].numel()
+        ctx.img_shape = img.shape
         img, snd = img.reshape(B, K).contiguous().float(), snd.contiguous().float()
         z = torch.empty((B, 1) + tuple(snd.shape[2:]), dtype=torch.float32, device=snd.device)
         call("avsep_innerprod_fwd", ptr(img), ptr(snd), ptr(scale), ptr(bias), B, K, HW, ptr(z))
@@ -38,7 +39,7 @@ class _InnerProdFn(torch.autograd.Function):
         call("avsep_innerprod_bwd", ptr(img), ptr(snd), ptr(scale), ptr(dz), B, K, HW, ptr(dsnd), ptr(r))
         dimg = r * scale if scale is not None else r
         dscale = (img * r).sum(0) if scale is not None else None
-        return dimg, dsnd, dscale, dz.sum().reshape(1)
+        return dimg.reshape(ctx.img_shape), dsnd, dscale, dz.sum().reshape(1)
 
 
 class InnerProd(nn.Module):

@@ -233,7 +233,20 @@ def test_synthesizer_entry_points_golden(dev, golden):
             out = getattr(mod, fn)(a, snd)
             assert_close(out, G[f"{name}.{fn}"], 1e-5, f"{name}.{fn} (autograd)")
             out.sum().backward()
-            assert a.grad is not None and snd.grad is not None
+            a64, s64 = arg.double().requires_grad_(True), G["fs"].double().requires_grad_(True)
+            w64 = {k: v.double() for k, v in mod.state_dict().items()}
+            Bq, Cq = s64.shape[:2]
+            fi = a64.view(Bq, Cq, -1) * w64["scale"].cpu().view(1, Cq, 1) if "scale" in w64 else a64.view(Bq, Cq, -1)
+            if fn == "forward":
+                ref = torch.bmm(fi.transpose(1, 2), s64.view(Bq, Cq, -1)).view(out.shape) + w64["bias"].cpu()
+            elif fn == "forward_nosum":
+                ref = fi.view(Bq, Cq, 1, 1) * s64 + w64["bias"].cpu()
+            else:
+                ref = torch.bmm(fi.transpose(1, 2), s64.view(Bq, Cq, -1)).view(out.shape) + w64["bias"].cpu()
+            assert_close(out, ref, 1e-5, f"{name}.{fn} (float64 expression)")
+            ref.sum().backward()
+            assert_close(a.grad, a64.grad, 1e-5, f"{name}.{fn} d img")
+            assert_close(snd.grad, s64.grad, 1e-5, f"{name}.{fn} d sound")
     g = torch.Generator().manual_seed(4)
     mod = P.models.synthesizer_net.InnerProd(32)
     with torch.no_grad():

@@ -1178,11 +1178,11 @@ def test_bss_eval_silent_source_takes_the_least_squares_fallback(dev):
 def test_attmodel_core_kernel(dev, att, B, S, K, H, W):
     """csrc/attention.hip (SoP++/attention_net.py:24-58: similarity maps, match term, clamp, context vectors) against the
     same formula in float64 torch with autograd: values and the gradients wrt the audio queries and the visual map,
-    with cotangents on all three outputs.  The cos maps are scaled into (-1.5, 1.5) by the test so that the clamp's
-    inactive branch is exercised too."""
+    with cotangents on all three outputs.  A cosine lies in [-1, 1] and a sigmoid in (0, 1): the clamp's lower branch is
+    taken by the negative cos maps, its upper branch is unreachable for both attention types."""
     from avsep_amd.models.attention_net import _AttInferFn, _ATT
     g = torch.Generator().manual_seed(B * 100 + K)
-    a = torch.randn(B, S, K, generator=g) * (1.0 if att == "sig" else 1.0)
+    a = torch.randn(B, S, K, generator=g)
     mix = torch.randn(B, K, H, W, generator=g)
     a64, m64 = a.double().requires_grad_(True), mix.double().requires_grad_(True)
     a5, v5 = a64[..., None, None], m64[:, None]
