@@ -13,6 +13,8 @@
 #include "common.h"
 #include "conv_families.h"
 #include <stdio.h>
+#include <string.h>
+#include <type_traits>
 
 enum { M_FWD = 0, M_DGRAD = 1, M_WGRAD = 2 };
 
@@ -67,7 +69,15 @@ __device__ __forceinline__ float load_virtual(const CArgs& a, long long nb0, lon
 
 // UP2X: the fused bilinear x2 gather is compiled in only where it is used (as a run-time flag it put four corner loads,
 // their interpolation and a scalar branch per element into every instantiation's K loop).
-template <int MODE, int BM, int BN, int BK, int WM, int WN, bool UP2X = false>
+// BUF (fwd, dgrad): the gathered operand comes through raw buffer loads with 32-bit byte offsets (igemm_buf32 decides on the
+// host).  What depends on the column alone is computed once per workgroup: a bit mask of the taps that fall outside the image
+// and the lane's byte offset.  What depends on the row k alone -- its byte offset (channel + tap), its tap index and its folded
+// BatchNorm pair -- is decoded by ONE thread per row into an LDS table two K-tiles ahead, instead of by every wave on its
+// scalar unit for every element.  Per element the loader then pays one LDS read, one add, one bit-field extract and one or: an
+// element outside the image (or past K) gets the offset 0xffffffff, which is out of the resource's range and loads as 0.
+// The weight gradient's form of it is described at its loader state below.  BUF = false is the 64-bit global_load loader, for
+// sources too large for 32-bit offsets and for the UP2X gather.
+template <int MODE, int BM, int BN, int BK, int WM, int WN, bool UP2X = false, bool BUF = false>
 __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -78,6 +88,12 @@ __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
   __shared__ int s_tab[(MODE == M_WGRAD) ? BN : 24];
   __shared__ float s_sc[(MODE == M_WGRAD) ? BN : 1], s_sh[(MODE == M_WGRAD) ? BN : 1];
   __shared__ int s_code[(MODE == M_WGRAD) ? BN : 1];
+  // BUF: rows of the K-tiles in flight.  fwd {byte offset, tap, scale, shift}, dgrad {byte offset, tap, packed weight row, -}.
+  // Slot kt & 1 is read by issue(kt) / finish(kt), both in iteration kt - 1, and rewritten for tile kt + 2 at the end of
+  // iteration kt: the K loop's one barrier (end of iteration kt - 1) lies between the last read and the write, and the barrier
+  // at the end of iteration kt between the write and the reads of issue(kt + 2).
+  constexpr bool DEC = BUF && MODE != M_WGRAD;
+  __shared__ __attribute__((aligned(16))) unsigned s_dec[DEC ? 2 : 1][DEC ? BK : 1][4];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -132,6 +148,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
         const float* hp = first ? a.sh0 : a.sh1;
         if (sp) { sc = sp[cs]; sh = hp[cs]; code = 1; }
         code |= (first ? a.act0 : a.act1) << 1;
+        if constexpr (BUF) code = __float_as_int(act_slope(first ? a.act0 : a.act1));   // BUF: the slope itself (sc = 1, sh = 0: no flag)
       }
       s_tab[c] = v;
       s_sc[c] = sc;
@@ -186,13 +203,238 @@ __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
   const bool has0 = a.sc0 != nullptr, has1 = a.sc1 != nullptr;
   const float slope0 = act_slope(a.act0), slope1 = act_slope(a.act1);   // branch-free activation (common.h)
   const int pixoff = hi0 * a.Ws + wi0;   // fwd: offset of the (possibly out-of-range) window origin
+  static_assert(!(BUF && UP2X), "the bilinear gather keeps the 64-bit loader");
+  // BUF loader state.  tinv: bit t set = tap t of this column lies outside the image (bit 31 is always set: the tap index
+  // an element past K is given).  voff0/voff1: byte offset of the lane's window origin in source 0/1 (fwd, modulo 2^32: it is
+  // negative where the window starts in the padding, and a valid tap's offset brings the sum back in range) or of its
+  // (hi / stride, wi / stride) pixel in dY (dgrad).
+  unsigned tinv = 0xffffffffu, voff0 = 0, voff1 = 0;
+  int dbh = 0, dbw = 0;   // dgrad: (hi + pad) % stride, (wi + pad) % stride: uniform over a parity class
+  __amdgpu_buffer_rsrc_t rs0, rs1;
+  if constexpr (BUF && MODE == M_FWD) {
+    for (int t = 0; t < KHW; ++t) {   // t, kh, kw uniform
+      const int hi = hi0 + (t / a.KW) * a.dil, wi = wi0 + (t % a.KW) * a.dil;
+      const bool ok = cvalid && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
+      tinv &= ~((unsigned)ok << t);
+    }
+    voff0 = 4u * (unsigned)(nb0 + pixoff);
+    voff1 = 4u * (unsigned)(nb1 + pixoff);
+    rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)a.x0, 0, (int)(4u * (unsigned)((long long)a.N * a.C0 * srcHW)), 0x00020000);
+    rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.C1 ? a.x1 : a.x0), 0,
+                                            (int)(4u * (unsigned)((long long)a.N * (a.C1 ? a.C1 : a.C0) * srcHW)), 0x00020000);
+  } else if constexpr (BUF && MODE == M_DGRAD) {
+    const int sm = a.stride - 1;   // stride is 1, 2 or 4
+    dbh = (ph + a.pad) & sm;
+    dbw = (pw + a.pad) & sm;
+    const int ah = hi0 >> a.lstride, aw = wi0 >> a.lstride;
+    const int nth = s_tab[0];
+    for (int ih = 0; ih < nth; ++ih)
+      for (int iw = 0; iw < ntw; ++iw) {   // a class tap's (db - k * dil) is a multiple of the stride: the shift is exact
+        const int ho = ah + ((dbh - s_tab[2 + ih] * a.dil) >> a.lstride), wo = aw + ((dbw - s_tab[12 + iw] * a.dil) >> a.lstride);
+        const bool ok = cvalid && (unsigned)ho < (unsigned)a.Ho && (unsigned)wo < (unsigned)a.Wo;
+        tinv &= ~((unsigned)ok << (ih * ntw + iw));
+      }
+    voff0 = 4u * (unsigned)(nbdy + ah * a.Wo + aw);
+    rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, (int)(4u * (unsigned)((long long)a.N * a.Cout * HoWo)), 0x00020000);
+  }
+  // BUF wgrad: a thread's columns (k) and dY rows (co) never change, so their byte offsets and tap indices are registers; per
+  // K-tile it decodes its pixel once, builds the pixel's mask of taps outside the image (tinv) from a row and a column mask,
+  // and an element is again one add, one bit-field extract and one or.  A workgroup whose columns straddle the two sources
+  // loads every element from both resources, one of them out of range.
+  constexpr int WBE = (BUF && MODE == M_WGRAD) ? BN / (256 / BK) : 1, WAE = (BUF && MODE == M_WGRAD) ? BM / (256 / BK) : 1;
+  unsigned wcoff[WBE], wrow[WAE], wfirst = 0, voffa = 0;
+  int wtap[WBE];
+  __amdgpu_buffer_rsrc_t rsd;
+  if constexpr (BUF && MODE == M_WGRAD) {
+    const int grp = tid / BK;
+#pragma unroll
+    for (int e = 0; e < WBE; ++e) {
+      const int tab = s_tab[grp + (256 / BK) * e], k = n0 + grp + (256 / BK) * e;
+      const int ci = tab & 0xffff;
+      const bool first = tab < 0 || ci < a.C0;
+      wcoff[e] = 4u * ((unsigned)(first ? ci : ci - a.C0) * (unsigned)srcHW + (unsigned)(((tab >> 16) & 0xff) * a.Ws + ((tab >> 24) & 0xff)));
+      wtap[e] = tab < 0 ? 31 : k % KHW;                     // a column past Ncols: the always-invalid tap
+      wfirst |= (unsigned)first << e;
+    }
+#pragma unroll
+    for (int e = 0; e < WAE; ++e) wrow[e] = 4u * (unsigned)min(m0 + grp + (256 / BK) * e, M - 1) * (unsigned)HoWo;
+    rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)a.x0, 0, (int)(4u * (unsigned)((long long)a.N * a.C0 * srcHW)), 0x00020000);
+    rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.C1 ? a.x1 : a.x0), 0,
+                                            (int)(4u * (unsigned)((long long)a.N * (a.C1 ? a.C1 : a.C0) * srcHW)), 0x00020000);
+    rsd = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, (int)(4u * (unsigned)((long long)a.N * a.Cout * HoWo)), 0x00020000);
+  }
 
   float braw[NBR], bsc[NSC], bsh[NSC];
   f32x4 areg4[AV];   // native vector type (a float4 struct array would live in scratch memory)
   float areg[(MODE == M_WGRAD) ? AE : 1];
   unsigned bmask = 0, bfirst = 0, amask = 0;
 
+  // ---- BUF: decode of the rows of K-tile kt by threads 0 .. BK-1 (dec_issue: arithmetic and the BatchNorm loads, before the
+  // MFMA loop; dec_finish: the LDS store, after it) ----
+  unsigned dk_off = 0, dk_tap = 31, dk_c = 0, dk_d = 0;
+  auto dec_issue = [&](int kt) __attribute__((always_inline)) {
+    if constexpr (DEC) {
+      if (tid < BK) {
+        const int k = kt * BK + tid;
+        const bool kok = k < K;
+        if (MODE == M_FWD) {
+          const int ci = k / KHW, r = k - ci * KHW, kh = r / a.KW, kw = r - kh * a.KW;
+          const int cc = min(ci, a.Cin - 1);
+          const bool first = cc < a.C0;
+          const int c = first ? cc : cc - a.C0;
+          dk_off = 4u * ((unsigned)c * (unsigned)srcHW + (unsigned)((kh * a.Ws + kw) * a.dil));
+          dk_tap = kok ? r : 31;
+          const float* sp = first ? a.sc0 : a.sc1;
+          const float* hp = first ? a.sh0 : a.sh1;
+          dk_c = __float_as_uint(sp ? sp[c] : 1.f);
+          dk_d = __float_as_uint(sp ? hp[c] : 0.f);
+        } else {
+          const int kk = kok ? k : 0, t = kk / a.Cout, co = kk - t * a.Cout, ih = t / ntw, iw = t - ih * ntw;
+          const int kh = s_tab[2 + ih], kw = s_tab[12 + iw];
+          const int tapoff = ((dbh - kh * a.dil) >> a.lstride) * a.Wo + ((dbw - kw * a.dil) >> a.lstride);
+          dk_off = 4u * (unsigned)(co * HoWo + tapoff);   // modulo 2^32: a valid lane's sum is in range
+          dk_tap = kok ? t : 31;
+          dk_c = kok ? (unsigned)((kh * a.KW + kw) * a.Cout + co) : 0xffffffffu;
+        }
+      }
+    }
+  };
+  auto dec_finish = [&](int buf) __attribute__((always_inline)) {
+    if constexpr (DEC) {
+      if (tid < BK) *reinterpret_cast<uint4*>(&s_dec[buf][tid][0]) = make_uint4(dk_off, dk_tap, dk_c, dk_d);
+    }
+  };
+  // the K-tile's rows of this wave against the switch from source 0 to source 1 (fwd): 0 / 1 = all in that source, 2 = mixed
+  const int S0 = a.C0 * KHW;
+  int cls = 0, kf = 0;
+  if constexpr (BUF && MODE == M_WGRAD) cls = (a.C1 == 0 || n0 + BN <= S0) ? 0 : (n0 >= S0 ? 1 : 2);   // the workgroup's columns
+  int binv[(BUF && MODE == M_FWD) ? BROWS : 1];   // 0 or -1 (outside the image / past K), kept for finish()
+  auto src_first = [&](auto tag, int e) __attribute__((always_inline)) {
+    constexpr int SRC = decltype(tag)::value;
+    return SRC == 0 || (SRC == 2 && kf + e < S0);
+  };
+  auto with_cls = [&](auto&& body) __attribute__((always_inline)) {
+    if (cls == 0) body(std::integral_constant<int, 0>{});
+    else if (cls == 1) body(std::integral_constant<int, 1>{});
+    else body(std::integral_constant<int, 2>{});
+  };
+  auto issue_buf = [&](int kt) __attribute__((always_inline)) {
+    const int db = kt & 1;
+    if constexpr (MODE == M_FWD) {
+#pragma unroll
+      for (int e = 0; e < AV; ++e) {
+        int idx = tid + 256 * e, row = idx / A4, c4 = idx % A4;
+        areg4[e] = *reinterpret_cast<const f32x4*>(a.wp + (long long)(kt * BK + row) * a.wp_ld + m0 + c4 * 4);
+      }
+      kf = kt * BK + brow0;                                // wave-uniform
+      cls = (a.C1 == 0 || kf + BROWS <= S0) ? 0 : (kf >= S0 ? 1 : 2);
+      with_cls([&](auto tag) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < BROWS; ++e) {
+          const uint2 d = *reinterpret_cast<const uint2*>(&s_dec[db][brow0 + e][0]);   // uniform address: a broadcast read
+          const bool first = src_first(tag, e);
+          binv[e] = __builtin_amdgcn_sbfe((int)tinv, d.y, 1u);
+          const unsigned off = ((first ? voff0 : voff1) + d.x) | (unsigned)binv[e];
+          braw[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(first ? rs0 : rs1, (int)off, 0, 0));
+        }
+      });
+    } else if constexpr (MODE == M_DGRAD) {
+      amask = 0;
+#pragma unroll
+      for (int e = 0; e < AV; ++e) {
+        int idx = tid + 256 * e, row = idx / A4, c4 = idx % A4;
+        const int wrow = (int)s_dec[db][row][2];
+        const bool ok = wrow >= 0;
+        areg4[e] = *reinterpret_cast<const f32x4*>(a.wp + (long long)(ok ? wrow : 0) * a.wp_ld + m0 + c4 * 4);
+        amask |= (unsigned)ok << e;
+      }
+#pragma unroll
+      for (int e = 0; e < BROWS; ++e) {
+        const uint2 d = *reinterpret_cast<const uint2*>(&s_dec[db][brow0 + e][0]);
+        const unsigned off = (voff0 + d.x) | (unsigned)__builtin_amdgcn_sbfe((int)tinv, d.y, 1u);
+        braw[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs0, (int)off, 0, 0));
+      }
+    } else {
+      const int p = p_begin + kt * BK + (tid % BK);
+      const bool pv = p < p_end;
+      const int pp = pv ? p : 0;
+      const int n = pp / HoWo, hw = pp - n * HoWo, ho = hw / a.Wo, wo = hw - ho * a.Wo;
+      const int hb = ho * a.stride - a.pad, wb = wo * a.stride - a.pad;
+      unsigned rinv = 0, cinv = 0;
+      for (int kh = 0; kh < a.KH; ++kh) rinv |= (unsigned)((unsigned)(hb + kh * a.dil) >= (unsigned)a.H) << kh;
+      for (int kw = 0; kw < a.KW; ++kw) cinv |= (unsigned)((unsigned)(wb + kw * a.dil) >= (unsigned)a.W) << kw;
+      const unsigned full = (1u << a.KW) - 1u;
+      tinv = 0x80000000u;
+      for (int kh = 0; kh < a.KH; ++kh) tinv |= (((rinv >> kh) & 1u) ? full : cinv) << (kh * a.KW);
+      if (!pv) tinv = 0xffffffffu;
+      const int pix = hb * a.Ws + wb;
+      voff0 = 4u * (unsigned)((long long)n * a.C0 * srcHW + pix);
+      voff1 = 4u * (unsigned)((long long)n * a.C1 * srcHW + pix);
+      voffa = 4u * (unsigned)((long long)n * a.Cout * HoWo + hw);
+      amask = pv ? 0xffffffffu : 0u;
+#pragma unroll
+      for (int e = 0; e < WAE; ++e)   // rows >= M are never stored by the epilogue
+        areg[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsd, (int)(voffa + wrow[e]), 0, 0));
+      with_cls([&](auto tag) __attribute__((always_inline)) {
+        constexpr int SRC = decltype(tag)::value;
+#pragma unroll
+        for (int e = 0; e < WBE; ++e) {
+          const unsigned inv = (unsigned)__builtin_amdgcn_sbfe((int)tinv, (unsigned)wtap[e], 1u);
+          if constexpr (SRC != 2) {
+            const unsigned off = ((SRC == 0 ? voff0 : voff1) + wcoff[e]) | inv;
+            braw[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(SRC == 0 ? rs0 : rs1, (int)off, 0, 0));
+          } else {
+            const unsigned f = 0u - ((wfirst >> e) & 1u);   // all ones: the column is in source 0
+            const int l0 = __builtin_amdgcn_raw_buffer_load_b32(rs0, (int)((voff0 + wcoff[e]) | inv | ~f), 0, 0);
+            const int l1 = __builtin_amdgcn_raw_buffer_load_b32(rs1, (int)((voff1 + wcoff[e]) | inv | f), 0, 0);
+            braw[e] = __builtin_bit_cast(float, l0 | l1);
+          }
+        }
+      });
+    }
+  };
+  auto finish_buf = [&](int buf) __attribute__((always_inline)) {
+    if constexpr (MODE == M_WGRAD) {
+      const int pl = tid % BK, grp = tid / BK;
+#pragma unroll
+      for (int e = 0; e < WAE; ++e) As[buf][pl][grp + (256 / BK) * e] = amask ? areg[e] : 0.f;
+#pragma unroll
+      for (int e = 0; e < WBE; ++e) {
+        const int col = grp + (256 / BK) * e;
+        const float v = act_by_slope(fmaf(braw[e], s_sc[col], s_sh[col]), __int_as_float(s_code[col]));
+        // the padding of an affine operand (and a pixel past the chunk) is zeroed here
+        Bs[buf][pl][col] = __uint_as_float(__float_as_uint(v) & ~(unsigned)__builtin_amdgcn_sbfe((int)tinv, (unsigned)wtap[e], 1u));
+      }
+      return;
+    }
+#pragma unroll
+    for (int e = 0; e < AV; ++e) {
+      int idx = tid + 256 * e, row = idx / A4, c4 = idx % A4;
+      f32x4 v = areg4[e];
+      if (MODE == M_DGRAD && !((amask >> e) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(&As[buf][row][c4 * 4]) = v;
+    }
+    if constexpr (MODE == M_FWD) {
+      with_cls([&](auto tag) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < BROWS; ++e) {
+          const float2 ss = *reinterpret_cast<const float2*>(&s_dec[buf][brow0 + e][2]);   // identity where there is no affine
+          float v = act_by_slope(fmaf(braw[e], ss.x, ss.y), src_first(tag, e) ? slope0 : slope1);
+          // act(affine(0)) != 0: the padding of an affine operand is zeroed here (a raw operand's already loaded as 0)
+          Bs[buf][brow0 + e][bcol] = __uint_as_float(__float_as_uint(v) & ~(unsigned)binv[e]);
+        }
+      });
+    } else {
+#pragma unroll
+      for (int e = 0; e < BROWS; ++e) Bs[buf][brow0 + e][bcol] = braw[e];   // outside the image: loaded as 0
+    }
+  };
+
   auto issue = [&](int kt) __attribute__((always_inline)) {
+    if constexpr (BUF) {
+      issue_buf(kt);
+      return;
+    }
     if (MODE == M_FWD) {
 #pragma unroll
       for (int e = 0; e < AV; ++e) {
@@ -298,6 +540,10 @@ __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
   };
 
   auto finish = [&](int buf) __attribute__((always_inline)) {
+    if constexpr (BUF) {
+      finish_buf(buf);
+      return;
+    }
     if (MODE == M_FWD) {
 #pragma unroll
       for (int e = 0; e < AV; ++e) {
@@ -350,6 +596,11 @@ __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+  if constexpr (DEC) {   // the tables of the first two K-tiles
+    if (nK > kt0) { dec_issue(kt0); dec_finish(kt0 & 1); }
+    if (nK > kt0 + 1) { dec_issue(kt0 + 1); dec_finish((kt0 + 1) & 1); }
+    __syncthreads();
+  }
   if (nK > kt0) {
     issue(kt0);
     finish(kt0 & 1);
@@ -359,6 +610,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
   for (int kt = kt0; kt < nK; ++kt) {
     const int buf = kt & 1;
     if (kt + 1 < nK) issue(kt + 1);
+    if (kt + 2 < nK) dec_issue(kt + 2);
     // operands of k-step k2+1 are read before the MFMAs of k-step k2 issue (order pinned with sched_barrier):
     // the LDS latency hides behind TM*TN*64 MFMA cycles instead of stalling the wave every step
     float av[2][TM], bv[2][TN];
@@ -382,6 +634,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(CArgs a) {
       __builtin_amdgcn_sched_barrier(0);
     }
     if (kt + 1 < nK) finish(buf ^ 1);
+    if (kt + 2 < nK) dec_finish(buf);   // tile kt's table was last read before the previous barrier
     __syncthreads();
   }
 
@@ -706,6 +959,27 @@ static WgradPlan wgrad_plan(const avsep_conv_desc* d) {
   return p;
 }
 
+// The buffer-load loader (igemm_kernel<..., BUF = true>) reaches a gathered tensor through 32-bit byte offsets: it serves a call
+// whose gathered tensors (both sources of x; dY for the data gradient; all three for the weight gradient) each stay below the
+// range with 16 bytes to spare, whose taps fit the loader's 31-bit tap mask and whose K is at least four tiles.  Everything
+// else keeps the 64-bit global_load loader.
+static inline bool igemm_src32(long long elems) { return 4 * elems + 16 < 0xfffffff0LL; }
+static bool igemm_range32(const avsep_conv_desc* d, int mode) {
+  const long long hw = (long long)d->H * d->W;
+  const bool dy_fits = igemm_src32((long long)d->N * d->Cout * d->Ho * d->Wo);
+  if (mode == 1) return dy_fits;
+  return (mode == 0 || dy_fits) && igemm_src32((long long)d->N * d->C0 * hw) && igemm_src32((long long)d->N * (d->Cin - d->C0) * hw);
+}
+static bool igemm_buf32(const avsep_conv_desc* d, int mode) {
+  if (d->up2x || d->KH * d->KW > 31) return false;
+  // the loader's per-workgroup prologue (tap mask, the tables of two K-tiles, one more barrier) is paid back over the K-tiles:
+  // with fewer than four of them (the Cin = 1 first conv has one) the call keeps the 64-bit loader
+  const int s = d->stride;
+  if (mode == 0 && d->Cin * d->KH * d->KW < 64) return false;
+  if (mode == 1 && d->Cout * cdiv(d->KH, s) * cdiv(d->KW, s) < 64) return false;
+  return igemm_range32(d, mode);
+}
+
 static size_t igemm_workspace_bytes(const avsep_conv_desc* d, int mode) {   // the split-K slabs
   const int S = mode == 0 ? fwd_split(d).splits : mode == 1 ? dgrad_split(d).splits : wgrad_plan(d).splits;
   if (S <= 1) return 0;
@@ -716,6 +990,13 @@ static size_t igemm_workspace_bytes(const avsep_conv_desc* d, int mode) {   // t
 static void igemm_variant(const avsep_conv_desc* d, int mode, char* buf, size_t cap) {
   if (mode == 0) snprintf(buf, cap, "BM%d,split%d", fwd_big(d) ? 128 : 64, fwd_split(d).splits);
   else if (mode == 1) snprintf(buf, cap, "BM%d,split%d", dgrad_big(d) ? 128 : 64, dgrad_split(d).splits);
+  // "ld64": a gathered tensor is beyond the buffer-load loader's 32-bit range (no benched geometry comes near it).  The suffix
+  // names the SIZE case only: a call with the fused upsample, more than 31 taps or fewer than four K-tiles also runs the 64-bit
+  // loader, as it always did, and says nothing.  (`buf` arrives as an empty string: avsep_conv_kernel_variant.)
+  if (!igemm_range32(d, mode)) {
+    size_t n = strlen(buf);
+    snprintf(buf + n, cap - n, "%sld64", n ? "," : "");
+  }
 }
 
 static int igemm_fwd(const avsep_conv_desc* d, const float* w_packed, const float* bias, float* y, double* stats, void* workspace,
@@ -737,10 +1018,12 @@ static int igemm_fwd(const avsep_conv_desc* d, const float* w_packed, const floa
   if (fwd_big(d)) {
     a.gridM = cdiv(a.M, 128);
     if (d->up2x) hipLaunchKernelGGL((igemm_kernel<M_FWD, 128, 128, 16, 2, 2, true>), dim3(a.gridM * cdiv(ncols, 128), sp.splits), dim3(256), 0, st, a);
+    else if (igemm_buf32(d, 0)) hipLaunchKernelGGL((igemm_kernel<M_FWD, 128, 128, 16, 2, 2, false, true>), dim3(a.gridM * cdiv(ncols, 128), sp.splits), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((igemm_kernel<M_FWD, 128, 128, 16, 2, 2, false>), dim3(a.gridM * cdiv(ncols, 128), sp.splits), dim3(256), 0, st, a);
   } else {
     a.gridM = cdiv(a.M, 64);
     if (d->up2x) hipLaunchKernelGGL((igemm_kernel<M_FWD, 64, 64, 16, 2, 2, true>), dim3(a.gridM * cdiv(ncols, 64), sp.splits), dim3(256), 0, st, a);
+    else if (igemm_buf32(d, 0)) hipLaunchKernelGGL((igemm_kernel<M_FWD, 64, 64, 16, 2, 2, false, true>), dim3(a.gridM * cdiv(ncols, 64), sp.splits), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((igemm_kernel<M_FWD, 64, 64, 16, 2, 2, false>), dim3(a.gridM * cdiv(ncols, 64), sp.splits), dim3(256), 0, st, a);
   }
   AVSEP_LAUNCH_CHECK();
@@ -766,12 +1049,14 @@ static int igemm_dgrad(const avsep_conv_desc* d, const float* w_packed_dgrad, co
   }
   if (dgrad_big(d)) {
     a.gridM = cdiv(a.M, 128);
-    hipLaunchKernelGGL((igemm_kernel<M_DGRAD, 128, 128, 16, 2, 2>), dim3(a.gridM * cdiv(ncols, 128), s * s, sp.splits),
-                       dim3(256), 0, st, a);
+    const dim3 grid(a.gridM * cdiv(ncols, 128), s * s, sp.splits);
+    if (igemm_buf32(d, 1)) hipLaunchKernelGGL((igemm_kernel<M_DGRAD, 128, 128, 16, 2, 2, false, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((igemm_kernel<M_DGRAD, 128, 128, 16, 2, 2>), grid, dim3(256), 0, st, a);
   } else {
     a.gridM = cdiv(a.M, 64);
-    hipLaunchKernelGGL((igemm_kernel<M_DGRAD, 64, 64, 16, 2, 2>), dim3(a.gridM * cdiv(ncols, 64), s * s, sp.splits),
-                       dim3(256), 0, st, a);
+    const dim3 grid(a.gridM * cdiv(ncols, 64), s * s, sp.splits);
+    if (igemm_buf32(d, 1)) hipLaunchKernelGGL((igemm_kernel<M_DGRAD, 64, 64, 16, 2, 2, false, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((igemm_kernel<M_DGRAD, 64, 64, 16, 2, 2>), grid, dim3(256), 0, st, a);
   }
   AVSEP_LAUNCH_CHECK();
   if (sp.splits > 1) {
@@ -794,10 +1079,12 @@ static int igemm_wgrad(const avsep_conv_desc* d, const float* dy, float* dw, flo
   if (p.big) {
     a.gridM = cdiv(a.M, 128);
     if (d->up2x) hipLaunchKernelGGL((igemm_kernel<M_WGRAD, 128, 128, 32, 2, 2, true>), dim3(a.gridM * cdiv(a.Ncols, 128), p.splits), dim3(256), 0, st, a);
+    else if (igemm_buf32(d, 2)) hipLaunchKernelGGL((igemm_kernel<M_WGRAD, 128, 128, 32, 2, 2, false, true>), dim3(a.gridM * cdiv(a.Ncols, 128), p.splits), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((igemm_kernel<M_WGRAD, 128, 128, 32, 2, 2, false>), dim3(a.gridM * cdiv(a.Ncols, 128), p.splits), dim3(256), 0, st, a);
   } else {
     a.gridM = cdiv(a.M, 64);
     if (d->up2x) hipLaunchKernelGGL((igemm_kernel<M_WGRAD, 64, 64, 32, 2, 2, true>), dim3(a.gridM * cdiv(a.Ncols, 64), p.splits), dim3(256), 0, st, a);
+    else if (igemm_buf32(d, 2)) hipLaunchKernelGGL((igemm_kernel<M_WGRAD, 64, 64, 32, 2, 2, false, true>), dim3(a.gridM * cdiv(a.Ncols, 64), p.splits), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((igemm_kernel<M_WGRAD, 64, 64, 32, 2, 2, false>), dim3(a.gridM * cdiv(a.Ncols, 64), p.splits), dim3(256), 0, st, a);
   }
   AVSEP_LAUNCH_CHECK();

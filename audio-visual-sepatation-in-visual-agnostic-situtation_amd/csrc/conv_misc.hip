@@ -3,8 +3,9 @@
 //   3x3 / stride 2 / pad 1 (layer2.0 / layer3.0 conv1): forward on the stride-2 patch (de-interleaved columns, like the
 //     4x4/s2 encoder convs); data gradient as four parity classes of the input pixel — class (ph, pw) is a
 //     (ph ? 2 : 1) x (pw ? 2 : 1)-tap stride-1 conv over dY without padding, stored at (2a + ph, 2b + pw);
-//   1x1 / stride 1 | 2 (the downsample convs): forward; data gradient = the 1x1 conv with transposed weights, for
-//     stride 2 stored at the sampled pixels of a zero-filled dX.
+//   1x1 / stride 1 | 2 (the downsample convs): forward (stride 2: the stride-1 kernel over every second row and column of the
+//     source, so only the sampled pixels are staged); data gradient = the 1x1 conv with transposed weights, for stride 2
+//     stored at the sampled pixels of dX together with the zeros of the three skipped pixels next to each.
 // Weight gradients of these classes stay on the im2col kernel.
 #include <stdlib.h>
 
@@ -75,7 +76,7 @@ int cm_pack(const avsep_conv_desc* d, const float* w, float* packed, int mode, h
   return AVSEP_OK;
 }
 
-template <int KH_, int KW_, int S_, int CK_>
+template <int KH_, int KW_, int S_, int CK_, bool ZF_ = false>
 static int cm_launch(C3Args& a, hipStream_t st) {
   const bool wide = a.Wo >= 32;
   a.tilesX = cdiv(a.Wo, wide ? 32 : 16);
@@ -83,10 +84,10 @@ static int cm_launch(C3Args& a, hipStream_t st) {
   const bool narrow = c3_narrow_rule(a.Cout, (long long)cdiv(a.Cout, 128) * a.tilesX * a.tilesY * c3_plan_n(a), false);
   a.gridM = cdiv(a.Cout, narrow ? 64 : 128);
   dim3 grid((unsigned)((long long)a.gridM * a.tilesX * a.tilesY * a.N));
-  if (wide && !narrow) hipLaunchKernelGGL((conv3x3_kernel<4, 32, 128, false, 3, S_, 1, CK_, KH_, KW_>), grid, dim3(256), 0, st, a);
-  else if (wide) hipLaunchKernelGGL((conv3x3_kernel<4, 32, 64, false, 3, S_, 1, CK_, KH_, KW_>), grid, dim3(256), 0, st, a);
-  else if (!narrow) hipLaunchKernelGGL((conv3x3_kernel<8, 16, 128, false, 3, S_, 1, CK_, KH_, KW_>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((conv3x3_kernel<8, 16, 64, false, 3, S_, 1, CK_, KH_, KW_>), grid, dim3(256), 0, st, a);
+  if (wide && !narrow) hipLaunchKernelGGL((conv3x3_kernel<4, 32, 128, false, 3, S_, 1, CK_, KH_, KW_, 0, ZF_>), grid, dim3(256), 0, st, a);
+  else if (wide) hipLaunchKernelGGL((conv3x3_kernel<4, 32, 64, false, 3, S_, 1, CK_, KH_, KW_, 0, ZF_>), grid, dim3(256), 0, st, a);
+  else if (!narrow) hipLaunchKernelGGL((conv3x3_kernel<8, 16, 128, false, 3, S_, 1, CK_, KH_, KW_, 0, ZF_>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((conv3x3_kernel<8, 16, 64, false, 3, S_, 1, CK_, KH_, KW_, 0, ZF_>), grid, dim3(256), 0, st, a);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -108,7 +109,10 @@ int cm_fwd(const avsep_conv_desc* d, const float* wp, const float* bias, float* 
   a.Ho = d->Ho; a.Wo = d->Wo; a.padh = a.padw = d->pad; a.os = 1; a.ooh = a.oow = 0; a.OHs = d->Ho; a.OWs = d->Wo;
   if (cm_class(d) == 5) return cm_launch<3, 3, 2, 2>(a, st);
   if (cm_class(d) == 6) return cm_launch<4, 4, 1, 2>(a, st);
-  return d->stride == 1 ? cm_launch<1, 1, 1, 16>(a, st) : cm_launch<1, 1, 2, 16>(a, st);
+  if (d->stride == 2) {   // a 1x1 / stride 2 output pixel needs exactly one input pixel: the stride-1 conv over the sampled ones
+    a.H = d->Ho; a.W = d->Wo; a.xs2 = 1;
+  }
+  return cm_launch<1, 1, 1, 16>(a, st);
 }
 
 int cm_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* dx, const avsep_act_bwd*, void*, size_t,
@@ -120,6 +124,9 @@ int cm_dgrad(const avsep_conv_desc* d, const float* wp, const float* dy, float* 
   a.x0 = dy; a.wp_ld = ld; a.out = dx; a.padh = a.padw = 0; a.OHs = d->H; a.OWs = d->W;
   if (cm_class(d) == 1) {
     a.wp = wp; a.Ho = d->Ho; a.Wo = d->Wo; a.os = d->stride; a.ooh = a.oow = 0;
+    // stride 2 (H, W even: cm_applicable): the kernel writes the skipped pixels' zeros itself, as 8-byte stores, and dX is
+    // written once; a dX that is only 4-byte aligned is filled first and takes the scalar stores
+    if (d->stride == 2 && ((uintptr_t)dx & 7) == 0) return cm_launch<1, 1, 1, 16, true>(a, st);
     if (d->stride == 2 && hipMemsetAsync(dx, 0, (size_t)d->N * d->Cin * d->H * d->W * sizeof(float), st) != hipSuccess)
       return AVSEP_ERR_LAUNCH;
     return cm_launch<1, 1, 1, 16>(a, st);

@@ -25,6 +25,7 @@ struct C3Args {
   int planN;             // host only: batch the tile-size heuristics are planned for (avsep_conv_desc.plan_n; 0 = N)
   int algo;              // host only: avsep_conv_desc.algo
   int out16;             // bf16 kernels: `out` is a B16 image ([N][Cout/16][OHs][OWs][16] bf16) instead of fp32 NCHW
+  int xs2;               // fp32 kernel: the [H x W] input is every second row and column of the [Hs x Ws] source (1x1 / stride 2)
 };
 static inline long long c3_plan_n(const C3Args& a) { return a.planN > 0 ? a.planN : a.N; }
 // 64-row instead of 128-row tiles (fp32 halo-patch kernels): small GEMM M, too few 128-row workgroups for the 256 CUs, or
@@ -60,10 +61,15 @@ __device__ __forceinline__ float c3_src(const C3Args& a, int n, int c, int hs, i
 // rows between them (the bottom padding of image n is the top padding of image n+1); the patch holds every virtual
 // row the 128 pixels touch plus the halo, full padded width.  Only the (pixel -> LDS base) and (patch element ->
 // global address) maps differ from the rectangular tile, and both are computed once in the prologue.
+//
+// ZF (1x1 / stride 2 data gradient, store stride os = 2 over an even-sized plane): the thread that stores (2a, 2b) also writes
+// the zeros of (2a, 2b+1), (2a+1, 2b) and (2a+1, 2b+1), as 8-byte row segments, so dX needs no fill pass before the launch.
+// The 8-byte stores need `out` itself 8-byte aligned (the host checks it) and an even OWs.
 template <int TH, int TW, int BM, bool UP2X, int KS = 3, int S = 1, int DIL = 1, int CK = 4, int KH_ = KS, int KW_ = KS,
-          int FW = 0>
+          int FW = 0, bool ZF = false>
 __global__ __launch_bounds__(256) void conv3x3_kernel(C3Args a) {
   constexpr bool FLAT = FW > 0;
+  static_assert(!ZF || (!FLAT && !UP2X), "zero fill: rectangular tiles");
   static_assert(!FLAT || (S == 1 && !UP2X && (KH_ & 1) && (KW_ & 1)), "flat tiles: stride 1, odd taps, no fused upsample");
   constexpr int NT = KH_ * KW_, C3_KT = CK * NT, C3_CK = CK;
   constexpr int PADH = DIL * (KH_ - 1) / 2, PADW = DIL * (KW_ - 1) / 2;     // flat mode: pad = dil * (k - 1) / 2
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(C3Args a) {
     int ghc = min(max(gh, 0), a.H - 1), gwc = min(max(gw, 0), a.W - 1);
     long long o[NRAW];
     if constexpr (!UP2X) {
-      o[0] = (long long)ghc * a.Ws + gwc;
+      o[0] = ((long long)ghc * a.Ws + gwc) << a.xs2;
     } else {  // nn.Upsample(x2, bilinear, align_corners=True): src = dst*(in-1)/(out-1)
       float fh = a.rh * (float)ghc, fw = a.rw * (float)gwc;
       int hh0 = (int)fh, ww0 = (int)fw;
@@ -320,7 +326,13 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(C3Args a) {
       for (int j = 0; j < 2; ++j) {
         float v = acc[i][j][r] + bias;
         if (rok && cok[j]) {
-          a.out[cbase[j] + (long long)row * HW] = v;
+          float* o = a.out + cbase[j] + (long long)row * HW;
+          if constexpr (ZF) {   // (2a, 2b) is 8-byte aligned: OWs is even and so is every plane, `out` is 8-byte aligned (cm_dgrad)
+            *reinterpret_cast<float2*>(o) = make_float2(v, 0.f);
+            *reinterpret_cast<float2*>(o + a.OWs) = make_float2(0.f, 0.f);
+          } else {
+            *o = v;
+          }
           s += v;
           q += v * v;
         }

@@ -198,7 +198,9 @@ int32_t avsep_conv2d_head_applicable(const avsep_conv_desc* d);
 const char* avsep_conv_kernel_name(const avsep_conv_desc* d, int32_t mode, int32_t with_stats);
 /* The same plus every launch decision that depends on the size of the grid (tile shape, 64- / 128-row tiles, 256- / 512-
  * thread workgroups, split-K), e.g. "convbf_kernel:8x32,128x256", "conv3x3_kernel:4x32,BM64", "igemm_kernel<fwd>:BM64,split6":
- * two descriptors with equal variants run the same kernel instantiation.  The parity tests assert that a batch-8 step
+ * two descriptors with equal variants run the same kernel instantiation.  An "igemm_kernel<...>" variant ends in "ld64"
+ * ("...,ld64"; the weight gradient's is "igemm_kernel<wgrad>:ld64") when a tensor the call gathers (a source of x; dY) has
+ * 4 * elements + 16 >= 0xfffffff0 bytes, which keeps it on the 64-bit loader.  The parity tests assert that a batch-8 step
  * planned for the bench batch (desc.plan_n) has, layer by layer, the variants of the batch-64 step bench.py times. */
 int avsep_conv_kernel_variant(const avsep_conv_desc* d, int32_t mode, int32_t with_stats, char* buf, size_t cap);
 int avsep_conv2d_dgrad_up2x(const avsep_conv_desc* d, const float* w, const float* dy, float* g0,
