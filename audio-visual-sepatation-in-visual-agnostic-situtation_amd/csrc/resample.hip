@@ -8,6 +8,9 @@
 // Two more kernels keep a file's channels apart with the same tiles and the same chains (rs_chains): resample_split_kernel
 // gives the down-mix and every channel of interleaved PCM in one pass, resample_join_kernel turns C rows back into
 // interleaved PCM and writes whole frames.
+// The *_fmt entry points take and give a file's frames as the bytes they are, in the sample formats of include/avsep.h, from
+// and to any byte address: the same kernels with another conversion in the staging loop (rs_frame) and at the store, the
+// chains untouched.
 #include "common.h"
 
 constexpr int RS_BLOCK = 256;
@@ -21,13 +24,61 @@ constexpr int RS_KEEP_CH = 8;      // channels split and join keep apart (7.1)
 constexpr int RJ_SPAN = 8704;      // join: staged floats of all C rows together (34 KiB + padding, beside a 16 KiB output tile;
                                    // eight rows of a 1/1 tile still fit)
 constexpr int RJ_LDS = RJ_SPAN + RJ_SPAN / 32 + 1;
+constexpr int RJ_SPAN_F32 = 7936;  // join to f32 frames: the output tile is 32 KiB, the staged rows get what is left of 64 KiB
+constexpr int RJ_LDS_F32 = RJ_SPAN_F32 + RJ_SPAN_F32 / 32 + 1;
+constexpr int RS_FMT_ROWS = 0;     // the entry points without a format: aligned int16 frames (or f32 rows) in, s16 / f32 out
+
+__device__ __forceinline__ int rs_fmt_bytes(int fmt) { return fmt == AVSEP_SAMPLE_S16 ? 2 : fmt == AVSEP_SAMPLE_S24 ? 3 : 4; }
+static inline bool rs_fmt_in_ok(int fmt) { return fmt >= AVSEP_SAMPLE_S16 && fmt <= AVSEP_SAMPLE_F32; }
+static inline bool rs_fmt_out_ok(int fmt) { return fmt == AVSEP_SAMPLE_S16 || fmt == AVSEP_SAMPLE_S24 || fmt == AVSEP_SAMPLE_F32; }
+
+// The `bytes` (2 ... 4) bytes at p, little-endian, in the low end of the result (the rest is whatever follows).  p has any
+// alignment: the loads are the one or two ALIGNED dwords that hold the sample, funnel-shifted, so lanes on consecutive
+// samples read consecutive (shared) dwords and nothing is loaded byte by byte.  No dword is touched that holds no byte of
+// the sample, so nothing outside the 4-byte granules of the caller's buffer is read.
+__device__ __forceinline__ uint32_t rs_bytes(const uint8_t* __restrict__ p, int bytes) {
+  const int sh = (int)((size_t)p & 3);
+  const uint32_t* __restrict__ q = (const uint32_t*)(p - sh);
+  const uint32_t lo = q[0];
+  const uint32_t hi = sh + bytes > 4 ? q[1] : 0u;
+  return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * sh));
+}
+
+// A PCM sample's integer from rs_bytes' result.
+__device__ __forceinline__ int rs_pcm(uint32_t v, int fmt) {
+  return fmt == AVSEP_SAMPLE_S16 ? (int)(int16_t)v : fmt == AVSEP_SAMPLE_S24 ? (int)(v << 8) >> 8 : (int)v;
+}
+
+// Frame n of interleaved frames [L, C] of format fmt at any byte address (include/avsep.h).  ch >= 0: that channel, an exact
+// scaling of the integer (s32: of the integer rounded to f32) or the float's own bits.  ch < 0: the down-mix, rounded once:
+// the exact 64-bit sum over C * 2^(bits-1), both exact in f64, divided there and rounded to f32 (the double rounding of a
+// quotient is innocuous at 53 >= 2 * 24 + 2 bits); floats are added in f64 in channel order.  One channel is its own mean.
+__device__ __forceinline__ float rs_frame(const void* __restrict__ x, long long n, int C, int ch, int fmt) {
+  const int bytes = rs_fmt_bytes(fmt);
+  const uint8_t* __restrict__ p = (const uint8_t*)x + n * C * bytes;
+  if (C == 1) ch = 0;
+  if (ch >= 0) {
+    const uint32_t v = rs_bytes(p + ch * bytes, bytes);
+    if (fmt == AVSEP_SAMPLE_F32) return __uint_as_float(v);
+    return (float)rs_pcm(v, fmt) * (fmt == AVSEP_SAMPLE_S16 ? 0x1p-15f : fmt == AVSEP_SAMPLE_S24 ? 0x1p-23f : 0x1p-31f);
+  }
+  if (fmt == AVSEP_SAMPLE_F32) {
+    double sum = 0.0;
+    for (int c = 0; c < C; ++c) sum += (double)__uint_as_float(rs_bytes(p + c * 4, 4));
+    return (float)(sum / (double)C);
+  }
+  long long sum = 0;
+  for (int c = 0; c < C; ++c) sum += rs_pcm(rs_bytes(p + c * bytes, bytes), fmt);
+  return (float)((double)sum / (double)((long long)C << (8 * bytes - 1)));
+}
 
 // Sample n of a row; zero outside it.  in_ch >= 1: interleaved int16 [L, in_ch]; ch < 0 is the exact integer sum of the
 // channels over in_ch * 32768 with a correctly rounded division (separate.read_wav's value for one and two channels),
-// ch >= 0 is channel ch over 32768 (exact).
-__device__ __forceinline__ float rs_sample(const void* __restrict__ x, long long n, long long L, int in_ch, int ch) {
+// ch >= 0 is channel ch over 32768 (exact).  fmt != RS_FMT_ROWS: frames of that format at any byte address (rs_frame).
+__device__ __forceinline__ float rs_sample(const void* __restrict__ x, long long n, long long L, int in_ch, int ch, int fmt) {
   if ((unsigned long long)n >= (unsigned long long)L) return 0.f;
   if (in_ch == 0) return ((const float*)x)[n];
+  if (fmt != RS_FMT_ROWS) return rs_frame(x, n, in_ch, ch, fmt);
   const int16_t* s = (const int16_t*)x + n * in_ch;
   if (ch >= 0) return (float)s[ch] * (1.f / 32768.f);
   int sum = 0;
@@ -40,6 +91,24 @@ __device__ __forceinline__ float rs_sample(const void* __restrict__ x, long long
 __device__ __forceinline__ int rs_slot(int s) { return s + (s >> 5); }
 
 __device__ __forceinline__ int16_t rs_s16(float v) { return (int16_t)(int)fminf(fmaxf(rintf(v * 32768.f), -32768.f), 32767.f); }
+__device__ __forceinline__ int rs_s24(float v) { return (int)fminf(fmaxf(rintf(v * 8388608.f), -8388608.f), 8388607.f); }
+
+// v as one sample of an output format, little-endian in the low bytes; the f32 form is the accumulator's bits.
+__device__ __forceinline__ uint32_t rs_encode(float v, int fmt) {
+  return fmt == AVSEP_SAMPLE_S16 ? (uint32_t)(uint16_t)rs_s16(v) : fmt == AVSEP_SAMPLE_S24 ? (uint32_t)rs_s24(v) & 0xffffffu
+                                                                                            : __float_as_uint(v);
+}
+
+// The low `bytes` bytes of v to p (global memory or LDS): one store where p is aligned for it, else byte by byte.
+__device__ __forceinline__ void rs_put(uint8_t* p, uint32_t v, int bytes) {
+  if (bytes == 4 && !((size_t)p & 3)) {
+    *(uint32_t*)p = v;
+  } else if (bytes == 2 && !((size_t)p & 1)) {
+    *(uint16_t*)p = (uint16_t)v;
+  } else {
+    for (int b = 0; b < bytes; ++b) p[b] = (uint8_t)(v >> (8 * b));
+  }
+}
 
 // A workgroup's tile: the RS_R * S outputs from j0 on.  Output j = j0 + dj sits at filter position
 // pos = j * down + half = pos0 + dj * down: phase p = pos mod up, newest input n = pos div up, taps i = 0 .. T-1 pair x[n - i]
@@ -69,8 +138,8 @@ __device__ __forceinline__ RsTile rs_tile(int up, int down, int half, int T, int
 // s_x (the host sized it for a full tile) or inside the row (rs_sample checks).
 template <bool STAGED>
 __device__ __forceinline__ void rs_chains(const float* s_x, const void* __restrict__ xr, long long n_lo, int L, int in_ch, int ch,
-                                          const float* __restrict__ ho, int up, int down, int M, int T, int S, int r0, int t0,
-                                          float acc[RS_R]) {
+                                          int fmt, const float* __restrict__ ho, int up, int down, int M, int T, int S, int r0,
+                                          int t0, float acc[RS_R]) {
   const int step = S / up * down;                            // input samples between a thread's outputs: S * down / up
   const int v = r0 + t0 * down, dq = v / up, p = v - dq * up;
   const float* __restrict__ h = ho + t0 % up;
@@ -80,7 +149,7 @@ __device__ __forceinline__ void rs_chains(const float* s_x, const void* __restri
     top[r] = dq + r * step + T - 1;
     acc[r] = 0.f;
   }
-#define RS_X(r, i) (STAGED ? s_x[rs_slot(top[r] - (i))] : rs_sample(xr, n_lo + top[r] - (i), L, in_ch, ch))
+#define RS_X(r, i) (STAGED ? s_x[rs_slot(top[r] - (i))] : rs_sample(xr, n_lo + top[r] - (i), L, in_ch, ch, fmt))
 #pragma unroll 4
   for (int i = 0; i < T - 1; ++i) {
     const float c = h[i * up];
@@ -95,29 +164,33 @@ __device__ __forceinline__ void rs_chains(const float* s_x, const void* __restri
 #undef RS_X
 }
 
-// grid (ceil(Lout / (RS_R * S)), B).
-template <bool STAGED>
+// grid (ceil(Lout / (RS_R * S)), B).  ANY: the *_fmt entry point, in_fmt / out_fmt are sample formats and the frames and y
+// have any byte alignment; else in_fmt is RS_FMT_ROWS and out_fmt the older entry point's out_s16.
+template <bool STAGED, bool ANY>
 __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const void* __restrict__ x, const float* __restrict__ ho, int up,
                                                                  int down, int half, int M, int T, int S, int L, int Lout,
-                                                                 int in_ch, int out_s16, void* __restrict__ y) {
+                                                                 int in_ch, int in_fmt, int out_fmt, void* __restrict__ y) {
   __shared__ float s_x[STAGED ? RS_LDS : 1];
   const int row = blockIdx.y;
+  const int fmt = ANY ? in_fmt : RS_FMT_ROWS;
   const RsTile tl = rs_tile(up, down, half, T, S, Lout);
   const void* xr = in_ch ? x : (const void*)((const float*)x + (long long)row * L);
   if (STAGED) {
-    for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(xr, tl.n_lo + s, L, in_ch, -1);
+    for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(xr, tl.n_lo + s, L, in_ch, -1, fmt);
     __syncthreads();
   }
   for (int t0 = threadIdx.x; t0 < S; t0 += RS_BLOCK) {
     if (t0 >= tl.nout) break;                                // none of this thread's outputs lies inside the row
     float acc[RS_R];
-    rs_chains<STAGED>(s_x, xr, tl.n_lo, L, in_ch, -1, ho, up, down, M, T, S, tl.r0, t0, acc);
+    rs_chains<STAGED>(s_x, xr, tl.n_lo, L, in_ch, -1, fmt, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
     for (int r = 0; r < RS_R; ++r) {
       const int dj = t0 + r * S;
       if (dj >= tl.nout) break;
       const long long o = (long long)row * Lout + tl.j0 + dj;
-      if (out_s16)
+      if (ANY)
+        rs_put((uint8_t*)y + o * rs_fmt_bytes(out_fmt), rs_encode(acc[r], out_fmt), rs_fmt_bytes(out_fmt));
+      else if (out_fmt)
         ((int16_t*)y)[o] = rs_s16(acc[r]);
       else
         ((float*)y)[o] = acc[r];
@@ -128,23 +201,25 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const void* __r
 // grid (ceil(Lout / (RS_R * S))).  Interleaved int16 [L, C] -> f32 [1 + C, Lout]: the workgroup makes its tile of every row
 // in turn, row 0 from the down-mix and row 1 + c from channel c, so the file is fetched from HBM once (the later rows find
 // the tile's frames in L2) and no de-interleaved copy of it exists.
-template <bool STAGED>
-__global__ __launch_bounds__(RS_BLOCK) void resample_split_kernel(const int16_t* __restrict__ x, const float* __restrict__ ho,
+// ANY: the *_fmt entry point, frames of sample format in_fmt at any byte address; else aligned int16.
+template <bool STAGED, bool ANY>
+__global__ __launch_bounds__(RS_BLOCK) void resample_split_kernel(const void* __restrict__ x, const float* __restrict__ ho,
                                                                   int up, int down, int half, int M, int T, int S, int L,
-                                                                  int Lout, int C, float* __restrict__ y) {
+                                                                  int Lout, int C, int in_fmt, float* __restrict__ y) {
   __shared__ float s_x[STAGED ? RS_LDS : 1];
+  const int fmt = ANY ? in_fmt : RS_FMT_ROWS;
   const RsTile tl = rs_tile(up, down, half, T, S, Lout);
   for (int row = 0; row <= C; ++row) {
     const int ch = row - 1;                                  // -1: the down-mix
     if (STAGED) {
       if (row) __syncthreads();                              // the previous row's chains have read s_x
-      for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(x, tl.n_lo + s, L, C, ch);
+      for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(x, tl.n_lo + s, L, C, ch, fmt);
       __syncthreads();
     }
     for (int t0 = threadIdx.x; t0 < S; t0 += RS_BLOCK) {
       if (t0 >= tl.nout) break;
       float acc[RS_R];
-      rs_chains<STAGED>(s_x, x, tl.n_lo, L, C, ch, ho, up, down, M, T, S, tl.r0, t0, acc);
+      rs_chains<STAGED>(s_x, x, tl.n_lo, L, C, ch, fmt, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
       for (int r = 0; r < RS_R; ++r) {
         const int dj = t0 + r * S;
@@ -170,7 +245,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __
   if (STAGED) {
     for (int c = 0; c < C; ++c)
       for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK)
-        s_x[c * pitch + rs_slot(s)] = rs_sample(x + (long long)c * L, tl.n_lo + s, L, 0, -1);
+        s_x[c * pitch + rs_slot(s)] = rs_sample(x + (long long)c * L, tl.n_lo + s, L, 0, -1, RS_FMT_ROWS);
     __syncthreads();
   }
   const bool words = ((size_t)y & 3) == 0;
@@ -179,7 +254,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __
     if (t0 < S && t0 < tl.nout) {
       for (int c = 0; c < C; ++c) {
         float acc[RS_R];
-        rs_chains<STAGED>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, ho, up, down, M, T, S, tl.r0, t0, acc);
+        rs_chains<STAGED>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, RS_FMT_ROWS, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
         for (int r = 0; r < RS_R; ++r) s_o[(r * RS_BLOCK + threadIdx.x) * C + c] = rs_s16(acc[r]);
       }
@@ -198,6 +273,59 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __
       } else {
         for (int i = threadIdx.x; i < cnt; i += RS_BLOCK) y[e0 + i] = src[i];
       }
+    }
+    __syncthreads();                                           // s_o is free for the next pass
+  }
+}
+
+// resample_join_kernel for the frames of any output format at any byte address: f32 [C, L] -> interleaved samples of BYTES
+// bytes (2: s16, 3: s24, 4: f32).  The tile holds bytes in file layout, BYTES a sample: 16, 24 or 32 KiB at eight channels.
+// The 32 KiB of the f32 form do not fit beside RJ_LDS in 64 KiB, so that form stages the smaller RJ_LDS_F32 (the host plans S
+// for it; the chains do not depend on S).  A run starts at byte phase (address & 3) of y, any of the four (three-byte
+// samples, an odd channel count, a data chunk at an odd file offset): every run sits in the tile at the phase its first byte has in y, four
+// spare bytes a run, so that an aligned dword of the file is an aligned dword of LDS.  The store is then a head of up to
+// three single bytes, a body of whole dwords on consecutive lanes and a tail of up to three bytes.
+template <bool STAGED, int BYTES>
+__global__ __launch_bounds__(RS_BLOCK) void resample_join_fmt_kernel(const float* __restrict__ x, const float* __restrict__ ho,
+                                                                     int up, int down, int half, int M, int T, int S, int L,
+                                                                     int Lout, int C, int pitch, uint8_t* __restrict__ y) {
+  constexpr int RUN = RS_BLOCK * RS_KEEP_CH * BYTES + 4;       // bytes of LDS per run: a multiple of 4
+  constexpr int FMT = BYTES == 2 ? AVSEP_SAMPLE_S16 : BYTES == 3 ? AVSEP_SAMPLE_S24 : AVSEP_SAMPLE_F32;
+  __shared__ float s_x[STAGED ? (BYTES == 4 ? RJ_LDS_F32 : RJ_LDS) : 1];
+  __shared__ __align__(4) uint8_t s_o[RS_R * RUN];
+  const RsTile tl = rs_tile(up, down, half, T, S, Lout);
+  if (STAGED) {
+    for (int c = 0; c < C; ++c)
+      for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK)
+        s_x[c * pitch + rs_slot(s)] = rs_sample(x + (long long)c * L, tl.n_lo + s, L, 0, -1, RS_FMT_ROWS);
+    __syncthreads();
+  }
+  for (int tb = 0; tb < S && tb < tl.nout; tb += RS_BLOCK) {   // the same for every thread: the loop holds barriers
+    const int t0 = tb + threadIdx.x;
+    int phase[RS_R];                                           // of each run's first byte in y
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) phase[r] = (int)(((size_t)y + (size_t)((tl.j0 + tb + r * S) * C * BYTES)) & 3);
+    if (t0 < S && t0 < tl.nout) {
+      for (int c = 0; c < C; ++c) {
+        float acc[RS_R];
+        rs_chains<STAGED>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, RS_FMT_ROWS, ho, up, down, M, T, S, tl.r0, t0, acc);
+#pragma unroll
+        for (int r = 0; r < RS_R; ++r)
+          rs_put(s_o + r * RUN + phase[r] + ((int)threadIdx.x * C + c) * BYTES, rs_encode(acc[r], FMT), BYTES);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) {
+      const int first = tb + r * S;                            // the run's first frame, relative to j0
+      if (first >= tl.nout) break;
+      const int cnt = min(min(RS_BLOCK, S - tb), tl.nout - first) * C * BYTES;      // bytes of the run
+      uint8_t* dst = y + (tl.j0 + first) * C * BYTES;
+      const uint8_t* src = s_o + r * RUN + phase[r];
+      const int head = min(cnt, (4 - phase[r]) & 3), body = (cnt - head) >> 2, tail = cnt - head - 4 * body;
+      if ((int)threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+      for (int i = threadIdx.x; i < body; i += RS_BLOCK) ((uint32_t*)(dst + head))[i] = ((const uint32_t*)(src + head))[i];
+      if ((int)threadIdx.x < tail) dst[head + 4 * body + threadIdx.x] = src[head + 4 * body + threadIdx.x];
     }
     __syncthreads();                                           // s_o is free for the next pass
   }
@@ -255,11 +383,30 @@ extern "C" int avsep_resample_poly(const void* x, const float* ho, int32_t B, in
   const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
   const dim3 grid(p.tiles, B);
   if (p.staged)
-    hipLaunchKernelGGL(resample_poly_kernel<true>, grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half, p.M, p.T,
-                       p.S, L, (int)lout, in_ch, out_s16, y);
+    hipLaunchKernelGGL((resample_poly_kernel<true, false>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, in_ch, RS_FMT_ROWS, out_s16, y);
   else
-    hipLaunchKernelGGL(resample_poly_kernel<false>, grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half, p.M, p.T,
-                       p.S, L, (int)lout, in_ch, out_s16, y);
+    hipLaunchKernelGGL((resample_poly_kernel<false, false>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, in_ch, RS_FMT_ROWS, out_s16, y);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_resample_poly_fmt(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down,
+                                       int32_t in_ch, int32_t in_fmt, int32_t out_fmt, void* y, avsep_stream_t stream) {
+  if (!x || !ho || !y) return AVSEP_ERR_ARG;
+  long long lout;
+  if (!rs_ratio_ok(up, down, L, &lout) || B < 1 || B > 65535) return AVSEP_ERR_ARG;
+  if (in_ch < 0 || in_ch > RS_MAX_CH || (in_ch >= 1 && B != 1) || !rs_fmt_in_ok(in_fmt) || !rs_fmt_out_ok(out_fmt)) return AVSEP_ERR_ARG;
+  if (in_ch == 0 && (in_fmt != AVSEP_SAMPLE_F32 || ((size_t)x & 3))) return AVSEP_ERR_ARG;      // rows are aligned floats
+  const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
+  const dim3 grid(p.tiles, B);
+  if (p.staged)
+    hipLaunchKernelGGL((resample_poly_kernel<true, true>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, in_ch, in_fmt, out_fmt, y);
+  else
+    hipLaunchKernelGGL((resample_poly_kernel<false, true>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
+                       p.M, p.T, p.S, L, (int)lout, in_ch, in_fmt, out_fmt, y);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -271,11 +418,27 @@ extern "C" int avsep_resample_split(const int16_t* x, const float* ho, int32_t L
   if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH) return AVSEP_ERR_ARG;
   const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
   if (p.staged)
-    hipLaunchKernelGGL(resample_split_kernel<true>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, C, y);
+    hipLaunchKernelGGL((resample_split_kernel<true, false>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, (const void*)x,
+                       ho, up, down, p.half, p.M, p.T, p.S, L, (int)lout, C, RS_FMT_ROWS, y);
   else
-    hipLaunchKernelGGL(resample_split_kernel<false>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, C, y);
+    hipLaunchKernelGGL((resample_split_kernel<false, false>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, (const void*)x,
+                       ho, up, down, p.half, p.M, p.T, p.S, L, (int)lout, C, RS_FMT_ROWS, y);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_resample_split_fmt(const void* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down,
+                                        int32_t in_fmt, float* y, avsep_stream_t stream) {
+  if (!x || !ho || !y) return AVSEP_ERR_ARG;
+  long long lout;
+  if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH || !rs_fmt_in_ok(in_fmt)) return AVSEP_ERR_ARG;
+  const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
+  if (p.staged)
+    hipLaunchKernelGGL((resample_split_kernel<true, true>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down,
+                       p.half, p.M, p.T, p.S, L, (int)lout, C, in_fmt, y);
+  else
+    hipLaunchKernelGGL((resample_split_kernel<false, true>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down,
+                       p.half, p.M, p.T, p.S, L, (int)lout, C, in_fmt, y);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -294,4 +457,27 @@ extern "C" int avsep_resample_join(const float* x, const float* ho, int32_t C, i
                        p.M, p.T, p.S, L, (int)lout, C, p.pitch, y);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
+}
+
+template <int BYTES>
+static int rs_join_fmt(const float* x, const float* ho, int C, int L, int up, int down, long long lout, uint8_t* y, hipStream_t stream) {
+  const RsPlan p = rs_plan(up, down, lout, C, BYTES == 4 ? RJ_LDS_F32 : RJ_LDS);
+  if (p.staged)
+    hipLaunchKernelGGL((resample_join_fmt_kernel<true, BYTES>), dim3(p.tiles), dim3(RS_BLOCK), 0, stream, x, ho, up, down, p.half, p.M,
+                       p.T, p.S, L, (int)lout, C, p.pitch, y);
+  else
+    hipLaunchKernelGGL((resample_join_fmt_kernel<false, BYTES>), dim3(p.tiles), dim3(RS_BLOCK), 0, stream, x, ho, up, down, p.half, p.M,
+                       p.T, p.S, L, (int)lout, C, p.pitch, y);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_resample_join_fmt(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down,
+                                       int32_t out_fmt, void* y, avsep_stream_t stream) {
+  if (!x || !ho || !y) return AVSEP_ERR_ARG;
+  long long lout;
+  if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH || !rs_fmt_out_ok(out_fmt)) return AVSEP_ERR_ARG;
+  if (out_fmt == AVSEP_SAMPLE_S16) return rs_join_fmt<2>(x, ho, C, L, up, down, lout, (uint8_t*)y, (hipStream_t)stream);
+  if (out_fmt == AVSEP_SAMPLE_S24) return rs_join_fmt<3>(x, ho, C, L, up, down, lout, (uint8_t*)y, (hipStream_t)stream);
+  return rs_join_fmt<4>(x, ho, C, L, up, down, lout, (uint8_t*)y, (hipStream_t)stream);
 }

@@ -888,6 +888,103 @@ def resample_poly(x, filt, up, down, in_ch=0, out_s16=False):
     return y
 
 
+SAMPLE_FORMATS = {"s16": (1, 2), "s24": (2, 3), "s32": (3, 4), "f32": (4, 4)}     # name -> (AVSEP_SAMPLE_* code, bytes a sample)
+SAMPLE_OUT_FORMATS = ("s16", "s24", "f32")
+
+
+def _sample_format(what, fmt, out=False):
+    if fmt not in (SAMPLE_OUT_FORMATS if out else SAMPLE_FORMATS):
+        raise lib.AvsepError(f"{what}: the {'output' if out else 'input'} sample format is one of "
+                             f"{', '.join(SAMPLE_OUT_FORMATS if out else SAMPLE_FORMATS)}, got {fmt!r}")
+    return SAMPLE_FORMATS[fmt]
+
+
+def _raw_frames(what, raw, C, nbytes):
+    """The frame count of raw uint8 [L*C*nbytes] (a file's data chunk, from any byte address)."""
+    if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < C * nbytes or raw.numel() % (C * nbytes):
+        got = f"{raw.dtype} {tuple(raw.shape)}" if torch.is_tensor(raw) else type(raw).__name__
+        raise lib.AvsepError(f"{what} takes raw frames as uint8 [L*{C}*{nbytes}], got {got}")
+    return raw.numel() // (C * nbytes)
+
+
+def _raw_out(what, out, n, device):
+    """The uint8 [n] a kernel writes file bytes into: ``out`` (a view at any byte address) or a new tensor."""
+    if out is None:
+        return torch.empty((n,), dtype=torch.uint8, device=device)
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (n,) or not out.is_contiguous() or out.device != device:
+        got = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else type(out).__name__
+        raise lib.AvsepError(f"{what}: out is contiguous uint8 [{n}] on {device}, got {got}")
+    return out
+
+
+def resample_poly_fmt(x, filt, up, down, in_ch=0, in_fmt="f32", out_fmt="f32", out=None):
+    """avsep_resample_poly_fmt (include/avsep.h).  in_ch = 0: x is f32 [B,L] (in_fmt 'f32'); in_ch = C >= 1: x is the raw
+    frames of one recording, uint8 [L*C*bytes] of in_fmt at any byte address, down-mixed while they are staged.  -> [B, Lout]
+    samples of out_fmt: f32, int16, or for 's24' uint8 [B, Lout*3]; ``out`` (uint8 [B*Lout*bytes], any byte address) takes
+    the bytes instead and is returned."""
+    lib.require_gpu(x)
+    lib.require_gpu(filt)
+    up, down, in_ch = int(up), int(down), int(in_ch)
+    icode, ibytes = _sample_format("resample_poly_fmt", in_fmt)
+    ocode, obytes = _sample_format("resample_poly_fmt", out_fmt, out=True)
+    if in_ch:
+        if not 1 <= in_ch <= 256:
+            raise lib.AvsepError(f"resample_poly_fmt down-mixes 1 to 256 channels, got {in_ch}")
+        B, L = 1, _raw_frames("resample_poly_fmt", x, in_ch, ibytes)
+    else:
+        if x.dtype != torch.float32 or x.dim() != 2 or in_fmt != "f32":
+            raise lib.AvsepError(f"resample_poly_fmt: in_ch=0 takes float32 [B,L] with in_fmt 'f32', got {x.dtype} {tuple(x.shape)} "
+                                 f"as {in_fmt!r}")
+        B, L = x.shape
+    _resample_table_check("resample_poly_fmt", filt, up, down, x.device)
+    Lout = -(-L * up // down)
+    if out is not None:
+        y = _raw_out("resample_poly_fmt", out, B * Lout * obytes, x.device)
+    elif out_fmt == "s24":
+        y = torch.empty((B, Lout * 3), dtype=torch.uint8, device=x.device)
+    else:
+        y = torch.empty((B, Lout), dtype=torch.int16 if out_fmt == "s16" else torch.float32, device=x.device)
+    x = x.contiguous()
+    call("avsep_resample_poly_fmt", ptr(x), ptr(filt), B, L, up, down, in_ch, icode, ocode, ptr(y))
+    return y
+
+
+def resample_split_fmt(raw, filt, up, down, C, in_fmt):
+    """avsep_resample_split_fmt (include/avsep.h): raw frames uint8 [L*C*bytes] of in_fmt at any byte address, 1 <= C <= 8
+    -> f32 [1+C, ceil(L*up/down)]: row 0 the down-mix resample_poly_fmt(.., in_ch=C) gives, row 1+c channel c."""
+    C = int(C)
+    icode, ibytes = _sample_format("resample_split_fmt", in_fmt)
+    if not 1 <= C <= RESAMPLE_MAX_KEPT_CHANNELS:
+        raise lib.AvsepError(f"resample_split_fmt keeps 1 to {RESAMPLE_MAX_KEPT_CHANNELS} channels, got {C}")
+    L = _raw_frames("resample_split_fmt", raw, C, ibytes)
+    lib.require_gpu(raw)
+    lib.require_gpu(filt)
+    up, down = int(up), int(down)
+    _resample_table_check("resample_split_fmt", filt, up, down, raw.device)
+    y = torch.empty((1 + C, -(-L * up // down)), dtype=torch.float32, device=raw.device)
+    raw = raw.contiguous()
+    call("avsep_resample_split_fmt", ptr(raw), ptr(filt), L, C, up, down, icode, ptr(y))
+    return y
+
+
+def resample_join_fmt(x, filt, up, down, out_fmt, out=None):
+    """avsep_resample_join_fmt (include/avsep.h): f32 [C,L], 1 <= C <= 8 -> uint8 [ceil(L*up/down)*C*bytes], interleaved
+    frames of out_fmt ('s16' | 's24' | 'f32') as they lie in a file; ``out``: a uint8 view of that size at any byte address."""
+    ocode, obytes = _sample_format("resample_join_fmt", out_fmt, out=True)
+    if x.dtype != torch.float32 or x.dim() != 2 or not 1 <= x.shape[0] <= RESAMPLE_MAX_KEPT_CHANNELS:
+        raise lib.AvsepError(f"resample_join_fmt takes float32 [C,L] with 1 <= C <= {RESAMPLE_MAX_KEPT_CHANNELS}, got "
+                             f"{x.dtype} {tuple(x.shape)}")
+    lib.require_gpu(x)
+    lib.require_gpu(filt)
+    up, down = int(up), int(down)
+    _resample_table_check("resample_join_fmt", filt, up, down, x.device)
+    Cc, L = x.shape
+    y = _raw_out("resample_join_fmt", out, -(-L * up // down) * Cc * obytes, x.device)
+    x = x.contiguous()
+    call("avsep_resample_join_fmt", ptr(x), ptr(filt), Cc, L, up, down, ocode, ptr(y))
+    return y
+
+
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 

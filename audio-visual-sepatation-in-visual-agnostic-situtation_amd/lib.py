@@ -95,6 +95,9 @@ SIGNATURES = {
     "avsep_resample_poly": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_resample_split": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "avsep_resample_join": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_poly_fmt": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_split_fmt": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_join_fmt": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

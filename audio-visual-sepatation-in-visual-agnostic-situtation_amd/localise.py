@@ -25,7 +25,7 @@ from . import kernels as K
 from . import lib
 from .lib import AvsepError
 from .models import activate
-from .separate import FOUT, WIDTH, plan_windows, read_wav, read_wav_pcm, wav_rate
+from .separate import FOUT, WIDTH, load_mixture, plan_windows
 
 
 def jet_table():
@@ -132,7 +132,8 @@ def build_parser():
     ap.add_other_arguments()
     p = ap.parser
     p.description = "Heat maps of where each source sounds, per video frame, from a trained checkpoint."
-    p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at any sample rate (resampled to --audRate on the GPU)")
+    p.add_argument("--wav", required=True, help="mixture, a WAV file (16-, 24- or 32-bit PCM or 32-bit float) at any sample rate "
+                                                "(resampled to --audRate on the GPU)")
     p.add_argument("--frames", nargs="+", required=True,
                    help="one .npy [T,3,H,W] (normalised floats) per source; ONE file with --num_mix 2 is a duet")
     p.add_argument("--fps", type=float, required=True, help="video frames per second of the .npy stacks")
@@ -166,7 +167,14 @@ def cli(argv=None):
     from .models import ModelBuilder
     args = parse_args(argv)
     from . import resample as R
-    rate = wav_rate(args.wav)
+    from . import wavio
+    try:
+        info = wavio.probe(args.wav)
+    except AvsepError as e:
+        raise SystemExit(str(e))
+    rate = info.rate
+    if info.channels > R.MAX_CHANNELS:
+        raise SystemExit(f"{args.wav}: files of up to {R.MAX_CHANNELS} channels are read, this one has {info.channels}")
     if rate != args.audRate:
         try:
             R.check_rates(rate, args.audRate)
@@ -175,10 +183,7 @@ def cli(argv=None):
     if not torch.cuda.is_available():
         raise AvsepError("localisation runs on an MI355X; there is no CPU fallback")
     dev = torch.device("cuda", 0)
-    if rate == args.audRate:
-        wav = torch.from_numpy(read_wav(args.wav)[0]).to(dev)
-    else:                                            # frame times are in seconds: only the input side needs the model's rate
-        wav = R.resample_pcm(torch.from_numpy(read_wav_pcm(args.wav)[0]).to(dev), rate, args.audRate)
+    wav = load_mixture(args.wav, info, args.audRate, dev)[0]      # frame times are in seconds: only the input side needs the model's rate
     args.ckpt = os.path.join(args.ckpt, args.id)
     if not args.weights_sound:
         args.weights_sound, args.weights_frame = ckpt.resume_paths(args, best=not args.latest)

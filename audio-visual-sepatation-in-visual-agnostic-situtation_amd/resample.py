@@ -5,7 +5,9 @@ choice, dataset.read_wav_segment, which stays on the CPU for its GPU-free worker
 float64 with NumPy alone, rounded once to f32 and handed to ``avsep_resample_poly`` (include/avsep.h, csrc/resample.hip) as
 a polyphase table cached per (up, down, device).  The kernel also reads interleaved 16-bit PCM directly (down-mix and
 conversion fused into its staging) and writes 16-bit PCM directly, so a long recording never exists as an f32 copy at the
-file's rate on the host.
+file's rate on the host.  The ``*_frames`` functions do the same for a file's frames in any of the sample formats of
+include/avsep.h (s16 / s24 / s32 PCM and f32 in, s16 / s24 / f32 out), taken and given as the bytes they are in the file
+(wavio.read_frames / write_frames).
 """
 import math
 
@@ -138,3 +140,58 @@ def join_pcm(x, rate_in, rate_out):
     _check_length(x.shape[1], up, down)
     lib.require_gpu(x)
     return K.resample_join(x.contiguous(), filter_table(up, down, x.device), up, down)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a file's frames as bytes, in any sample format (wavio.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def _raw_length(what, raw, fmt, C, most):
+    """The frame count of raw uint8 [L*C*bytes]; AvsepError for another format, tensor or channel count."""
+    if fmt not in K.SAMPLE_FORMATS:
+        raise AvsepError(f"{what} takes the sample formats {', '.join(K.SAMPLE_FORMATS)}, got {fmt!r}")
+    if int(C) != C or not 1 <= C <= most:
+        raise AvsepError(f"{what} takes 1 to {most} channels, got {C!r}")
+    nbytes = K.SAMPLE_FORMATS[fmt][1] * int(C)
+    if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() % nbytes:
+        got = f"{raw.dtype} {tuple(raw.shape)}" if torch.is_tensor(raw) else type(raw).__name__
+        raise AvsepError(f"{what} takes a file's frames as uint8 [L*{int(C)}*{nbytes // int(C)}] ({fmt}), got {got}")
+    return raw.numel() // nbytes
+
+
+def resample_frames(raw, fmt, C, rate_in, rate_out):
+    """raw: a file's frames, uint8 [L*C*bytes] on the GPU at any byte address, fmt 's16' | 's24' | 's32' | 'f32', 1 <= C <= 256
+    -> f32 mono [Lout] at rate_out: the correctly rounded mean of the channels (include/avsep.h), resampled, in one kernel.
+    Equal rates go through the same kernel with the unit-impulse filter: the converted mono signal."""
+    L = _raw_length("resample_frames", raw, fmt, C, MAX_CHANNELS)
+    up, down = check_rates(rate_in, rate_out)
+    _check_length(L, up, down)
+    lib.require_gpu(raw)
+    return K.resample_poly_fmt(raw, filter_table(up, down, raw.device), up, down, int(C), fmt, "f32")[0]
+
+
+def split_frames(raw, fmt, C, rate_in, rate_out):
+    """raw as for resample_frames, 1 <= C <= 8 -> f32 [1+C, Lout] at rate_out in one kernel: row 0 is resample_frames'
+    down-mix (the network's input), row 1+c is channel c through the same filter."""
+    L = _raw_length("split_frames", raw, fmt, C, MAX_KEPT_CHANNELS)
+    up, down = check_rates(rate_in, rate_out)
+    _check_length(L, up, down)
+    lib.require_gpu(raw)
+    return K.resample_split_fmt(raw, filter_table(up, down, raw.device), up, down, int(C), fmt)
+
+
+def join_frames(x, rate_in, rate_out, fmt, out=None):
+    """x: f32 [C,L] on the GPU, 1 <= C <= 8 -> uint8 [Lout*C*bytes] at rate_out: the frames of a WAV file in fmt 's16' | 's24' |
+    'f32', in one kernel.  s16 is join_pcm's bytes, s24 clip(rint(v * 2^23)) of the same f32 value v, f32 its bits.  Equal
+    rates go through the kernel with the unit-impulse filter: only the rounding.  ``out``: a uint8 view of that size at any
+    byte address, filled and returned."""
+    if fmt not in K.SAMPLE_OUT_FORMATS:
+        raise AvsepError(f"join_frames writes the sample formats {', '.join(K.SAMPLE_OUT_FORMATS)}, got {fmt!r}")
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2:
+        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
+        raise AvsepError(f"join_frames takes float32 [C,L], got {got}")
+    if not 1 <= x.shape[0] <= MAX_KEPT_CHANNELS:
+        raise AvsepError(f"join_frames writes 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {x.shape[0]}")
+    up, down = check_rates(rate_in, rate_out)
+    _check_length(x.shape[1], up, down)
+    lib.require_gpu(x)
+    return K.resample_join_fmt(x, filter_table(up, down, x.device), up, down, fmt, out=out)

@@ -151,7 +151,7 @@ def build_parser():
     p = argparse.ArgumentParser(prog="python -m avsep_amd.score",
                                 description="Score separated stems against their references: windowed SDR / ISR / SIR / SAR "
                                             "(image-form BSS-eval, median over windows).")
-    p.add_argument("--ref", nargs="+", required=True, help="the true stems, one 16-bit PCM WAV per source")
+    p.add_argument("--ref", nargs="+", required=True, help="the true stems, one WAV per source (16-, 24- or 32-bit PCM or 32-bit float)")
     p.add_argument("--est", nargs="+", required=True, help="the separated stems, as many files (matched to --ref by plain SDR)")
     p.add_argument("--win", type=float, default=1.0, help="window length in seconds")
     p.add_argument("--hop", type=float, default=1.0, help="seconds between window starts")
@@ -174,9 +174,15 @@ def parse_args(argv=None):
 def read_stems(ref_paths, est_paths):
     """-> (refs, ests: float64 numpy [S, C, L] in [-1, 1), rate).  All files share one rate and one channel count (nothing is
     resampled or down-mixed here); the lengths are trimmed to the shortest file."""
-    from .separate import read_wav_pcm
-    data = [read_wav_pcm(p) for p in list(ref_paths) + list(est_paths)]
+    from . import wavio
     paths = list(ref_paths) + list(est_paths)
+    data = []
+    for path in paths:                               # every format decodes to its exact values on the host (wavio.decode)
+        try:
+            raw, info = wavio.read_frames(path)
+        except AvsepError as e:
+            raise SystemExit(str(e))
+        data.append((wavio.decode(raw, info.fmt, info.channels), info.rate))
     rate, ch = data[0][1], data[0][0].shape[1]
     for path, (pcm, r) in zip(paths, data):
         if r != rate:
@@ -187,7 +193,7 @@ def read_stems(ref_paths, est_paths):
     L = min(pcm.shape[0] for pcm, _ in data)
     if L < 1:
         raise SystemExit("the shortest file is empty")
-    x = np.stack([pcm[:L].T.astype(np.float64) / 32768.0 for pcm, _ in data])                # [2 S, C, L]
+    x = np.stack([pcm[:L].T for pcm, _ in data])                                             # [2 S, C, L]
     return x[:len(ref_paths)], x[len(ref_paths):], rate
 
 

@@ -15,8 +15,9 @@ for ``use_vis=False`` the swap draw is pinned to "no swap" and consecutive windo
 (``avsep_window_agreement`` + ``align_permutations``) before blending.
 
 CLI: ``python -m avsep_amd.separate --wav mix.wav --frames a.npy b.npy --id <experiment> --out dir`` (flag set of
-arguments.py; 16-bit PCM WAV at any rate: a file that is not at ``--audRate`` is resampled on the GPU, resample.py, and
-the sources are written at the file's rate unless ``--out_rate model``).
+arguments.py; 16-, 24- or 32-bit PCM or 32-bit float WAV at any rate, read by wavio.py: a file that is not at ``--audRate``
+is resampled on the GPU, resample.py, and the sources are written at the file's rate unless ``--out_rate model``, in the
+file's sample format unless ``--out_format`` names another).
 
 The model is trained on mono and always sees the down-mix.  With ``channels`` (``--channels keep``) the one blended mask is
 also applied to each channel's own magnitude (``avsep_mask_stitch_channels``) and inverted with that channel's own phase,
@@ -283,6 +284,30 @@ def write_wav_pcm_channels(path, pcm, rate):
         w.writeframes(np.ascontiguousarray(pcm).astype("<i2", copy=False).tobytes())
 
 
+def load_mixture(path, info, model_rate, dev, keep=False):
+    """The file ``path`` (info: its wavio.probe) on ``dev`` at ``model_rate`` -> (mono f32 [L], the network's input; with
+    ``keep`` its channels f32 [C, L], else None).  A 16-bit file takes the steps it always took (read_wav's host conversion at
+    the model's rate, resample_pcm / split_pcm otherwise); every other format goes up as the bytes it is and is converted,
+    down-mixed and filtered by one kernel (resample_frames / split_frames)."""
+    from . import resample as R
+    from . import wavio
+    raw = wavio.read_frames(path)[0]
+    if info.fmt == "s16":
+        pcm = raw.view("<i2").astype(np.int16).reshape(-1, info.channels)      # read_wav_pcm's array
+        if keep:
+            rows = R.split_pcm(torch.from_numpy(pcm).to(dev), info.rate, model_rate)
+            return rows[0], rows[1:]
+        if info.rate == model_rate:                  # read_wav's arithmetic
+            data = pcm.reshape(-1).astype(np.float32) / 32768.0
+            return torch.from_numpy(data.reshape(-1, info.channels).mean(1) if info.channels > 1 else data).to(dev), None
+        return R.resample_pcm(torch.from_numpy(pcm).to(dev), info.rate, model_rate), None
+    raw = torch.from_numpy(raw).to(dev)
+    if keep:
+        rows = R.split_frames(raw, info.fmt, info.channels, info.rate, model_rate)
+        return rows[0], rows[1:]
+    return R.resample_frames(raw, info.fmt, info.channels, info.rate, model_rate), None
+
+
 def build_parser():
     from .arguments import ArgParser
     ap = ArgParser()
@@ -290,7 +315,11 @@ def build_parser():
     ap.add_other_arguments()
     p = ap.parser
     p.description = "Separate a WAV of any length with a trained checkpoint (windowed inference, stitched masks)."
-    p.add_argument("--wav", required=True, help="mixture, 16-bit PCM WAV at any sample rate (resampled to --audRate on the GPU)")
+    p.add_argument("--wav", required=True, help="mixture, a WAV file (16-, 24- or 32-bit PCM or 32-bit float) at any sample rate "
+                                                "(resampled to --audRate on the GPU)")
+    p.add_argument("--out_format", choices=("file", "s16", "s24", "f32"), default="file",
+                   help="sample format of the written sources: the input file's own (default; a 32-bit PCM file gives 24-bit), "
+                        "16-bit PCM, 24-bit PCM or 32-bit float")
     p.add_argument("--out_rate", choices=("file", "model"), default="file",
                    help="rate of the written sources: the input file's own (default) or the model's --audRate")
     p.add_argument("--channels", choices=("mix", "keep"), default="mix",
@@ -329,8 +358,17 @@ def cli(argv=None):
     from .models import ModelBuilder
     args = parse_args(argv)
     from . import resample as R
-    rate = wav_rate(args.wav)
+    from . import wavio
+    try:
+        info = wavio.probe(args.wav)
+    except AvsepError as e:
+        raise SystemExit(str(e))
+    rate = info.rate
+    out_fmt = {"file": "s24" if info.fmt == "s32" else info.fmt}.get(args.out_format, args.out_format)
     keep = args.channels == "keep"
+    if info.channels > (R.MAX_KEPT_CHANNELS if keep else R.MAX_CHANNELS):
+        raise SystemExit(f"{args.wav}: " + (f"--channels keep takes files of up to {R.MAX_KEPT_CHANNELS} channels" if keep else
+                                            f"files of up to {R.MAX_CHANNELS} channels are read") + f", this one has {info.channels}")
     if rate != args.audRate:
         try:
             R.check_rates(rate, args.audRate)
@@ -339,17 +377,8 @@ def cli(argv=None):
     if not torch.cuda.is_available():
         raise AvsepError("separation runs on an MI355X; there is no CPU fallback")
     dev = torch.device("cuda", 0)
-    channels = None
-    if keep:                                         # one kernel: the down-mix for the network and every channel beside it
-        pcm = read_wav_pcm(args.wav)[0]
-        if pcm.shape[1] > R.MAX_KEPT_CHANNELS:
-            raise SystemExit(f"{args.wav}: --channels keep takes files of up to {R.MAX_KEPT_CHANNELS} channels, this one has {pcm.shape[1]}")
-        rows = R.split_pcm(torch.from_numpy(pcm).to(dev), rate, args.audRate)
-        wav, channels = rows[0], rows[1:]
-    elif rate == args.audRate:
-        wav = torch.from_numpy(read_wav(args.wav)[0]).to(dev)
-    else:                                            # the raw frames go up; down-mix, conversion and filter are one kernel
-        wav = R.resample_pcm(torch.from_numpy(read_wav_pcm(args.wav)[0]).to(dev), rate, args.audRate)
+    # the raw frames go up; down-mix (and with keep every channel beside it), conversion and filter are one kernel
+    wav, channels = load_mixture(args.wav, info, args.audRate, dev, keep)
     args.ckpt = os.path.join(args.ckpt, args.id)
     if not args.weights_sound:
         args.weights_sound, args.weights_frame = ckpt.resume_paths(args, best=not args.latest)
@@ -367,8 +396,13 @@ def cli(argv=None):
                         stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener,
                         phase_iters=args.phase_iters)
     os.makedirs(args.out, exist_ok=True)
-    if keep:
-        out_rate = rate if args.out_rate == "file" else args.audRate
+    out_rate = rate if args.out_rate == "file" else args.audRate
+    if out_fmt != "s16":                             # the kernel writes the file's frames: every stem is one join
+        stems = out["channel_wavs"] if keep else out["wavs"][:, None]
+        for n, cw in enumerate(stems):
+            wavio.write_frames(os.path.join(args.out, f"source{n}.wav"), R.join_frames(cw, args.audRate, out_rate, out_fmt).cpu().numpy(),
+                               out_rate, cw.shape[0], out_fmt)
+    elif keep:
         for n, cw in enumerate(out["channel_wavs"]):
             write_wav_pcm_channels(os.path.join(args.out, f"source{n}.wav"), R.join_pcm(cw, args.audRate, out_rate).cpu().numpy(), out_rate)
     elif rate != args.audRate and args.out_rate == "file":

@@ -586,6 +586,38 @@ int avsep_resample_split(const int16_t* x, const float* ho, int32_t L, int32_t C
                          avsep_stream_t stream);
 int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int16_t* y,
                         avsep_stream_t stream);
+/* The same three with a file's frames as the bytes they are, in any of four sample formats.  Frames (x of _poly_fmt with
+ * in_ch >= 1 and of _split_fmt, y of _join_fmt and of _poly_fmt) are packed little-endian samples at ANY byte address: a
+ * file's data chunk rarely starts on a dword and a three-byte frame never stays on one.  One sample as f32:
+ *   AVSEP_SAMPLE_S16  2 bytes, WAVE tag 1           v / 2^15 (exact)
+ *   AVSEP_SAMPLE_S24  3 bytes packed, WAVE tag 1    sign-extended v / 2^23 (exact)
+ *   AVSEP_SAMPLE_S32  4 bytes, WAVE tag 1           the integer rounded to f32 once (nearest-even), times 2^-31
+ *   AVSEP_SAMPLE_F32  IEEE binary32, WAVE tag 3     the bits as they are (no range or NaN check)
+ * Down-mix (the mono row of _poly_fmt with in_ch = C and row 0 of _split_fmt), integer formats: the exact 64-bit sum of the C
+ *   channels over C * 2^(bits-1), rounded to f32 ONCE.  It is computed as (float)((double)sum / (double)(C << (bits-1))): sum
+ *   and divisor are exact in f64 and the f64 -> f32 double rounding of a quotient is innocuous at 53 >= 2*24 + 2 bits.  For
+ *   S16 this is avsep_resample_poly's value.  F32: the channels added in f64 in the order c = 0 ... C-1, divided by C in f64,
+ *   rounded to f32 once.  One channel (C = 1) is the sample itself.
+ * Output formats: S16 as avsep_resample_poly's out_s16; S24 = clip(rintf(v * 2^23), -2^23, 2^23 - 1), ties to even, three
+ *   little-endian bytes; F32 the accumulator's bits, not clipped.  There is no S32 output (an f32 value has 24 significant
+ *   bits) and no dither.
+ * The accumulation chains are the ones above: with S16 in and S16 / F32 out every entry point gives the bits of its older
+ * twin, and each format changes only what is staged and how the result is stored.
+ * avsep_resample_poly_fmt: in_ch = 0: x is f32 [B, L] on a 4-byte boundary and in_fmt must be AVSEP_SAMPLE_F32; in_ch = C in
+ *   [1, 256]: x is frames [L, C] of in_fmt (B must be 1).  y: [B, Lout] samples of out_fmt, packed.
+ * avsep_resample_split_fmt: x is frames [L, C] of in_fmt, y f32 [1 + C, Lout].
+ * avsep_resample_join_fmt: x is f32 [C, L], y frames [Lout, C] of out_fmt, stored as whole dwords between a head and a tail
+ *   of up to three bytes, whatever the address. */
+#define AVSEP_SAMPLE_S16 1
+#define AVSEP_SAMPLE_S24 2
+#define AVSEP_SAMPLE_S32 3
+#define AVSEP_SAMPLE_F32 4
+int avsep_resample_poly_fmt(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down, int32_t in_ch,
+                            int32_t in_fmt, int32_t out_fmt, void* y, avsep_stream_t stream);
+int avsep_resample_split_fmt(const void* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, int32_t in_fmt,
+                             float* y, avsep_stream_t stream);
+int avsep_resample_join_fmt(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int32_t out_fmt,
+                            void* y, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.

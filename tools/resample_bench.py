@@ -15,8 +15,12 @@ Prints and writes to --out (default profiles/resample_bench.json):
     the older entry points on the device — resample_pcm for the down-mix, a de-interleave to f32 rows and one batched
     resample for the channels; resample(out_s16) and a transpose back to interleaved frames — outputs compared bit for bit,
     in the same process, alternating.
+(5) beside every 16-bit row of (1) and (4) the same work on 24-bit PCM and 32-bit float frames (the *_fmt entry points:
+    resample_frames, split_frames, join_frames; a mono stem is one join_frames call of one channel), frames and outputs as
+    the bytes of a file.  --sections picks among kernels, channels, cli.
 The last line is one JSON object.
-Usage: python tools/resample_bench.py [--seconds 600] [--reps 20] [--cpu-reps 3] [--cli-reps 3] [--out FILE]"""
+Usage: python tools/resample_bench.py [--seconds 600] [--reps 20] [--cpu-reps 3] [--cli-reps 3] [--sections kernels,channels,cli]
+       [--out FILE]"""
 import argparse
 import json
 import os
@@ -94,7 +98,39 @@ def kernel_cases(seconds, dev, reps, cpu_reps):
     src64 = src.astype(np.float64)
     add("two_sources_11025_to_44100_s16", src, MODEL_RATE, 44100, 0, True, lambda: resample_poly(src64, 4, 1, axis=1))
     add("two_sources_11025_to_48000_s16", src, MODEL_RATE, 48000, 0, True, lambda: resample_poly(src64, 640, 147, axis=1))
+
+    def add_fn(name, fn, rate_in, rate_out, nbytes_in, like):
+        """A *_frames row beside the 16-bit row ``like``: the same samples in another format."""
+        up, down = RS.rational(rate_in, rate_out)
+        y = fn()
+        ys = y if isinstance(y, list) else [y]
+        nbytes = nbytes_in + sum(t.numel() * t.element_size() for t in ys) + RS.filter_table(up, down, dev).numel() * 4
+        ms = median_ms(fn, reps)
+        cases[name] = {"up": up, "down": down, "kernel_ms": ms, "algorithmic_bytes": nbytes, "bytes_per_s": nbytes / (ms * 1e-3),
+                       "share_of_hbm_peak": nbytes / (ms * 1e-3) / HBM_PEAK, "over_the_s16_row": ms / cases[like]["kernel_ms"]}
+        print(f"{name}: {up}/{down}, kernel {ms:.3f} ms ({nbytes / (ms * 1e-3) / 1e12:.2f} TB/s algorithmic, "
+              f"{100 * cases[name]['share_of_hbm_peak']:.1f}% of 8 TB/s), {cases[name]['over_the_s16_row']:.2f} x the s16 row", flush=True)
+
+    for fmt in ("s24", "f32"):
+        raw = frames_of(pcm, fmt).to(dev)
+        add_fn(f"{fmt}_stereo_44100_to_11025", lambda: RS.resample_frames(raw, fmt, 2, 44100, MODEL_RATE), 44100, MODEL_RATE,
+               raw.numel(), "pcm_stereo_44100_to_11025")
+        del raw
+    srcs = torch.from_numpy(src).to(dev)
+    for rate in (44100, 48000):
+        for fmt in ("s24", "f32"):
+            add_fn(f"two_sources_11025_to_{rate}_{fmt}", lambda: [RS.join_frames(srcs[n:n + 1], MODEL_RATE, rate, fmt) for n in range(2)],
+                   MODEL_RATE, rate, srcs.numel() * 4, f"two_sources_11025_to_{rate}_s16")
     return cases
+
+
+def frames_of(pcm, fmt):
+    """int16 [L, C] -> the same samples as a file's bytes in ``fmt`` (s24: shifted left by 8; f32: over 32768), uint8 [L*C*bytes]."""
+    if fmt == "f32":
+        return torch.from_numpy((pcm.astype(np.float32) / 32768.0).view(np.uint8).reshape(-1))
+    out = np.zeros(pcm.shape + (3,), np.uint8)
+    out[..., 1:] = np.ascontiguousarray(pcm.astype("<i2")).view(np.uint8).reshape(pcm.shape + (2,))
+    return torch.from_numpy(out.reshape(-1))
 
 
 def channel_cases(seconds, dev, reps, rate=48000, channels=2):
@@ -127,6 +163,24 @@ def channel_cases(seconds, dev, reps, rate=48000, channels=2):
         print(f"{name}: {up}/{down}, kernel {ms_f:.3f} ms ({c['bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
               f"{100 * c['share_of_hbm_peak']:.1f}% of 8 TB/s), composed {ms_c:.3f} ms ({ms_c / ms_f:.2f} x), "
               f"bit-identical {c['bit_identical_to_composed']}", flush=True)
+    # the same two ends on 24-bit and float frames: one launch each, as their 16-bit rows
+    pcm_np = pcm.cpu().numpy()
+    for fmt in ("s24", "f32"):
+        raw = frames_of(pcm_np, fmt).to(dev)
+        for name, fn, like, nin in ((f"split_{fmt}_stereo_48000_to_11025", lambda: RS.split_frames(raw, fmt, channels, rate, MODEL_RATE),
+                                     "split_pcm_stereo_48000_to_11025", raw.numel()),
+                                    (f"join_stereo_11025_to_48000_{fmt}", lambda: RS.join_frames(x, MODEL_RATE, rate, fmt),
+                                     "join_stereo_11025_to_48000_s16", x.numel() * 4)):
+            up, down = RS.rational(rate, MODEL_RATE) if name.startswith("split") else RS.rational(MODEL_RATE, rate)
+            y = fn()
+            nbytes = nin + y.numel() * y.element_size() + RS.filter_table(up, down, dev).numel() * 4
+            ms = median_ms(fn, reps)
+            out[name] = {"up": up, "down": down, "channels": channels, "kernel_ms": ms, "algorithmic_bytes": nbytes,
+                         "bytes_per_s": nbytes / (ms * 1e-3), "share_of_hbm_peak": nbytes / (ms * 1e-3) / HBM_PEAK,
+                         "over_the_s16_row": ms / out[like]["kernel_ms"]}
+            print(f"{name}: {up}/{down}, kernel {ms:.3f} ms ({nbytes / (ms * 1e-3) / 1e12:.2f} TB/s algorithmic, "
+                  f"{100 * out[name]['share_of_hbm_peak']:.1f}% of 8 TB/s), {out[name]['over_the_s16_row']:.2f} x the s16 row", flush=True)
+        del raw
     return out
 
 
@@ -179,16 +233,23 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--cpu-reps", type=int, default=3)
     ap.add_argument("--cli-reps", type=int, default=3)
+    ap.add_argument("--sections", default="kernels,channels,cli", help="comma-separated: kernels, channels, cli")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resample_bench.json"))
     o = ap.parse_args()
+    sections = set(o.sections.split(","))
+    if not sections or sections - {"kernels", "channels", "cli"}:
+        raise SystemExit(f"--sections takes kernels, channels, cli, got {o.sections!r}")
     if not torch.cuda.is_available():
         raise SystemExit("resample_bench measures on an MI355X; there is nothing to report without one")
     dev = torch.device("cuda", 0)
-    result = {"seconds": o.seconds, "kernel_reps": o.reps, "cpu_reps": o.cpu_reps, "cpu_threads": torch.get_num_threads(),
-              "kernels": kernel_cases(o.seconds, dev, o.reps, o.cpu_reps),
-              "channels": channel_cases(o.seconds, dev, o.reps),
-              "separate_cli": cli_stages(o.seconds, dev, o.cli_reps),
-              "command": "python tools/resample_bench.py"}
+    result = {"seconds": o.seconds, "kernel_reps": o.reps, "cpu_reps": o.cpu_reps, "cpu_threads": torch.get_num_threads()}
+    if "kernels" in sections:
+        result["kernels"] = kernel_cases(o.seconds, dev, o.reps, o.cpu_reps)
+    if "channels" in sections:
+        result["channels"] = channel_cases(o.seconds, dev, o.reps)
+    if "cli" in sections:
+        result["separate_cli"] = cli_stages(o.seconds, dev, o.cli_reps)
+    result["command"] = "python tools/resample_bench.py" + ("" if o.sections == "kernels,channels,cli" else f" --sections {o.sections}")
     with open(o.out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
