@@ -6,6 +6,7 @@ libavsep_gfx950.so.  Tensors are dense fp32 NCHW on the current cuda device.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import lib
@@ -983,6 +984,54 @@ def resample_join_fmt(x, filt, up, down, out_fmt, out=None):
     x = x.contiguous()
     call("avsep_resample_join_fmt", ptr(x), ptr(filt), Cc, L, up, down, ocode, ptr(y))
     return y
+
+
+TRUE_PEAK_TAPS = 21               # rows of avsep_true_peak's polyphase table
+
+
+def _level_rows(what, x):
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or not 1 <= x.shape[0] <= 65535 or x.shape[1] < 1:
+        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
+        raise lib.AvsepError(f"{what} takes float32 rows [R,L] with 1 <= R <= 65535 and L >= 1, got {got}")
+    return x.shape
+
+
+def loudness_energies(x, sos, h):
+    """avsep_loudness_energies (include/avsep.h): x f32 [R,L] on the GPU, sos float64 [2,6] on the host (two biquads
+    b0 b1 b2 1 a1 a2), h the sub-block length -> f64 [R, L // h] on the GPU: the energy of the filtered row per sub-block."""
+    R, L = _level_rows("loudness_energies", x)
+    sos = np.ascontiguousarray(np.asarray(sos, dtype=np.float64))
+    if sos.shape != (2, 6) or not np.isfinite(sos).all() or (sos[:, 3] != 1.0).any():
+        raise lib.AvsepError(f"loudness_energies takes sos as float64 [2,6], finite, with a0 = 1; got shape {sos.shape}")
+    if isinstance(h, bool) or int(h) != h or not 1 <= h <= L or L >= 2 ** 31:
+        raise lib.AvsepError(f"loudness_energies takes 1 <= h <= L < 2^31, got h={h!r} L={L}")
+    h = int(h)
+    lib.require_gpu(x)
+    x = x.contiguous()
+    nbytes = lib.load().avsep_loudness_energies_workspace_bytes(R, L, h)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
+    E = torch.empty((R, L // h), dtype=torch.float64, device=x.device)
+    call("avsep_loudness_energies", ptr(x), sos.ctypes.data, R, L, h, ptr(E), ptr(ws), nbytes)
+    return E
+
+
+def true_peak(x, taps, os):
+    """avsep_true_peak (include/avsep.h): x f32 [R,L], taps f64 [21, os] on x's device (the polyphase table of the
+    interpolation filter), os 1 | 2 | 4 -> f64 [R,2] on the GPU: (sample peak, true peak) per row, +inf for a row that holds
+    a NaN or an infinity."""
+    R, L = _level_rows("true_peak", x)
+    if isinstance(os, bool) or os not in (1, 2, 4) or os * L >= 2 ** 31:
+        raise lib.AvsepError(f"true_peak oversamples by 1, 2 or 4 with os * L < 2^31, got os={os!r} L={L}")
+    if not torch.is_tensor(taps) or taps.dtype != torch.float64 or tuple(taps.shape) != (TRUE_PEAK_TAPS, os) or taps.device != x.device:
+        got = f"{taps.dtype} {tuple(taps.shape)} on {taps.device}" if torch.is_tensor(taps) else type(taps).__name__
+        raise lib.AvsepError(f"true_peak: the table of os={os} is float64 [{TRUE_PEAK_TAPS},{os}] on {x.device}, got {got}")
+    lib.require_gpu(x)
+    x, taps = x.contiguous(), taps.contiguous()
+    nbytes = lib.load().avsep_true_peak_workspace_bytes(R, L)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
+    peaks = torch.empty((R, 2), dtype=torch.float64, device=x.device)
+    call("avsep_true_peak", ptr(x), ptr(taps), R, L, int(os), ptr(peaks), ptr(ws), nbytes)
+    return peaks
 
 
 def _ptr_array(tensors):

@@ -99,7 +99,7 @@ def _visual_features(net_frame, frames, args, Kw, batch):
 
 
 def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None,
-                  wiener=0, phase_iters=0):
+                  wiener=0, phase_iters=0, clamp=True):
     """Separate one recording ``wav`` [L] (on the GPU, L >= args.stft_frame; several recordings: one call each).
 
     nets: (net_sound, net_frame), both in eval() — train-mode BatchNorm over the windows of one recording is never what
@@ -130,6 +130,9 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
     channel's N stems against that channel, started from the channel's own phase or, with ``wiener``, from the filter's
     magnitudes and per-source phases.  The stems are clamped as before and are not forced to sum to the mixture.
     "perms", "masks" and "lin_masks" do not depend on it.
+
+    clamp: False leaves "wavs" and "channel_wavs" as the inverse transform gives them, overshoots past full scale included
+    (levels.py then measures them and rescales instead of clipping).  Nothing else changes.
     """
     net_sound, net_frame = nets
     if isinstance(wiener, bool) or not isinstance(wiener, int) or not 0 <= wiener <= MAX_WIENER:
@@ -193,9 +196,11 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
         mags, lin = K.mask_stitch(masks, starts_t, perms.to(dev), mag, binary, getattr(args, "mask_thres", 0.5), return_masks)
         out_len = plan.hop * (mag.shape[1] - 1)
         if phase_iters:
-            wavs = plan.misi(wav.float()[None, :out_len], mags[:, None], phase[None], phase_iters)[:, 0].clamp_(-1.0, 1.0)
+            wavs = plan.misi(wav.float()[None, :out_len], mags[:, None], phase[None], phase_iters)[:, 0]
         else:
-            wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous()).clamp_(-1.0, 1.0)
+            wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous())
+        if clamp:
+            wavs = wavs.clamp_(-1.0, 1.0)
         if channels is not None:                                         # the same masks on every channel's own STFT
             mag_c, phase_c = plan.stft(channels.contiguous())
             Cc, Fin, Fr = mag_c.shape
@@ -205,12 +210,14 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
             if wiener:                                                   # soft source images in, one phase per source out
                 mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener)
             if phase_iters:                                              # every channel is the mixture of its N stems
-                channel_wavs = plan.misi(channels[:, :out_len], mags_c, phases_c, phase_iters).clamp_(-1.0, 1.0)
+                channel_wavs = plan.misi(channels[:, :out_len], mags_c, phases_c, phase_iters)
             else:
                 if not wiener:
                     phases_c = phase_c[None].expand(N, -1, -1, -1).contiguous()
                 channel_wavs = plan.istft(mags_c.reshape(N * Cc, Fin, Fr), phases_c.reshape(N * Cc, Fin, Fr))
-                channel_wavs = channel_wavs.clamp_(-1.0, 1.0).reshape(N, Cc, -1)
+                channel_wavs = channel_wavs.reshape(N, Cc, -1)
+            if clamp:
+                channel_wavs = channel_wavs.clamp_(-1.0, 1.0)
     out = {"wavs": wavs, "starts": starts, "perms": perms}
     if channels is not None:
         out["channel_wavs"] = channel_wavs
@@ -331,6 +338,13 @@ def build_parser():
     p.add_argument("--phase_iters", type=int, default=0, metavar="K",
                    help="K mixture-consistent phase iterations (0 ... 32) in place of the one inverse transform: every source "
                         "gets a phase of its own (0, the default: the mixture's phase; no gain with --binary_mask 1)")
+    p.add_argument("--levels", action="store_true",
+                   help="measure the mixture and the written sources (BS.1770-4 loudness, true peak) into <out>/levels.json")
+    p.add_argument("--peak", type=float, default=None, metavar="DBTP",
+                   help="rescale instead of clipping: one gain for all sources so that no true peak exceeds DBTP (<= 0)")
+    p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                   help="one gain for all sources that brings the mixture to LUFS (-70 ... 0) integrated loudness; "
+                        "with --peak the ceiling wins")
     p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]")
     p.add_argument("--out", default="separated", help="output directory (source<n>.wav)")
     p.add_argument("--audio_only", action="store_true", help="no frames: audio-only branch with aligned windows")
@@ -350,7 +364,48 @@ def parse_args(argv=None):
         raise SystemExit(f"--phase_iters takes 0 ... {MAX_PHASE_ITERS} passes, got {args.phase_iters}")
     if args.wiener and args.channels != "keep":
         raise SystemExit("--wiener filters the file's channels: it needs --channels keep")
+    if args.peak is not None and not args.peak <= 0.0:
+        raise SystemExit(f"--peak takes a true-peak ceiling of at most 0 dBTP, got {args.peak}")
+    if args.loudness is not None and not -70.0 <= args.loudness <= 0.0:
+        raise SystemExit(f"--loudness takes a target in -70 ... 0 LUFS, got {args.loudness}")
     return args
+
+
+def output_mixture(path, info, out_rate, wav, channels, dev):
+    """What the stems are stems of, at the output rate, f32 [C, L] on ``dev``: the file's channels under --channels keep
+    (``channels`` is not None), else the down-mix row.  At the model's rate these are the network's own inputs."""
+    from . import resample as R
+    from . import wavio
+    if out_rate != info.rate:
+        return channels if channels is not None else wav[None]
+    raw = torch.from_numpy(wavio.read_frames(path)[0]).to(dev)
+    if channels is not None:
+        return R.split_frames(raw, info.fmt, info.channels, info.rate, info.rate)[1:]
+    return R.resample_frames(raw, info.fmt, info.channels, info.rate, info.rate)[None]
+
+
+def write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev):
+    """--peak / --loudness: the unclamped stems at the output rate, one gain for all of them (levels.output_gain), every
+    format through join_frames at equal rates.  -> the levels.json dict."""
+    from . import levels as LV
+    from . import resample as R
+    from . import wavio
+    stems = out["channel_wavs"] if keep else out["wavs"][:, None]
+    N, Cc, Lm = stems.shape
+    rows = R.resample(stems.reshape(N * Cc, Lm).contiguous(), args.audRate, out_rate).reshape(N, Cc, -1)
+    mix = output_mixture(args.wav, info, out_rate, wav, channels, dev)
+    m_stems, m_mix = LV.measure(rows, out_rate), LV.measure(mix, out_rate)
+    try:
+        gain, limited_by = LV.output_gain(m_mix["integrated"][0], m_stems["true_peak"], args.loudness, args.peak)
+    except AvsepError as e:
+        raise SystemExit(f"{args.wav}: {e}")
+    if gain != 1.0:                                  # both meters are linear: the figures after the gain follow from those before
+        rows = rows * gain
+        m_stems, m_mix = LV.scaled(m_stems, gain), LV.scaled(m_mix, gain)
+    for n in range(N):
+        wavio.write_frames(os.path.join(args.out, f"source{n}.wav"),
+                           R.join_frames(rows[n].contiguous(), out_rate, out_rate, out_fmt).cpu().numpy(), out_rate, Cc, out_fmt)
+    return LV.report(out_rate, gain, limited_by, m_mix, m_stems)
 
 
 def cli(argv=None):
@@ -374,6 +429,11 @@ def cli(argv=None):
             R.check_rates(rate, args.audRate)
         except AvsepError as e:
             raise SystemExit(f"{args.wav}: {e}")
+    if args.levels or args.peak is not None or args.loudness is not None:
+        from . import levels as LV
+        measured_rate = rate if args.out_rate == "file" else args.audRate
+        if not LV.MIN_RATE <= measured_rate <= LV.MAX_RATE:
+            raise SystemExit(f"{args.wav}: levels are measured at {LV.MIN_RATE} ... {LV.MAX_RATE} Hz, the sources are written at {measured_rate} Hz")
     if not torch.cuda.is_available():
         raise AvsepError("separation runs on an MI355X; there is no CPU fallback")
     dev = torch.device("cuda", 0)
@@ -392,12 +452,16 @@ def cli(argv=None):
     for path in args.frames:
         fr = torch.from_numpy(np.load(path)).float()
         frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
+    levelled = args.peak is not None or args.loudness is not None
     out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
                         stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener,
-                        phase_iters=args.phase_iters)
+                        phase_iters=args.phase_iters, clamp=not levelled)
     os.makedirs(args.out, exist_ok=True)
     out_rate = rate if args.out_rate == "file" else args.audRate
-    if out_fmt != "s16":                             # the kernel writes the file's frames: every stem is one join
+    report = None
+    if levelled:                                     # rescaled, not clipped: measured and written at the output rate
+        report = write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev)
+    elif out_fmt != "s16":                             # the kernel writes the file's frames: every stem is one join
         stems = out["channel_wavs"] if keep else out["wavs"][:, None]
         for n, cw in enumerate(stems):
             wavio.write_frames(os.path.join(args.out, f"source{n}.wav"), R.join_frames(cw, args.audRate, out_rate, out_fmt).cpu().numpy(),
@@ -411,7 +475,19 @@ def cli(argv=None):
     else:
         for n, w in enumerate(out["wavs"].cpu().numpy()):
             write_wav(os.path.join(args.out, f"source{n}.wav"), w, args.audRate)
+    if args.levels and report is None:               # the clamped stems as they were written, at the output rate
+        from . import levels as LV
+        stems = out["channel_wavs"] if keep else out["wavs"][:, None]
+        rows = R.resample(stems.reshape(-1, stems.shape[-1]).contiguous(), args.audRate, out_rate).reshape(*stems.shape[:2], -1)
+        report = LV.report(out_rate, 1.0, None, LV.measure(output_mixture(args.wav, info, out_rate, wav, channels, dev), out_rate),
+                           LV.measure(rows, out_rate))
+    if report is not None:
+        import json
+        with open(os.path.join(args.out, "levels.json"), "w") as f:
+            json.dump(report, f, indent=1)
     kept = f", {channels.shape[0]} channel{'s' if channels.shape[0] != 1 else ''} each" if keep else ""
+    if report is not None and report["limited_by"]:
+        kept += f", gain {report['gain_db']:+.2f} dB (limited by {report['limited_by']})"
     if args.wiener:
         kept += f", multichannel Wiener filter x{args.wiener}"
     if args.phase_iters:

@@ -620,6 +620,34 @@ int avsep_resample_join_fmt(const float* x, const float* ho, int32_t C, int32_t 
                             void* y, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Stem levels (csrc/levels.hip; avsep_amd/levels.py): what ITU-R BS.1770-4 loudness and true peak need from every sample of
+ * R rows x f32 [R, L] in device memory.  float64 throughout (a sample is converted once), no atomics, no waveform written;
+ * every sum has a fixed order, so a row gives the same bits alone, inside a batch and on a second call.
+ * avsep_loudness_energies: sos is 12 doubles in HOST memory, read before the call returns: two biquads b0 b1 b2 1 a1 a2
+ *   (scipy's sos rows; every value finite, a0 = 1), applied in cascade from rest at sample 0 of every row (transposed
+ *   direct form II).  E f64 [R, S], S = L div h: E[r, s] = sum of y^2 over the samples [s*h, (s+1)*h) of the filtered row
+ *   y; the tail L mod h counts nowhere.  The row is cut into pieces by a plan that depends on h only (a sub-block is
+ *   ceil(h / 128) pieces of floor or ceil of their mean length; none straddles a sub-block edge): the pieces run from rest,
+ *   their start states follow from v' = M v + e with the 4x4 transition M of a piece (built in float64 inside the call),
+ *   then they run again from their true state and their sums are added per sub-block in ascending order.  Hence the first
+ *   S' energies of a row do not change when L grows.  1 <= R <= 65535, 1 <= h <= L < 2^31.
+ * avsep_true_peak: taps f64 [21, os] in DEVICE memory, the polyphase table of an interpolation filter g of 20*os + 1 taps,
+ *   taps[i][p] = g[p + i*os] (0 past the filter's end), os in {1, 2, 4}.  peaks f64 [R, 2]: peaks[r, 0] = max_n |x[r, n]|,
+ *   peaks[r, 1] = the maximum of that and of |u[m]| over m in [0, os*L), where with pos = m + 10*os, p = pos mod os,
+ *   n0 = pos div os:  u[m] = sum_{i = 0 .. 20, in this order} fma(x[r, n0 - i], taps[i][p], .), samples outside [0, L) being 0:
+ *   avsep_resample_poly's indexing at down = 1.  A NaN or infinite sample makes both peaks of its row +inf.  The maxima are
+ *   taken per workgroup and then over the workgroups' partials: exact, whatever the order.  1 <= R <= 65535, 1 <= L,
+ *   os*L < 2^31.
+ * Anything outside these limits or a null pointer is AVSEP_ERR_ARG before any launch (the workspace query returns 0); ws:
+ * the query's bytes, else AVSEP_ERR_WORKSPACE. */
+size_t avsep_loudness_energies_workspace_bytes(int32_t R, int32_t L, int32_t h);
+int avsep_loudness_energies(const float* x, const double* sos, int32_t R, int32_t L, int32_t h, double* E, void* ws,
+                            size_t ws_bytes, avsep_stream_t stream);
+size_t avsep_true_peak_workspace_bytes(int32_t R, int32_t L);
+int avsep_true_peak(const float* x, const double* taps, int32_t R, int32_t L, int32_t os, double* peaks, void* ws, size_t ws_bytes,
+                    avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
  * that are accumulated into, exactly as for the fp32 NCHW entry points of the same names below.
