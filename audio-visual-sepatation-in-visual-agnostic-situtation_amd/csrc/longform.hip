@@ -125,7 +125,7 @@ __device__ __forceinline__ void stitch_window_run(const int* __restrict__ starts
 }
 
 // The blended mask M of source n at frame t and the output row whose warp coordinate is gy: walks the run [k_lo, k_hi] and
-// keeps the windows the frame lies in, in ascending k.  The one body of both stitch kernels: they cannot disagree on M.
+// keeps the windows the frame lies in, in ascending k.
 __device__ __forceinline__ float stitch_point(const float* __restrict__ masks, const int* __restrict__ starts,
                                               const int* __restrict__ perm, int k_lo, int k_hi, int N, int n, int Fout, int W,
                                               int t, float gy) {
@@ -148,51 +148,16 @@ __device__ __forceinline__ float stitch_point(const float* __restrict__ masks, c
 }
 
 // grid (ceil(F / 256), ceil(Fin / LF_ROWS), N); one thread searches the window run, a thread then owns one frame of
-// LF_ROWS rows.
+// LF_ROWS rows.  M is blended once per point (the gather through L2 is what the kernel's time goes to) and multiplied into
+// the C magnitudes.  Rows of [N, C, Fin, F] pass 2^31 elements on a multi-hour recording: every offset is formed in 64 bits.
+// MONO: C is 1 at compile time (the down-mix alone, most calls): no channel loop.
+template <bool MONO>
 __global__ __launch_bounds__(LF_BLOCK) void mask_stitch_kernel(const float* __restrict__ masks, const int* __restrict__ starts,
                                                                const int* __restrict__ perm, const float* __restrict__ mag,
-                                                               int K, int N, int Fout, int W, int Fin, int F, int binary,
+                                                               int K, int N, int Fout, int W, int channels, int Fin, int F, int binary,
                                                                float thres, float* __restrict__ out,
                                                                float* __restrict__ mask_out) {
-  const int t0 = blockIdx.x * LF_BLOCK, f0 = blockIdx.y * LF_ROWS, n = blockIdx.z, rows = min(LF_ROWS, Fin - f0);
-  __shared__ float s_gy[LF_ROWS];
-  __shared__ int s_lo, s_hi;
-  if (threadIdx.x < rows) s_gy[threadIdx.x] = warp_gy(f0 + threadIdx.x, Fin, 0);
-  if (threadIdx.x == LF_BLOCK - 1) stitch_window_run(starts, K, W, t0, F, s_lo, s_hi);
-  __syncthreads();
-  const int t = t0 + threadIdx.x;
-  if (t >= F) return;
-  const int k_lo = s_lo, k_hi = s_hi;
-  for (int r = 0; r < rows; ++r) {
-    const float M = stitch_point(masks, starts, perm, k_lo, k_hi, N, n, Fout, W, t, s_gy[r]);
-    const int f = f0 + r;
-    const long long o = ((long long)n * Fin + f) * F + t;
-    out[o] = mag[(long long)f * F + t] * (binary ? (M > thres ? 1.f : 0.f) : M);
-    if (mask_out) mask_out[o] = M;
-  }
-}
-
-extern "C" int avsep_mask_stitch(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
-                                 int32_t N, int32_t Fout, int32_t W, int32_t Fin, int32_t F, int32_t binary, float thres,
-                                 float* out, float* mask_out, avsep_stream_t stream) {
-  if (!masks || !starts || !perm || !mag || !out) return AVSEP_ERR_ARG;
-  if (K <= 0 || K > 65535 || N <= 0 || N > 65535 || Fout <= 0 || W <= 0 || Fin <= 0 || Fin > 65535 || F <= 0)
-    return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(mask_stitch_kernel, dim3(cdiv(F, LF_BLOCK), cdiv(Fin, LF_ROWS), N), dim3(LF_BLOCK), 0, (hipStream_t)stream, masks,
-                     starts, perm, mag, K, N, Fout, W, Fin, F, binary, thres, out, mask_out);
-  AVSEP_LAUNCH_CHECK();
-  return AVSEP_OK;
-}
-
-// The same grid for a recording of C channels: M is blended once per point (the gather through L2 is what the kernel's time
-// goes to) and multiplied into the C magnitudes.  Rows of [N, C, Fin, F] pass 2^31 elements on a multi-hour recording: every
-// offset is formed in 64 bits.
-__global__ __launch_bounds__(LF_BLOCK) void mask_stitch_channels_kernel(const float* __restrict__ masks,
-                                                                        const int* __restrict__ starts,
-                                                                        const int* __restrict__ perm,
-                                                                        const float* __restrict__ mag, int K, int N, int Fout,
-                                                                        int W, int C, int Fin, int F, int binary, float thres,
-                                                                        float* __restrict__ out, float* __restrict__ mask_out) {
+  const int C = MONO ? 1 : channels;
   const int t0 = blockIdx.x * LF_BLOCK, f0 = blockIdx.y * LF_ROWS, n = blockIdx.z, rows = min(LF_ROWS, Fin - f0);
   __shared__ float s_gy[LF_ROWS];
   __shared__ int s_lo, s_hi;
@@ -213,15 +178,16 @@ __global__ __launch_bounds__(LF_BLOCK) void mask_stitch_channels_kernel(const fl
   }
 }
 
-extern "C" int avsep_mask_stitch_channels(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag,
-                                          int32_t K, int32_t N, int32_t Fout, int32_t W, int32_t C, int32_t Fin, int32_t F,
-                                          int32_t binary, float thres, float* out, float* mask_out, avsep_stream_t stream) {
+extern "C" int avsep_mask_stitch(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
+                                 int32_t N, int32_t Fout, int32_t W, int32_t C, int32_t Fin, int32_t F, int32_t binary, float thres,
+                                 float* out, float* mask_out, avsep_stream_t stream) {
   if (!masks || !starts || !perm || !mag || !out) return AVSEP_ERR_ARG;
   if (K <= 0 || K > 65535 || N <= 0 || N > 65535 || Fout <= 0 || W <= 0 || C <= 0 || C > 65535 || Fin <= 0 || Fin > 65535 ||
       F <= 0)
     return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(mask_stitch_channels_kernel, dim3(cdiv(F, LF_BLOCK), cdiv(Fin, LF_ROWS), N), dim3(LF_BLOCK), 0,
-                     (hipStream_t)stream, masks, starts, perm, mag, K, N, Fout, W, C, Fin, F, binary, thres, out, mask_out);
+  hipLaunchKernelGGL(C == 1 ? mask_stitch_kernel<true> : mask_stitch_kernel<false>, dim3(cdiv(F, LF_BLOCK), cdiv(Fin, LF_ROWS), N),
+                     dim3(LF_BLOCK), 0, (hipStream_t)stream, masks, starts, perm, mag, K, N, Fout, W, C, Fin, F, binary, thres, out,
+                     mask_out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }

@@ -1559,7 +1559,7 @@ extern "C" int avsep_glue_plan(const char* op, int32_t N, int32_t C, int32_t H, 
   return AVSEP_OK;
 }
 
-extern "C" int avsep_version(void) { return 100; }
+extern "C" int avsep_version(void) { return 101; }
 extern "C" const char* avsep_arch(void) { return "gfx950"; }
 extern "C" const char* avsep_strerror(int code) {
   switch (code) {

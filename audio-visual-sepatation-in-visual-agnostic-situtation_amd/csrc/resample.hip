@@ -6,11 +6,13 @@
 // columns of the table: coalesced) and used RS_R times.
 // No atomics: every output is one sequential f32 fused-multiply-add chain whose order depends on (up, down, j) only.
 // Two more kernels keep a file's channels apart with the same tiles and the same chains (rs_chains): resample_split_kernel
-// gives the down-mix and every channel of interleaved PCM in one pass, resample_join_kernel turns C rows back into
-// interleaved PCM and writes whole frames.
-// The *_fmt entry points take and give a file's frames as the bytes they are, in the sample formats of include/avsep.h, from
-// and to any byte address: the same kernels with another conversion in the staging loop (rs_frame) and at the store, the
-// chains untouched.
+// gives the down-mix and every channel of a file's frames in one pass, resample_join_kernel turns C rows back into frames
+// and writes them whole.
+// Frames are taken and given as the bytes they are in a file, in the sample formats of include/avsep.h, from and to any byte
+// address: a format shows in the conversion of the staging loop (rs_frame) and at the store, never in the chains.
+// 16-bit frames and f32 rows on their natural boundary are most of what arrives and have a compile-time form of their own in
+// every kernel (FAST, and resample_join_s16_kernel): typed loads and stores in place of rs_bytes / rs_put, the same values.
+// The entry points pick it from the formats and the addresses they are handed; a caller never does.
 #include "common.h"
 
 constexpr int RS_BLOCK = 256;
@@ -26,7 +28,6 @@ constexpr int RJ_SPAN = 8704;      // join: staged floats of all C rows together
 constexpr int RJ_LDS = RJ_SPAN + RJ_SPAN / 32 + 1;
 constexpr int RJ_SPAN_F32 = 7936;  // join to f32 frames: the output tile is 32 KiB, the staged rows get what is left of 64 KiB
 constexpr int RJ_LDS_F32 = RJ_SPAN_F32 + RJ_SPAN_F32 / 32 + 1;
-constexpr int RS_FMT_ROWS = 0;     // the entry points without a format: aligned int16 frames (or f32 rows) in, s16 / f32 out
 
 __device__ __forceinline__ int rs_fmt_bytes(int fmt) { return fmt == AVSEP_SAMPLE_S16 ? 2 : fmt == AVSEP_SAMPLE_S24 ? 3 : 4; }
 static inline bool rs_fmt_in_ok(int fmt) { return fmt >= AVSEP_SAMPLE_S16 && fmt <= AVSEP_SAMPLE_F32; }
@@ -72,13 +73,14 @@ __device__ __forceinline__ float rs_frame(const void* __restrict__ x, long long 
   return (float)((double)sum / (double)((long long)C << (8 * bytes - 1)));
 }
 
-// Sample n of a row; zero outside it.  in_ch >= 1: interleaved int16 [L, in_ch]; ch < 0 is the exact integer sum of the
-// channels over in_ch * 32768 with a correctly rounded division (separate.read_wav's value for one and two channels),
-// ch >= 0 is channel ch over 32768 (exact).  fmt != RS_FMT_ROWS: frames of that format at any byte address (rs_frame).
+// Sample n of a row; zero outside it.  in_ch = 0: an aligned f32 row; in_ch >= 1: frames [L, in_ch] of format fmt at any
+// byte address, channel ch or (ch < 0) their down-mix (rs_frame).  FAST: the frames are int16 on a 2-byte boundary; the sum
+// of up to 256 channels and the divisor are exact in f32 and the f32 division is correctly rounded: rs_frame's value.
+template <bool FAST>
 __device__ __forceinline__ float rs_sample(const void* __restrict__ x, long long n, long long L, int in_ch, int ch, int fmt) {
   if ((unsigned long long)n >= (unsigned long long)L) return 0.f;
   if (in_ch == 0) return ((const float*)x)[n];
-  if (fmt != RS_FMT_ROWS) return rs_frame(x, n, in_ch, ch, fmt);
+  if (!FAST) return rs_frame(x, n, in_ch, ch, fmt);
   const int16_t* s = (const int16_t*)x + n * in_ch;
   if (ch >= 0) return (float)s[ch] * (1.f / 32768.f);
   int sum = 0;
@@ -136,7 +138,7 @@ __device__ __forceinline__ RsTile rs_tile(int up, int down, int half, int T, int
 // fit) every tap reads global memory: the same values in the same order, so the mode never shows in the result.
 // Outputs past the row's end compute on whatever the tile holds and are not stored by the callers; their reads stay inside
 // s_x (the host sized it for a full tile) or inside the row (rs_sample checks).
-template <bool STAGED>
+template <bool STAGED, bool FAST>
 __device__ __forceinline__ void rs_chains(const float* s_x, const void* __restrict__ xr, long long n_lo, int L, int in_ch, int ch,
                                           int fmt, const float* __restrict__ ho, int up, int down, int M, int T, int S, int r0,
                                           int t0, float acc[RS_R]) {
@@ -149,7 +151,7 @@ __device__ __forceinline__ void rs_chains(const float* s_x, const void* __restri
     top[r] = dq + r * step + T - 1;
     acc[r] = 0.f;
   }
-#define RS_X(r, i) (STAGED ? s_x[rs_slot(top[r] - (i))] : rs_sample(xr, n_lo + top[r] - (i), L, in_ch, ch, fmt))
+#define RS_X(r, i) (STAGED ? s_x[rs_slot(top[r] - (i))] : rs_sample<FAST>(xr, n_lo + top[r] - (i), L, in_ch, ch, fmt))
 #pragma unroll 4
   for (int i = 0; i < T - 1; ++i) {
     const float c = h[i * up];
@@ -164,33 +166,32 @@ __device__ __forceinline__ void rs_chains(const float* s_x, const void* __restri
 #undef RS_X
 }
 
-// grid (ceil(Lout / (RS_R * S)), B).  ANY: the *_fmt entry point, in_fmt / out_fmt are sample formats and the frames and y
-// have any byte alignment; else in_fmt is RS_FMT_ROWS and out_fmt the older entry point's out_s16.
-template <bool STAGED, bool ANY>
+// grid (ceil(Lout / (RS_R * S)), B).  Frames (in_ch >= 1) and y have any byte alignment; one output per lane.
+// FAST: f32 rows or aligned int16 frames in, s16 or f32 out on its own boundary.
+template <bool STAGED, bool FAST>
 __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const void* __restrict__ x, const float* __restrict__ ho, int up,
                                                                  int down, int half, int M, int T, int S, int L, int Lout,
-                                                                 int in_ch, int in_fmt, int out_fmt, void* __restrict__ y) {
+                                                                 int in_ch, int fmt, int out_fmt, void* __restrict__ y) {
   __shared__ float s_x[STAGED ? RS_LDS : 1];
   const int row = blockIdx.y;
-  const int fmt = ANY ? in_fmt : RS_FMT_ROWS;
   const RsTile tl = rs_tile(up, down, half, T, S, Lout);
   const void* xr = in_ch ? x : (const void*)((const float*)x + (long long)row * L);
   if (STAGED) {
-    for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(xr, tl.n_lo + s, L, in_ch, -1, fmt);
+    for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample<FAST>(xr, tl.n_lo + s, L, in_ch, -1, fmt);
     __syncthreads();
   }
   for (int t0 = threadIdx.x; t0 < S; t0 += RS_BLOCK) {
     if (t0 >= tl.nout) break;                                // none of this thread's outputs lies inside the row
     float acc[RS_R];
-    rs_chains<STAGED>(s_x, xr, tl.n_lo, L, in_ch, -1, fmt, ho, up, down, M, T, S, tl.r0, t0, acc);
+    rs_chains<STAGED, FAST>(s_x, xr, tl.n_lo, L, in_ch, -1, fmt, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
     for (int r = 0; r < RS_R; ++r) {
       const int dj = t0 + r * S;
       if (dj >= tl.nout) break;
       const long long o = (long long)row * Lout + tl.j0 + dj;
-      if (ANY)
+      if (!FAST)
         rs_put((uint8_t*)y + o * rs_fmt_bytes(out_fmt), rs_encode(acc[r], out_fmt), rs_fmt_bytes(out_fmt));
-      else if (out_fmt)
+      else if (out_fmt == AVSEP_SAMPLE_S16)
         ((int16_t*)y)[o] = rs_s16(acc[r]);
       else
         ((float*)y)[o] = acc[r];
@@ -198,28 +199,26 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_poly_kernel(const void* __r
   }
 }
 
-// grid (ceil(Lout / (RS_R * S))).  Interleaved int16 [L, C] -> f32 [1 + C, Lout]: the workgroup makes its tile of every row
-// in turn, row 0 from the down-mix and row 1 + c from channel c, so the file is fetched from HBM once (the later rows find
-// the tile's frames in L2) and no de-interleaved copy of it exists.
-// ANY: the *_fmt entry point, frames of sample format in_fmt at any byte address; else aligned int16.
-template <bool STAGED, bool ANY>
+// grid (ceil(Lout / (RS_R * S))).  Frames [L, C] of format fmt at any byte address -> f32 [1 + C, Lout]: the workgroup makes
+// its tile of every row in turn, row 0 from the down-mix and row 1 + c from channel c, so the file is fetched from HBM once
+// (the later rows find the tile's frames in L2) and no de-interleaved copy of it exists.  FAST: aligned int16 frames.
+template <bool STAGED, bool FAST>
 __global__ __launch_bounds__(RS_BLOCK) void resample_split_kernel(const void* __restrict__ x, const float* __restrict__ ho,
                                                                   int up, int down, int half, int M, int T, int S, int L,
-                                                                  int Lout, int C, int in_fmt, float* __restrict__ y) {
+                                                                  int Lout, int C, int fmt, float* __restrict__ y) {
   __shared__ float s_x[STAGED ? RS_LDS : 1];
-  const int fmt = ANY ? in_fmt : RS_FMT_ROWS;
   const RsTile tl = rs_tile(up, down, half, T, S, Lout);
   for (int row = 0; row <= C; ++row) {
     const int ch = row - 1;                                  // -1: the down-mix
     if (STAGED) {
       if (row) __syncthreads();                              // the previous row's chains have read s_x
-      for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample(x, tl.n_lo + s, L, C, ch, fmt);
+      for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK) s_x[rs_slot(s)] = rs_sample<FAST>(x, tl.n_lo + s, L, C, ch, fmt);
       __syncthreads();
     }
     for (int t0 = threadIdx.x; t0 < S; t0 += RS_BLOCK) {
       if (t0 >= tl.nout) break;
       float acc[RS_R];
-      rs_chains<STAGED>(s_x, x, tl.n_lo, L, C, ch, fmt, ho, up, down, M, T, S, tl.r0, t0, acc);
+      rs_chains<STAGED, FAST>(s_x, x, tl.n_lo, L, C, ch, fmt, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
       for (int r = 0; r < RS_R; ++r) {
         const int dj = t0 + r * S;
@@ -230,13 +229,13 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_split_kernel(const void* __
   }
 }
 
-// grid (ceil(Lout / (RS_R * S))).  f32 [C, L] -> interleaved int16 [Lout, C].  A pass of the workgroup makes RS_R runs of
-// RS_BLOCK consecutive frames; it computes them for every channel into the LDS tile s_o, laid out as the file is
+// grid (ceil(Lout / (RS_R * S))).  f32 [C, L] -> frames [Lout, C] of int16 on a 2-byte boundary.  A pass of the workgroup makes
+// RS_R runs of RS_BLOCK consecutive frames; it computes them for every channel into the LDS tile s_o, laid out as the file is
 // ([run][frame][channel]), and then stores each run as one contiguous stretch of RS_BLOCK * C samples, lanes on consecutive
 // 4-byte words (2-byte samples where the run starts on an odd sample): no store with a stride of 2C bytes.  The C rows of the
 // input tile are staged side by side, `pitch` slots apart.
 template <bool STAGED>
-__global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __restrict__ x, const float* __restrict__ ho, int up,
+__global__ __launch_bounds__(RS_BLOCK) void resample_join_s16_kernel(const float* __restrict__ x, const float* __restrict__ ho, int up,
                                                                  int down, int half, int M, int T, int S, int L, int Lout,
                                                                  int C, int pitch, int16_t* __restrict__ y) {
   __shared__ float s_x[STAGED ? RJ_LDS : 1];
@@ -245,7 +244,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __
   if (STAGED) {
     for (int c = 0; c < C; ++c)
       for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK)
-        s_x[c * pitch + rs_slot(s)] = rs_sample(x + (long long)c * L, tl.n_lo + s, L, 0, -1, RS_FMT_ROWS);
+        s_x[c * pitch + rs_slot(s)] = rs_sample<true>(x + (long long)c * L, tl.n_lo + s, L, 0, -1, AVSEP_SAMPLE_F32);
     __syncthreads();
   }
   const bool words = ((size_t)y & 3) == 0;
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __
     if (t0 < S && t0 < tl.nout) {
       for (int c = 0; c < C; ++c) {
         float acc[RS_R];
-        rs_chains<STAGED>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, RS_FMT_ROWS, ho, up, down, M, T, S, tl.r0, t0, acc);
+        rs_chains<STAGED, true>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, AVSEP_SAMPLE_F32, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
         for (int r = 0; r < RS_R; ++r) s_o[(r * RS_BLOCK + threadIdx.x) * C + c] = rs_s16(acc[r]);
       }
@@ -278,7 +277,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __
   }
 }
 
-// resample_join_kernel for the frames of any output format at any byte address: f32 [C, L] -> interleaved samples of BYTES
+// resample_join_s16_kernel for the frames of any output format at any byte address: f32 [C, L] -> interleaved samples of BYTES
 // bytes (2: s16, 3: s24, 4: f32).  The tile holds bytes in file layout, BYTES a sample: 16, 24 or 32 KiB at eight channels.
 // The 32 KiB of the f32 form do not fit beside RJ_LDS in 64 KiB, so that form stages the smaller RJ_LDS_F32 (the host plans S
 // for it; the chains do not depend on S).  A run starts at byte phase (address & 3) of y, any of the four (three-byte
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __
 // spare bytes a run, so that an aligned dword of the file is an aligned dword of LDS.  The store is then a head of up to
 // three single bytes, a body of whole dwords on consecutive lanes and a tail of up to three bytes.
 template <bool STAGED, int BYTES>
-__global__ __launch_bounds__(RS_BLOCK) void resample_join_fmt_kernel(const float* __restrict__ x, const float* __restrict__ ho,
+__global__ __launch_bounds__(RS_BLOCK) void resample_join_kernel(const float* __restrict__ x, const float* __restrict__ ho,
                                                                      int up, int down, int half, int M, int T, int S, int L,
                                                                      int Lout, int C, int pitch, uint8_t* __restrict__ y) {
   constexpr int RUN = RS_BLOCK * RS_KEEP_CH * BYTES + 4;       // bytes of LDS per run: a multiple of 4
@@ -297,7 +296,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_fmt_kernel(const float
   if (STAGED) {
     for (int c = 0; c < C; ++c)
       for (int s = threadIdx.x; s < tl.span; s += RS_BLOCK)
-        s_x[c * pitch + rs_slot(s)] = rs_sample(x + (long long)c * L, tl.n_lo + s, L, 0, -1, RS_FMT_ROWS);
+        s_x[c * pitch + rs_slot(s)] = rs_sample<true>(x + (long long)c * L, tl.n_lo + s, L, 0, -1, AVSEP_SAMPLE_F32);
     __syncthreads();
   }
   for (int tb = 0; tb < S && tb < tl.nout; tb += RS_BLOCK) {   // the same for every thread: the loop holds barriers
@@ -308,7 +307,7 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_join_fmt_kernel(const float
     if (t0 < S && t0 < tl.nout) {
       for (int c = 0; c < C; ++c) {
         float acc[RS_R];
-        rs_chains<STAGED>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, RS_FMT_ROWS, ho, up, down, M, T, S, tl.r0, t0, acc);
+        rs_chains<STAGED, true>(s_x + c * pitch, x + (long long)c * L, tl.n_lo, L, 0, -1, AVSEP_SAMPLE_F32, ho, up, down, M, T, S, tl.r0, t0, acc);
 #pragma unroll
         for (int r = 0; r < RS_R; ++r)
           rs_put(s_o + r * RUN + phase[r] + ((int)threadIdx.x * C + c) * BYTES, rs_encode(acc[r], FMT), BYTES);
@@ -374,110 +373,60 @@ static bool rs_ratio_ok(int up, int down, int L, long long* lout) {
   return *lout <= 0x7fffffffLL;
 }
 
-extern "C" int avsep_resample_poly(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down,
-                                   int32_t in_ch, int32_t out_s16, void* y, avsep_stream_t stream) {
-  if (!x || !ho || !y) return AVSEP_ERR_ARG;
-  long long lout;
-  if (!rs_ratio_ok(up, down, L, &lout) || B < 1 || B > 65535) return AVSEP_ERR_ARG;
-  if (in_ch < 0 || in_ch > RS_MAX_CH || (in_ch >= 1 && B != 1) || (out_s16 != 0 && out_s16 != 1)) return AVSEP_ERR_ARG;
-  const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
-  const dim3 grid(p.tiles, B);
-  if (p.staged)
-    hipLaunchKernelGGL((resample_poly_kernel<true, false>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, in_ch, RS_FMT_ROWS, out_s16, y);
-  else
-    hipLaunchKernelGGL((resample_poly_kernel<false, false>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, in_ch, RS_FMT_ROWS, out_s16, y);
+// One launch of a kernel in the form the plan asks for.
+template <typename... P, typename... A>
+static int rs_launch(const RsPlan& p, void (*staged)(P...), void (*unstaged)(P...), dim3 grid, avsep_stream_t stream, A... args) {
+  hipLaunchKernelGGL(p.staged ? staged : unstaged, grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, args...);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
 
-extern "C" int avsep_resample_poly_fmt(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down,
-                                       int32_t in_ch, int32_t in_fmt, int32_t out_fmt, void* y, avsep_stream_t stream) {
+// p is where a typed load or store of a sample of fmt (S16 or F32) may go.
+static inline bool rs_aligned(const void* p, int fmt) { return !((size_t)p & (fmt == AVSEP_SAMPLE_S16 ? 1 : 3)); }
+
+extern "C" int avsep_resample_poly(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down, int32_t in_ch,
+                                   int32_t in_fmt, int32_t out_fmt, void* y, avsep_stream_t stream) {
   if (!x || !ho || !y) return AVSEP_ERR_ARG;
   long long lout;
   if (!rs_ratio_ok(up, down, L, &lout) || B < 1 || B > 65535) return AVSEP_ERR_ARG;
   if (in_ch < 0 || in_ch > RS_MAX_CH || (in_ch >= 1 && B != 1) || !rs_fmt_in_ok(in_fmt) || !rs_fmt_out_ok(out_fmt)) return AVSEP_ERR_ARG;
   if (in_ch == 0 && (in_fmt != AVSEP_SAMPLE_F32 || ((size_t)x & 3))) return AVSEP_ERR_ARG;      // rows are aligned floats
   const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
-  const dim3 grid(p.tiles, B);
-  if (p.staged)
-    hipLaunchKernelGGL((resample_poly_kernel<true, true>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, in_ch, in_fmt, out_fmt, y);
-  else
-    hipLaunchKernelGGL((resample_poly_kernel<false, true>), grid, dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, in_ch, in_fmt, out_fmt, y);
-  AVSEP_LAUNCH_CHECK();
-  return AVSEP_OK;
+  const bool fast = (in_ch == 0 || (in_fmt == AVSEP_SAMPLE_S16 && rs_aligned(x, in_fmt))) && out_fmt != AVSEP_SAMPLE_S24 &&
+                    rs_aligned(y, out_fmt);
+  return rs_launch(p, fast ? resample_poly_kernel<true, true> : resample_poly_kernel<true, false>,
+                   fast ? resample_poly_kernel<false, true> : resample_poly_kernel<false, false>, dim3(p.tiles, B), stream, x, ho, up,
+                   down, p.half, p.M, p.T, p.S, L, (int)lout, in_ch, in_fmt, out_fmt, y);
 }
 
-extern "C" int avsep_resample_split(const int16_t* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, float* y,
-                                    avsep_stream_t stream) {
-  if (!x || !ho || !y) return AVSEP_ERR_ARG;
-  long long lout;
-  if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH) return AVSEP_ERR_ARG;
-  const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
-  if (p.staged)
-    hipLaunchKernelGGL((resample_split_kernel<true, false>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, (const void*)x,
-                       ho, up, down, p.half, p.M, p.T, p.S, L, (int)lout, C, RS_FMT_ROWS, y);
-  else
-    hipLaunchKernelGGL((resample_split_kernel<false, false>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, (const void*)x,
-                       ho, up, down, p.half, p.M, p.T, p.S, L, (int)lout, C, RS_FMT_ROWS, y);
-  AVSEP_LAUNCH_CHECK();
-  return AVSEP_OK;
-}
-
-extern "C" int avsep_resample_split_fmt(const void* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down,
-                                        int32_t in_fmt, float* y, avsep_stream_t stream) {
+extern "C" int avsep_resample_split(const void* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, int32_t in_fmt,
+                                    float* y, avsep_stream_t stream) {
   if (!x || !ho || !y) return AVSEP_ERR_ARG;
   long long lout;
   if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH || !rs_fmt_in_ok(in_fmt)) return AVSEP_ERR_ARG;
   const RsPlan p = rs_plan(up, down, lout, 1, RS_LDS);
-  if (p.staged)
-    hipLaunchKernelGGL((resample_split_kernel<true, true>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down,
-                       p.half, p.M, p.T, p.S, L, (int)lout, C, in_fmt, y);
-  else
-    hipLaunchKernelGGL((resample_split_kernel<false, true>), dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down,
-                       p.half, p.M, p.T, p.S, L, (int)lout, C, in_fmt, y);
-  AVSEP_LAUNCH_CHECK();
-  return AVSEP_OK;
+  const bool fast = in_fmt == AVSEP_SAMPLE_S16 && rs_aligned(x, in_fmt);
+  return rs_launch(p, fast ? resample_split_kernel<true, true> : resample_split_kernel<true, false>,
+                   fast ? resample_split_kernel<false, true> : resample_split_kernel<false, false>, dim3(p.tiles), stream, x, ho, up,
+                   down, p.half, p.M, p.T, p.S, L, (int)lout, C, in_fmt, y);
 }
 
-extern "C" int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int16_t* y,
-                                   avsep_stream_t stream) {
-  if (!x || !ho || !y) return AVSEP_ERR_ARG;
-  long long lout;
-  if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH) return AVSEP_ERR_ARG;
-  const RsPlan p = rs_plan(up, down, lout, C, RJ_LDS);
-  if (p.staged)
-    hipLaunchKernelGGL(resample_join_kernel<true>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, C, p.pitch, y);
-  else
-    hipLaunchKernelGGL(resample_join_kernel<false>, dim3(p.tiles), dim3(RS_BLOCK), 0, (hipStream_t)stream, x, ho, up, down, p.half,
-                       p.M, p.T, p.S, L, (int)lout, C, p.pitch, y);
-  AVSEP_LAUNCH_CHECK();
-  return AVSEP_OK;
-}
-
-template <int BYTES>
-static int rs_join_fmt(const float* x, const float* ho, int C, int L, int up, int down, long long lout, uint8_t* y, hipStream_t stream) {
-  const RsPlan p = rs_plan(up, down, lout, C, BYTES == 4 ? RJ_LDS_F32 : RJ_LDS);
-  if (p.staged)
-    hipLaunchKernelGGL((resample_join_fmt_kernel<true, BYTES>), dim3(p.tiles), dim3(RS_BLOCK), 0, stream, x, ho, up, down, p.half, p.M,
-                       p.T, p.S, L, (int)lout, C, p.pitch, y);
-  else
-    hipLaunchKernelGGL((resample_join_fmt_kernel<false, BYTES>), dim3(p.tiles), dim3(RS_BLOCK), 0, stream, x, ho, up, down, p.half, p.M,
-                       p.T, p.S, L, (int)lout, C, p.pitch, y);
-  AVSEP_LAUNCH_CHECK();
-  return AVSEP_OK;
-}
-
-extern "C" int avsep_resample_join_fmt(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down,
-                                       int32_t out_fmt, void* y, avsep_stream_t stream) {
+extern "C" int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int32_t out_fmt,
+                                   void* y, avsep_stream_t stream) {
   if (!x || !ho || !y) return AVSEP_ERR_ARG;
   long long lout;
   if (!rs_ratio_ok(up, down, L, &lout) || C < 1 || C > RS_KEEP_CH || !rs_fmt_out_ok(out_fmt)) return AVSEP_ERR_ARG;
-  if (out_fmt == AVSEP_SAMPLE_S16) return rs_join_fmt<2>(x, ho, C, L, up, down, lout, (uint8_t*)y, (hipStream_t)stream);
-  if (out_fmt == AVSEP_SAMPLE_S24) return rs_join_fmt<3>(x, ho, C, L, up, down, lout, (uint8_t*)y, (hipStream_t)stream);
-  return rs_join_fmt<4>(x, ho, C, L, up, down, lout, (uint8_t*)y, (hipStream_t)stream);
+  const RsPlan p = rs_plan(up, down, lout, C, out_fmt == AVSEP_SAMPLE_F32 ? RJ_LDS_F32 : RJ_LDS);
+  const dim3 grid(p.tiles);
+  if (out_fmt == AVSEP_SAMPLE_S16 && rs_aligned(y, out_fmt))
+    return rs_launch(p, resample_join_s16_kernel<true>, resample_join_s16_kernel<false>, grid, stream, x, ho, up, down, p.half, p.M,
+                     p.T, p.S, L, (int)lout, C, p.pitch, (int16_t*)y);
+  if (out_fmt == AVSEP_SAMPLE_S16)
+    return rs_launch(p, resample_join_kernel<true, 2>, resample_join_kernel<false, 2>, grid, stream, x, ho, up, down, p.half, p.M,
+                     p.T, p.S, L, (int)lout, C, p.pitch, (uint8_t*)y);
+  if (out_fmt == AVSEP_SAMPLE_S24)
+    return rs_launch(p, resample_join_kernel<true, 3>, resample_join_kernel<false, 3>, grid, stream, x, ho, up, down, p.half, p.M,
+                     p.T, p.S, L, (int)lout, C, p.pitch, (uint8_t*)y);
+  return rs_launch(p, resample_join_kernel<true, 4>, resample_join_kernel<false, 4>, grid, stream, x, ho, up, down, p.half, p.M,
+                   p.T, p.S, L, (int)lout, C, p.pitch, (uint8_t*)y);
 }

@@ -732,29 +732,20 @@ def window_agreement(masks, starts):
 
 def mask_stitch(masks, starts, perm, mag, binary, thres, want_mask=False):
     """masks [K,N,Fout,W], starts int32 [K], perm int32 [K,N], mag [Fin,F] -> per-source magnitude [N,Fin,F] (and the blended
-    linear-frequency mask [N,Fin,F] with want_mask): un-warp, triangular cross-fade, threshold, x mag in one pass."""
+    linear-frequency mask [N,Fin,F] with want_mask): un-warp, triangular cross-fade, threshold, x mag in one pass.
+    mag [C,Fin,F], a recording that keeps its channels -> [N,C,Fin,F]: the mask at (n, f, t) is blended once and multiplied
+    into the C magnitudes, so out[:, c] has the bits of mask_stitch(.., mag[c])."""
     lib.require_gpu(masks)
     Kw, N, Fo, W = masks.shape
-    Fin, F = mag.shape
-    out = _f32((N, Fin, F), mag)
+    Cc, Fin, F = mag.shape if mag.dim() == 3 else (1, *mag.shape)
+    out = _f32((N, Cc, Fin, F) if mag.dim() == 3 else (N, Fin, F), mag)
     lin = _f32((N, Fin, F), mag) if want_mask else None
-    call("avsep_mask_stitch", ptr(masks), ptr(starts), ptr(perm), ptr(mag), Kw, N, Fo, W, Fin, F, int(bool(binary)),
+    call("avsep_mask_stitch", ptr(masks), ptr(starts), ptr(perm), ptr(mag), Kw, N, Fo, W, Cc, Fin, F, int(bool(binary)),
          float(thres), ptr(out), ptr(lin))
     return out, lin
 
 
-def mask_stitch_channels(masks, starts, perm, mag_c, binary, thres, want_mask=False):
-    """mask_stitch for a recording that keeps its channels: mag_c [C,Fin,F] -> per-source, per-channel magnitude [N,C,Fin,F]
-    (and the blended mask [N,Fin,F] with want_mask).  The mask at (n, f, t) is blended once and multiplied into the C
-    magnitudes; out[:, c] has the bits of mask_stitch(.., mag_c[c])."""
-    lib.require_gpu(masks)
-    Kw, N, Fo, W = masks.shape
-    Cc, Fin, F = mag_c.shape
-    out = _f32((N, Cc, Fin, F), mag_c)
-    lin = _f32((N, Fin, F), mag_c) if want_mask else None
-    call("avsep_mask_stitch_channels", ptr(masks), ptr(starts), ptr(perm), ptr(mag_c), Kw, N, Fo, W, Cc, Fin, F,
-         int(bool(binary)), float(thres), ptr(out), ptr(lin))
-    return out, lin
+mask_stitch_channels = mask_stitch     # the name callers of the channel path know: mag [C,Fin,F] -> [N,C,Fin,F]
 
 
 MWF_MAX_CHANNELS = 8     # avsep_mwf_*: C and N up to 8
@@ -801,7 +792,7 @@ def mwf_cov(ymag, yph):
 
 def mwf(xmag, xph, ymag, yph, iterations=1, reg=1e-3):
     """Multichannel Wiener filter (include/avsep.h): xmag, xph [C,Fin,F] the channels' STFT, ymag [N,C,Fin,F] the source
-    images' magnitudes (mask_stitch_channels), yph their phase, [C,Fin,F] shared or [N,C,Fin,F] -> (mag, phase), both
+    images' magnitudes (mask_stitch), yph their phase, [C,Fin,F] shared or [N,C,Fin,F] -> (mag, phase), both
     [N,C,Fin,F], after ``iterations`` passes (each pass re-estimates the covariances from the previous pass's output).
     ``reg`` is relative to each bin's power: the sources sum to X / (1 + ~reg)."""
     N, Cc, Fin, F = _mwf_check("mwf", ymag, yph)
@@ -831,64 +822,6 @@ def _resample_table_check(what, filt, up, down, device):
                              f"{filt.dtype} {tuple(filt.shape)} on {filt.device}")
 
 
-def resample_split(pcm, filt, up, down):
-    """avsep_resample_split (include/avsep.h): interleaved int16 [L,C], 1 <= C <= 8 -> f32 [1+C, ceil(L*up/down)]: row 0 the
-    down-mix resample_poly(.., in_ch=C) gives, row 1+c channel c over 32768 through the same filter.  filt as resample_poly."""
-    if pcm.dtype != torch.int16 or pcm.dim() != 2 or not 1 <= pcm.shape[1] <= RESAMPLE_MAX_KEPT_CHANNELS:
-        raise lib.AvsepError(f"resample_split takes interleaved int16 [L,C] with 1 <= C <= {RESAMPLE_MAX_KEPT_CHANNELS}, got "
-                             f"{pcm.dtype} {tuple(pcm.shape)}")
-    lib.require_gpu(pcm)
-    lib.require_gpu(filt)
-    up, down = int(up), int(down)
-    _resample_table_check("resample_split", filt, up, down, pcm.device)
-    L, Cc = pcm.shape
-    y = torch.empty((1 + Cc, -(-L * up // down)), dtype=torch.float32, device=pcm.device)
-    call("avsep_resample_split", ptr(pcm), ptr(filt), L, Cc, up, down, ptr(y))
-    return y
-
-
-def resample_join(x, filt, up, down):
-    """avsep_resample_join (include/avsep.h): f32 [C,L], 1 <= C <= 8 -> interleaved int16 [ceil(L*up/down), C], each value
-    clip(rint(v * 32768)) of what resample_poly computes for row c (its out_s16 value).  filt as resample_poly."""
-    if x.dtype != torch.float32 or x.dim() != 2 or not 1 <= x.shape[0] <= RESAMPLE_MAX_KEPT_CHANNELS:
-        raise lib.AvsepError(f"resample_join takes float32 [C,L] with 1 <= C <= {RESAMPLE_MAX_KEPT_CHANNELS}, got "
-                             f"{x.dtype} {tuple(x.shape)}")
-    lib.require_gpu(x)
-    lib.require_gpu(filt)
-    up, down = int(up), int(down)
-    _resample_table_check("resample_join", filt, up, down, x.device)
-    Cc, L = x.shape
-    y = torch.empty((-(-L * up // down), Cc), dtype=torch.int16, device=x.device)
-    call("avsep_resample_join", ptr(x), ptr(filt), Cc, L, up, down, ptr(y))
-    return y
-
-
-def resample_poly(x, filt, up, down, in_ch=0, out_s16=False):
-    """Rational polyphase resampling (avsep_resample_poly, include/avsep.h).  x: f32 [B,L] (in_ch = 0) or interleaved int16
-    [L,in_ch] straight from a WAV file (one recording, down-mixed to mono while it is staged); filt: the f32 polyphase table
-    [T, up] of resample.filter_table on x's device -> f32 (or, with out_s16, int16) [B, ceil(L*up/down)]."""
-    lib.require_gpu(x)
-    lib.require_gpu(filt)
-    up, down, in_ch = int(up), int(down), int(in_ch)
-    if in_ch:
-        if x.dtype != torch.int16 or x.dim() != 2 or x.shape[1] != in_ch:
-            raise lib.AvsepError(f"resample_poly: in_ch={in_ch} takes interleaved int16 [L,{in_ch}], got {x.dtype} {tuple(x.shape)}")
-        B, L = 1, x.shape[0]
-    else:
-        if x.dtype != torch.float32 or x.dim() != 2:
-            raise lib.AvsepError(f"resample_poly takes float32 [B,L], got {x.dtype} {tuple(x.shape)}")
-        B, L = x.shape
-    if up < 1 or down < 1:
-        raise lib.AvsepError(f"resample_poly: up={up} down={down}")
-    T = -(-(20 * max(up, down) + 1) // up)
-    if filt.dtype != torch.float32 or tuple(filt.shape) != (T, up) or filt.device != x.device:
-        raise lib.AvsepError(f"resample_poly: the table of {up}/{down} is float32 [{T},{up}] on {x.device}, got "
-                             f"{filt.dtype} {tuple(filt.shape)} on {filt.device}")
-    y = torch.empty((B, -(-L * up // down)), dtype=torch.int16 if out_s16 else torch.float32, device=x.device)
-    call("avsep_resample_poly", ptr(x), ptr(filt), B, L, up, down, in_ch, int(bool(out_s16)), ptr(y))
-    return y
-
-
 SAMPLE_FORMATS = {"s16": (1, 2), "s24": (2, 3), "s32": (3, 4), "f32": (4, 4)}     # name -> (AVSEP_SAMPLE_* code, bytes a sample)
 SAMPLE_OUT_FORMATS = ("s16", "s24", "f32")
 
@@ -900,9 +833,9 @@ def _sample_format(what, fmt, out=False):
     return SAMPLE_FORMATS[fmt]
 
 
-def _raw_frames(what, raw, C, nbytes):
+def raw_frames(what, raw, C, nbytes):
     """The frame count of raw uint8 [L*C*nbytes] (a file's data chunk, from any byte address)."""
-    if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < C * nbytes or raw.numel() % (C * nbytes):
+    if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() % (C * nbytes):
         got = f"{raw.dtype} {tuple(raw.shape)}" if torch.is_tensor(raw) else type(raw).__name__
         raise lib.AvsepError(f"{what} takes raw frames as uint8 [L*{C}*{nbytes}], got {got}")
     return raw.numel() // (C * nbytes)
@@ -918,71 +851,72 @@ def _raw_out(what, out, n, device):
     return out
 
 
-def resample_poly_fmt(x, filt, up, down, in_ch=0, in_fmt="f32", out_fmt="f32", out=None):
-    """avsep_resample_poly_fmt (include/avsep.h).  in_ch = 0: x is f32 [B,L] (in_fmt 'f32'); in_ch = C >= 1: x is the raw
-    frames of one recording, uint8 [L*C*bytes] of in_fmt at any byte address, down-mixed while they are staged.  -> [B, Lout]
+def resample_poly(x, filt, up, down, in_ch=0, in_fmt="f32", out_fmt="f32", out=None):
+    """Rational polyphase resampling (avsep_resample_poly, include/avsep.h); filt: the f32 polyphase table [T, up] of
+    resample.filter_table on x's device.  in_ch = 0: x is f32 [B,L] (in_fmt 'f32'); in_ch = C >= 1: x is the raw frames of one
+    recording, uint8 [L*C*bytes] of in_fmt at any byte address, down-mixed while they are staged.  -> [B, ceil(L*up/down)]
     samples of out_fmt: f32, int16, or for 's24' uint8 [B, Lout*3]; ``out`` (uint8 [B*Lout*bytes], any byte address) takes
     the bytes instead and is returned."""
     lib.require_gpu(x)
     lib.require_gpu(filt)
     up, down, in_ch = int(up), int(down), int(in_ch)
-    icode, ibytes = _sample_format("resample_poly_fmt", in_fmt)
-    ocode, obytes = _sample_format("resample_poly_fmt", out_fmt, out=True)
+    icode, ibytes = _sample_format("resample_poly", in_fmt)
+    ocode, obytes = _sample_format("resample_poly", out_fmt, out=True)
     if in_ch:
         if not 1 <= in_ch <= 256:
-            raise lib.AvsepError(f"resample_poly_fmt down-mixes 1 to 256 channels, got {in_ch}")
-        B, L = 1, _raw_frames("resample_poly_fmt", x, in_ch, ibytes)
+            raise lib.AvsepError(f"resample_poly down-mixes 1 to 256 channels, got {in_ch}")
+        B, L = 1, raw_frames("resample_poly", x, in_ch, ibytes)
     else:
         if x.dtype != torch.float32 or x.dim() != 2 or in_fmt != "f32":
-            raise lib.AvsepError(f"resample_poly_fmt: in_ch=0 takes float32 [B,L] with in_fmt 'f32', got {x.dtype} {tuple(x.shape)} "
+            raise lib.AvsepError(f"resample_poly: in_ch=0 takes float32 [B,L] with in_fmt 'f32', got {x.dtype} {tuple(x.shape)} "
                                  f"as {in_fmt!r}")
         B, L = x.shape
-    _resample_table_check("resample_poly_fmt", filt, up, down, x.device)
+    _resample_table_check("resample_poly", filt, up, down, x.device)
     Lout = -(-L * up // down)
     if out is not None:
-        y = _raw_out("resample_poly_fmt", out, B * Lout * obytes, x.device)
+        y = _raw_out("resample_poly", out, B * Lout * obytes, x.device)
     elif out_fmt == "s24":
         y = torch.empty((B, Lout * 3), dtype=torch.uint8, device=x.device)
     else:
         y = torch.empty((B, Lout), dtype=torch.int16 if out_fmt == "s16" else torch.float32, device=x.device)
     x = x.contiguous()
-    call("avsep_resample_poly_fmt", ptr(x), ptr(filt), B, L, up, down, in_ch, icode, ocode, ptr(y))
+    call("avsep_resample_poly", ptr(x), ptr(filt), B, L, up, down, in_ch, icode, ocode, ptr(y))
     return y
 
 
-def resample_split_fmt(raw, filt, up, down, C, in_fmt):
-    """avsep_resample_split_fmt (include/avsep.h): raw frames uint8 [L*C*bytes] of in_fmt at any byte address, 1 <= C <= 8
-    -> f32 [1+C, ceil(L*up/down)]: row 0 the down-mix resample_poly_fmt(.., in_ch=C) gives, row 1+c channel c."""
+def resample_split(raw, filt, up, down, C, in_fmt):
+    """avsep_resample_split (include/avsep.h): raw frames uint8 [L*C*bytes] of in_fmt at any byte address, 1 <= C <= 8
+    -> f32 [1+C, ceil(L*up/down)]: row 0 the down-mix resample_poly(.., in_ch=C) gives, row 1+c channel c."""
     C = int(C)
-    icode, ibytes = _sample_format("resample_split_fmt", in_fmt)
+    icode, ibytes = _sample_format("resample_split", in_fmt)
     if not 1 <= C <= RESAMPLE_MAX_KEPT_CHANNELS:
-        raise lib.AvsepError(f"resample_split_fmt keeps 1 to {RESAMPLE_MAX_KEPT_CHANNELS} channels, got {C}")
-    L = _raw_frames("resample_split_fmt", raw, C, ibytes)
+        raise lib.AvsepError(f"resample_split keeps 1 to {RESAMPLE_MAX_KEPT_CHANNELS} channels, got {C}")
+    L = raw_frames("resample_split", raw, C, ibytes)
     lib.require_gpu(raw)
     lib.require_gpu(filt)
     up, down = int(up), int(down)
-    _resample_table_check("resample_split_fmt", filt, up, down, raw.device)
+    _resample_table_check("resample_split", filt, up, down, raw.device)
     y = torch.empty((1 + C, -(-L * up // down)), dtype=torch.float32, device=raw.device)
     raw = raw.contiguous()
-    call("avsep_resample_split_fmt", ptr(raw), ptr(filt), L, C, up, down, icode, ptr(y))
+    call("avsep_resample_split", ptr(raw), ptr(filt), L, C, up, down, icode, ptr(y))
     return y
 
 
-def resample_join_fmt(x, filt, up, down, out_fmt, out=None):
-    """avsep_resample_join_fmt (include/avsep.h): f32 [C,L], 1 <= C <= 8 -> uint8 [ceil(L*up/down)*C*bytes], interleaved
+def resample_join(x, filt, up, down, out_fmt, out=None):
+    """avsep_resample_join (include/avsep.h): f32 [C,L], 1 <= C <= 8 -> uint8 [ceil(L*up/down)*C*bytes], interleaved
     frames of out_fmt ('s16' | 's24' | 'f32') as they lie in a file; ``out``: a uint8 view of that size at any byte address."""
-    ocode, obytes = _sample_format("resample_join_fmt", out_fmt, out=True)
+    ocode, obytes = _sample_format("resample_join", out_fmt, out=True)
     if x.dtype != torch.float32 or x.dim() != 2 or not 1 <= x.shape[0] <= RESAMPLE_MAX_KEPT_CHANNELS:
-        raise lib.AvsepError(f"resample_join_fmt takes float32 [C,L] with 1 <= C <= {RESAMPLE_MAX_KEPT_CHANNELS}, got "
+        raise lib.AvsepError(f"resample_join takes float32 [C,L] with 1 <= C <= {RESAMPLE_MAX_KEPT_CHANNELS}, got "
                              f"{x.dtype} {tuple(x.shape)}")
     lib.require_gpu(x)
     lib.require_gpu(filt)
     up, down = int(up), int(down)
-    _resample_table_check("resample_join_fmt", filt, up, down, x.device)
+    _resample_table_check("resample_join", filt, up, down, x.device)
     Cc, L = x.shape
-    y = _raw_out("resample_join_fmt", out, -(-L * up // down) * Cc * obytes, x.device)
+    y = _raw_out("resample_join", out, -(-L * up // down) * Cc * obytes, x.device)
     x = x.contiguous()
-    call("avsep_resample_join_fmt", ptr(x), ptr(filt), Cc, L, up, down, ocode, ptr(y))
+    call("avsep_resample_join", ptr(x), ptr(filt), Cc, L, up, down, ocode, ptr(y))
     return y
 
 

@@ -83,8 +83,7 @@ SIGNATURES = {
     "avsep_warp": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_window_prepare": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "avsep_window_agreement": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "avsep_mask_stitch": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
-    "avsep_mask_stitch_channels": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "avsep_mask_stitch": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "avsep_mwf_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "avsep_mwf_cov": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "avsep_mwf_apply": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
@@ -92,12 +91,9 @@ SIGNATURES = {
     "avsep_misi": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "avsep_localise_maps": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avsep_heatmap_overlay": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "avsep_resample_poly": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "avsep_resample_split": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "avsep_resample_join": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "avsep_resample_poly_fmt": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "avsep_resample_split_fmt": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "avsep_resample_join_fmt": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_poly": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_split": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_resample_join": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_loudness_energies_workspace_bytes": (_Z, [_I, _I, _I]),
     "avsep_loudness_energies": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "avsep_true_peak_workspace_bytes": (_Z, [_I, _I]),

@@ -3,11 +3,11 @@
 A rational polyphase FIR resampler with the filter ``scipy.signal.resample_poly`` uses by default (the training loader's
 choice, dataset.read_wav_segment, which stays on the CPU for its GPU-free workers).  The filter is designed here in
 float64 with NumPy alone, rounded once to f32 and handed to ``avsep_resample_poly`` (include/avsep.h, csrc/resample.hip) as
-a polyphase table cached per (up, down, device).  The kernel also reads interleaved 16-bit PCM directly (down-mix and
-conversion fused into its staging) and writes 16-bit PCM directly, so a long recording never exists as an f32 copy at the
-file's rate on the host.  The ``*_frames`` functions do the same for a file's frames in any of the sample formats of
-include/avsep.h (s16 / s24 / s32 PCM and f32 in, s16 / s24 / f32 out), taken and given as the bytes they are in the file
-(wavio.read_frames / write_frames).
+a polyphase table cached per (up, down, device).  The kernels read a file's frames directly (down-mix and conversion fused
+into their staging) and write them directly, so a long recording never exists as an f32 copy at the file's rate on the
+host.  The ``*_frames`` functions take and give frames as the bytes they are in the file (wavio.read_frames /
+write_frames), in any of the sample formats of include/avsep.h (s16 / s24 / s32 PCM and f32 in, s16 / s24 / f32 out);
+``resample_pcm`` / ``split_pcm`` / ``join_pcm`` are the same calls for frames held as an int16 tensor [L, C].
 """
 import math
 
@@ -98,48 +98,8 @@ def resample(x, rate_in, rate_out, out_s16=False):
         return x
     _check_length(x.shape[-1], up, down)
     rows = x.contiguous() if x.dim() == 2 else x.contiguous()[None]
-    y = K.resample_poly(rows, filter_table(up, down, x.device), up, down, 0, out_s16)
+    y = K.resample_poly(rows, filter_table(up, down, x.device), up, down, out_fmt="s16" if out_s16 else "f32")
     return y if x.dim() == 2 else y[0]
-
-
-def resample_pcm(pcm, rate_in, rate_out):
-    """pcm: interleaved int16 [L,C] on the GPU (a WAV file's frames) -> f32 mono [Lout] at rate_out: the channels' mean over
-    32768, resampled, in one kernel.  Equal rates go through the same kernel with the unit-impulse filter: the converted mono
-    signal, bit for bit separate.read_wav's array."""
-    lib.require_gpu(pcm)
-    if pcm.dtype != torch.int16 or pcm.dim() != 2 or not 1 <= pcm.shape[1] <= MAX_CHANNELS:
-        raise AvsepError(f"resample_pcm takes interleaved int16 [L,C] with 1 <= C <= {MAX_CHANNELS}, got {pcm.dtype} {tuple(pcm.shape)}")
-    up, down = check_rates(rate_in, rate_out)
-    _check_length(pcm.shape[0], up, down)
-    return K.resample_poly(pcm.contiguous(), filter_table(up, down, pcm.device), up, down, pcm.shape[1], False)[0]
-
-
-def split_pcm(pcm, rate_in, rate_out):
-    """pcm: interleaved int16 [L,C] on the GPU, 1 <= C <= 8 -> f32 [1+C, Lout] at rate_out in one kernel: row 0 is
-    resample_pcm's down-mix (the network's input), row 1+c is channel c over 32768 through the same filter.  Equal rates go
-    through the kernel with the unit-impulse filter: the converted samples, bit for bit."""
-    if pcm.dtype != torch.int16 or pcm.dim() != 2:
-        raise AvsepError(f"split_pcm takes interleaved int16 [L,C], got {pcm.dtype} {tuple(pcm.shape)}")
-    if not 1 <= pcm.shape[1] <= MAX_KEPT_CHANNELS:
-        raise AvsepError(f"split_pcm keeps 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {pcm.shape[1]}")
-    up, down = check_rates(rate_in, rate_out)
-    _check_length(pcm.shape[0], up, down)
-    lib.require_gpu(pcm)
-    return K.resample_split(pcm.contiguous(), filter_table(up, down, pcm.device), up, down)
-
-
-def join_pcm(x, rate_in, rate_out):
-    """x: f32 [C,L] on the GPU, 1 <= C <= 8 -> interleaved int16 [Lout,C] at rate_out, a WAV file's frames, in one kernel:
-    column c is resample(x[c], .., out_s16=True).  Equal rates go through the kernel with the unit-impulse filter: only the
-    rounding clip(rint(x * 32768))."""
-    if x.dtype != torch.float32 or x.dim() != 2:
-        raise AvsepError(f"join_pcm takes float32 [C,L], got {x.dtype} {tuple(x.shape)}")
-    if not 1 <= x.shape[0] <= MAX_KEPT_CHANNELS:
-        raise AvsepError(f"join_pcm writes 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {x.shape[0]}")
-    up, down = check_rates(rate_in, rate_out)
-    _check_length(x.shape[1], up, down)
-    lib.require_gpu(x)
-    return K.resample_join(x.contiguous(), filter_table(up, down, x.device), up, down)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -151,11 +111,7 @@ def _raw_length(what, raw, fmt, C, most):
         raise AvsepError(f"{what} takes the sample formats {', '.join(K.SAMPLE_FORMATS)}, got {fmt!r}")
     if int(C) != C or not 1 <= C <= most:
         raise AvsepError(f"{what} takes 1 to {most} channels, got {C!r}")
-    nbytes = K.SAMPLE_FORMATS[fmt][1] * int(C)
-    if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() % nbytes:
-        got = f"{raw.dtype} {tuple(raw.shape)}" if torch.is_tensor(raw) else type(raw).__name__
-        raise AvsepError(f"{what} takes a file's frames as uint8 [L*{int(C)}*{nbytes // int(C)}] ({fmt}), got {got}")
-    return raw.numel() // nbytes
+    return K.raw_frames(what, raw, int(C), K.SAMPLE_FORMATS[fmt][1])
 
 
 def resample_frames(raw, fmt, C, rate_in, rate_out):
@@ -166,7 +122,7 @@ def resample_frames(raw, fmt, C, rate_in, rate_out):
     up, down = check_rates(rate_in, rate_out)
     _check_length(L, up, down)
     lib.require_gpu(raw)
-    return K.resample_poly_fmt(raw, filter_table(up, down, raw.device), up, down, int(C), fmt, "f32")[0]
+    return K.resample_poly(raw, filter_table(up, down, raw.device), up, down, int(C), fmt, "f32")[0]
 
 
 def split_frames(raw, fmt, C, rate_in, rate_out):
@@ -176,12 +132,12 @@ def split_frames(raw, fmt, C, rate_in, rate_out):
     up, down = check_rates(rate_in, rate_out)
     _check_length(L, up, down)
     lib.require_gpu(raw)
-    return K.resample_split_fmt(raw, filter_table(up, down, raw.device), up, down, int(C), fmt)
+    return K.resample_split(raw, filter_table(up, down, raw.device), up, down, int(C), fmt)
 
 
 def join_frames(x, rate_in, rate_out, fmt, out=None):
     """x: f32 [C,L] on the GPU, 1 <= C <= 8 -> uint8 [Lout*C*bytes] at rate_out: the frames of a WAV file in fmt 's16' | 's24' |
-    'f32', in one kernel.  s16 is join_pcm's bytes, s24 clip(rint(v * 2^23)) of the same f32 value v, f32 its bits.  Equal
+    'f32', in one kernel: s16 clip(rint(v * 2^15)) and s24 clip(rint(v * 2^23)) of the same f32 value v, f32 its bits.  Equal
     rates go through the kernel with the unit-impulse filter: only the rounding.  ``out``: a uint8 view of that size at any
     byte address, filled and returned."""
     if fmt not in K.SAMPLE_OUT_FORMATS:
@@ -194,4 +150,41 @@ def join_frames(x, rate_in, rate_out, fmt, out=None):
     up, down = check_rates(rate_in, rate_out)
     _check_length(x.shape[1], up, down)
     lib.require_gpu(x)
-    return K.resample_join_fmt(x, filter_table(up, down, x.device), up, down, fmt, out=out)
+    return K.resample_join(x, filter_table(up, down, x.device), up, down, fmt, out=out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the same three for 16-bit frames held as an int16 tensor [L, C] (what separate.read_wav_pcm returns)
+# ---------------------------------------------------------------------------------------------------------------------
+def _pcm_bytes(pcm):
+    return pcm.contiguous().view(torch.uint8).reshape(-1)
+
+
+def resample_pcm(pcm, rate_in, rate_out):
+    """pcm: interleaved int16 [L,C] on the GPU (a WAV file's frames) -> f32 mono [Lout] at rate_out: resample_frames of its
+    bytes as 's16'.  At equal rates, bit for bit separate.read_wav's array."""
+    lib.require_gpu(pcm)
+    if pcm.dtype != torch.int16 or pcm.dim() != 2 or not 1 <= pcm.shape[1] <= MAX_CHANNELS:
+        raise AvsepError(f"resample_pcm takes interleaved int16 [L,C] with 1 <= C <= {MAX_CHANNELS}, got {pcm.dtype} {tuple(pcm.shape)}")
+    return resample_frames(_pcm_bytes(pcm), "s16", pcm.shape[1], rate_in, rate_out)
+
+
+def split_pcm(pcm, rate_in, rate_out):
+    """pcm: interleaved int16 [L,C] on the GPU, 1 <= C <= 8 -> f32 [1+C, Lout] at rate_out: split_frames of its bytes as
+    's16'; row 0 is resample_pcm's down-mix, row 1+c is channel c over 32768 through the same filter."""
+    if pcm.dtype != torch.int16 or pcm.dim() != 2:
+        raise AvsepError(f"split_pcm takes interleaved int16 [L,C], got {pcm.dtype} {tuple(pcm.shape)}")
+    if not 1 <= pcm.shape[1] <= MAX_KEPT_CHANNELS:
+        raise AvsepError(f"split_pcm keeps 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {pcm.shape[1]}")
+    return split_frames(_pcm_bytes(pcm), "s16", pcm.shape[1], rate_in, rate_out)
+
+
+def join_pcm(x, rate_in, rate_out):
+    """x: f32 [C,L] on the GPU, 1 <= C <= 8 -> interleaved int16 [Lout,C] at rate_out: join_frames(.., 's16') as a typed
+    tensor; column c is resample(x[c], .., out_s16=True)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2:
+        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
+        raise AvsepError(f"join_pcm takes float32 [C,L], got {got}")
+    if not 1 <= x.shape[0] <= MAX_KEPT_CHANNELS:
+        raise AvsepError(f"join_pcm writes 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {x.shape[0]}")
+    return join_frames(x, rate_in, rate_out, "s16").view(torch.int16).reshape(-1, x.shape[0])

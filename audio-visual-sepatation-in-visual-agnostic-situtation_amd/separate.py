@@ -20,7 +20,7 @@ is resampled on the GPU, resample.py, and the sources are written at the file's 
 file's sample format unless ``--out_format`` names another).
 
 The model is trained on mono and always sees the down-mix.  With ``channels`` (``--channels keep``) the one blended mask is
-also applied to each channel's own magnitude (``avsep_mask_stitch_channels``) and inverted with that channel's own phase,
+also applied to each channel's own magnitude (``avsep_mask_stitch`` with C channels) and inverted with that channel's own phase,
 so a stereo file gives stereo sources.  ``wiener=k`` (``--wiener k``) then runs k passes of a multichannel Wiener filter
 (``kernels.mwf``) over those source images: the masked channels give every source a spatial covariance per bin, and each
 time-frequency bin of the mixture is filtered again with them, so a source keeps its own place in the stereo image.
@@ -204,8 +204,7 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
         if channels is not None:                                         # the same masks on every channel's own STFT
             mag_c, phase_c = plan.stft(channels.contiguous())
             Cc, Fin, Fr = mag_c.shape
-            mags_c, _ = K.mask_stitch_channels(masks, starts_t, perms.to(dev), mag_c, binary and not wiener,
-                                               getattr(args, "mask_thres", 0.5))
+            mags_c, _ = K.mask_stitch(masks, starts_t, perms.to(dev), mag_c, binary and not wiener, getattr(args, "mask_thres", 0.5))
             phases_c = phase_c                                           # shared by the sources
             if wiener:                                                   # soft source images in, one phase per source out
                 mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener)
@@ -227,7 +226,8 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 16-bit PCM WAV through the standard library, and the command line
+# 16-bit PCM WAV through the standard library (the host's own statement of what a 16-bit file means: the command lines
+# read and write through wavio.py and the kernels), and the command line
 # ---------------------------------------------------------------------------------------------------------------------
 def read_wav(path):
     """-> (float32 mono waveform in [-1, 1), sample rate).  16-bit PCM only; channels are averaged."""
@@ -293,22 +293,11 @@ def write_wav_pcm_channels(path, pcm, rate):
 
 def load_mixture(path, info, model_rate, dev, keep=False):
     """The file ``path`` (info: its wavio.probe) on ``dev`` at ``model_rate`` -> (mono f32 [L], the network's input; with
-    ``keep`` its channels f32 [C, L], else None).  A 16-bit file takes the steps it always took (read_wav's host conversion at
-    the model's rate, resample_pcm / split_pcm otherwise); every other format goes up as the bytes it is and is converted,
-    down-mixed and filtered by one kernel (resample_frames / split_frames)."""
+    ``keep`` its channels f32 [C, L], else None).  The frames go up as the bytes they are and are converted, down-mixed and
+    filtered by one kernel (resample_frames / split_frames); at the model's rate that is read_wav's array for a 16-bit file."""
     from . import resample as R
     from . import wavio
-    raw = wavio.read_frames(path)[0]
-    if info.fmt == "s16":
-        pcm = raw.view("<i2").astype(np.int16).reshape(-1, info.channels)      # read_wav_pcm's array
-        if keep:
-            rows = R.split_pcm(torch.from_numpy(pcm).to(dev), info.rate, model_rate)
-            return rows[0], rows[1:]
-        if info.rate == model_rate:                  # read_wav's arithmetic
-            data = pcm.reshape(-1).astype(np.float32) / 32768.0
-            return torch.from_numpy(data.reshape(-1, info.channels).mean(1) if info.channels > 1 else data).to(dev), None
-        return R.resample_pcm(torch.from_numpy(pcm).to(dev), info.rate, model_rate), None
-    raw = torch.from_numpy(raw).to(dev)
+    raw = torch.from_numpy(wavio.read_frames(path)[0]).to(dev)
     if keep:
         rows = R.split_frames(raw, info.fmt, info.channels, info.rate, model_rate)
         return rows[0], rows[1:]
@@ -461,20 +450,11 @@ def cli(argv=None):
     report = None
     if levelled:                                     # rescaled, not clipped: measured and written at the output rate
         report = write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev)
-    elif out_fmt != "s16":                             # the kernel writes the file's frames: every stem is one join
+    else:                                            # the kernel writes the file's frames: every stem is one join
         stems = out["channel_wavs"] if keep else out["wavs"][:, None]
         for n, cw in enumerate(stems):
             wavio.write_frames(os.path.join(args.out, f"source{n}.wav"), R.join_frames(cw, args.audRate, out_rate, out_fmt).cpu().numpy(),
                                out_rate, cw.shape[0], out_fmt)
-    elif keep:
-        for n, cw in enumerate(out["channel_wavs"]):
-            write_wav_pcm_channels(os.path.join(args.out, f"source{n}.wav"), R.join_pcm(cw, args.audRate, out_rate).cpu().numpy(), out_rate)
-    elif rate != args.audRate and args.out_rate == "file":
-        for n, w in enumerate(R.resample(out["wavs"], args.audRate, rate, out_s16=True).cpu().numpy()):
-            write_wav_pcm(os.path.join(args.out, f"source{n}.wav"), w, rate)
-    else:
-        for n, w in enumerate(out["wavs"].cpu().numpy()):
-            write_wav(os.path.join(args.out, f"source{n}.wav"), w, args.audRate)
     if args.levels and report is None:               # the clamped stems as they were written, at the output rate
         from . import levels as LV
         stems = out["channel_wavs"] if keep else out["wavs"][:, None]

@@ -447,24 +447,19 @@ int avsep_window_agreement(const float* masks, const int32_t* starts, int32_t K,
                            double* D, avsep_stream_t stream);
 /* Cross-faded masks x mixture magnitude (main.py:205-246 for a recording of any length):
  *   M[n,f,t] = sum_k w(t-s_k) * unwarp(m[k, perm[k,n]])(f, t-s_k) / sum_k w(t-s_k)   over windows with 0 <= t-s_k < W,
- *   w(j) = min(j+1, W-j);   out[n,f,t] = mag[f,t] * (binary ? (M > thres) : M)      (threshold after blending).
+ *   w(j) = min(j+1, W-j);   out[n,c,f,t] = mag[c,f,t] * (binary ? (M > thres) : M)      (threshold after blending).
  * unwarp = grid_sample on warpgrid(.., Fin, W, warp=False) (utils.py:12-26), per window, time axis resampled too, as
  * avsep_warp(.., warp=0) does.  A frame covered by ONE window gets that window's un-warped mask unchanged, so a one-tile
  * recording reproduces avsep_warp + threshold + multiply bit for bit.  perm: int32 [K, N], entries in [0, N) (others
- * contribute nothing).  out: [N, Fin, F]; mask_out (optional, may be null): the blended M, [N, Fin, F]. */
+ * contribute nothing).
+ * mag: [C, Fin, F], one magnitude per channel the recording keeps (C = 1: the down-mix alone).  The model hears the down-mix
+ * and its masks are functions of (source, bin, frame) only: M is blended once per (n, f, t) and multiplied into the C
+ * magnitudes, so out[:, c] does not depend on the other channels.  out: [N, C, Fin, F], the layout avsep_istft takes as N*C
+ * rows ([N, Fin, F] at C = 1); mask_out (optional, may be null): the blended M, [N, Fin, F].  C <= 65535; offsets are formed
+ * in 64 bits ([N, C, Fin, F] passes 2^31 elements on a multi-hour recording). */
 int avsep_mask_stitch(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
-                      int32_t N, int32_t Fout, int32_t W, int32_t Fin, int32_t F, int32_t binary, float thres,
+                      int32_t N, int32_t Fout, int32_t W, int32_t C, int32_t Fin, int32_t F, int32_t binary, float thres,
                       float* out, float* mask_out, avsep_stream_t stream);
-/* avsep_mask_stitch for a recording that keeps its C channels (the model hears their down-mix; its masks are functions of
- * (source, bin, frame) only): mag is [C, Fin, F], one magnitude per channel, and
- *   out[n,c,f,t] = mag[c,f,t] * (binary ? (M[n,f,t] > thres) : M[n,f,t]),
- * with M blended once per (n, f, t) by the code avsep_mask_stitch runs: out[:, c] and mask_out are bit for bit what
- * avsep_mask_stitch gives for mag[c].  out: [N, C, Fin, F], the layout avsep_istft takes as N*C rows; mask_out (optional, may
- * be null): [N, Fin, F].  C <= 65535; offsets are formed in 64 bits ([N, C, Fin, F] passes 2^31 elements on a multi-hour
- * recording). */
-int avsep_mask_stitch_channels(const float* masks, const int32_t* starts, const int32_t* perm, const float* mag, int32_t K,
-                               int32_t N, int32_t Fout, int32_t W, int32_t C, int32_t Fin, int32_t F, int32_t binary,
-                               float thres, float* out, float* mask_out, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Multichannel Wiener filter over the stitched source images (csrc/mwf.hip): what turns N masked copies of a C-channel
@@ -564,60 +559,49 @@ int avsep_heatmap_overlay(const float* maps, const float* const* frames, const u
  * a sample outside [0, L) is 0 and the last tap takes no sample when p + (T-1)*up >= M.  The order depends on (up, down, j)
  * only: not on B, the launch geometry or the run; there are no atomics.  A row gives the same bits alone, inside a batch
  * and on a second call.
- * Input:  in_ch = 0: x is f32 [B, L].  in_ch = C in [1, 256]: x is interleaved int16 [L, C] as it lies in a WAV file (B must
- *   be 1); the sample is the exact integer sum of the C channels divided (IEEE f32 division) by C * 32768, converted while
- *   the tile is staged: no f32 copy of the file exists.
- * Output: out_s16 = 0: y is f32 [B, Lout].  out_s16 = 1: y is int16 [B, Lout] = clip(rint(v * 32768), -32768, 32767) of
- *   exactly the f32 value v the other mode stores (round half to even; v * 32768 is exact).
- * 1 <= L, Lout < 2^31, B <= 65535; anything else is AVSEP_ERR_ARG before any launch.
- * ------------------------------------------------------------------------- */
-int avsep_resample_poly(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down, int32_t in_ch,
-                        int32_t out_s16, void* y, avsep_stream_t stream);
-/* The two ends of a pipeline that keeps a file's channels apart, 1 <= C <= 8 (up to 7.1); filter table, limits and the
- * per-output arithmetic are avsep_resample_poly's (one chain per output, its order a function of (up, down, j) only), so
- * every value below is bit for bit the value avsep_resample_poly gives for the same row.
- * avsep_resample_split: x is interleaved int16 [L, C]; y is f32 [1 + C, Lout].  Row 0 is the down-mix, what
- *   avsep_resample_poly(in_ch = C) gives; row 1 + c is channel c over 32768 (exact), what avsep_resample_poly(in_ch = 0)
- *   gives for that channel as an f32 row.  One pass over the file: no de-interleaved copy of it exists.
- * avsep_resample_join: x is f32 [C, L]; y is interleaved int16 [Lout, C], y[j, c] = clip(rint(v * 32768), -32768, 32767) of
- *   the value v avsep_resample_poly gives row c (its out_s16 output, transposed).  A workgroup makes all C channels of its
- *   frames and stores them as whole frames, contiguously. */
-int avsep_resample_split(const int16_t* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, float* y,
-                         avsep_stream_t stream);
-int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int16_t* y,
-                        avsep_stream_t stream);
-/* The same three with a file's frames as the bytes they are, in any of four sample formats.  Frames (x of _poly_fmt with
- * in_ch >= 1 and of _split_fmt, y of _join_fmt and of _poly_fmt) are packed little-endian samples at ANY byte address: a
- * file's data chunk rarely starts on a dword and a three-byte frame never stays on one.  One sample as f32:
+ * Frames (x of avsep_resample_poly with in_ch >= 1 and of avsep_resample_split, y of avsep_resample_join and of
+ * avsep_resample_poly) are a file's packed little-endian samples at ANY byte address: a data chunk rarely starts on a dword
+ * and a three-byte frame never stays on one.  One sample as f32:
  *   AVSEP_SAMPLE_S16  2 bytes, WAVE tag 1           v / 2^15 (exact)
  *   AVSEP_SAMPLE_S24  3 bytes packed, WAVE tag 1    sign-extended v / 2^23 (exact)
  *   AVSEP_SAMPLE_S32  4 bytes, WAVE tag 1           the integer rounded to f32 once (nearest-even), times 2^-31
  *   AVSEP_SAMPLE_F32  IEEE binary32, WAVE tag 3     the bits as they are (no range or NaN check)
- * Down-mix (the mono row of _poly_fmt with in_ch = C and row 0 of _split_fmt), integer formats: the exact 64-bit sum of the C
- *   channels over C * 2^(bits-1), rounded to f32 ONCE.  It is computed as (float)((double)sum / (double)(C << (bits-1))): sum
- *   and divisor are exact in f64 and the f64 -> f32 double rounding of a quotient is innocuous at 53 >= 2*24 + 2 bits.  For
- *   S16 this is avsep_resample_poly's value.  F32: the channels added in f64 in the order c = 0 ... C-1, divided by C in f64,
- *   rounded to f32 once.  One channel (C = 1) is the sample itself.
- * Output formats: S16 as avsep_resample_poly's out_s16; S24 = clip(rintf(v * 2^23), -2^23, 2^23 - 1), ties to even, three
- *   little-endian bytes; F32 the accumulator's bits, not clipped.  There is no S32 output (an f32 value has 24 significant
- *   bits) and no dither.
- * The accumulation chains are the ones above: with S16 in and S16 / F32 out every entry point gives the bits of its older
- * twin, and each format changes only what is staged and how the result is stored.
- * avsep_resample_poly_fmt: in_ch = 0: x is f32 [B, L] on a 4-byte boundary and in_fmt must be AVSEP_SAMPLE_F32; in_ch = C in
- *   [1, 256]: x is frames [L, C] of in_fmt (B must be 1).  y: [B, Lout] samples of out_fmt, packed.
- * avsep_resample_split_fmt: x is frames [L, C] of in_fmt, y f32 [1 + C, Lout].
- * avsep_resample_join_fmt: x is f32 [C, L], y frames [Lout, C] of out_fmt, stored as whole dwords between a head and a tail
- *   of up to three bytes, whatever the address. */
+ * Down-mix (the mono row of avsep_resample_poly with in_ch = C and row 0 of avsep_resample_split), integer formats: the exact
+ *   64-bit sum of the C channels over C * 2^(bits-1), rounded to f32 ONCE.  It is computed as
+ *   (float)((double)sum / (double)(C << (bits-1))): sum and divisor are exact in f64 and the f64 -> f32 double rounding of a
+ *   quotient is innocuous at 53 >= 2*24 + 2 bits.  F32: the channels added in f64 in the order c = 0 ... C-1, divided by C in
+ *   f64, rounded to f32 once.  One channel (C = 1) is the sample itself.  The conversion happens while the tile is staged: no
+ *   f32 copy of the file exists.
+ * Output formats, of exactly the f32 value v of the chain: S16 = clip(rintf(v * 2^15), -2^15, 2^15 - 1), S24 =
+ *   clip(rintf(v * 2^23), -2^23, 2^23 - 1), ties to even (the products are exact), little-endian; F32 the accumulator's bits,
+ *   not clipped.  There is no S32 output (an f32 value has 24 significant bits) and no dither.
+ * A format changes only what is staged and how a result is stored, never the chain.  No alignment is ever required of frames; S16
+ *   frames on a 2-byte boundary (and f32 rows, S16 / F32 outputs on their own boundary) are moved with typed loads and stores
+ *   in place of byte assembly: the same values, chosen by the entry point from the formats and addresses it is handed.
+ * avsep_resample_poly: in_ch = 0: x is f32 [B, L] on a 4-byte boundary and in_fmt must be AVSEP_SAMPLE_F32; in_ch = C in
+ *   [1, 256]: x is frames [L, C] of in_fmt (B must be 1), down-mixed.  y: [B, Lout] samples of out_fmt, packed.
+ * 1 <= L, Lout < 2^31, B <= 65535; anything else, a format code outside the table or a null pointer is AVSEP_ERR_ARG before
+ * any launch.
+ * ------------------------------------------------------------------------- */
 #define AVSEP_SAMPLE_S16 1
 #define AVSEP_SAMPLE_S24 2
 #define AVSEP_SAMPLE_S32 3
 #define AVSEP_SAMPLE_F32 4
-int avsep_resample_poly_fmt(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down, int32_t in_ch,
-                            int32_t in_fmt, int32_t out_fmt, void* y, avsep_stream_t stream);
-int avsep_resample_split_fmt(const void* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, int32_t in_fmt,
-                             float* y, avsep_stream_t stream);
-int avsep_resample_join_fmt(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int32_t out_fmt,
-                            void* y, avsep_stream_t stream);
+int avsep_resample_poly(const void* x, const float* ho, int32_t B, int32_t L, int32_t up, int32_t down, int32_t in_ch,
+                        int32_t in_fmt, int32_t out_fmt, void* y, avsep_stream_t stream);
+/* The two ends of a pipeline that keeps a file's channels apart, 1 <= C <= 8 (up to 7.1); filter table, formats, limits and
+ * the per-output arithmetic are avsep_resample_poly's (one chain per output, its order a function of (up, down, j) only), so
+ * every value below is bit for bit the value avsep_resample_poly gives for the same row.
+ * avsep_resample_split: x is frames [L, C] of in_fmt; y is f32 [1 + C, Lout].  Row 0 is the down-mix, what
+ *   avsep_resample_poly(in_ch = C) gives; row 1 + c is channel c, what avsep_resample_poly(in_ch = 0) gives for that channel
+ *   as an f32 row.  One pass over the file: no de-interleaved copy of it exists.
+ * avsep_resample_join: x is f32 [C, L]; y is frames [Lout, C] of out_fmt, y[j, c] the out_fmt form of the value
+ *   avsep_resample_poly gives row c.  A workgroup makes all C channels of its frames and stores them as whole frames: whole
+ *   dwords between a head and a tail of up to three bytes, whatever the address. */
+int avsep_resample_split(const void* x, const float* ho, int32_t L, int32_t C, int32_t up, int32_t down, int32_t in_fmt,
+                         float* y, avsep_stream_t stream);
+int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, int32_t up, int32_t down, int32_t out_fmt,
+                        void* y, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Stem levels (csrc/levels.hip; avsep_amd/levels.py): what ITU-R BS.1770-4 loudness and true peak need from every sample of

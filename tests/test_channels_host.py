@@ -94,24 +94,25 @@ def test_cpu_tensors_are_refused_by_split_and_join():
 
 def test_new_entry_points_refuse_bad_arguments_before_launching():
     """include/avsep.h: C outside [1, 8], a ratio term outside [1, 1280], L < 1, Lout >= 2^31 and null pointers are argument
-    errors (-1) of avsep_resample_split / _join; C = 0 and null pointers of avsep_mask_stitch_channels."""
+    errors (-1) of avsep_resample_split / _join; C = 0 and null pointers of avsep_mask_stitch."""
     import ctypes as C
     lib = avsep_amd.lib.load()
     buf = (C.c_float * 64)()
     p = C.addressof(buf)
+    S16 = 1                                                                              # AVSEP_SAMPLE_S16
     for f in (lib.avsep_resample_split, lib.avsep_resample_join):
         la = (lambda L, Cc: (L, Cc)) if f is lib.avsep_resample_split else (lambda L, Cc: (Cc, L))
-        assert f(p, p, *la(16, 0), 1, 4, p, None) == -1
-        assert f(p, p, *la(16, 9), 1, 4, p, None) == -1
-        assert f(p, p, *la(0, 2), 1, 4, p, None) == -1
-        assert f(p, p, *la(16, 2), 0, 4, p, None) == -1
-        assert f(p, p, *la(16, 2), 1281, 1, p, None) == -1
-        assert f(p, p, *la(16, 2), 1, 1281, p, None) == -1
-        assert f(p, p, *la(2 ** 31 - 1, 2), 4, 1, p, None) == -1
-        assert f(None, p, *la(16, 2), 1, 4, p, None) == -1
-        assert f(p, None, *la(16, 2), 1, 4, p, None) == -1
-        assert f(p, p, *la(16, 2), 1, 4, None, None) == -1
-    g = lib.avsep_mask_stitch_channels
+        assert f(p, p, *la(16, 0), 1, 4, S16, p, None) == -1
+        assert f(p, p, *la(16, 9), 1, 4, S16, p, None) == -1
+        assert f(p, p, *la(0, 2), 1, 4, S16, p, None) == -1
+        assert f(p, p, *la(16, 2), 0, 4, S16, p, None) == -1
+        assert f(p, p, *la(16, 2), 1281, 1, S16, p, None) == -1
+        assert f(p, p, *la(16, 2), 1, 1281, S16, p, None) == -1
+        assert f(p, p, *la(2 ** 31 - 1, 2), 4, 1, S16, p, None) == -1
+        assert f(None, p, *la(16, 2), 1, 4, S16, p, None) == -1
+        assert f(p, None, *la(16, 2), 1, 4, S16, p, None) == -1
+        assert f(p, p, *la(16, 2), 1, 4, S16, None, None) == -1
+    g = lib.avsep_mask_stitch
     assert g(p, p, p, p, 1, 2, 4, 4, 0, 4, 4, 0, 0.5, p, None, None) == -1              # C = 0
     assert g(p, p, p, p, 1, 2, 4, 4, 65536, 4, 4, 0, 0.5, p, None, None) == -1
     assert g(p, p, p, None, 1, 2, 4, 4, 2, 4, 4, 0, 0.5, p, None, None) == -1

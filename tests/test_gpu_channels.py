@@ -1,4 +1,4 @@
-"""gpu: keeping a recording's channels (avsep_mask_stitch_channels in csrc/longform.hip, avsep_resample_split / _join in
+"""gpu: keeping a recording's channels (avsep_mask_stitch with C channels in csrc/longform.hip, avsep_resample_split / _join in
 csrc/resample.hip, separate_long(channels=...) and --channels keep of avsep_amd/separate.py).
 
 Every comparison is torch.equal / equal bytes against the same result composed from the entry points that were there
@@ -193,13 +193,13 @@ def test_join_where_the_tile_does_not_fit_in_lds(dev):
 
 def test_split_and_join_wrapper_refusals(dev):
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_split(torch.zeros(100, 2, dtype=torch.int16, device=dev), RS.filter_table(1, 2, dev), 1, 4)
+        P.kernels.resample_split(torch.zeros(400, dtype=torch.uint8, device=dev), RS.filter_table(1, 2, dev), 1, 4, 2, "s16")
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_join(torch.zeros(2, 100, device=dev), RS.filter_table(1, 2, dev), 1, 4)
+        P.kernels.resample_join(torch.zeros(2, 100, device=dev), RS.filter_table(1, 2, dev), 1, 4, "s16")
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_split(torch.zeros(100, 9, dtype=torch.int16, device=dev), RS.filter_table(1, 4, dev), 1, 4)
+        P.kernels.resample_split(torch.zeros(1800, dtype=torch.uint8, device=dev), RS.filter_table(1, 4, dev), 1, 4, 9, "s16")
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_join(torch.zeros(9, 100, device=dev), RS.filter_table(1, 4, dev), 1, 4)
+        P.kernels.resample_join(torch.zeros(9, 100, device=dev), RS.filter_table(1, 4, dev), 1, 4, "s16")
 
 
 # ---------------------------------------------------------------------------------------------------------------------

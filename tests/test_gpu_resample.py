@@ -156,7 +156,7 @@ def test_s16_output_is_write_wavs_rounding_of_the_f32_output(dev, up, down):
     xt = torch.from_numpy(x).to(dev)
     filt = _table(up, down, dev)
     y32 = P.kernels.resample_poly(xt, filt, up, down).cpu().numpy()
-    y16 = P.kernels.resample_poly(xt, filt, up, down, out_s16=True)
+    y16 = P.kernels.resample_poly(xt, filt, up, down, out_fmt="s16")
     assert y16.dtype == torch.int16 and y16.shape == y32.shape
     want = np.clip(np.rint(y32.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
     assert np.array_equal(y16.cpu().numpy(), want)

@@ -1,4 +1,4 @@
-"""gpu: a file's frames in any sample format through the PCM kernels (the *_fmt entry points of csrc/resample.hip,
+"""gpu: a file's frames in any sample format through the PCM kernels (the entry points of csrc/resample.hip,
 resample.resample_frames / split_frames / join_frames, wavio.py and the command lines).
 
 Every comparison is bit for bit.  The accumulation chains are shared with avsep_resample_poly, so a format can only show in
@@ -60,7 +60,7 @@ def _f32_path(mono, up, down, dev):
 # 1. input side
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("up,down", RATIOS)
-@pytest.mark.parametrize("fmt", ["s24", "s32", "f32"])
+@pytest.mark.parametrize("fmt", ["s16", "s24", "s32", "f32"])
 def test_frames_input_is_the_f32_path_fed_the_down_mix(dev, fmt, up, down):
     """C in {1, 2, 3, 6}; L in {1, 2, 3, 4, 4001}: the last s24 frame ends on every dword phase; the frames start on each of
     the four byte phases."""
@@ -102,7 +102,7 @@ def test_down_mix_of_256_channels_at_both_ends_of_the_range(dev, fmt):
 
 
 @pytest.mark.parametrize("up,down", RATIOS)
-@pytest.mark.parametrize("fmt", ["s24", "s32", "f32"])
+@pytest.mark.parametrize("fmt", ["s16", "s24", "s32", "f32"])
 def test_split_rows_are_the_single_row_results(dev, fmt, up, down):
     rate_in, rate_out = _rates(up, down)
     for C in (1, 2, 8):
@@ -171,7 +171,10 @@ def test_equal_rates_only_round(dev):
 
 
 @pytest.mark.parametrize("up,down", [(640, 147), (1, 4), (1, 1), (1, 1280)])
-def test_fmt_entry_points_with_s16_give_the_older_entry_points_bits(dev, up, down):
+def test_int16_adapters_are_the_byte_calls_and_poly_rows_sit_at_any_byte_address(dev, up, down):
+    """resample_pcm / split_pcm / join_pcm on an int16 tensor are resample_frames / split_frames / join_frames on its bytes
+    (what those give at every byte phase is tied to the host's down-mix by the tests above); rows of resample_poly in every
+    output format, from byte offsets 1 to 3, are the host's encoding of its f32 output."""
     rate_in, rate_out = _rates(up, down)
     filt = RS.filter_table(up, down, dev)
     for C in (1, 2, 6):
@@ -179,24 +182,21 @@ def test_fmt_entry_points_with_s16_give_the_older_entry_points_bits(dev, up, dow
         pcm[:2] = np.array([-32768, 32767], np.int16)[:, None]
         raw = np.ascontiguousarray(pcm.astype("<i2")).view(np.uint8).reshape(-1)
         pt = torch.from_numpy(pcm).to(dev)
-        mono = RS.resample_pcm(pt, rate_in, rate_out)
-        rows = RS.split_pcm(pt, rate_in, rate_out)
-        for k in range(4):
-            dev_raw = _at_phase(raw, k, dev)
-            assert torch.equal(RS.resample_frames(dev_raw, "s16", C, rate_in, rate_out), mono), (C, k)
-            assert torch.equal(RS.split_frames(dev_raw, "s16", C, rate_in, rate_out), rows), (C, k)
+        dev_raw = _at_phase(raw, 0, dev)
+        assert torch.equal(RS.resample_pcm(pt, rate_in, rate_out), RS.resample_frames(dev_raw, "s16", C, rate_in, rate_out)), C
+        assert torch.equal(RS.split_pcm(pt, rate_in, rate_out), RS.split_frames(dev_raw, "s16", C, rate_in, rate_out)), C
     x = torch.from_numpy(_stems(3, 3001)).to(dev)
     y32 = P.kernels.resample_poly(x, filt, up, down)
-    y16 = P.kernels.resample_poly(x, filt, up, down, out_s16=True)
-    assert torch.equal(P.kernels.resample_poly_fmt(x, filt, up, down, 0, "f32", "f32"), y32)
-    assert torch.equal(P.kernels.resample_poly_fmt(x, filt, up, down, 0, "f32", "s16"), y16)
-    got24 = P.kernels.resample_poly_fmt(x, filt, up, down, 0, "f32", "s24")
+    y16 = P.kernels.resample_poly(x, filt, up, down, out_fmt="s16")
+    assert y16.dtype == torch.int16 and y16.shape == y32.shape
+    assert np.array_equal(y16.cpu().numpy().view(np.uint8).reshape(-1), F.encode(y32.cpu().numpy().reshape(-1), "s16"))
+    got24 = P.kernels.resample_poly(x, filt, up, down, 0, "f32", "s24")
     assert got24.shape == (3, 3 * y32.shape[1]) and np.array_equal(got24.cpu().numpy().reshape(-1), F.encode(y32.cpu().numpy().reshape(-1), "s24"))
     for k in (1, 2, 3):                                                                # rows of samples at any byte address
         for fmt in ("s16", "s24", "f32"):
             n = 3 * y32.shape[1] * F.BYTES[fmt]
             buf = torch.zeros(n + k, dtype=torch.uint8, device=dev)
-            got = P.kernels.resample_poly_fmt(x, filt, up, down, 0, "f32", fmt, out=buf[k:])
+            got = P.kernels.resample_poly(x, filt, up, down, 0, "f32", fmt, out=buf[k:])
             assert np.array_equal(got.cpu().numpy(), F.encode(y32.cpu().numpy().reshape(-1), fmt)), (fmt, k)
     assert np.array_equal(RS.join_frames(x, rate_in, rate_out, "s16").cpu().numpy(),
                           RS.join_pcm(x, rate_in, rate_out).cpu().numpy().view(np.uint8).reshape(-1))
@@ -207,17 +207,17 @@ def test_wrapper_refusals(dev):
     x = torch.zeros(2, 100, device=dev)
     filt = RS.filter_table(1, 4, dev)
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_poly_fmt(raw, RS.filter_table(1, 2, dev), 1, 4, 2, "s24", "f32")      # another ratio's table
+        P.kernels.resample_poly(raw, RS.filter_table(1, 2, dev), 1, 4, 2, "s24", "f32")      # another ratio's table
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_poly_fmt(raw, filt, 1, 4, 5, "s24", "f32")                            # 48 bytes are no 5-channel frames
+        P.kernels.resample_poly(raw, filt, 1, 4, 5, "s24", "f32")                            # 48 bytes are no 5-channel frames
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_poly_fmt(x, filt, 1, 4, 0, "s24", "f32")                              # rows are f32
+        P.kernels.resample_poly(x, filt, 1, 4, 0, "s24", "f32")                              # rows are f32
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_split_fmt(raw, filt, 1, 4, 2, "s20")
+        P.kernels.resample_split(raw, filt, 1, 4, 2, "s20")
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_join_fmt(x, filt, 1, 4, "s32")
+        P.kernels.resample_join(x, filt, 1, 4, "s32")
     with pytest.raises(P.lib.AvsepError):
-        P.kernels.resample_join_fmt(x, filt, 1, 4, "s24", out=torch.zeros(10, dtype=torch.uint8, device=dev))      # too small
+        P.kernels.resample_join(x, filt, 1, 4, "s24", out=torch.zeros(10, dtype=torch.uint8, device=dev))      # too small
     with pytest.raises(P.lib.AvsepError):
         RS.resample_frames(raw.cpu(), "s24", 2, 48000, 11025)                                    # no CPU fallback
 

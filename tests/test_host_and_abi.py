@@ -25,6 +25,10 @@ def test_library_exports_every_declared_symbol():
     missing = [n for n in sorted(declared) if not hasattr(lib, n)]
     assert not missing, f"declared in avsep.h but not exported: {missing}"
     assert set(P.lib.SIGNATURES) == declared, set(P.lib.SIGNATURES) ^ declared
+    import subprocess
+    nm = subprocess.run(["nm", "-D", "--defined-only", P.lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r"\b(avsep_[a-z0-9_]+)$", nm, flags=re.M))
+    assert exported == declared, exported ^ declared                 # and nothing the header does not declare
     L = P.lib.load()
     assert L.avsep_arch() == b"gfx950" and L.avsep_version() >= 100
     assert L.avsep_strerror(-1).startswith(b"invalid argument")

@@ -81,20 +81,38 @@ def test_entry_point_refuses_bad_arguments_before_launching():
     buf = (C.c_float * 64)()
     p = C.addressof(buf)
     f = lib.avsep_resample_poly
-    assert f(p, p, 1, 16, 0, 1, 0, 0, p, None) == -1                    # up = 0
-    assert f(p, p, 1, 16, 1, 1281, 0, 0, p, None) == -1                 # down over the limit
-    assert f(p, p, 1, 16, 1281, 1, 0, 0, p, None) == -1
-    assert f(p, p, 1, 16, 1, -4, 0, 0, p, None) == -1
-    assert f(p, p, 1, 0, 1, 4, 0, 0, p, None) == -1                     # L = 0
-    assert f(p, p, 0, 16, 1, 4, 0, 0, p, None) == -1                    # B = 0
-    assert f(p, p, 2, 16, 1, 4, 2, 0, p, None) == -1                    # PCM input is one recording
-    assert f(p, p, 1, 16, 1, 4, 257, 0, p, None) == -1
-    assert f(p, p, 1, 16, 1, 4, -1, 0, p, None) == -1
-    assert f(p, p, 1, 16, 1, 4, 0, 2, p, None) == -1
-    assert f(p, p, 1, 2 ** 31 - 1, 4, 1, 0, 0, p, None) == -1           # Lout >= 2^31
-    assert f(None, p, 1, 16, 1, 4, 0, 0, p, None) == -1
-    assert f(p, None, 1, 16, 1, 4, 0, 0, p, None) == -1
-    assert f(p, p, 1, 16, 1, 4, 0, 0, None, None) == -1
+    S16, F32 = 1, 4                                                      # AVSEP_SAMPLE_*
+    assert f(p, p, 1, 16, 0, 1, 0, F32, F32, p, None) == -1             # up = 0
+    assert f(p, p, 1, 16, 1, 1281, 0, F32, F32, p, None) == -1          # down over the limit
+    assert f(p, p, 1, 16, 1281, 1, 0, F32, F32, p, None) == -1
+    assert f(p, p, 1, 16, 1, -4, 0, F32, F32, p, None) == -1
+    assert f(p, p, 1, 0, 1, 4, 0, F32, F32, p, None) == -1              # L = 0
+    assert f(p, p, 0, 16, 1, 4, 0, F32, F32, p, None) == -1             # B = 0
+    assert f(p, p, 2, 16, 1, 4, 2, S16, F32, p, None) == -1             # PCM input is one recording
+    assert f(p, p, 1, 16, 1, 4, 257, S16, F32, p, None) == -1
+    assert f(p, p, 1, 16, 1, 4, -1, S16, F32, p, None) == -1
+    assert f(p, p, 1, 16, 1, 4, 0, F32, 5, p, None) == -1               # no such output format
+    assert f(p, p, 1, 2 ** 31 - 1, 4, 1, 0, F32, F32, p, None) == -1    # Lout >= 2^31
+    assert f(None, p, 1, 16, 1, 4, 0, F32, F32, p, None) == -1
+    assert f(p, None, 1, 16, 1, 4, 0, F32, F32, p, None) == -1
+    assert f(p, p, 1, 16, 1, 4, 0, F32, F32, None, None) == -1
+
+
+@pytest.mark.parametrize("C", range(1, 9))
+def test_read_wav_is_the_once_rounded_mean(tmp_path, C):
+    """include/avsep.h's down-mix of 16-bit frames, (float32)(sum / (C * 32768)) with one rounding, is what read_wav's own
+    arithmetic (each sample to f32 over 32768, then NumPy's mean over the channels) gives: the kernels' value at the model's
+    rate is the array the standard-library reader returns."""
+    rng = np.random.default_rng(C)
+    pcm = rng.integers(-32768, 32768, size=(20000, C)).astype(np.int16)
+    edge = np.array([-32768, 32767, 0, 1], np.int16)
+    pcm[:4] = edge[:, None]                                              # every channel at the same extreme
+    pcm[4:8, 0] = edge                                                   # one channel at an extreme beside random ones
+    path = str(tmp_path / "x.wav")
+    S.write_wav_pcm_channels(path, pcm, 11025)
+    got, rate = S.read_wav(path)
+    want = (pcm.astype(np.int64).sum(1).astype(np.float64) / (C * 32768.0)).astype(np.float32)
+    assert rate == 11025 and got.dtype == np.float32 and np.array_equal(got, want)
 
 
 def test_polyphase_table_layout():

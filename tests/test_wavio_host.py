@@ -1,5 +1,5 @@
 """not-gpu: the RIFF/WAVE reader and writer (avsep_amd/wavio.py), the host statement of the four sample formats
-(wavio.decode, tests/sample_formats_ref.py), the *_fmt entry points' argument checks and the --out_format flag."""
+(wavio.decode, tests/sample_formats_ref.py), the resample entry points' format checks and the --out_format flag."""
 import os
 import re
 import struct
@@ -353,7 +353,7 @@ def test_fmt_entry_points_refuse_bad_arguments_before_launching():
     buf = (C.c_float * 64)()
     p = C.addressof(buf)
     S16, S24, S32, F32 = 1, 2, 3, 4
-    f = lib.avsep_resample_poly_fmt
+    f = lib.avsep_resample_poly
     assert f(p, p, 1, 16, 1, 4, 2, 0, F32, p, None) == -1                # no such input format
     assert f(p, p, 1, 16, 1, 4, 2, 5, F32, p, None) == -1
     assert f(p, p, 1, 16, 1, 4, 2, S24, S32, p, None) == -1              # no S32 output
@@ -366,14 +366,14 @@ def test_fmt_entry_points_refuse_bad_arguments_before_launching():
     assert f(p, p, 1, 0, 1, 4, 2, S24, F32, p, None) == -1
     assert f(None, p, 1, 16, 1, 4, 2, S24, F32, p, None) == -1
     assert f(p, p, 1, 16, 1, 4, 2, S24, F32, None, None) == -1
-    g = lib.avsep_resample_split_fmt
+    g = lib.avsep_resample_split
     assert g(p, p, 16, 2, 1, 4, 0, p, None) == -1
     assert g(p, p, 16, 2, 1, 4, 5, p, None) == -1
     assert g(p, p, 16, 9, 1, 4, S24, p, None) == -1
     assert g(p, p, 16, 0, 1, 4, S24, p, None) == -1
     assert g(p, p, 16, 2, 1281, 4, S24, p, None) == -1
     assert g(p, None, 16, 2, 1, 4, S24, p, None) == -1
-    h = lib.avsep_resample_join_fmt
+    h = lib.avsep_resample_join
     assert h(p, p, 2, 16, 1, 4, S32, p, None) == -1
     assert h(p, p, 2, 16, 1, 4, 0, p, None) == -1
     assert h(p, p, 9, 16, 1, 4, S24, p, None) == -1

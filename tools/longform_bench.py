@@ -8,7 +8,7 @@ algorithmic bytes, bytes/s against the 8 TB/s HBM peak, and the same result comp
 (gathered slices + K.warp + log; K.warp(.., 0) on every window + a torch cross-fade), outputs compared.
 With --channels C (C >= 1) also (3) the audio-visual call with the recording's C channels kept (separate_long(channels=...)):
 wall time and stage split, the stages of the channel path (second STFT, stitch_channels, iSTFT over N*C rows) next to the
-mono ones; and avsep_mask_stitch_channels alone against C launches of avsep_mask_stitch on the same magnitudes, outputs
+mono ones; and avsep_mask_stitch on the C magnitudes alone against C launches of it on one magnitude each, outputs
 compared bit for bit.
 With --wiener K as well (4) that call runs K passes of the multichannel Wiener filter (separate_long(wiener=K)): the stage
 split gains mwf_cov and mwf_apply; and kernels.mwf alone (one pass on the soft source images of the C channels) against the
@@ -113,13 +113,12 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, w
     clk.wrap(K.Stft, "stft", "stft" if channels is None else ["stft", "stft_channels"])
     clk.wrap(K.Stft, "istft", "istft" if channels is None else ["istft", "istft_channels"])
     clk.wrap(K.Stft, "misi", "misi" if channels is None else ["misi", "misi_channels"])
-    clk.wrap(K, "mask_stitch_channels", "stitch_channels")
     clk.wrap(K, "_mwf_cov", "mwf_cov")
     clk.wrap(K, "_mwf_apply", "mwf_apply")
     clk.wrap(K, "window_prepare", "window_prepare")
     clk.wrap(K, "window_agreement", "agreement")
     clk.wrap(S, "align_permutations", "agreement")
-    clk.wrap(K, "mask_stitch", "stitch")
+    clk.wrap(K, "mask_stitch", "stitch" if channels is None else ["stitch", "stitch_channels"])
     clk.wrap(nets[0], "forward", "unet")
     clk.wrap(nets[1], "forward", "visual_trunk")
     try:
@@ -208,7 +207,7 @@ def kernel_rows(mag, starts_t, masks, perm, args, reps):
 
 
 def channel_stitch_row(mag_c, starts_t, masks, perm, args, reps):
-    """avsep_mask_stitch_channels on mag_c [C,Fin,F] against C launches of avsep_mask_stitch (stacked: what the caller would
+    """avsep_mask_stitch on mag_c [C,Fin,F] against C launches of it on one channel each (stacked: what the caller would
     have to do for the [N,C,Fin,F] layout one iSTFT takes; and the launches alone, without the stack)."""
     K = P.kernels
     Cc, Fin, F = mag_c.shape
@@ -218,10 +217,10 @@ def channel_stitch_row(mag_c, starts_t, masks, perm, args, reps):
 
     def launches():
         return [K.mask_stitch(masks, starts_t, perm, m, binary, thres)[0] for m in rows]
-    a = K.mask_stitch_channels(masks, starts_t, perm, mag_c, binary, thres)[0]
+    a = K.mask_stitch(masks, starts_t, perm, mag_c, binary, thres)[0]
     same = bool(torch.equal(a, torch.stack(launches(), 1)))
     nbytes = 4 * (Kw * N * Fo * W + Cc * Fin * F + N * Cc * Fin * F) + 4 * (Kw + Kw * N)
-    ms_f = median_ms(lambda: K.mask_stitch_channels(masks, starts_t, perm, mag_c, binary, thres), reps)
+    ms_f = median_ms(lambda: K.mask_stitch(masks, starts_t, perm, mag_c, binary, thres), reps)
     ms_l = median_ms(launches, reps)
     ms_s = median_ms(lambda: torch.stack(launches(), 1), reps)
     return {"channels": Cc, "fused_ms": ms_f, "launches_ms": ms_l, "launches_stacked_ms": ms_s, "algorithmic_bytes": nbytes,

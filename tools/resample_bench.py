@@ -8,16 +8,18 @@ Prints and writes to --out (default profiles/resample_bench.json):
 (2) scipy.signal.resample_poly on this machine's CPU for the same four cases (float64 in, as dataset.read_wav_segment
     calls it; the PCM case includes its down-mix), median of --cpu-reps;
 (3) the `separate` command line's stages on a ten-minute 48 kHz mono file with the full-size model (train_MUSIC flags:
-    unet7 + resnet18dilated, fp32): read, upload, resample in, separate_long, resample out, download, write — each
-    bracketed by device synchronisations, median of --cli-reps — and the share of the wall time each resample takes.
+    unet7 + resnet18dilated, fp32): read, upload, resample in, separate_long, resample out (one join_frames per stem, as
+    the command line writes them), download, write — each bracketed by device synchronisations, median of --cli-reps —
+    and the share of the wall time each resample takes.
 (4) the two ends of `--channels keep` on a 48 kHz stereo file: avsep_resample_split (PCM -> down-mix + 2 channels at 11 025)
-    and avsep_resample_join (2 channels at 11 025 -> 48 kHz interleaved int16), each against the same result composed from
-    the older entry points on the device — resample_pcm for the down-mix, a de-interleave to f32 rows and one batched
-    resample for the channels; resample(out_s16) and a transpose back to interleaved frames — outputs compared bit for bit,
-    in the same process, alternating.
-(5) beside every 16-bit row of (1) and (4) the same work on 24-bit PCM and 32-bit float frames (the *_fmt entry points:
-    resample_frames, split_frames, join_frames; a mono stem is one join_frames call of one channel), frames and outputs as
-    the bytes of a file.  --sections picks among kernels, channels, cli.
+    and avsep_resample_join (2 channels at 11 025 -> 48 kHz interleaved int16), each against the same result composed on the
+    device without them — resample_pcm for the down-mix, a de-interleave to f32 rows and one batched resample for the
+    channels; resample(out_s16) and a transpose back to interleaved frames — outputs compared bit for bit, in the same
+    process, alternating.
+(5) beside every 16-bit row of (1) and (4) the same work on 24-bit PCM and 32-bit float frames (resample_frames,
+    split_frames, join_frames; a mono stem is one join_frames call of one channel, which the `_s16_per_stem` rows time for
+    16-bit output against the one batched launch of the `_s16` rows), frames and outputs as the bytes of a file.
+    --sections picks among kernels, channels, cli.
 The last line is one JSON object.
 Usage: python tools/resample_bench.py [--seconds 600] [--reps 20] [--cpu-reps 3] [--cli-reps 3] [--sections kernels,channels,cli]
        [--out FILE]"""
@@ -37,6 +39,7 @@ sys.path.insert(0, ROOT)
 import avsep_amd as P  # noqa: E402
 from avsep_amd import resample as RS  # noqa: E402
 from avsep_amd import separate as S  # noqa: E402
+from avsep_amd import wavio as W  # noqa: E402
 
 HBM_PEAK = 8.0e12
 MODEL_RATE = 11025
@@ -72,13 +75,16 @@ def kernel_cases(seconds, dev, reps, cpu_reps):
     rng = np.random.default_rng(0)
     cases = {}
 
-    def add(name, x_np, rate_in, rate_out, in_ch, out_s16, cpu_fn):
+    def add(name, x_np, rate_in, rate_out, in_ch, out_fmt, cpu_fn):
         up, down = RS.rational(rate_in, rate_out)
         filt = RS.filter_table(up, down, dev)
         x = torch.from_numpy(x_np).to(dev)
-        y = P.kernels.resample_poly(x, filt, up, down, in_ch, out_s16)
+        if in_ch:                                                        # 16-bit frames as the bytes they are
+            x = x.view(torch.uint8).reshape(-1)
+        in_fmt = "s16" if in_ch else "f32"
+        y = P.kernels.resample_poly(x, filt, up, down, in_ch, in_fmt, out_fmt)
         nbytes = x.numel() * x.element_size() + y.numel() * y.element_size() + filt.numel() * 4
-        ms = median_ms(lambda: P.kernels.resample_poly(x, filt, up, down, in_ch, out_s16), reps)
+        ms = median_ms(lambda: P.kernels.resample_poly(x, filt, up, down, in_ch, in_fmt, out_fmt), reps)
         cpu_ms = cpu_median_ms(cpu_fn, cpu_reps)
         cases[name] = {"up": up, "down": down, "taps_per_output": -(-(20 * max(up, down) + 1) // up), "rows": y.shape[0],
                        "samples_in": x_np.shape[0] if in_ch else x_np.shape[1], "samples_out": y.shape[1], "kernel_ms": ms,
@@ -89,15 +95,15 @@ def kernel_cases(seconds, dev, reps, cpu_reps):
               f"{100 * c['share_of_hbm_peak']:.1f}% of 8 TB/s), scipy on this CPU {cpu_ms:.0f} ms ({cpu_ms / ms:.0f} x)", flush=True)
 
     pcm = rng.integers(-20000, 20000, size=(int(seconds * 44100), 2)).astype(np.int16)
-    add("pcm_stereo_44100_to_11025", pcm, 44100, MODEL_RATE, 2, False,
+    add("pcm_stereo_44100_to_11025", pcm, 44100, MODEL_RATE, 2, "f32",
         lambda: resample_poly(pcm.astype(np.float64).mean(1) / 32768.0, 1, 4))
     mono = (rng.random((1, int(seconds * 48000)), dtype=np.float32) * 2 - 1) * 0.5
     mono64 = mono[0].astype(np.float64)
-    add("f32_mono_48000_to_11025", mono, 48000, MODEL_RATE, 0, False, lambda: resample_poly(mono64, 147, 640))
+    add("f32_mono_48000_to_11025", mono, 48000, MODEL_RATE, 0, "f32", lambda: resample_poly(mono64, 147, 640))
     src = (rng.random((2, int(seconds * MODEL_RATE)), dtype=np.float32) * 2 - 1) * 0.5
     src64 = src.astype(np.float64)
-    add("two_sources_11025_to_44100_s16", src, MODEL_RATE, 44100, 0, True, lambda: resample_poly(src64, 4, 1, axis=1))
-    add("two_sources_11025_to_48000_s16", src, MODEL_RATE, 48000, 0, True, lambda: resample_poly(src64, 640, 147, axis=1))
+    add("two_sources_11025_to_44100_s16", src, MODEL_RATE, 44100, 0, "s16", lambda: resample_poly(src64, 4, 1, axis=1))
+    add("two_sources_11025_to_48000_s16", src, MODEL_RATE, 48000, 0, "s16", lambda: resample_poly(src64, 640, 147, axis=1))
 
     def add_fn(name, fn, rate_in, rate_out, nbytes_in, like):
         """A *_frames row beside the 16-bit row ``like``: the same samples in another format."""
@@ -118,8 +124,8 @@ def kernel_cases(seconds, dev, reps, cpu_reps):
         del raw
     srcs = torch.from_numpy(src).to(dev)
     for rate in (44100, 48000):
-        for fmt in ("s24", "f32"):
-            add_fn(f"two_sources_11025_to_{rate}_{fmt}", lambda: [RS.join_frames(srcs[n:n + 1], MODEL_RATE, rate, fmt) for n in range(2)],
+        for fmt in ("s16_per_stem", "s24", "f32"):
+            add_fn(f"two_sources_11025_to_{rate}_{fmt}", lambda: [RS.join_frames(srcs[n:n + 1], MODEL_RATE, rate, fmt[:3]) for n in range(2)],
                    MODEL_RATE, rate, srcs.numel() * 4, f"two_sources_11025_to_{rate}_s16")
     return cases
 
@@ -210,13 +216,13 @@ def cli_stages(seconds, dev, reps, frame_size=224):
                 torch.cuda.synchronize()
                 ms[name] = (time.perf_counter() - t0) * 1e3
                 return r
-            pcm = stage("read_wav_pcm", lambda: S.read_wav_pcm(path)[0])
+            pcm = stage("read_wav_pcm", lambda: W.read_frames(path)[0])
             up = stage("upload_pcm", lambda: torch.from_numpy(pcm).to(dev))
-            wav = stage("resample_in", lambda: RS.resample_pcm(up, rate, args.audRate))
+            wav = stage("resample_in", lambda: RS.resample_frames(up, "s16", 1, rate, args.audRate))
             out = stage("separate_long", lambda: S.separate_long(nets, wav, frames, args))
-            s16 = stage("resample_out", lambda: RS.resample(out["wavs"], args.audRate, rate, out_s16=True))
-            host = stage("download_s16", lambda: s16.cpu().numpy())
-            stage("write_wav_pcm", lambda: [S.write_wav_pcm(os.path.join(d, f"source{n}.wav"), w, rate) for n, w in enumerate(host)])
+            s16 = stage("resample_out", lambda: [RS.join_frames(w[None], args.audRate, rate, "s16") for w in out["wavs"]])
+            host = stage("download_s16", lambda: [w.cpu().numpy() for w in s16])
+            stage("write_wav_pcm", lambda: [W.write_frames(os.path.join(d, f"source{n}.wav"), w, rate, 1, "s16") for n, w in enumerate(host)])
             ms["total"] = sum(ms.values())
             if it:
                 runs.append(ms)
