@@ -782,19 +782,61 @@ def _mwf_apply(xmag, xph, ymag, cov, reg):
     return out_mag, out_ph
 
 
-def mwf_cov(ymag, yph):
+MWF_MIN_SPAN, MWF_MAX_SPAN = 64, 4096     # avsep_mwf_*_tv: the span H, a multiple of 64
+
+
+def mwf_span_check(what, span):
+    """The rule of include/avsep.h for the span of the time-varying covariances; 0 is the time-invariant filter."""
+    if isinstance(span, bool) or not isinstance(span, int) or (span != 0 and not (
+            MWF_MIN_SPAN <= span <= MWF_MAX_SPAN and span % 64 == 0)):
+        raise lib.AvsepError(f"{what} takes the span as an int: 0 (one covariance for the whole recording) or a multiple of 64 "
+                             f"frames in {MWF_MIN_SPAN} ... {MWF_MAX_SPAN}, got {span!r}")
+    return span
+
+
+def mwf_centres(F, span):
+    """K of include/avsep.h: centres at frames 0, span, 2 span, ..., the last one at or past frame F - 1."""
+    return 1 if F == 1 else -(-(F - 1) // span) + 1
+
+
+def _mwf_cov_tv(ymag, yph, span):
+    """-> f32 [N, K, Fin, C, C, 2]"""
+    N, Cc, Fin, F = ymag.shape
+    nbytes = lib.load().avsep_mwf_tv_workspace_bytes(N, Cc, Fin, F, span)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=ymag.device)
+    cov = _f32((N, mwf_centres(F, span), Fin, Cc, Cc, 2), ymag)
+    call("avsep_mwf_cov_tv", ptr(ymag), ptr(yph), int(yph.dim() == 4), N, Cc, Fin, F, span, ptr(cov), ptr(ws), nbytes)
+    return cov
+
+
+def _mwf_apply_tv(xmag, xph, ymag, cov, span, reg):
+    N, Cc, Fin, F = ymag.shape
+    out_mag, out_ph = _f32((N, Cc, Fin, F), ymag), _f32((N, Cc, Fin, F), ymag)
+    call("avsep_mwf_apply_tv", ptr(xmag), ptr(xph), ptr(ymag), ptr(cov), N, Cc, Fin, F, span, reg, ptr(out_mag), ptr(out_ph))
+    return out_mag, out_ph
+
+
+def mwf_cov(ymag, yph, span=0):
     """Spatial covariance of every source per bin row: ymag [N,C,Fin,F], yph [C,Fin,F] (one phase for all sources) or
     [N,C,Fin,F] -> complex64 [N,Fin,C,C], R_n[f] = sum_t Y Y^H / max(sum_t mean_c |Y|^2, FLT_MIN) (trace C, or 0 for a source
-    that is silent in the row).  Fixed summation order: the same bits on every call."""
+    that is silent in the row).  Fixed summation order: the same bits on every call.
+    ``span`` > 0 (a multiple of 64 frames in 64 ... 4096): one covariance per centre k * span, both sums weighted by the hat
+    max(0, 1 - |t - k span| / span) -> complex64 [N,K,Fin,C,C], K = ceil((F - 1) / span) + 1 (a source that is silent over a
+    centre's support has 0 there)."""
     _mwf_check("mwf_cov", ymag, yph)
+    if mwf_span_check("mwf_cov", span):
+        return torch.view_as_complex(_mwf_cov_tv(ymag.contiguous(), yph.contiguous(), span))
     return torch.view_as_complex(_mwf_cov(ymag.contiguous(), yph.contiguous()))
 
 
-def mwf(xmag, xph, ymag, yph, iterations=1, reg=1e-3):
+def mwf(xmag, xph, ymag, yph, iterations=1, reg=1e-3, span=0):
     """Multichannel Wiener filter (include/avsep.h): xmag, xph [C,Fin,F] the channels' STFT, ymag [N,C,Fin,F] the source
     images' magnitudes (mask_stitch), yph their phase, [C,Fin,F] shared or [N,C,Fin,F] -> (mag, phase), both
     [N,C,Fin,F], after ``iterations`` passes (each pass re-estimates the covariances from the previous pass's output).
-    ``reg`` is relative to each bin's power: the sources sum to X / (1 + ~reg)."""
+    ``reg`` is relative to each bin's power: the sources sum to X / (1 + ~reg).
+    ``span`` = 0: one covariance per source and bin row for the whole recording.  ``span`` > 0 (a multiple of 64 frames in
+    64 ... 4096): time-varying covariances, one per centre k * span, and every frame is filtered with the blend of the two
+    centres next to it; for sources that move through the image."""
     N, Cc, Fin, F = _mwf_check("mwf", ymag, yph)
     lib.require_gpu(xmag)
     lib.require_gpu(xph)
@@ -804,9 +846,13 @@ def mwf(xmag, xph, ymag, yph, iterations=1, reg=1e-3):
     iterations, reg = int(iterations), float(reg)
     if iterations < 1 or not reg >= 0.0:
         raise lib.AvsepError(f"mwf needs iterations >= 1 and reg >= 0, got {iterations} and {reg}")
+    mwf_span_check("mwf", span)
     xmag, xph, mag, ph = xmag.contiguous(), xph.contiguous(), ymag.contiguous(), yph.contiguous()
     for _ in range(iterations):
-        mag, ph = _mwf_apply(xmag, xph, mag, _mwf_cov(mag, ph), reg)
+        if span:
+            mag, ph = _mwf_apply_tv(xmag, xph, mag, _mwf_cov_tv(mag, ph, span), span, reg)
+        else:
+            mag, ph = _mwf_apply(xmag, xph, mag, _mwf_cov(mag, ph), reg)
     return mag, ph
 
 

@@ -87,6 +87,9 @@ SIGNATURES = {
     "avsep_mwf_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "avsep_mwf_cov": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "avsep_mwf_apply": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "avsep_mwf_tv_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "avsep_mwf_cov_tv": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "avsep_mwf_apply_tv": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "avsep_misi_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "avsep_misi": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "avsep_localise_maps": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

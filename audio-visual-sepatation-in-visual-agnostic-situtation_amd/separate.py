@@ -24,6 +24,8 @@ also applied to each channel's own magnitude (``avsep_mask_stitch`` with C chann
 so a stereo file gives stereo sources.  ``wiener=k`` (``--wiener k``) then runs k passes of a multichannel Wiener filter
 (``kernels.mwf``) over those source images: the masked channels give every source a spatial covariance per bin, and each
 time-frequency bin of the mixture is filtered again with them, so a source keeps its own place in the stereo image.
+``wiener_span=H`` (``--wiener_span H``) estimates those covariances locally, around centres H frames apart, and blends the
+two next to every frame: for sources that move through the image over the recording.
 
 A masked magnitude on the mixture's phase is not the STFT of any signal.  ``phase_iters=k`` (``--phase_iters k``) runs k
 mixture-consistent phase iterations (MISI, ``kernels.Stft.misi``) in place of the one inverse transform: every stem gets a
@@ -99,7 +101,7 @@ def _visual_features(net_frame, frames, args, Kw, batch):
 
 
 def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None,
-                  wiener=0, phase_iters=0, clamp=True):
+                  wiener=0, phase_iters=0, clamp=True, wiener_span=0):
     """Separate one recording ``wav`` [L] (on the GPU, L >= args.stft_frame; several recordings: one call each).
 
     nets: (net_sound, net_frame), both in eval() — train-mode BatchNorm over the windows of one recording is never what
@@ -121,8 +123,15 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
     above, bit for bit.  With wiener >= 1 the channel stitch uses the SOFT mask whatever ``args.binary_mask`` says: the
     filter weighs every source by the power its mask leaves it, and a thresholded mask has thrown that posterior away.
     Each source then gets its own phase (one iSTFT over N*C rows), and the sources of a bin sum to the mixture over
-    1 + ~1e-3, not to the mixture exactly.  The covariances are one per bin row for the whole recording (time-invariant).
-    "wavs", "perms", "masks" and "lin_masks" do not depend on ``wiener``.
+    1 + ~1e-3, not to the mixture exactly.  The covariances are one per bin row for the whole recording (time-invariant)
+    unless ``wiener_span`` says otherwise.  "wavs", "perms", "masks" and "lin_masks" do not depend on ``wiener``.
+
+    wiener_span: int, 0 or a multiple of 64 frames in 64 ... 4096; needs wiener >= 1.  0 is the time-invariant filter above,
+    bit for bit.  With H > 0 every pass estimates one covariance per bin row and centre (frames 0, H, 2H, ...), each from
+    the frames within H of it under a triangular weight, and filters frame t with the blend of the two centres next to it
+    (``kernels.mwf(span=H)``): a source that moves through the image is followed instead of smeared over its path.  Fewer
+    frames go into each estimate, so sources that stay put lose a few tenths of a dB; 64 ... 128 frames suit pans that cross
+    the image within some hundreds of frames.  "wavs", "perms", "masks" and "lin_masks" do not depend on it.
 
     phase_iters: int in 0 ... 32, mixture-consistent phase iterations (``kernels.Stft.misi``) in place of the one inverse
     transform.  0 is the path above, bit for bit.  With k >= 1 "wavs" are the stitched magnitudes after k passes against
@@ -141,6 +150,9 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
         raise AvsepError(f"separate_long takes phase_iters as an int in 0 ... {MAX_PHASE_ITERS} (mixture-consistent phase iterations), got {phase_iters!r}")
     if wiener and channels is None:
         raise AvsepError("separate_long(wiener=...) filters the recording's channels: pass channels= as well")
+    K.mwf_span_check("separate_long(wiener_span=...)", wiener_span)
+    if wiener_span and not wiener:
+        raise AvsepError("separate_long(wiener_span=...) is the span of the Wiener filter's covariances: it needs wiener >= 1")
     lib.require_gpu(wav)
     if wav.dim() != 1 or wav.numel() < args.stft_frame:
         raise AvsepError(f"separate_long takes one recording [L] with L >= stft_frame, got {tuple(wav.shape)}")
@@ -206,7 +218,9 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
             Cc, Fin, Fr = mag_c.shape
             mags_c, _ = K.mask_stitch(masks, starts_t, perms.to(dev), mag_c, binary and not wiener, getattr(args, "mask_thres", 0.5))
             phases_c = phase_c                                           # shared by the sources
-            if wiener:                                                   # soft source images in, one phase per source out
+            if wiener and wiener_span:                                   # the same, with covariances that follow the sources
+                mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener, span=wiener_span)
+            elif wiener:                                                 # soft source images in, one phase per source out
                 mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener)
             if phase_iters:                                              # every channel is the mixture of its N stems
                 channel_wavs = plan.misi(channels[:, :out_len], mags_c, phases_c, phase_iters)
@@ -324,6 +338,10 @@ def build_parser():
     p.add_argument("--wiener", type=int, default=0, metavar="K",
                    help="with --channels keep: K passes (0 ... 8) of a multichannel Wiener filter over the masked channels, "
                         "so every source keeps its own place in the stereo image (0, the default: the mask on every channel)")
+    p.add_argument("--wiener_span", type=int, default=0, metavar="FRAMES",
+                   help="with --wiener: estimate the spatial covariances locally, around centres FRAMES STFT frames apart (a "
+                        "multiple of 64 in 64 ... 4096), for sources that move through the image (0, the default: one "
+                        "covariance for the whole recording)")
     p.add_argument("--phase_iters", type=int, default=0, metavar="K",
                    help="K mixture-consistent phase iterations (0 ... 32) in place of the one inverse transform: every source "
                         "gets a phase of its own (0, the default: the mixture's phase; no gain with --binary_mask 1)")
@@ -353,6 +371,10 @@ def parse_args(argv=None):
         raise SystemExit(f"--phase_iters takes 0 ... {MAX_PHASE_ITERS} passes, got {args.phase_iters}")
     if args.wiener and args.channels != "keep":
         raise SystemExit("--wiener filters the file's channels: it needs --channels keep")
+    if args.wiener_span and not (K.MWF_MIN_SPAN <= args.wiener_span <= K.MWF_MAX_SPAN and args.wiener_span % 64 == 0):
+        raise SystemExit(f"--wiener_span takes 0 or a multiple of 64 frames in {K.MWF_MIN_SPAN} ... {K.MWF_MAX_SPAN}, got {args.wiener_span}")
+    if args.wiener_span and not args.wiener:
+        raise SystemExit("--wiener_span is the span of the Wiener filter's covariances: it needs --wiener K with K >= 1")
     if args.peak is not None and not args.peak <= 0.0:
         raise SystemExit(f"--peak takes a true-peak ceiling of at most 0 dBTP, got {args.peak}")
     if args.loudness is not None and not -70.0 <= args.loudness <= 0.0:
@@ -444,7 +466,7 @@ def cli(argv=None):
     levelled = args.peak is not None or args.loudness is not None
     out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
                         stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener,
-                        phase_iters=args.phase_iters, clamp=not levelled)
+                        phase_iters=args.phase_iters, clamp=not levelled, wiener_span=args.wiener_span)
     os.makedirs(args.out, exist_ok=True)
     out_rate = rate if args.out_rate == "file" else args.audRate
     report = None
@@ -470,6 +492,9 @@ def cli(argv=None):
         kept += f", gain {report['gain_db']:+.2f} dB (limited by {report['limited_by']})"
     if args.wiener:
         kept += f", multichannel Wiener filter x{args.wiener}"
+        if args.wiener_span:
+            kept += (f" with local covariances every {args.wiener_span} frames "
+                     f"({args.wiener_span * args.stft_hop / args.audRate:.2f} s)")
     if args.phase_iters:
         kept += f", phase iterations x{args.phase_iters}"
     print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav{kept}")

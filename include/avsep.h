@@ -488,6 +488,28 @@ int avsep_mwf_apply(const float* xmag, const float* xph, const float* ymag, cons
                     int32_t F, float reg, float* out_mag, float* out_phase, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The same filter with time-varying spatial covariances, for sources that move through the image (csrc/mwf.hip, DESIGN.md
+ * §24 beside §16).  H is the span in frames: a multiple of 64 with 64 <= H <= 4096.  Centres sit at frames k H,
+ * k = 0 ... K - 1, K = ceil((F - 1) / H) + 1 (K = 1 for F = 1); frame t lies in segment s = t / H at u = (t - s H) / H, and
+ * centre s weighs it with 1 - u, centre s + 1 with u: the hat w_k(t) = max(0, 1 - |t - k H| / H).  Steps 1, 4 and 5 are those
+ * above; in their place steps 2 and 3 read
+ *   2'. R_n[k,f] = (sum_t w_k(t) Y_n Y_n^H) / max(sum_t w_k(t) v_n[f,t], FLT_MIN)     a source silent over the support: R = 0
+ *   3'. R_n[f,t] = (1 - u) R_n[s,f] + u R_n[s + 1,f], used for R_n[f] in S and in Y_n' = v_n R_n[f,t] z
+ * The limits on N, C, Fin and F, the 64-bit offsets and the no-atomics rule are those above; every sum has a fixed order that
+ * depends on (F, H) alone (a wave walks one segment of H frames), so a second call gives the same bits.
+ * avsep_mwf_cov_tv:   steps 1-2'.  ymag, yph and phase_per_source as avsep_mwf_cov.  cov: f32 [N, K, Fin, C, C, 2], every
+ *   R_n[k,f] in full as (re, im), diagonal imaginary parts exactly 0, upper triangle the exact conjugate of the lower.
+ *   ws: avsep_mwf_tv_workspace_bytes(N, C, Fin, F, H) bytes, two slabs of C (C + 1) + 1 floats per (segment, source, bin row).
+ * avsep_mwf_apply_tv: steps 3'-5 from that cov with the same H; out_mag / out_phase [N, C, Fin, F], not aliasing ymag; reg >= 0.
+ * An H that is no multiple of 64 or outside 64 ... 4096, anything outside the limits above, a null pointer or a workspace that
+ * is too small is AVSEP_ERR_ARG before any launch (the workspace query returns 0). */
+size_t avsep_mwf_tv_workspace_bytes(int32_t N, int32_t C, int32_t Fin, int32_t F, int32_t H);
+int avsep_mwf_cov_tv(const float* ymag, const float* yph, int32_t phase_per_source, int32_t N, int32_t C, int32_t Fin, int32_t F,
+                     int32_t H, float* cov, float* ws, size_t ws_bytes, avsep_stream_t stream);
+int avsep_mwf_apply_tv(const float* xmag, const float* xph, const float* ymag, const float* cov, int32_t N, int32_t C, int32_t Fin,
+                       int32_t F, int32_t H, float reg, float* out_mag, float* out_phase, avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Mixture-consistent phase iterations (csrc/misi.hip; MISI, Gunawan & Sen 2010): give every stem of a mixture a phase of its
  * own.  R = N * G rows: N sources, G groups; a group is the set of N rows that sum to one mixture (G = 1 for mono stems,
  * G = C for channel stems).  mix [G, out_len] with out_len = hop * (frames - 1); mag [N, G, bins, frames] the target

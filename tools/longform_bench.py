@@ -14,6 +14,11 @@ With --wiener K as well (4) that call runs K passes of the multichannel Wiener f
 split gains mwf_cov and mwf_apply; and kernels.mwf alone (one pass on the soft source images of the C channels) against the
 same result composed on the device from torch ops (torch.polar, einsum, torch.linalg.solve on complex64), the two timed in
 alternation: time, algorithmic bytes, share of the HBM peak, outputs compared as complex numbers.
+With --wiener_span H as well (4b) the audio-visual call runs those passes with time-varying covariances
+(separate_long(wiener_span=H)): the stage split gains mwf_cov_tv and mwf_apply_tv; and one pass of kernels.mwf(span=H) is
+event-timed against one time-invariant pass of kernels.mwf on the same inputs, the two in alternation: time, algorithmic
+bytes (the invariant pass's plus the slab and covariance traffic) and share of the HBM peak.  --wiener_span_rows runs
+only that comparison, without the model: C = 2 and 8 channels, N = 2, spans 64 ... 4096, on a spectrogram as long as --seconds.
 With --phase_iters K (5) the audio-visual call runs K mixture-consistent phase iterations (separate_long(phase_iters=K), with
 the channels and the Wiener passes of the options above when they are given): wall time, and the split gains misi (and
 misi_channels); and one kernels.Stft.misi call of K passes on the recording at N = 2, G = 1 and N = 2, G = 2 against the same
@@ -21,7 +26,7 @@ result composed on the device from Stft.istft, torch arithmetic and Stft.stft, t
 events; the two kernels the call adds (overlap-add + consistency, re-phase) are timed per launch from a profiler trace of
 one call: algorithmic bytes per pass and their share of the HBM peak.
 Every number is a median over --reps runs after warm-up; the last line is one JSON object.
-Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20] [--channels C [--wiener K]] [--phase_iters K]"""
+Usage: python tools/longform_bench.py [--seconds 600] [--reps 5] [--kernel-reps 20] [--channels C [--wiener K [--wiener_span H]]] [--phase_iters K]"""
 import argparse
 import json
 import os
@@ -106,7 +111,7 @@ class StageClock:
         self._undo = []
 
 
-def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, wiener=0, phase_iters=0):
+def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, wiener=0, phase_iters=0, wiener_span=0):
     K = P.kernels
     clk = StageClock()
     # with channels the second call of each transform is the channel path's: C rows in, N*C rows out
@@ -115,6 +120,8 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, w
     clk.wrap(K.Stft, "misi", "misi" if channels is None else ["misi", "misi_channels"])
     clk.wrap(K, "_mwf_cov", "mwf_cov")
     clk.wrap(K, "_mwf_apply", "mwf_apply")
+    clk.wrap(K, "_mwf_cov_tv", "mwf_cov_tv")
+    clk.wrap(K, "_mwf_apply_tv", "mwf_apply_tv")
     clk.wrap(K, "window_prepare", "window_prepare")
     clk.wrap(K, "window_agreement", "agreement")
     clk.wrap(S, "align_permutations", "agreement")
@@ -124,7 +131,8 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, w
     try:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener, phase_iters=phase_iters)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener, phase_iters=phase_iters,
+                        wiener_span=wiener_span)
         torch.cuda.synchronize()
         total = (time.perf_counter() - t0) * 1e3
     finally:
@@ -134,17 +142,18 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, w
     return clk.ms
 
 
-def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps, channels=None, wiener=0, phase_iters=0):
+def whole_runs(nets, wav, frames, args, use_vis, stride, batch, reps, channels=None, wiener=0, phase_iters=0, wiener_span=0):
     """Median wall time of the unwrapped call, and the median per-stage split of wrapped calls."""
     def once():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener, phase_iters=phase_iters)
+        S.separate_long(nets, wav, frames, args, use_vis, stride, batch, channels=channels, wiener=wiener, phase_iters=phase_iters,
+                        wiener_span=wiener_span)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3
     once()                                                               # warm-up: code objects, conv plans
     wall = statistics.median(once() for _ in range(reps))
-    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch, channels, wiener, phase_iters) for _ in range(reps)]
+    splits = [staged_run(nets, wav, frames, args, use_vis, stride, batch, channels, wiener, phase_iters, wiener_span) for _ in range(reps)]
     split = {k: statistics.median(s.get(k, 0.0) for s in splits) for k in splits[0]}
     return wall, split
 
@@ -265,6 +274,46 @@ def mwf_row(mag_c, phase_c, masks_lin, reps):
             "composed_over_fused": ms_c / ms_f, "max_rel_diff_vs_composed": diff}
 
 
+def mwf_tv_row(mag_c, phase_c, masks_lin, span, reps):
+    """One pass of kernels.mwf(span=H) (time-varying covariances) against one time-invariant pass of kernels.mwf on the
+    same soft source images, the two timed in alternation."""
+    K = P.kernels
+    Cc, Fin, F = mag_c.shape
+    N = masks_lin.shape[0]
+    ymag = (masks_lin[:, None] * mag_c[None]).contiguous()
+    inv_bytes = 4 * Fin * F * (N * Cc + Cc + 2 * Cc + N * Cc + 2 * N * Cc)
+    # on top of the invariant pass: two slabs of C (C + 1) + 1 floats per (segment, source, row) written once and read once,
+    # and the K covariances per (source, row) written once and read once
+    segments, centres = -(-F // span), K.mwf_centres(F, span)
+    nbytes = inv_bytes + 2 * 4 * N * Fin * (segments * 2 * (Cc * (Cc + 1) + 1) + centres * Cc * Cc * 2)
+    ms_tv, ms_inv = alternating_median_ms([lambda: K.mwf(mag_c, phase_c, ymag, phase_c, span=span),
+                                           lambda: K.mwf(mag_c, phase_c, ymag, phase_c)], reps)
+    return {"channels": Cc, "sources": N, "span": span, "local_ms": ms_tv, "invariant_ms": ms_inv, "local_over_invariant": ms_tv / ms_inv,
+            "algorithmic_bytes": nbytes, "invariant_algorithmic_bytes": inv_bytes, "local_bytes_per_s": nbytes / (ms_tv * 1e-3),
+            "share_of_hbm_peak": nbytes / (ms_tv * 1e-3) / HBM_PEAK,
+            "invariant_share_of_hbm_peak": inv_bytes / (ms_inv * 1e-3) / HBM_PEAK}
+
+
+def wiener_span_rows(seconds, reps, dev):
+    """mwf_tv_row over channels and spans on a random spectrogram of ``seconds`` at 11 025 Hz (Fin = 512, hop 256)."""
+    Fin, F, N = 512, int(round(seconds * 11025)) // 256 + 1, 2
+    rows = []
+    with torch.no_grad():
+        for Cc in (2, 8):
+            mag = torch.rand(Fin, F, device=dev) * 30
+            lin = torch.rand(N, Fin, F, device=dev)
+            ph_c = (torch.rand(Cc, Fin, F, device=dev) * 2 - 1) * 3.14159
+            mag_r = (mag[None] * (0.5 + torch.rand(Cc, Fin, F, device=dev))).contiguous()
+            for span in (64, 128, 256, 1024, 4096):
+                r = mwf_tv_row(mag_r, ph_c, lin, span, reps)
+                rows.append(r)
+                print(f"mwf C={Cc} N={N} F={F}, covariances every {span} frames: {r['local_ms']:.3f} ms ({100 * r['share_of_hbm_peak']:.0f}% of "
+                      f"8 TB/s on {r['algorithmic_bytes'] / 1e6:.0f} MB); time-invariant pass {r['invariant_ms']:.3f} ms "
+                      f"({100 * r['invariant_share_of_hbm_peak']:.0f}%): {r['local_over_invariant']:.2f} x", flush=True)
+            del mag, lin, ph_c, mag_r
+    return rows
+
+
 def composed_misi(plan, mix, A, phase, passes):
     """The passes from the older entry points: Stft.istft, torch arithmetic, Stft.stft (magnitude and angle written, the
     magnitude thrown away, the angle read back through the inverse)."""
@@ -339,14 +388,26 @@ def main():
     ap.add_argument("--frame-size", type=int, default=224)
     ap.add_argument("--channels", type=int, default=0, help="also measure the call that keeps C channels (0: skip)")
     ap.add_argument("--wiener", type=int, default=0, help="with --channels: also K passes of the multichannel Wiener filter (0: skip)")
+    ap.add_argument("--wiener_span", type=int, default=0, help="with --wiener: also the passes with time-varying covariances H frames apart "
+                                                               "(a multiple of 64 in 64 ... 4096; 0: skip)")
+    ap.add_argument("--wiener_span_rows", action="store_true", help="only one local against one time-invariant pass of kernels.mwf, "
+                                                                    "C = 2 and 8, spans 64 ... 4096 (no model)")
     ap.add_argument("--phase_iters", type=int, default=0, help="also K mixture-consistent phase iterations: the call and Stft.misi alone (0: skip)")
     ap.add_argument("--mwf-reps", type=int, default=5, help="timed repetitions of the mwf row (the composition is slow)")
     o = ap.parse_args()
     if o.wiener and o.channels < 1:
         raise SystemExit("--wiener measures the channel path: pass --channels C as well")
+    if o.wiener_span and not o.wiener:
+        raise SystemExit("--wiener_span measures the Wiener passes: pass --wiener K as well")
+    if o.wiener_span and not (64 <= o.wiener_span <= 4096 and o.wiener_span % 64 == 0):
+        raise SystemExit(f"--wiener_span takes a multiple of 64 frames in 64 ... 4096, got {o.wiener_span}")
     if not torch.cuda.is_available():
         raise SystemExit("longform_bench measures on an MI355X; there is nothing to report without one")
     dev = torch.device("cuda", 0)
+    if o.wiener_span_rows:
+        torch.manual_seed(0)
+        print(json.dumps({"seconds": o.seconds, "mwf_tv_rows": wiener_span_rows(o.seconds, o.mwf_reps, dev)}), flush=True)
+        return
     args = P.arguments.train_music_args()
     args.stft_pad_mode = "reflect"
     torch.manual_seed(0)
@@ -382,10 +443,19 @@ def main():
             print(f"AV, {o.channels} channels kept, Wiener x{o.wiener}: {wall:9.1f} ms = {audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
             for k, v in split.items():
                 print(f"    {k:16s} {v:9.2f} ms", flush=True)
+        if o.wiener_span:
+            wall, split = whole_runs(nets, wav, frames, args, True, o.stride, o.batch, o.reps, channels=ch, wiener=o.wiener,
+                                     wiener_span=o.wiener_span)
+            result["av_channels_wiener_span"] = {"channels": o.channels, "wiener": o.wiener, "wiener_span": o.wiener_span, "wall_ms": wall,
+                                                 "audio_seconds_per_second": audio_s / (wall * 1e-3), "split_ms": split}
+            print(f"AV, {o.channels} channels kept, Wiener x{o.wiener}, covariances every {o.wiener_span} frames: {wall:9.1f} ms = "
+                  f"{audio_s / (wall * 1e-3):8.1f} x real time", flush=True)
+            for k, v in split.items():
+                print(f"    {k:16s} {v:9.2f} ms", flush=True)
     if o.phase_iters:
         ch = (wav[None] * torch.linspace(1.0, 0.5, o.channels, device=dev)[:, None]).contiguous() if o.channels > 0 else None
         wall, split = whole_runs(nets, wav, frames, args, True, o.stride, o.batch, o.reps, channels=ch, wiener=o.wiener,
-                                 phase_iters=o.phase_iters)
+                                 phase_iters=o.phase_iters, wiener_span=o.wiener_span)
         result["av_phase_iters"] = {"channels": o.channels, "wiener": o.wiener, "phase_iters": o.phase_iters, "wall_ms": wall,
                                     "audio_seconds_per_second": audio_s / (wall * 1e-3), "split_ms": split}
         print(f"AV, phase iterations x{o.phase_iters}" + (f", {o.channels} channels kept" if o.channels else "")
@@ -427,8 +497,14 @@ def main():
             print(f"mwf C={o.channels} N={args.num_mix}, one pass: {r['fused_ms']:.3f} ms ({r['fused_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
                   f"{100 * r['share_of_hbm_peak']:.0f}% of 8 TB/s); composed from torch ops {r['composed_ms']:.3f} ms "
                   f"({r['composed_over_fused']:.1f} x); max |diff| / max |ref| {r['max_rel_diff_vs_composed']:.2e}", flush=True)
+            if o.wiener_span:
+                r = result["kernels"]["mwf_tv"] = mwf_tv_row(mag_r, ph_c, lin, o.wiener_span, o.mwf_reps)
+                print(f"mwf C={o.channels} N={args.num_mix}, one pass with covariances every {o.wiener_span} frames: {r['local_ms']:.3f} ms "
+                      f"({r['local_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, {100 * r['share_of_hbm_peak']:.0f}% of 8 TB/s); "
+                      f"time-invariant pass {r['invariant_ms']:.3f} ms ({100 * r['invariant_share_of_hbm_peak']:.0f}%): "
+                      f"{r['local_over_invariant']:.2f} x", flush=True)
     for k, r in result["kernels"].items():
-        if k in ("mask_stitch_channels", "mwf"):
+        if k in ("mask_stitch_channels", "mwf", "mwf_tv"):
             continue
         if "composed_ms" in r:
             print(f"{k}: fused {r['fused_ms']:.3f} ms ({r['fused_bytes_per_s'] / 1e12:.2f} TB/s algorithmic, "
