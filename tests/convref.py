@@ -26,6 +26,60 @@ ACT_NONE, ACT_RELU, ACT_LRELU02 = 0, 1, 2
 F64 = torch.float64
 LRELU_SLOPE = float(torch.tensor(0.2, dtype=torch.float32))     # the kernels' 0.2f
 
+# ---- the gate's tolerances, shared by test_gpu_benched_conv_calls.py (where they were measured) and test_gpu_conv_variants.py
+WINOGRAD = ("wino4_kernel", "wino_kernel", "winow4_kernel", "winow_kernel")
+CEIL_DIRECT, CEIL_WINO = 2e-5, 1.2e-4
+# tau per (family, precision): 4x the measured worst ratio, at most the ceiling; families not listed take their ceiling
+TAU = {
+    ("conv3x3_kernel", "f32"): 2.7e-6,       # fwd 6.52e-7, dgrad 6.26e-7
+    ("convbf_kernel", "bf16"): CEIL_DIRECT,  # fwd 1.99e-5, dgrad 1.99e-5: B16 outputs, the half-ulp rounding term dominates
+    ("head_fwd_kernel", "f32"): 3.9e-6,      # 9.55e-7
+    ("head_fwd_kernel", "bf16"): 3.9e-6,     # 9.68e-7
+    ("head_dgrad_kernel", "f32"): CEIL_DIRECT,   # dgrad_up2x 1.86e-5
+    ("head_dgrad_kernel", "bf16"): CEIL_DIRECT,  # dgrad_up2x 1.86e-5
+    ("head_wgrad_kernel", "f32"): 3.8e-6,    # 9.46e-7
+    ("head_wgrad_kernel", "bf16"): 3.8e-6,   # 9.31e-7
+    ("igemm_kernel<fwd>", "f32"): 1.7e-6,    # 4.14e-7
+    ("igemm_kernel<fwd>", "bf16"): 1.7e-6,   # 4.23e-7
+    ("igemm_kernel<dgrad>", "f32"): 8.0e-6,  # 1.98e-6
+    ("igemm_kernel<dgrad>", "bf16"): 7.1e-6, # 1.75e-6
+    ("igemm_kernel<wgrad>", "f32"): 4.4e-6,  # 1.10e-6
+    ("igemm_kernel<wgrad>", "bf16"): 6.6e-8, # 1.64e-8
+    ("smallci_dgrad", "f32"): 2.1e-6,        # 5.23e-7
+    ("smallci_dgrad", "bf16"): 2.2e-6,       # 5.33e-7
+    ("smallci_wgrad_kernel", "f32"): 6.5e-8, # 1.61e-8
+    ("wgrad3x3_kernel", "f32"): 1.2e-7,      # 2.80e-8
+    ("wgrad3x3_kernel", "bf16"): 2.5e-6,     # 6.18e-7
+    ("wgrad4d_kernel", "f32"): 1.9e-6,       # 4.76e-7
+    ("wgrad4d_kernel", "bf16"): 1.5e-6,      # 3.61e-7
+    ("wgradb_kernel", "bf16"): 4.2e-6,       # 1.04e-6
+    ("wino4_kernel", "f32"): 7.3e-5,         # fwd 3.42e-6, dgrad 1.64e-5, dgrad_act 1.80e-5 (tile absref)
+    ("wino_kernel", "f32"): 6.2e-7,          # fwd 1.41e-7, dgrad 1.54e-7 (tile absref)
+    ("winow4_kernel", "f32"): 5.7e-5,        # wgrad 1.41e-5 (tile absref)
+}
+
+
+def tau_of(family, prec):
+    return TAU.get((family, prec), CEIL_WINO if family in WINOGRAD else CEIL_DIRECT)
+
+
+# Per (variant string, precision) entries of the variant gate (test_gpu_conv_variants.py) alone; the benched gate keeps TAU.
+# Same rule: 4x the measured worst ratio, at most the ceiling.  Both are N = 1 weight gradients that sum a few hundred
+# products in an fp32 MFMA accumulator.  Their benched entries were measured on sums of 10^4 ... 10^6 terms of either sign,
+# where |ref| << absref and the roundings of the partial sums average out; over a short sum an element whose terms mostly
+# share a sign has |ref| ~ absref, and ONE rounding of an fp32 result of that size is already 2^-24 = 5.96e-8 of absref, which
+# is 0.9 / 0.5 of the two benched values.  The misses were 1.5 and 2.4 times 2^-24 at elements of |ref| = 0.17 absref (6 and 13
+# ulps of the result, i.e. 0.8 and 1.6 ulps at the partial sums' size), and the same kernel on the same operands sits at
+# 7.4e-8 / 1.7e-7 under the other precision's entry: rounding.  A dropped or misplaced term would be ~absref / K = 1e-3.
+VARIANT_TAU = {
+    ("igemm_kernel<wgrad>", "bf16"): 3.6e-7,   # 8.86e-8: layer2.1x1s2 at N = 1 (K = 784), f32 kernel under AVSEP_ALGO_NO_BF16_KERNELS
+    ("wgrad3x3_kernel", "f32"): 5.8e-7,        # 1.44e-7: ragged18x30 at N = 1 (K = 540)
+}
+
+
+def tau_of_variant(variant, prec):
+    return VARIANT_TAU.get((variant, prec), tau_of(variant.split(":")[0], prec))
+
 
 class Geometry:
     """The geometry a Conv descriptor carries, for host tests that cannot build a kernels.Conv."""

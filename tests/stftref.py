@@ -8,7 +8,7 @@ Next to every value the reference returns the same linear map applied to absolut
 an fp32 evaluation in any summation order stays within  terms * 2^-24 * absref  of the exact value, whatever cancels.
 
 The gates.  One tau for every element, not fitted to the kernels: the project's ceiling for direct-form fp32 kernels,
-CEIL_DIRECT = 2e-5 of tests/test_gpu_benched_conv_calls.py (the fp32 worst case at K = 4096 terms is K * 2^-24 = 2.4e-4; the
+CEIL_DIRECT = 2e-5 of tests/convref.py (the fp32 worst case at K = 4096 terms is K * 2^-24 = 2.4e-4; the
 direct-form ratios measured there stay below 2e-6 up to K = 8192; the float32 numpy control of tests/test_stftref.py reaches
 3.2e-7, the kernels 4.0e-7 on an MI355X).  With z = re + i im and g = tau * hypot(a_re, a_im):
     magnitude   |mag - |z||               <= g + 2^-22 |z|     (two squares, an add and sqrtf)

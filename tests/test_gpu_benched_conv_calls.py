@@ -7,7 +7,7 @@ reference of that call, |out - ref| <= tau * absref (absref: the same linear ope
 launch variant at the true grid — a ragged tile, a split-K slab, a border — fails here even where the network-level
 statistics of test_gpu_model.py would absorb it.
 
-tau per (family, precision), stated once in TAU below: 4x the worst |out - ref| / absref measured over the four parameters
+tau per (family, precision), stated once in convref.TAU: 4x the worst |out - ref| / absref measured over the four parameters
 (configs 3 and 5, f32 and bf16), capped at the ceilings (2e-5 direct-form fp32 / bf16 on exactly modelled operands, 1.2e-4
 Winograd).  The measured worst ratios, per family, precision and mode, are written next to each entry.  Two findings behind
 the gate's form:
@@ -28,49 +28,16 @@ import pytest
 import torch
 
 import convref as R
+from convref import CEIL_DIRECT, CEIL_WINO, TAU, WINOGRAD, tau_of    # noqa: F401  (the tolerances live beside the reference)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WINOGRAD = ("wino4_kernel", "wino_kernel", "winow4_kernel", "winow_kernel")
-CEIL_DIRECT, CEIL_WINO = 2e-5, 1.2e-4
-# tau per (family, precision): 4x the measured worst ratio, at most the ceiling; families not listed take their ceiling
-TAU = {
-    ("conv3x3_kernel", "f32"): 2.7e-6,       # fwd 6.52e-7, dgrad 6.26e-7
-    ("convbf_kernel", "bf16"): CEIL_DIRECT,  # fwd 1.99e-5, dgrad 1.99e-5: B16 outputs, the half-ulp rounding term dominates
-    ("head_fwd_kernel", "f32"): 3.9e-6,      # 9.55e-7
-    ("head_fwd_kernel", "bf16"): 3.9e-6,     # 9.68e-7
-    ("head_dgrad_kernel", "f32"): CEIL_DIRECT,   # dgrad_up2x 1.86e-5
-    ("head_dgrad_kernel", "bf16"): CEIL_DIRECT,  # dgrad_up2x 1.86e-5
-    ("head_wgrad_kernel", "f32"): 3.8e-6,    # 9.46e-7
-    ("head_wgrad_kernel", "bf16"): 3.8e-6,   # 9.31e-7
-    ("igemm_kernel<fwd>", "f32"): 1.7e-6,    # 4.14e-7
-    ("igemm_kernel<fwd>", "bf16"): 1.7e-6,   # 4.23e-7
-    ("igemm_kernel<dgrad>", "f32"): 8.0e-6,  # 1.98e-6
-    ("igemm_kernel<dgrad>", "bf16"): 7.1e-6, # 1.75e-6
-    ("igemm_kernel<wgrad>", "f32"): 4.4e-6,  # 1.10e-6
-    ("igemm_kernel<wgrad>", "bf16"): 6.6e-8, # 1.64e-8
-    ("smallci_dgrad", "f32"): 2.1e-6,        # 5.23e-7
-    ("smallci_dgrad", "bf16"): 2.2e-6,       # 5.33e-7
-    ("smallci_wgrad_kernel", "f32"): 6.5e-8, # 1.61e-8
-    ("wgrad3x3_kernel", "f32"): 1.2e-7,      # 2.80e-8
-    ("wgrad3x3_kernel", "bf16"): 2.5e-6,     # 6.18e-7
-    ("wgrad4d_kernel", "f32"): 1.9e-6,       # 4.76e-7
-    ("wgrad4d_kernel", "bf16"): 1.5e-6,      # 3.61e-7
-    ("wgradb_kernel", "bf16"): 4.2e-6,       # 1.04e-6
-    ("wino4_kernel", "f32"): 7.3e-5,         # fwd 3.42e-6, dgrad 1.64e-5, dgrad_act 1.80e-5 (tile absref)
-    ("wino_kernel", "f32"): 6.2e-7,          # fwd 1.41e-7, dgrad 1.54e-7 (tile absref)
-    ("winow4_kernel", "f32"): 5.7e-5,        # wgrad 1.41e-5 (tile absref)
-}
 MUST_F32 = ("wino4_kernel", "winow4_kernel", "wino_kernel", "wgrad4d_kernel", "conv3x3_kernel", "head_fwd_kernel",
             "head_dgrad_kernel", "head_wgrad_kernel")
 MUST_BF16 = ("convbf_kernel", "wgradb_kernel")
 ENTRY = {"fwd": "avsep_conv2d_fwd", "dgrad": "avsep_conv2d_dgrad", "dgrad_act": "avsep_conv2d_dgrad_act",
          "dgrad_up2x": "avsep_conv2d_dgrad_up2x", "wgrad": "avsep_conv2d_wgrad"}
-
-
-def tau_of(family, prec):
-    return TAU.get((family, prec), CEIL_WINO if family in WINOGRAD else CEIL_DIRECT)
 
 
 class _Shadow:
