@@ -765,23 +765,6 @@ def _mwf_check(what, ymag, yph):
     return N, Cc, Fin, F
 
 
-def _mwf_cov(ymag, yph):
-    """-> f32 [N, Fin, C, C, 2]"""
-    N, Cc, Fin, F = ymag.shape
-    nbytes = lib.load().avsep_mwf_workspace_bytes(N, Cc, Fin, F)
-    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=ymag.device)
-    cov = _f32((N, Fin, Cc, Cc, 2), ymag)
-    call("avsep_mwf_cov", ptr(ymag), ptr(yph), int(yph.dim() == 4), N, Cc, Fin, F, ptr(cov), ptr(ws), nbytes)
-    return cov
-
-
-def _mwf_apply(xmag, xph, ymag, cov, reg):
-    N, Cc, Fin, F = ymag.shape
-    out_mag, out_ph = _f32((N, Cc, Fin, F), ymag), _f32((N, Cc, Fin, F), ymag)
-    call("avsep_mwf_apply", ptr(xmag), ptr(xph), ptr(ymag), ptr(cov), N, Cc, Fin, F, reg, ptr(out_mag), ptr(out_ph))
-    return out_mag, out_ph
-
-
 MWF_MIN_SPAN, MWF_MAX_SPAN = 64, 4096     # avsep_mwf_*_tv: the span H, a multiple of 64
 
 
@@ -799,20 +782,23 @@ def mwf_centres(F, span):
     return 1 if F == 1 else -(-(F - 1) // span) + 1
 
 
-def _mwf_cov_tv(ymag, yph, span):
-    """-> f32 [N, K, Fin, C, C, 2]"""
+def _mwf_cov(ymag, yph, span):
+    """-> f32 [N, Fin, C, C, 2], or [N, K, Fin, C, C, 2] with a span: span == 0 calls the time-invariant entries, here and in
+    _mwf_apply"""
     N, Cc, Fin, F = ymag.shape
-    nbytes = lib.load().avsep_mwf_tv_workspace_bytes(N, Cc, Fin, F, span)
+    tv, H = ("_tv", (span,)) if span else ("", ())
+    nbytes = getattr(lib.load(), f"avsep_mwf{tv}_workspace_bytes")(N, Cc, Fin, F, *H)
     ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=ymag.device)
-    cov = _f32((N, mwf_centres(F, span), Fin, Cc, Cc, 2), ymag)
-    call("avsep_mwf_cov_tv", ptr(ymag), ptr(yph), int(yph.dim() == 4), N, Cc, Fin, F, span, ptr(cov), ptr(ws), nbytes)
+    cov = _f32((N, mwf_centres(F, span), Fin, Cc, Cc, 2) if span else (N, Fin, Cc, Cc, 2), ymag)
+    call(f"avsep_mwf_cov{tv}", ptr(ymag), ptr(yph), int(yph.dim() == 4), N, Cc, Fin, F, *H, ptr(cov), ptr(ws), nbytes)
     return cov
 
 
-def _mwf_apply_tv(xmag, xph, ymag, cov, span, reg):
+def _mwf_apply(xmag, xph, ymag, cov, span, reg):
     N, Cc, Fin, F = ymag.shape
+    tv, H = ("_tv", (span,)) if span else ("", ())
     out_mag, out_ph = _f32((N, Cc, Fin, F), ymag), _f32((N, Cc, Fin, F), ymag)
-    call("avsep_mwf_apply_tv", ptr(xmag), ptr(xph), ptr(ymag), ptr(cov), N, Cc, Fin, F, span, reg, ptr(out_mag), ptr(out_ph))
+    call(f"avsep_mwf_apply{tv}", ptr(xmag), ptr(xph), ptr(ymag), ptr(cov), N, Cc, Fin, F, *H, reg, ptr(out_mag), ptr(out_ph))
     return out_mag, out_ph
 
 
@@ -824,9 +810,7 @@ def mwf_cov(ymag, yph, span=0):
     max(0, 1 - |t - k span| / span) -> complex64 [N,K,Fin,C,C], K = ceil((F - 1) / span) + 1 (a source that is silent over a
     centre's support has 0 there)."""
     _mwf_check("mwf_cov", ymag, yph)
-    if mwf_span_check("mwf_cov", span):
-        return torch.view_as_complex(_mwf_cov_tv(ymag.contiguous(), yph.contiguous(), span))
-    return torch.view_as_complex(_mwf_cov(ymag.contiguous(), yph.contiguous()))
+    return torch.view_as_complex(_mwf_cov(ymag.contiguous(), yph.contiguous(), mwf_span_check("mwf_cov", span)))
 
 
 def mwf(xmag, xph, ymag, yph, iterations=1, reg=1e-3, span=0):
@@ -849,10 +833,7 @@ def mwf(xmag, xph, ymag, yph, iterations=1, reg=1e-3, span=0):
     mwf_span_check("mwf", span)
     xmag, xph, mag, ph = xmag.contiguous(), xph.contiguous(), ymag.contiguous(), yph.contiguous()
     for _ in range(iterations):
-        if span:
-            mag, ph = _mwf_apply_tv(xmag, xph, mag, _mwf_cov_tv(mag, ph, span), span, reg)
-        else:
-            mag, ph = _mwf_apply(xmag, xph, mag, _mwf_cov(mag, ph), reg)
+        mag, ph = _mwf_apply(xmag, xph, mag, _mwf_cov(mag, ph, span), span, reg)
     return mag, ph
 
 

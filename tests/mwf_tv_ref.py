@@ -119,6 +119,11 @@ VALUE_SHAPES = [(1, 1, 63, 64), (1, 3, F_LONG, 192), (2, 1, 1, 64), (2, 2, 64, 6
                 (8, 2, 65, 64), (8, 1, 257, 192), (8, 3, F_LONG, 192)]
 VALUE_CASES = [(C, N, F, H, it) for (C, N, F, H) in VALUE_SHAPES for it in (1, 2)]
 
+# (C, N, F, H) at which the two apply kernels are tied to each other (one covariance repeated at every centre makes the blend
+# a no-op up to rounding): a one-frame second tile, a span that does not divide the 256-frame tile, and the clamped last
+# centre at the widest C
+TIE_SHAPES = [(2, 2, 257, 64), (3, 2, 257, 192), (8, 2, 65, 64)]
+
 
 # Worst max|d|/max|ref| of the float32 mode against the float64 mode over VALUE_CASES, measured on the CPU
 # (test_mwf_tv_host.py re-measures it): 4.703e-07 for the filtered images and 8.474e-07 for the covariances (both at C = 8,

@@ -82,6 +82,24 @@ def test_mwf_span_zero_is_the_invariant_filter_and_bad_spans_are_refused(dev):
             K.mwf_cov(ym, xp, span=bad)
 
 
+@pytest.mark.parametrize("C,N,F,H", T.TIE_SHAPES)
+def test_apply_tv_with_one_covariance_at_every_centre_is_the_invariant_apply(dev, C, N, F, H):
+    """The two apply kernels are one template (mwf_apply_kernel<C, TV>) and differ in where an entry of R_n comes from.  With the time-invariant
+    covariance repeated at all K centres the blend w R + u R is R up to rounding, so avsep_mwf_apply_tv must give what
+    avsep_mwf_apply gives on the same inputs, the whole output, within BOUND_Y (the float32 restatements do:
+    test_mwf_tv_host.py).  Not bit-equal, not even where u == 0: the two instantiations may fuse differently."""
+    xmag, xph, ymag = T.value_inputs(C, N, F)
+    xm, xp, ym = _dev(xmag, dev), _dev(xph, dev), _dev(ymag, dev)
+    cov = K._mwf_cov(ym, xp, 0)                                                          # f32 [N, Fin, C, C, 2]
+    rep = cov[:, None].expand(N, T.centres(F, H), T.FIN, C, C, 2).contiguous()
+    ref = _complex(*K._mwf_apply(xm, xp, ym, cov, 0, M.REG))
+    got = _complex(*K._mwf_apply(xm, xp, ym, rep, H, M.REG))
+    err = M.rel_err(got, ref)
+    print(f"C={C} N={N} F={F} H={H}: apply_tv against apply {err:.3e} (bound {T.BOUND_Y:.2e})")
+    assert got.shape == (N, C, T.FIN, F) and np.abs(ref).max() > 10.0
+    assert err <= T.BOUND_Y
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # exactness
 # ---------------------------------------------------------------------------------------------------------------------

@@ -186,3 +186,20 @@ def test_float32_restatement_error_is_what_the_gpu_tolerance_was_sized_from():
     assert {c[0] for c in T.VALUE_CASES} == {1, 2, 3, 8} and {c[1] for c in T.VALUE_CASES} == {1, 2, 3}
     assert {c[2] for c in T.VALUE_CASES} == {1, 63, 64, 65, 257, 2 * 2048 + 77} and {c[3] for c in T.VALUE_CASES} == {64, 128, 192}
     assert {c[4] for c in T.VALUE_CASES} == {1, 2} and T.FIN == 5
+
+
+@pytest.mark.parametrize("Cc,N,F,H", T.TIE_SHAPES)
+def test_float32_restatements_agree_when_every_centre_holds_the_invariant_covariance(Cc, N, F, H):
+    """What test_gpu_mwf_tv.py asks of the two apply kernels, asked of the references first: with the time-invariant
+    covariance repeated at all K centres the blend (1 - u) R + u R is R up to one rounding, so the float32 mode of
+    mwf_tv_ref.apply must give what the float32 mode of mwf_ref.apply gives, polar conversions included, within BOUND_Y
+    (measured: 0.9e-07 ... 1.9e-07); in float64 the two agree to 1e-12, the figure of the test above (measured: 4e-16)."""
+    xmag, xph, ymag = T.value_inputs(Cc, N, F)
+    for dtype, bound in ((np.float64, 1e-12), (np.float32, T.BOUND_Y)):
+        R, v = M.cov(ymag, xph, dtype)
+        rep = np.ascontiguousarray(np.broadcast_to(R[:, None], (N, T.centres(F, H)) + R.shape[1:]))
+        a = M.polar_to_complex(*M.complex_to_polar(M.apply(xmag, xph, v, R, dtype=dtype), dtype))
+        b = M.polar_to_complex(*M.complex_to_polar(T.apply(xmag, xph, v, rep, H, dtype=dtype), dtype))
+        err = M.rel_err(b, a)
+        print(f"C={Cc} N={N} F={F} H={H} {np.dtype(dtype).name}: local against invariant restatement {err:.3e} (bound {bound:.2e})")
+        assert err <= bound and np.abs(a).max() > 10.0

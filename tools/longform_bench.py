@@ -118,10 +118,9 @@ def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, w
     clk.wrap(K.Stft, "stft", "stft" if channels is None else ["stft", "stft_channels"])
     clk.wrap(K.Stft, "istft", "istft" if channels is None else ["istft", "istft_channels"])
     clk.wrap(K.Stft, "misi", "misi" if channels is None else ["misi", "misi_channels"])
-    clk.wrap(K, "_mwf_cov", "mwf_cov")
-    clk.wrap(K, "_mwf_apply", "mwf_apply")
-    clk.wrap(K, "_mwf_cov_tv", "mwf_cov_tv")
-    clk.wrap(K, "_mwf_apply_tv", "mwf_apply_tv")
+    tv = "_tv" if wiener_span else ""                                    # one pair of wrappers serves both filters; a run has one span
+    clk.wrap(K, "_mwf_cov", "mwf_cov" + tv)
+    clk.wrap(K, "_mwf_apply", "mwf_apply" + tv)
     clk.wrap(K, "window_prepare", "window_prepare")
     clk.wrap(K, "window_agreement", "agreement")
     clk.wrap(S, "align_permutations", "agreement")
