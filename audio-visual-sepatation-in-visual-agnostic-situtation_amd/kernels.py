@@ -947,6 +947,79 @@ def resample_join(x, filt, up, down, out_fmt, out=None):
     return y
 
 
+BAND_MAX_SOURCES = 8              # avsep_band_gains / avsep_band_extend: N and G up to 8
+BAND_MAX_ROWS = 8
+BAND_MAX_HOP = 4096
+
+
+def _got(t):
+    return f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+
+
+def band_gains(stem_mag, mix_mag, lo_bin=None):
+    """avsep_band_gains (include/avsep.h): stem_mag f32 [N,G,bins,F], mix_mag f32 [G,bins,F] -> f32 [N,G,F], per frame the share
+    of the mixture's RMS amplitude every source holds over the bins [lo_bin, bins), at most 1; ``lo_bin`` defaults to
+    bins // 2 (the top octave).  A frame that is silent in the band gives exactly 0."""
+    if not torch.is_tensor(stem_mag) or not torch.is_tensor(mix_mag) or stem_mag.dtype != torch.float32 or stem_mag.dim() != 4 \
+            or mix_mag.dtype != torch.float32 or tuple(mix_mag.shape) != tuple(stem_mag.shape[1:]) or mix_mag.device != stem_mag.device:
+        raise lib.AvsepError(f"band_gains takes stem_mag float32 [N,G,bins,F] and mix_mag float32 [G,bins,F] on one device, got "
+                             f"{_got(stem_mag)} and {_got(mix_mag)}")
+    lib.require_gpu(stem_mag)
+    N, G, bins, F = stem_mag.shape
+    if not (1 <= N <= BAND_MAX_SOURCES and 1 <= G <= BAND_MAX_ROWS and F >= 1):
+        raise lib.AvsepError(f"band_gains: 1 <= N <= {BAND_MAX_SOURCES}, 1 <= G <= {BAND_MAX_ROWS}, F >= 1; got {tuple(stem_mag.shape)}")
+    if lo_bin is None:
+        lo_bin = bins // 2
+    if isinstance(lo_bin, bool) or not isinstance(lo_bin, int) or not 1 <= lo_bin < bins:
+        raise lib.AvsepError(f"band_gains takes lo_bin as an int with 1 <= lo_bin < bins = {bins}, got {lo_bin!r}")
+    gains = _f32((N, G, F), stem_mag)
+    stem_mag, mix_mag = stem_mag.contiguous(), mix_mag.contiguous()
+    call("avsep_band_gains", ptr(stem_mag), ptr(mix_mag), N, G, bins, F, lo_bin, ptr(gains))
+    return gains
+
+
+def band_extend(stems, low, file, gains, filt, up, down, hop):
+    """avsep_band_extend (include/avsep.h): stems f32 [N,G,Lm] at the model's rate, low f32 [G,Ll] (Ll >= Lm) the model-rate
+    mixture rows they were made from, file f32 [G,Lf] the same rows at the file's rate, gains f32 [N,G,F] (band_gains), filt
+    the polyphase table of up/down > 1, hop the STFT hop of the gains' frames -> f32 [N,G,ceil(Lm*up/down)]:
+    resample(stems) + gain * (file - resample(low)), the gain interpolated between the frames next to each output."""
+    for name, t, nd in (("stems", stems, 3), ("low", low, 2), ("file", file, 2), ("gains", gains, 3)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != nd:
+            raise lib.AvsepError(f"band_extend takes {name} as float32 with {nd} dimensions (stems [N,G,Lm], low [G,Ll], file [G,Lf], "
+                                 f"gains [N,G,F]), got {_got(t)}")
+    lib.require_gpu(stems)
+    lib.require_gpu(filt)
+    N, G, Lm = stems.shape
+    if not (1 <= N <= BAND_MAX_SOURCES and 1 <= G <= BAND_MAX_ROWS and Lm >= 1):
+        raise lib.AvsepError(f"band_extend: 1 <= N <= {BAND_MAX_SOURCES}, 1 <= G <= {BAND_MAX_ROWS}, Lm >= 1; got stems {tuple(stems.shape)}")
+    for name, t in (("low", low), ("file", file), ("gains", gains)):
+        if t.device != stems.device:
+            raise lib.AvsepError(f"band_extend takes {name} on {stems.device}, the stems' device, got {t.device}")
+    if low.shape[0] != G or low.shape[1] < Lm:
+        raise lib.AvsepError(f"band_extend takes low as [{G},Ll] with Ll >= Lm = {Lm}, got {tuple(low.shape)}")
+    if file.shape[0] != G or file.shape[1] < 1:
+        raise lib.AvsepError(f"band_extend takes file as [{G},Lf] with Lf >= 1, got {tuple(file.shape)}")
+    if tuple(gains.shape[:2]) != (N, G) or gains.shape[2] < 1:
+        raise lib.AvsepError(f"band_extend takes gains as [{N},{G},F] with F >= 1, got {tuple(gains.shape)}")
+    for name, v in (("up", up), ("down", down), ("hop", hop)):
+        if isinstance(v, bool) or int(v) != v:
+            raise lib.AvsepError(f"band_extend takes {name} as an int, got {v!r}")
+    up, down, hop = int(up), int(down), int(hop)
+    if not 1 <= down < up <= 1280:
+        raise lib.AvsepError(f"band_extend extends upwards: 1 <= down < up <= 1280, got up={up} down={down}")
+    if not 1 <= hop <= BAND_MAX_HOP:
+        raise lib.AvsepError(f"band_extend takes 1 <= hop <= {BAND_MAX_HOP}, got {hop}")
+    _resample_table_check("band_extend", filt, up, down, stems.device)
+    Lout = -(-Lm * up // down)
+    if Lout >= 2 ** 31:
+        raise lib.AvsepError(f"band_extend: ceil(Lm*{up}/{down}) < 2^31, got Lm={Lm}")
+    out = _f32((N, G, Lout), stems)
+    stems, low, file, gains = stems.contiguous(), low.contiguous(), file.contiguous(), gains.contiguous()
+    call("avsep_band_extend", ptr(stems), ptr(low), ptr(file), ptr(gains), ptr(filt), N, G, Lm, low.shape[1], file.shape[1],
+         gains.shape[2], hop, up, down, ptr(out))
+    return out
+
+
 TRUE_PEAK_TAPS = 21               # rows of avsep_true_peak's polyphase table
 
 

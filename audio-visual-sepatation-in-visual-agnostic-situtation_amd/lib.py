@@ -97,6 +97,8 @@ SIGNATURES = {
     "avsep_resample_poly": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_resample_split": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_resample_join": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_band_gains": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_band_extend": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_loudness_energies_workspace_bytes": (_Z, [_I, _I, _I]),
     "avsep_loudness_energies": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "avsep_true_peak_workspace_bytes": (_Z, [_I, _I]),

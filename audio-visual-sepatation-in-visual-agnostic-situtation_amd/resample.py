@@ -102,6 +102,24 @@ def resample(x, rate_in, rate_out, out_s16=False):
     return y if x.dim() == 2 else y[0]
 
 
+def band_extend(stems, low, file_rows, gains, rate_model, rate_file, hop):
+    """Full-band stems (include/avsep.h, avsep_band_extend): stems f32 [N,G,Lm] at ``rate_model``, low f32 [G,Ll] the
+    model-rate mixture rows they were made from (Ll >= Lm), file_rows f32 [G,Lf] the same rows at ``rate_file``, gains f32
+    [N,G,F] (kernels.band_gains), hop the STFT hop -> f32 [N,G,ceil(Lm*up/down)] at ``rate_file``:
+    resample(stems) + gain * (file_rows - resample(low)).  The resampler is zero-phase, so the bracket is exactly what the
+    model never heard; with gains of 0 the result is resample(stems), bit for bit."""
+    up, down = check_rates(rate_model, rate_file)
+    if up <= down:
+        raise AvsepError(f"band_extend adds what a file holds above the model's band: the file's rate ({rate_file} Hz) has to "
+                         f"exceed the model's ({rate_model} Hz)")
+    if not torch.is_tensor(stems) or stems.dim() != 3:
+        got = f"{stems.dtype} {tuple(stems.shape)}" if torch.is_tensor(stems) else type(stems).__name__
+        raise AvsepError(f"band_extend takes stems as float32 [N,G,Lm], got {got}")
+    lib.require_gpu(stems)
+    _check_length(stems.shape[-1], up, down)
+    return K.band_extend(stems, low, file_rows, gains, filter_table(up, down, stems.device), up, down, hop)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # a file's frames as bytes, in any sample format (wavio.py)
 # ---------------------------------------------------------------------------------------------------------------------

@@ -101,7 +101,7 @@ def _visual_features(net_frame, frames, args, Kw, batch):
 
 
 def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None,
-                  wiener=0, phase_iters=0, clamp=True, wiener_span=0):
+                  wiener=0, phase_iters=0, clamp=True, wiener_span=0, band_gains=False):
     """Separate one recording ``wav`` [L] (on the GPU, L >= args.stft_frame; several recordings: one call each).
 
     nets: (net_sound, net_frame), both in eval() — train-mode BatchNorm over the windows of one recording is never what
@@ -142,6 +142,12 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
 
     clamp: False leaves "wavs" and "channel_wavs" as the inverse transform gives them, overshoots past full scale included
     (levels.py then measures them and rescales instead of clipping).  Nothing else changes.
+
+    band_gains: True adds "band_gains", f32 [N, C, F] with ``channels`` and [N, 1, F] without: per STFT frame the share of the
+    mixture's RMS amplitude every source holds over the top octave of the model's band (``kernels.band_gains``), from the
+    magnitudes that go into the inverse transform (with ``wiener`` the filtered ones, per channel) against the mixture's.
+    ``resample.band_extend`` hands a file's band above the model's to the stems under these gains.  Nothing else changes;
+    False is the path above, bit for bit.
     """
     net_sound, net_frame = nets
     if isinstance(wiener, bool) or not isinstance(wiener, int) or not 0 <= wiener <= MAX_WIENER:
@@ -213,6 +219,8 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
             wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous())
         if clamp:
             wavs = wavs.clamp_(-1.0, 1.0)
+        if band_gains and channels is None:
+            gains = K.band_gains(mags[:, None], mag[None])
         if channels is not None:                                         # the same masks on every channel's own STFT
             mag_c, phase_c = plan.stft(channels.contiguous())
             Cc, Fin, Fr = mag_c.shape
@@ -222,6 +230,8 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
                 mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener, span=wiener_span)
             elif wiener:                                                 # soft source images in, one phase per source out
                 mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener)
+            if band_gains:                                               # of what is inverted below: after the filter, per channel
+                gains = K.band_gains(mags_c, mag_c)
             if phase_iters:                                              # every channel is the mixture of its N stems
                 channel_wavs = plan.misi(channels[:, :out_len], mags_c, phases_c, phase_iters)
             else:
@@ -234,6 +244,8 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
     out = {"wavs": wavs, "starts": starts, "perms": perms}
     if channels is not None:
         out["channel_wavs"] = channel_wavs
+    if band_gains:
+        out["band_gains"] = gains
     if return_masks:
         out.update(masks=masks, lin_masks=lin)
     return out
@@ -345,6 +357,10 @@ def build_parser():
     p.add_argument("--phase_iters", type=int, default=0, metavar="K",
                    help="K mixture-consistent phase iterations (0 ... 32) in place of the one inverse transform: every source "
                         "gets a phase of its own (0, the default: the mixture's phase; no gain with --binary_mask 1)")
+    p.add_argument("--band", choices=("model", "full"), default="model",
+                   help="model: the sources end at the model's band, half of --audRate (default); full: every source also gets "
+                        "its share of what the file holds above that band, frame by frame as much as it holds of the band's top "
+                        "octave (needs the file's rate as the output rate)")
     p.add_argument("--levels", action="store_true",
                    help="measure the mixture and the written sources (BS.1770-4 loudness, true peak) into <out>/levels.json")
     p.add_argument("--peak", type=float, default=None, metavar="DBTP",
@@ -375,6 +391,8 @@ def parse_args(argv=None):
         raise SystemExit(f"--wiener_span takes 0 or a multiple of 64 frames in {K.MWF_MIN_SPAN} ... {K.MWF_MAX_SPAN}, got {args.wiener_span}")
     if args.wiener_span and not args.wiener:
         raise SystemExit("--wiener_span is the span of the Wiener filter's covariances: it needs --wiener K with K >= 1")
+    if args.band == "full" and args.out_rate == "model":
+        raise SystemExit("--band full adds what the file holds above the model's band: it cannot be written at --out_rate model")
     if args.peak is not None and not args.peak <= 0.0:
         raise SystemExit(f"--peak takes a true-peak ceiling of at most 0 dBTP, got {args.peak}")
     if args.loudness is not None and not -70.0 <= args.loudness <= 0.0:
@@ -395,16 +413,27 @@ def output_mixture(path, info, out_rate, wav, channels, dev):
     return R.resample_frames(raw, info.fmt, info.channels, info.rate, info.rate)[None]
 
 
-def write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev):
-    """--peak / --loudness: the unclamped stems at the output rate, one gain for all of them (levels.output_gain), every
-    format through join_frames at equal rates.  -> the levels.json dict."""
+def output_rows(out, args, out_rate, wav, channels, keep, mix=None):
+    """The stems at the output rate, f32 [N, C, Lout], as separate_long left them (clamped or not): resampled, or with
+    ``mix`` (--band full: output_mixture's rows at the file's rate) extended by the file's band above the model's."""
+    from . import resample as R
+    stems = out["channel_wavs"] if keep else out["wavs"][:, None]
+    N, Cc, Lm = stems.shape
+    if mix is not None:
+        return R.band_extend(stems.contiguous(), channels if keep else wav[None], mix, out["band_gains"], args.audRate, out_rate,
+                             args.stft_hop)
+    return R.resample(stems.reshape(N * Cc, Lm).contiguous(), args.audRate, out_rate).reshape(N, Cc, -1)
+
+
+def write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev, full=False):
+    """--peak / --loudness: the unclamped stems at the output rate (``full``: the full-band rows), one gain for all of them
+    (levels.output_gain), every format through join_frames at equal rates.  -> the levels.json dict."""
     from . import levels as LV
     from . import resample as R
     from . import wavio
-    stems = out["channel_wavs"] if keep else out["wavs"][:, None]
-    N, Cc, Lm = stems.shape
-    rows = R.resample(stems.reshape(N * Cc, Lm).contiguous(), args.audRate, out_rate).reshape(N, Cc, -1)
     mix = output_mixture(args.wav, info, out_rate, wav, channels, dev)
+    rows = output_rows(out, args, out_rate, wav, channels, keep, mix if full else None)
+    N, Cc = rows.shape[:2]
     m_stems, m_mix = LV.measure(rows, out_rate), LV.measure(mix, out_rate)
     try:
         gain, limited_by = LV.output_gain(m_mix["integrated"][0], m_stems["true_peak"], args.loudness, args.peak)
@@ -464,14 +493,23 @@ def cli(argv=None):
         fr = torch.from_numpy(np.load(path)).float()
         frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
     levelled = args.peak is not None or args.loudness is not None
+    full = args.band == "full" and rate > args.audRate       # at or below the model's rate the file holds nothing above its band
     out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
                         stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener,
-                        phase_iters=args.phase_iters, clamp=not levelled, wiener_span=args.wiener_span)
+                        phase_iters=args.phase_iters, clamp=not (levelled or full), wiener_span=args.wiener_span,
+                        **({"band_gains": True} if full else {}))
     os.makedirs(args.out, exist_ok=True)
     out_rate = rate if args.out_rate == "file" else args.audRate
     report = None
     if levelled:                                     # rescaled, not clipped: measured and written at the output rate
-        report = write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev)
+        report = write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev, full)
+    elif full:                                       # the full-band rows are clamped as a whole, then every stem is one join
+        rows = output_rows(out, args, out_rate, wav, channels, keep,
+                           output_mixture(args.wav, info, out_rate, wav, channels, dev)).clamp_(-1.0, 1.0)
+        for n in range(rows.shape[0]):
+            wavio.write_frames(os.path.join(args.out, f"source{n}.wav"),
+                               R.join_frames(rows[n].contiguous(), out_rate, out_rate, out_fmt).cpu().numpy(), out_rate,
+                               rows.shape[1], out_fmt)
     else:                                            # the kernel writes the file's frames: every stem is one join
         stems = out["channel_wavs"] if keep else out["wavs"][:, None]
         for n, cw in enumerate(stems):
@@ -479,10 +517,9 @@ def cli(argv=None):
                                out_rate, cw.shape[0], out_fmt)
     if args.levels and report is None:               # the clamped stems as they were written, at the output rate
         from . import levels as LV
-        stems = out["channel_wavs"] if keep else out["wavs"][:, None]
-        rows = R.resample(stems.reshape(-1, stems.shape[-1]).contiguous(), args.audRate, out_rate).reshape(*stems.shape[:2], -1)
-        report = LV.report(out_rate, 1.0, None, LV.measure(output_mixture(args.wav, info, out_rate, wav, channels, dev), out_rate),
-                           LV.measure(rows, out_rate))
+        mix = output_mixture(args.wav, info, out_rate, wav, channels, dev)
+        rows = output_rows(out, args, out_rate, wav, channels, keep, mix if full else None)
+        report = LV.report(out_rate, 1.0, None, LV.measure(mix, out_rate), LV.measure(rows.clamp_(-1.0, 1.0) if full else rows, out_rate))
     if report is not None:
         import json
         with open(os.path.join(args.out, "levels.json"), "w") as f:
@@ -497,6 +534,10 @@ def cli(argv=None):
                      f"({args.wiener_span * args.stft_hop / args.audRate:.2f} s)")
     if args.phase_iters:
         kept += f", phase iterations x{args.phase_iters}"
+    if full:
+        kept += ", full band"
+    elif args.band == "full":
+        kept += ", the file's rate is within the model's band: --band full wrote what --band model writes"
     print(f"{len(out['starts'])} windows -> {args.out}/source[0-{args.num_mix - 1}].wav{kept}")
     return out
 

@@ -626,6 +626,45 @@ int avsep_resample_join(const float* x, const float* ho, int32_t C, int32_t L, i
                         void* y, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Full-band stems (csrc/fullband.hip; avsep_amd/resample.py band_extend): the model hears a file at its own rate, so a stem
+ * ends at that rate's Nyquist; what the file holds above it, high = file - up(down(file)), is handed to the sources under a
+ * time-varying gain.  N sources, G rows per source (1 for mono stems, C for channel stems); 1 <= N, G <= 8.
+ * avsep_band_gains: stem_mag f32 [N, G, bins, F], mix_mag f32 [G, bins, F], 1 <= lo_bin < bins, F >= 1 -> gains f32 [N, G, F],
+ *   the share of the mixture's RMS amplitude source n holds over the bins [lo_bin, bins) of frame t.  With B = bins - lo_bin:
+ *     num = 0;  for f = lo_bin .. bins-1 (in this order):  num = fma(stem_mag[n,g,f,t], stem_mag[n,g,f,t], num)
+ *     den = 0;  for f = lo_bin .. bins-1 (in this order):  den = fma(mix_mag[g,f,t], mix_mag[g,f,t], den)
+ *     gains[n,g,t] = min(1, sqrt(num / (den + 1e-20f * (float)B)))        (f32, division and root correctly rounded)
+ *   A frame whose sums are zero gets exactly 0, a source at or above the mixture exactly 1.  The order depends on
+ *   (bins, lo_bin) only; there are no atomics: a second call gives the same bits and a (n, g) row gives the same bits alone
+ *   as inside a batch.  One thread per (g, t) walks the bins (F is the contiguous axis: coalesced) with den formed once.
+ * avsep_band_extend: stems f32 [N, G, Lm] at the model's rate; low f32 [G, Ll], Ll >= Lm, the model-rate mixture rows the
+ *   stems were made from (not trimmed to Lm: the filter sees real samples past the stems' end); file f32 [G, Lf] the same
+ *   rows at the file's rate; gains f32 [N, G, F]; hop the STFT hop of the gains' frames (frame t is centred on model sample
+ *   t * hop); ho the polyphase table of (up, down) above, up / down = file rate / model rate > 1 -> out f32 [N, G, Lout],
+ *   Lout = ceil(Lm * up / down).  With chain(row, L)[j] exactly the per-output arithmetic of avsep_resample_poly above (same
+ *   tap order, one fma per tap, samples outside [0, L) zero), per output j:
+ *     s   = chain(stems[n,g], Lm)[j]          the bits avsep_resample_poly gives that row
+ *     l   = chain(low[g], Ll)[j]              once per (g, j), shared by the N sources
+ *     h   = j < Lf ? file[g,j] - l : 0
+ *     num = j * down (64-bit),  den = up * hop           output j sits at model sample j * down / up
+ *     t0  = min(num div den, F-1),  t1 = min(t0 + 1, F-1)
+ *     fr  = (float)(num - t0 * den) / (float)den         both exact in f32 while t0 < F-1: den < 2^24
+ *     gi  = fma(fr, gains[n,g,t1] - gains[n,g,t0], gains[n,g,t0])
+ *     out[n,g,j] = fma(gi, h, s)
+ *   Past the last frame t1 = t0, so gi = gains[n,g,F-1] whatever fr is.  Gains of 0 give avsep_resample_poly's bits; with
+ *   N = 1, gains of 1 and stems = low the file comes back to one rounding.  The order depends on (up, down, j) only; there
+ *   are no atomics: a row gives the same bits alone, inside a batch and on a second call.  A workgroup stages its tile of
+ *   low[g] and of the N stem rows of that g in LDS and produces its outputs for every n.
+ *   up > down, both in [1, 1280]; 1 <= hop <= 4096; F >= 1; Lm, Lf >= 1; Lout < 2^31.  Every offset is formed in 64 bits.
+ * Anything outside these limits or a null pointer is AVSEP_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------- */
+int avsep_band_gains(const float* stem_mag, const float* mix_mag, int32_t N, int32_t G, int32_t bins, int32_t F, int32_t lo_bin,
+                     float* gains, avsep_stream_t stream);
+int avsep_band_extend(const float* stems, const float* low, const float* file, const float* gains, const float* ho, int32_t N,
+                      int32_t G, int32_t Lm, int32_t Ll, int32_t Lf, int32_t F, int32_t hop, int32_t up, int32_t down, float* out,
+                      avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Stem levels (csrc/levels.hip; avsep_amd/levels.py): what ITU-R BS.1770-4 loudness and true peak need from every sample of
  * R rows x f32 [R, L] in device memory.  float64 throughout (a sample is converted once), no atomics, no waveform written;
  * every sum has a fixed order, so a row gives the same bits alone, inside a batch and on a second call.
