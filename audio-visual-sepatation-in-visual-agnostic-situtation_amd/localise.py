@@ -24,8 +24,7 @@ import torch
 from . import kernels as K
 from . import lib
 from .lib import AvsepError
-from .models import activate
-from .separate import FOUT, WIDTH, frame_columns, load_mixture, plan_windows
+from .separate import FOUT, WIDTH, frame_columns, load_nets, open_recording, plan_windows, trunk_features
 
 
 def jet_table():
@@ -46,11 +45,7 @@ def window_of_frames(frame_times, starts, rate, hop, width=WIDTH):
 
 
 def _frame_features(net_frame, fr, args, batch, act):
-    parts = []
-    for i in range(0, fr.shape[0], batch):
-        f = net_frame.forward(fr[i:i + batch], pool=args.not_pool_vis)
-        parts.append(activate(f, args.img_activation) if act else f)
-    f = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+    f = trunk_features(net_frame, fr, batch, fr.device, args.not_pool_vis, args.img_activation if act else None)
     if f.dim() != 4:
         raise AvsepError(f"localisation needs a spatial visual feature map [T,Dc,h,w], net_frame gives {tuple(f.shape)}")
     return f.float().contiguous()
@@ -158,36 +153,10 @@ def parse_args(argv=None):
 
 
 def cli(argv=None):
-    from . import checkpoint as ckpt
-    from .models import ModelBuilder
     args = parse_args(argv)
-    from . import resample as R
-    from . import wavio
-    try:
-        info = wavio.probe(args.wav)
-    except AvsepError as e:
-        raise SystemExit(str(e))
-    rate = info.rate
-    if info.channels > R.MAX_CHANNELS:
-        raise SystemExit(f"{args.wav}: files of up to {R.MAX_CHANNELS} channels are read, this one has {info.channels}")
-    if rate != args.audRate:
-        try:
-            R.check_rates(rate, args.audRate)
-        except AvsepError as e:
-            raise SystemExit(f"{args.wav}: {e}")
-    if not torch.cuda.is_available():
-        raise AvsepError("localisation runs on an MI355X; there is no CPU fallback")
-    dev = torch.device("cuda", 0)
-    wav = load_mixture(args.wav, info, args.audRate, dev)[0]      # frame times are in seconds: only the input side needs the model's rate
-    args.ckpt = os.path.join(args.ckpt, args.id)
-    if not args.weights_sound:
-        args.weights_sound, args.weights_frame = ckpt.resume_paths(args, best=not args.latest)
-    builder = ModelBuilder()
-    net_frame = builder.build_frame(arch=args.arch_frame, fc_dim=args.vis_channels, pool_type=args.img_pool,
-                                    weights=args.weights_frame)
-    net_sound = builder.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, weights=args.weights_sound,
-                                    fusion_type=args.fusion_type, att_type=args.att_type)
-    nets = (net_sound.to(dev).eval(), net_frame.to(dev).eval())
+    wav = open_recording(args, "localisation")[1]      # frame times are in seconds: only the input side needs the model's rate
+    dev = wav.device
+    nets = load_nets(args, dev)
     frames = [torch.from_numpy(np.load(path)).float().to(dev) for path in args.frames]
     times = args.frame_offset + torch.arange(frames[0].shape[0], dtype=torch.float64) / args.fps
     out = localise(nets, wav, frames, times, args, stride_frames=args.window_stride,

@@ -130,6 +130,17 @@ def frames_of_windows(frame_times, starts, rate, hop, width=WIDTH):
     return torch.from_numpy(np.stack([first, count], 1).astype(np.int32))
 
 
+def trunk_features(net_frame, fr, batch, dev, pool, activation=None):
+    """fr [T,3,H,W] through the visual trunk, ``batch`` frames at a time (each batch is moved to ``dev``, as float32) ->
+    the features of all T frames, concatenated.  activation: applied to every batch's features (img_activation); None
+    leaves it out.  The one trunk loop of ``separate_long`` (frames and clips) and of ``localise``."""
+    parts = []
+    for i in range(0, fr.shape[0], batch):
+        f = net_frame.forward(fr[i:i + batch].to(dev).float().contiguous(), pool=pool)
+        parts.append(f if activation is None else activate(f, activation))
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+
 def _visual_features(net_frame, frames, args, Kw, batch, act=True):
     """One feature tensor per source: [1,...] for a frame shared by all windows, [K,...] for one frame per window.
     act=False (the duet) leaves img_activation out."""
@@ -138,10 +149,7 @@ def _visual_features(net_frame, frames, args, Kw, batch, act=True):
         if fr.dim() != 4 or fr.shape[0] not in (1, Kw):
             raise AvsepError(f"frames[{n}] must be [1,3,H,W] or [{Kw},3,H,W] (one per window), got {tuple(fr.shape)}")
         lib.require_gpu(fr)
-        parts = [net_frame.forward(fr[i:i + batch].float().contiguous(), pool=args.not_pool_vis) for i in range(0, fr.shape[0], batch)]
-        if act:
-            parts = [activate(p, args.img_activation) for p in parts]
-        feats.append(parts[0] if len(parts) == 1 else torch.cat(parts, 0))
+        feats.append(trunk_features(net_frame, fr, batch, fr.device, args.not_pool_vis, args.img_activation if act else None))
     return feats
 
 
@@ -168,11 +176,104 @@ def _clip_features(net_frame, frames, frame_times, starts, args, batch, dev, act
         raise AvsepError(f"separate_long(frame_times=...): {e}") from e
     feats = []
     for fr in frames:
-        parts = [net_frame.forward(fr[i:i + batch].to(dev).float().contiguous(), pool=False).float() for i in range(0, T, batch)]
-        f = (parts[0] if len(parts) == 1 else torch.cat(parts, 0)).contiguous()
-        w = K.window_reduce(f, ranges, "mean")
+        w = K.window_reduce(trunk_features(net_frame, fr, batch, dev, False).float().contiguous(), ranges, "mean")
         feats.append(activate(w, args.img_activation) if act else w)
     return feats
+
+
+def _check_filter(channels, wiener, phase_iters, wiener_span):
+    """separate_long's checks of the arguments that need neither the recording, nor ``args``, nor the nets: they run first."""
+    if isinstance(wiener, bool) or not isinstance(wiener, int) or not 0 <= wiener <= MAX_WIENER:
+        raise AvsepError(f"separate_long takes wiener as an int in 0 ... {MAX_WIENER} (passes of the multichannel Wiener filter), got {wiener!r}")
+    if isinstance(phase_iters, bool) or not isinstance(phase_iters, int) or not 0 <= phase_iters <= MAX_PHASE_ITERS:
+        raise AvsepError(f"separate_long takes phase_iters as an int in 0 ... {MAX_PHASE_ITERS} (mixture-consistent phase iterations), got {phase_iters!r}")
+    if wiener and channels is None:
+        raise AvsepError("separate_long(wiener=...) filters the recording's channels: pass channels= as well")
+    K.mwf_span_check("separate_long(wiener_span=...)", wiener_span)
+    if wiener_span and not wiener:
+        raise AvsepError("separate_long(wiener_span=...) is the span of the Wiener filter's covariances: it needs wiener >= 1")
+
+
+def _check_inputs(nets, wav, frames, args, use_vis, channels, return_maps):
+    """separate_long's checks of the recording, its channels, the nets and the frame list -> whether the call is a duet."""
+    net_sound, net_frame = nets
+    lib.require_gpu(wav)
+    if wav.dim() != 1 or wav.numel() < args.stft_frame:
+        raise AvsepError(f"separate_long takes one recording [L] with L >= stft_frame, got {tuple(wav.shape)}")
+    if channels is not None:
+        if not torch.is_tensor(channels) or channels.dtype != torch.float32 or channels.dim() != 2 or channels.shape[0] < 1 \
+                or channels.shape[1] != wav.numel() or channels.device != wav.device:
+            what = f"{channels.dtype} {tuple(channels.shape)} on {channels.device}" if torch.is_tensor(channels) else type(channels).__name__
+            raise AvsepError(f"separate_long takes channels as float32 [C,{wav.numel()}] on {wav.device} (the recording's "
+                             f"channels, as long as wav), got {what}")
+    if net_sound.training or (use_vis and net_frame.training):
+        raise AvsepError("separate_long needs the nets in eval(): call .eval() on both before separating")
+    if use_vis:
+        if args.fusion_type == "MixVis":
+            raise NotImplementedError("long-form separation does not provide the MixVis fusion")
+        if len(frames) == 1 and args.num_mix != 1:
+            if args.num_mix != 2:
+                raise AvsepError(f"one frame tensor for all sources is a duet: it needs num_mix == 2, got {args.num_mix}")
+        elif len(frames) != args.num_mix:
+            raise AvsepError(f"separate_long needs one frame tensor per source ({args.num_mix}), got {len(frames)}")
+    if return_maps and (not use_vis or args.not_pool_vis):
+        raise AvsepError("separate_long(return_maps=True) returns the fusion's attention maps: it needs frames (use_vis) and a "
+                         "spatial visual feature map (pooled features, not_pool_vis, have none)")
+    return bool(use_vis) and len(frames) == 1 and args.num_mix == 2
+
+
+def _window_masks(net_sound, logm, starts_t, feats, args, batch, align, return_maps=False):
+    """The windows logm [K,1,256,256] through the U-Net, ``batch`` at a time -> (masks [K,N,256,256] in the network's channel
+    order, perms int32 [K,N] on the CPU, maps [K,N,h,w] or None).  feats: one visual feature tensor per source, [1,...]
+    (broadcast over the windows) or [K,...]; None is the audio-only branch, whose swap draw is pinned to "no swap" for the
+    call.  align: the channel order is the network's own (audio only, the duet), so consecutive windows are aligned on the
+    frames they share; else perms is the identity.  return_maps: the fusion's attention maps, maps[k, n] for output source n."""
+    Kw, N, dev = logm.shape[0], args.num_mix, logm.device
+    masks = torch.empty((Kw, N, FOUT, WIDTH), dtype=torch.float32, device=dev)
+    att, pinned = [], net_sound.ao_draws
+    try:
+        for i in range(0, Kw, batch):
+            b, vs = min(batch, Kw - i), None
+            if feats is None:        # "no swap" for every window: a bool coin for two sources, permutation index 0 for more
+                net_sound.ao_draws = torch.zeros(b, dtype=torch.bool if N == 2 else torch.int64)
+            else:
+                vs = [(f.expand(b, *f.shape[1:]) if f.shape[0] == 1 else f[i:i + b]).contiguous() for f in feats]
+            feat, meta = net_sound(logm[i:i + b], vs)
+            if feats is not None:    # every source's channel on its own, as inference.NetWrapper.forward_av
+                for n in range(N):
+                    masks[i:i + b, n] = activate(feat[:, n].unsqueeze(1), args.output_activation)[:, 0]
+            elif feat.shape[1] != N:
+                raise AvsepError(f"net_sound gives {feat.shape[1]} channels for num_mix={N}")
+            else:
+                masks[i:i + b] = activate(feat, args.output_activation)
+            if return_maps:
+                att.append(meta[1].float())
+    finally:
+        net_sound.ao_draws = pinned
+    if align:
+        perms = align_permutations(K.window_agreement(masks, starts_t))
+    else:
+        perms = torch.arange(N, dtype=torch.int32).repeat(Kw, 1)
+    maps = None
+    if return_maps:                                                      # maps[k, n]: channel perms[k][n] of window k
+        att = att[0] if len(att) == 1 else torch.cat(att, 0)
+        maps = att.gather(1, perms.to(dev).long()[:, :, None, None].expand(-1, -1, *att.shape[2:])).contiguous()
+    return masks, perms, maps
+
+
+def _inverse(plan, rows, mags, phases, phase_iters, clamp):
+    """The magnitudes mags [N,G,Fin,F] of the N stems of each of the G ``rows`` [G,L] -> their waveforms [N,G,hop*(F-1)]: one
+    iSTFT over the N*G rows, or ``phase_iters`` mixture-consistent iterations against the rows.  phases: [G,Fin,F], the rows'
+    own, shared by their stems, or [N,G,Fin,F], one per stem (the Wiener filter's).  clamp: to [-1,1].  The mono path is
+    G = 1 with the down-mix as the one row."""
+    N, G, Fin, Fr = mags.shape
+    if phase_iters:                                                      # every row is the mixture of its N stems
+        out = plan.misi(rows[:, :plan.hop * (Fr - 1)], mags, phases, phase_iters)
+    else:
+        if phases.dim() == 3:
+            phases = phases[None].expand(N, -1, -1, -1).contiguous()
+        out = plan.istft(mags.reshape(N * G, Fin, Fr), phases.reshape(N * G, Fin, Fr)).reshape(N, G, -1)
+    return out.clamp_(-1.0, 1.0) if clamp else out
 
 
 def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batch=16, return_masks=False, channels=None,
@@ -240,118 +341,38 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
     ``resample.band_extend`` hands a file's band above the model's to the stems under these gains.  Nothing else changes;
     False is the path above, bit for bit.
     """
+    _check_filter(channels, wiener, phase_iters, wiener_span)
+    duet = _check_inputs(nets, wav, frames, args, use_vis, channels, return_maps)
     net_sound, net_frame = nets
-    if isinstance(wiener, bool) or not isinstance(wiener, int) or not 0 <= wiener <= MAX_WIENER:
-        raise AvsepError(f"separate_long takes wiener as an int in 0 ... {MAX_WIENER} (passes of the multichannel Wiener filter), got {wiener!r}")
-    if isinstance(phase_iters, bool) or not isinstance(phase_iters, int) or not 0 <= phase_iters <= MAX_PHASE_ITERS:
-        raise AvsepError(f"separate_long takes phase_iters as an int in 0 ... {MAX_PHASE_ITERS} (mixture-consistent phase iterations), got {phase_iters!r}")
-    if wiener and channels is None:
-        raise AvsepError("separate_long(wiener=...) filters the recording's channels: pass channels= as well")
-    K.mwf_span_check("separate_long(wiener_span=...)", wiener_span)
-    if wiener_span and not wiener:
-        raise AvsepError("separate_long(wiener_span=...) is the span of the Wiener filter's covariances: it needs wiener >= 1")
-    lib.require_gpu(wav)
-    if wav.dim() != 1 or wav.numel() < args.stft_frame:
-        raise AvsepError(f"separate_long takes one recording [L] with L >= stft_frame, got {tuple(wav.shape)}")
-    if channels is not None:
-        if not torch.is_tensor(channels) or channels.dtype != torch.float32 or channels.dim() != 2 or channels.shape[0] < 1 \
-                or channels.shape[1] != wav.numel() or channels.device != wav.device:
-            what = f"{channels.dtype} {tuple(channels.shape)} on {channels.device}" if torch.is_tensor(channels) else type(channels).__name__
-            raise AvsepError(f"separate_long takes channels as float32 [C,{wav.numel()}] on {wav.device} (the recording's "
-                             f"channels, as long as wav), got {what}")
-    if net_sound.training or (use_vis and net_frame.training):
-        raise AvsepError("separate_long needs the nets in eval(): call .eval() on both before separating")
-    if use_vis:
-        if args.fusion_type == "MixVis":
-            raise NotImplementedError("long-form separation does not provide the MixVis fusion")
-        if len(frames) == 1 and args.num_mix != 1:
-            if args.num_mix != 2:
-                raise AvsepError(f"one frame tensor for all sources is a duet: it needs num_mix == 2, got {args.num_mix}")
-        elif len(frames) != args.num_mix:
-            raise AvsepError(f"separate_long needs one frame tensor per source ({args.num_mix}), got {len(frames)}")
-    duet = bool(use_vis) and len(frames) == 1 and args.num_mix == 2
-    if return_maps and (not use_vis or args.not_pool_vis):
-        raise AvsepError("separate_long(return_maps=True) returns the fusion's attention maps: it needs frames (use_vis) and a "
-                         "spatial visual feature map (pooled features, not_pool_vis, have none)")
-    N, dev = args.num_mix, wav.device
+    dev, binary, thres = wav.device, bool(args.binary_mask), getattr(args, "mask_thres", 0.5)
     with torch.no_grad():
         plan = K.Stft(dev, args.stft_frame, args.stft_hop, getattr(args, "stft_pad_mode", "reflect"))
         mag, phase = plan.stft(wav.float().contiguous()[None])
         mag, phase = mag[0], phase[0]                                    # [Fin, F]
         starts = plan_windows(mag.shape[1], stride_frames, WIDTH)
-        Kw = len(starts)
         starts_t = torch.tensor(starts, dtype=torch.int32, device=dev)
         _, logm = K.window_prepare(mag, starts_t, FOUT, WIDTH)
-        masks = torch.empty((Kw, N, FOUT, WIDTH), dtype=torch.float32, device=dev)
-        if use_vis:
-            if frame_times is None:
-                feats = _visual_features(net_frame, frames, args, Kw, batch, act=not duet)
-            else:
-                feats = _clip_features(net_frame, frames, frame_times, starts, args, batch, dev, act=not duet)
-            if duet:                                                         # the one map on both sides of the fusion
-                feats = feats * 2
-            att = []
-            for i in range(0, Kw, batch):
-                b = min(batch, Kw - i)
-                vs = [(f.expand(b, *f.shape[1:]) if f.shape[0] == 1 else f[i:i + b]).contiguous() for f in feats]
-                feat, meta = net_sound(logm[i:i + b], vs)
-                for n in range(N):
-                    masks[i:i + b, n] = activate(feat[:, n].unsqueeze(1), args.output_activation)[:, 0]
-                if return_maps:
-                    att.append(meta[1].float())
-            if duet:                                                         # the scores tie: the order is the network's own
-                perms = align_permutations(K.window_agreement(masks, starts_t))
-            else:
-                perms = torch.arange(N, dtype=torch.int32).repeat(Kw, 1)
-            if return_maps:                                                  # maps[k, n]: channel perms[k][n] of window k
-                att = att[0] if len(att) == 1 else torch.cat(att, 0)
-                order = perms.to(dev).long()[:, :, None, None].expand(-1, -1, *att.shape[2:])
-                maps = att.gather(1, order).contiguous()
-        else:
-            pinned = net_sound.ao_draws
-            try:
-                for i in range(0, Kw, batch):
-                    b = min(batch, Kw - i)
-                    # "no swap" for every window: a bool coin for two sources, permutation index 0 for more
-                    net_sound.ao_draws = torch.zeros(b, dtype=torch.bool if N == 2 else torch.int64)
-                    feat, _ = net_sound(logm[i:i + b], None)
-                    if feat.shape[1] != N:
-                        raise AvsepError(f"net_sound gives {feat.shape[1]} channels for num_mix={N}")
-                    masks[i:i + b] = activate(feat, args.output_activation)
-            finally:
-                net_sound.ao_draws = pinned
-            perms = align_permutations(K.window_agreement(masks, starts_t))
-        binary = bool(args.binary_mask)
-        mags, lin = K.mask_stitch(masks, starts_t, perms.to(dev), mag, binary, getattr(args, "mask_thres", 0.5), return_masks)
-        out_len = plan.hop * (mag.shape[1] - 1)
-        if phase_iters:
-            wavs = plan.misi(wav.float()[None, :out_len], mags[:, None], phase[None], phase_iters)[:, 0]
-        else:
-            wavs = plan.istft(mags, phase[None].expand(N, -1, -1).contiguous())
-        if clamp:
-            wavs = wavs.clamp_(-1.0, 1.0)
+        feats = None                                                     # audio only
+        if use_vis and frame_times is None:
+            feats = _visual_features(net_frame, frames, args, len(starts), batch, act=not duet)
+        elif use_vis:
+            feats = _clip_features(net_frame, frames, frame_times, starts, args, batch, dev, act=not duet)
+        if duet:                                                         # the one map on both sides of the fusion
+            feats = feats * 2
+        masks, perms, maps = _window_masks(net_sound, logm, starts_t, feats, args, batch, duet or not use_vis, return_maps)
+        perms_d = perms.to(dev)
+        mags, lin = K.mask_stitch(masks, starts_t, perms_d, mag, binary, thres, return_masks)
+        wavs = _inverse(plan, wav.float()[None], mags[:, None], phase[None], phase_iters, clamp)[:, 0]
         if band_gains and channels is None:
             gains = K.band_gains(mags[:, None], mag[None])
         if channels is not None:                                         # the same masks on every channel's own STFT
-            mag_c, phase_c = plan.stft(channels.contiguous())
-            Cc, Fin, Fr = mag_c.shape
-            mags_c, _ = K.mask_stitch(masks, starts_t, perms.to(dev), mag_c, binary and not wiener, getattr(args, "mask_thres", 0.5))
-            phases_c = phase_c                                           # shared by the sources
-            if wiener and wiener_span:                                   # the same, with covariances that follow the sources
-                mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener, span=wiener_span)
-            elif wiener:                                                 # soft source images in, one phase per source out
-                mags_c, phases_c = K.mwf(mag_c, phase_c, mags_c, phase_c, iterations=wiener)
+            mag_c, phases_c = plan.stft(channels.contiguous())
+            mags_c, _ = K.mask_stitch(masks, starts_t, perms_d, mag_c, binary and not wiener, thres)
+            if wiener:                                                   # soft source images in, one phase per source out
+                mags_c, phases_c = K.mwf(mag_c, phases_c, mags_c, phases_c, iterations=wiener, span=wiener_span)
             if band_gains:                                               # of what is inverted below: after the filter, per channel
                 gains = K.band_gains(mags_c, mag_c)
-            if phase_iters:                                              # every channel is the mixture of its N stems
-                channel_wavs = plan.misi(channels[:, :out_len], mags_c, phases_c, phase_iters)
-            else:
-                if not wiener:
-                    phases_c = phase_c[None].expand(N, -1, -1, -1).contiguous()
-                channel_wavs = plan.istft(mags_c.reshape(N * Cc, Fin, Fr), phases_c.reshape(N * Cc, Fin, Fr))
-                channel_wavs = channel_wavs.reshape(N, Cc, -1)
-            if clamp:
-                channel_wavs = channel_wavs.clamp_(-1.0, 1.0)
+            channel_wavs = _inverse(plan, channels, mags_c, phases_c, phase_iters, clamp)
     out = {"wavs": wavs, "starts": starts, "perms": perms}
     if channels is not None:
         out["channel_wavs"] = channel_wavs
@@ -531,85 +552,41 @@ def parse_args(argv=None):
     return args
 
 
-def output_mixture(path, info, out_rate, wav, channels, dev):
-    """What the stems are stems of, at the output rate, f32 [C, L] on ``dev``: the file's channels under --channels keep
-    (``channels`` is not None), else the down-mix row.  At the model's rate these are the network's own inputs."""
-    from . import resample as R
-    from . import wavio
-    if out_rate != info.rate:
-        return channels if channels is not None else wav[None]
-    raw = torch.from_numpy(wavio.read_frames(path)[0]).to(dev)
-    if channels is not None:
-        return R.split_frames(raw, info.fmt, info.channels, info.rate, info.rate)[1:]
-    return R.resample_frames(raw, info.fmt, info.channels, info.rate, info.rate)[None]
-
-
-def output_rows(out, args, out_rate, wav, channels, keep, mix=None):
-    """The stems at the output rate, f32 [N, C, Lout], as separate_long left them (clamped or not): resampled, or with
-    ``mix`` (--band full: output_mixture's rows at the file's rate) extended by the file's band above the model's."""
-    from . import resample as R
-    stems = out["channel_wavs"] if keep else out["wavs"][:, None]
-    N, Cc, Lm = stems.shape
-    if mix is not None:
-        return R.band_extend(stems.contiguous(), channels if keep else wav[None], mix, out["band_gains"], args.audRate, out_rate,
-                             args.stft_hop)
-    return R.resample(stems.reshape(N * Cc, Lm).contiguous(), args.audRate, out_rate).reshape(N, Cc, -1)
-
-
-def write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev, full=False):
-    """--peak / --loudness: the unclamped stems at the output rate (``full``: the full-band rows), one gain for all of them
-    (levels.output_gain), every format through join_frames at equal rates.  -> the levels.json dict."""
-    from . import levels as LV
-    from . import resample as R
-    from . import wavio
-    mix = output_mixture(args.wav, info, out_rate, wav, channels, dev)
-    rows = output_rows(out, args, out_rate, wav, channels, keep, mix if full else None)
-    N, Cc = rows.shape[:2]
-    m_stems, m_mix = LV.measure(rows, out_rate), LV.measure(mix, out_rate)
-    try:
-        gain, limited_by = LV.output_gain(m_mix["integrated"][0], m_stems["true_peak"], args.loudness, args.peak)
-    except AvsepError as e:
-        raise SystemExit(f"{args.wav}: {e}")
-    if gain != 1.0:                                  # both meters are linear: the figures after the gain follow from those before
-        rows = rows * gain
-        m_stems, m_mix = LV.scaled(m_stems, gain), LV.scaled(m_mix, gain)
-    for n in range(N):
-        wavio.write_frames(os.path.join(args.out, f"source{n}.wav"),
-                           R.join_frames(rows[n].contiguous(), out_rate, out_rate, out_fmt).cpu().numpy(), out_rate, Cc, out_fmt)
-    return LV.report(out_rate, gain, limited_by, m_mix, m_stems)
-
-
-def cli(argv=None):
-    from . import checkpoint as ckpt
-    from .models import ModelBuilder
-    args = parse_args(argv)
+def open_recording(args, what, keep=False, levels=False):
+    """The command lines' way from ``args.wav`` to (info: its wavio.probe; the down-mix f32 [L] at --audRate on cuda:0, the
+    network's input; with ``keep`` its channels f32 [C, L], else None).  What the file cannot be answers the shell
+    (SystemExit) before a GPU is asked for; ``what`` is the caller's noun in "no CPU fallback".  levels: the rate the
+    sources are written at (--out_rate) must be one levels.py measures."""
     from . import resample as R
     from . import wavio
     try:
         info = wavio.probe(args.wav)
     except AvsepError as e:
         raise SystemExit(str(e))
-    rate = info.rate
-    out_fmt = {"file": "s24" if info.fmt == "s32" else info.fmt}.get(args.out_format, args.out_format)
-    keep = args.channels == "keep"
     if info.channels > (R.MAX_KEPT_CHANNELS if keep else R.MAX_CHANNELS):
         raise SystemExit(f"{args.wav}: " + (f"--channels keep takes files of up to {R.MAX_KEPT_CHANNELS} channels" if keep else
                                             f"files of up to {R.MAX_CHANNELS} channels are read") + f", this one has {info.channels}")
-    if rate != args.audRate:
+    if info.rate != args.audRate:
         try:
-            R.check_rates(rate, args.audRate)
+            R.check_rates(info.rate, args.audRate)
         except AvsepError as e:
             raise SystemExit(f"{args.wav}: {e}")
-    if args.levels or args.peak is not None or args.loudness is not None:
+    if levels:
         from . import levels as LV
-        measured_rate = rate if args.out_rate == "file" else args.audRate
+        measured_rate = info.rate if args.out_rate == "file" else args.audRate
         if not LV.MIN_RATE <= measured_rate <= LV.MAX_RATE:
             raise SystemExit(f"{args.wav}: levels are measured at {LV.MIN_RATE} ... {LV.MAX_RATE} Hz, the sources are written at {measured_rate} Hz")
     if not torch.cuda.is_available():
-        raise AvsepError("separation runs on an MI355X; there is no CPU fallback")
-    dev = torch.device("cuda", 0)
+        raise AvsepError(f"{what} runs on an MI355X; there is no CPU fallback")
     # the raw frames go up; down-mix (and with keep every channel beside it), conversion and filter are one kernel
-    wav, channels = load_mixture(args.wav, info, args.audRate, dev, keep)
+    return (info, *load_mixture(args.wav, info, args.audRate, torch.device("cuda", 0), keep))
+
+
+def load_nets(args, dev):
+    """The command lines' nets -> (net_sound, net_frame) on ``dev`` in eval(): built from the flags, with the weights of
+    --weights_sound / --weights_frame or, without them, of the checkpoint --ckpt/--id (--latest: *_latest.pth)."""
+    from . import checkpoint as ckpt
+    from .models import ModelBuilder
     args.ckpt = os.path.join(args.ckpt, args.id)
     if not args.weights_sound:
         args.weights_sound, args.weights_frame = ckpt.resume_paths(args, best=not args.latest)
@@ -618,7 +595,47 @@ def cli(argv=None):
                                     weights=args.weights_frame)
     net_sound = builder.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, weights=args.weights_sound,
                                     fusion_type=args.fusion_type, att_type=args.att_type)
-    nets = (net_sound.to(dev).eval(), net_frame.to(dev).eval())
+    return net_sound.to(dev).eval(), net_frame.to(dev).eval()
+
+
+def output_mixture(path, info, out_rate, low, keep):
+    """What the stems are stems of, at the output rate, f32 [C, L]: the file's channels under --channels keep, else the
+    down-mix row.  At the model's rate these are the network's own inputs ``low``; at the file's the file is read again."""
+    if out_rate != info.rate:
+        return low
+    mono, channels = load_mixture(path, info, info.rate, low.device, keep)
+    return channels if keep else mono[None]
+
+
+def output_rows(stems, low, mix, gains, args, out_rate):
+    """The stems [N, C, L] at the output rate, f32 [N, C, Lout], as separate_long left them (clamped or not): resampled, or
+    with ``gains`` (--band full: separate_long's band_gains; ``mix`` is then output_mixture's rows at the file's rate)
+    extended by the file's band above the model's."""
+    from . import resample as R
+    N, Cc, Lm = stems.shape
+    if gains is not None:
+        return R.band_extend(stems.contiguous(), low, mix, gains, args.audRate, out_rate, args.stft_hop)
+    return R.resample(stems.reshape(N * Cc, Lm).contiguous(), args.audRate, out_rate).reshape(N, Cc, -1)
+
+
+def write_stems(out_dir, rows, rate_in, rate_out, fmt):
+    """rows f32 [N, C, L] at ``rate_in`` -> <out_dir>/source<n>.wav with C channels at ``rate_out`` in the sample format
+    ``fmt``: the kernel writes the file's frames, every stem is one join (at equal rates a conversion alone)."""
+    from . import resample as R
+    from . import wavio
+    for n, r in enumerate(rows):
+        wavio.write_frames(os.path.join(out_dir, f"source{n}.wav"), R.join_frames(r.contiguous(), rate_in, rate_out, fmt).cpu().numpy(),
+                           rate_out, r.shape[0], fmt)
+
+
+def cli(argv=None):
+    args = parse_args(argv)
+    keep = args.channels == "keep"
+    levelled = args.peak is not None or args.loudness is not None
+    info, wav, channels = open_recording(args, "separation", keep, levels=args.levels or levelled)
+    rate, dev = info.rate, wav.device
+    out_fmt = {"file": "s24" if info.fmt == "s32" else info.fmt}.get(args.out_format, args.out_format)
+    nets = load_nets(args, dev)
     frames, times = [], None
     for path in args.frames:
         fr = torch.from_numpy(np.load(path)).float()
@@ -630,7 +647,6 @@ def cli(argv=None):
             frames.append((fr[None] if fr.dim() == 3 else fr).to(dev))
     if args.fps is not None and not args.audio_only:
         times = args.frame_offset + torch.arange(frames[0].shape[0], dtype=torch.float64) / args.fps
-    levelled = args.peak is not None or args.loudness is not None
     full = args.band == "full" and rate > args.audRate       # at or below the model's rate the file holds nothing above its band
     out = separate_long(nets, wav, frames, args, use_vis=not args.audio_only,
                         stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener,
@@ -641,26 +657,28 @@ def cli(argv=None):
     if args.maps:
         np.save(os.path.join(args.out, "maps.npy"), out["maps"].cpu().numpy())
     out_rate = rate if args.out_rate == "file" else args.audRate
-    report = None
-    if levelled:                                     # rescaled, not clipped: measured and written at the output rate
-        report = write_levelled(out, args, info, out_rate, out_fmt, wav, channels, keep, dev, full)
-    elif full:                                       # the full-band rows are clamped as a whole, then every stem is one join
-        rows = output_rows(out, args, out_rate, wav, channels, keep,
-                           output_mixture(args.wav, info, out_rate, wav, channels, dev)).clamp_(-1.0, 1.0)
-        for n in range(rows.shape[0]):
-            wavio.write_frames(os.path.join(args.out, f"source{n}.wav"),
-                               R.join_frames(rows[n].contiguous(), out_rate, out_rate, out_fmt).cpu().numpy(), out_rate,
-                               rows.shape[1], out_fmt)
-    else:                                            # the kernel writes the file's frames: every stem is one join
-        stems = out["channel_wavs"] if keep else out["wavs"][:, None]
-        for n, cw in enumerate(stems):
-            wavio.write_frames(os.path.join(args.out, f"source{n}.wav"), R.join_frames(cw, args.audRate, out_rate, out_fmt).cpu().numpy(),
-                               out_rate, cw.shape[0], out_fmt)
-    if args.levels and report is None:               # the clamped stems as they were written, at the output rate
-        from . import levels as LV
-        mix = output_mixture(args.wav, info, out_rate, wav, channels, dev)
-        rows = output_rows(out, args, out_rate, wav, channels, keep, mix if full else None)
-        report = LV.report(out_rate, 1.0, None, LV.measure(mix, out_rate), LV.measure(rows.clamp_(-1.0, 1.0) if full else rows, out_rate))
+    stems = out["channel_wavs"] if keep else out["wavs"][:, None]
+    rate_in, report = args.audRate, None
+    if levelled or full or args.levels:              # the mixture and the stems at the output rate, once for all that follows
+        low = channels if keep else wav[None]
+        mix = output_mixture(args.wav, info, out_rate, low, keep)
+        rows = output_rows(stems, low, mix, out["band_gains"] if full else None, args, out_rate)
+        if full and not levelled:                    # the full-band rows are clamped as a whole; levelled ones are rescaled instead
+            rows = rows.clamp_(-1.0, 1.0)
+        if levelled or args.levels:                  # measured as they are written, but for the one gain (None, None: gain 1)
+            from . import levels as LV
+            m_stems, m_mix = LV.measure(rows, out_rate), LV.measure(mix, out_rate)
+            try:
+                gain, limited_by = LV.output_gain(m_mix["integrated"][0], m_stems["true_peak"], args.loudness, args.peak)
+            except AvsepError as e:
+                raise SystemExit(f"{args.wav}: {e}")
+            if gain != 1.0:                          # both meters are linear: the figures after the gain follow from those before
+                rows = rows * gain
+                m_stems, m_mix = LV.scaled(m_stems, gain), LV.scaled(m_mix, gain)
+            report = LV.report(out_rate, gain, limited_by, m_mix, m_stems)
+        if levelled or full:                         # written from the rows; else from the model-rate stems, resampled by the join
+            stems, rate_in = rows, out_rate
+    write_stems(args.out, stems, rate_in, out_rate, out_fmt)
     if report is not None:
         import json
         with open(os.path.join(args.out, "levels.json"), "w") as f:

@@ -33,6 +33,7 @@ from avsep_amd import wavio
 
 import fullband_ref as FB
 import resample_ref as R
+from test_gpu_levels import _check_figures
 from test_gpu_channels import _args, _bytes, _nets, _small_nets, _tone_mix, _tone_mix_stereo, _write_pcm
 from test_gpu_resample import _rows
 
@@ -377,3 +378,22 @@ def test_cli_band_full_with_a_peak_ceiling(dev, cli_case, tmp_path):
     # and they are not the peaks of the band-limited rows
     plain = LV.measure(RS.resample(out["channel_wavs"].reshape(4, -1), args.audRate, 48000).reshape(2, 2, -1), 48000)
     assert not torch.equal(plain["true_peak"], m["true_peak"])
+
+
+def test_cli_band_full_with_levels_reports_and_changes_nothing(dev, cli_case, tmp_path):
+    """--band full --levels: the files are those of --band full alone, and the report holds the figures of the clamped
+    full-band rows and of the file's channels, under no gain."""
+    d, flags, ones = cli_case
+    argv = ["--wav", str(d / "mix48.wav"), "--frames", *ones, "--channels", "keep", *flags]
+    S.cli(argv + ["--out", str(tmp_path / "full"), "--band", "full"])
+    S.cli(argv + ["--out", str(tmp_path / "lv"), "--band", "full", "--levels"])
+    assert not (tmp_path / "full" / "levels.json").exists()
+    for n in range(2):
+        assert _bytes(tmp_path / "lv" / f"source{n}.wav") == _bytes(tmp_path / "full" / f"source{n}.wav")
+    rep = json.loads(_bytes(tmp_path / "lv" / "levels.json"))
+    assert rep["gain_db"] == 0.0 and rep["limited_by"] is None and rep["rate"] == 48000 and len(rep["sources"]) == 2
+    args, out, full, mix = _by_hand(dev, argv, ones)
+    m = LV.measure(full.clamp(-1.0, 1.0), 48000)
+    for n in range(2):
+        _check_figures(rep["sources"][n], m, n)
+    _check_figures(rep["mixture"], LV.measure(mix, 48000), 0)

@@ -357,6 +357,41 @@ def test_cli_without_the_flags_writes_the_bytes_it_wrote_before(dev, case, tmp_p
         assert abs(rep["sources"][n]["true_peak_dbtp"][0] - 20 * math.log10(m["true_peak"][n, 0].item())) < 1e-9
 
 
+def _check_figures(fig, m, p, tol=1e-9):
+    """One entry of levels.json against programme p of an LV.measure result: the loudness figures as they are (None for -inf),
+    the peaks per channel in dB."""
+    for key in ("integrated", "momentary_max", "short_term_max"):
+        got, want = fig[key + "_lufs"], m[key][p].item()
+        assert got is None if math.isinf(want) else abs(got - want) < tol, (key, got, want)
+    for key, name in (("true_peak", "true_peak_dbtp"), ("sample_peak", "sample_peak_dbfs")):
+        assert len(fig[name]) == m[key].shape[1]
+        for c, v in enumerate(m[key][p].tolist()):
+            assert abs(fig[name][c] - 20.0 * math.log10(v)) < tol, (name, c, fig[name][c], v)
+
+
+def test_cli_levels_with_kept_channels_reports_and_changes_nothing(dev, case, tmp_path):
+    """--levels --channels keep: the files are those of the run without --levels, and the report holds the figures of every
+    source's channels (the clamped stems at the output rate, as the join wrote them) and of the file's own channels."""
+    d, flags = case
+    argv = ["--wav", str(d / "mix16.wav"), "--channels", "keep", *flags]
+    S.cli(argv + ["--out", str(tmp_path / "plain")])
+    out = S.cli(argv + ["--out", str(tmp_path / "lv"), "--levels"])
+    assert not (tmp_path / "plain" / "levels.json").exists()
+    for n in range(2):
+        assert _bytes(tmp_path / "lv" / f"source{n}.wav") == _bytes(tmp_path / "plain" / f"source{n}.wav")
+        assert _read_rows(tmp_path / "lv" / f"source{n}.wav", dev)[1].channels == 2
+    rep = json.loads(_bytes(tmp_path / "lv" / "levels.json"))
+    assert rep["gain_db"] == 0.0 and rep["limited_by"] is None and rep["rate"] == 48000 and len(rep["sources"]) == 2
+    N, Cc, Lm = out["channel_wavs"].shape
+    assert (N, Cc) == (2, 2) and out["channel_wavs"].abs().max().item() <= 1.0
+    rows = RS.resample(out["channel_wavs"].reshape(N * Cc, Lm).contiguous(), 11025, 48000).reshape(N, Cc, -1)
+    m = LV.measure(rows, 48000)
+    for n in range(2):
+        assert len(rep["sources"][n]["true_peak_dbtp"]) == 2
+        _check_figures(rep["sources"][n], m, n)
+    _check_figures(rep["mixture"], LV.measure(_read_rows(d / "mix16.wav", dev)[0], 48000), 0)
+
+
 def test_levels_cli(dev, case, tmp_path, capsys):
     d, _ = case
     res = LV.cli([str(d / "mix16.wav"), str(d / "hot.wav"), "--json", str(tmp_path / "l.json")])

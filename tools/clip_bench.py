@@ -22,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import avsep_amd as P  # noqa: E402
 from avsep_amd import separate as S  # noqa: E402
+from stage_clock import StageClock  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -53,30 +54,17 @@ def wall_ms(fn):
 
 def staged_run(call, net_frame):
     """One call with net_frame.forward and kernels.window_reduce bracketed by device synchronisations."""
-    ms, undo = {"visual_trunk": 0.0, "window_reduce": 0.0}, []
-
-    def wrap(owner, attr, stage):
-        fn = getattr(owner, attr)
-
-        def timed(*a, **kw):
-            t, r = wall_ms(lambda: fn(*a, **kw))
-            ms[stage] += t
-            return r
-        undo.append((owner, attr, fn, attr in vars(owner)))
-        setattr(owner, attr, timed)
-    wrap(net_frame, "forward", "visual_trunk")
-    wrap(P.kernels, "window_reduce", "window_reduce")
+    clk = StageClock()
+    clk.ms.update(visual_trunk=0.0, window_reduce=0.0)
+    clk.wrap(net_frame, "forward", "visual_trunk")
+    clk.wrap(P.kernels, "window_reduce", "window_reduce")
     try:
         total, _ = wall_ms(call)
     finally:
-        for owner, attr, fn, had in reversed(undo):
-            if had:
-                setattr(owner, attr, fn)
-            else:
-                delattr(owner, attr)
-    ms["other"] = total - ms["visual_trunk"] - ms["window_reduce"]
-    ms["total"] = total
-    return ms
+        clk.restore()
+    clk.ms["other"] = total - clk.ms["visual_trunk"] - clk.ms["window_reduce"]
+    clk.ms["total"] = total
+    return clk.ms
 
 
 def main():

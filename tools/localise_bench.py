@@ -21,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import avsep_amd as P  # noqa: E402
 from avsep_amd import localise as L  # noqa: E402
+from stage_clock import StageClock  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -49,31 +50,6 @@ def wall_ms(fn):
     r = fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, r
-
-
-class StageClock:
-    """Wraps the stage functions localise() calls; every wrapped call is bracketed by device synchronisations."""
-
-    def __init__(self):
-        self.ms, self._undo = {}, []
-
-    def wrap(self, owner, attr, stage):
-        fn = getattr(owner, attr)
-
-        def timed(*a, **kw):
-            ms, r = wall_ms(lambda: fn(*a, **kw))
-            self.ms[stage] = self.ms.get(stage, 0.0) + ms
-            return r
-        self._undo.append((owner, attr, fn, attr in vars(owner)))
-        setattr(owner, attr, timed)
-
-    def restore(self):
-        for owner, attr, fn, had in reversed(self._undo):
-            if had:
-                setattr(owner, attr, fn)
-            else:
-                delattr(owner, attr)
-        self._undo = []
 
 
 def staged_run(nets, wav, frames, times, args, batch):

@@ -39,6 +39,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import avsep_amd as P  # noqa: E402
 from avsep_amd import separate as S  # noqa: E402
+from stage_clock import StageClock  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -74,41 +75,6 @@ def alternating_median_ms(fns, reps, warmup=2):
             torch.cuda.synchronize()
             out[i].append(e0.elapsed_time(e1))
     return [statistics.median(o) for o in out]
-
-
-class StageClock:
-    """Wraps the stage functions separate_long calls; every wrapped call is bracketed by device synchronisations."""
-
-    def __init__(self):
-        self.ms = {}
-        self._undo = []
-
-    def wrap(self, owner, attr, stage):
-        """stage: a name, or a list of names for the first, second, ... call (the last one for every later call)."""
-        fn = getattr(owner, attr)
-        names = [stage] if isinstance(stage, str) else list(stage)
-        calls = [0]
-
-        def timed(*a, **kw):
-            name = names[min(calls[0], len(names) - 1)]
-            calls[0] += 1
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            r = fn(*a, **kw)
-            torch.cuda.synchronize()
-            self.ms[name] = self.ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
-            return r
-        had = attr in vars(owner)
-        self._undo.append((owner, attr, fn, had))
-        setattr(owner, attr, timed)
-
-    def restore(self):
-        for owner, attr, fn, had in reversed(self._undo):
-            if had:
-                setattr(owner, attr, fn)
-            else:
-                delattr(owner, attr)
-        self._undo = []
 
 
 def staged_run(nets, wav, frames, args, use_vis, stride, batch, channels=None, wiener=0, phase_iters=0, wiener_span=0):
