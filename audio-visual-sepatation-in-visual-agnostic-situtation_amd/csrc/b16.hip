@@ -12,7 +12,6 @@
 //   space-to-depth of the frames straight into a one-block B16 image
 #include "common.h"
 #include "conv_families.h"
-#include <string.h>
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -112,45 +111,61 @@ __global__ __launch_bounds__(256) void f32_bn_bwd_apply_to_b16_kernel(const floa
     op[2 * p + 1] = u32x4{b16_pack2(v[8], v[9]), b16_pack2(v[10], v[11]), b16_pack2(v[12], v[13]), b16_pack2(v[14], v[15])};
   }
 }
-static bool b16_dims_ok(int N, int C, long long HW);
+// a B16 image [N][C/16][HW][16] whose blocks and images fit grid.y and grid.z
+static bool b16_dims_ok(int N, int C, long long HW) {
+  return N > 0 && N <= 65535 && C > 0 && C % 16 == 0 && C / 16 <= 65535 && HW > 0 && HW < (1LL << 30);
+}
 // the fp32 <-> B16 boundary kernels: a thread per position, grid-stride beyond 64 workgroups per (block, image)
-static GluePlan b16_convert_plan(int N, int C, int HW) {
-  return GluePlan{"position", dim3(min(cdiv(HW, 256), 64), C / 16, N)};
+static GluePlan b16_convert_plan(int N, int C, long long HW) {
+  if (!b16_dims_ok(N, C, HW)) return glue_refused();
+  return GluePlan{0, dim3(min(cdiv(HW, 256), 64), C / 16, N)};
 }
 extern "C" int avsep_bn_bwd_apply_to_b16(const float* dz, const float* y, const float* pqr, int32_t N, int32_t C, int32_t HW, void* out,
                                          avsep_stream_t stream) {
-  if (!dz || !y || !pqr || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(f32_bn_bwd_apply_to_b16_kernel, b16_convert_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, dz, y,
+  const GluePlan pl = b16_convert_plan(N, C, HW);
+  if (!dz || !y || !pqr || !out || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(f32_bn_bwd_apply_to_b16_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, y,
                      pqr, C, HW, (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
-static bool b16_dims_ok(int N, int C, long long HW) {
-  return N > 0 && N <= 65535 && C > 0 && C % 16 == 0 && C / 16 <= 65535 && HW > 0 && HW < (1LL << 30);
-}
 extern "C" int avsep_f32_to_b16(const float* x, int32_t N, int32_t C, int32_t HW, void* out, avsep_stream_t stream) {
-  if (!x || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(f32_to_b16_kernel, b16_convert_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, x, C, HW,
+  const GluePlan pl = b16_convert_plan(N, C, HW);
+  if (!x || !out || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(f32_to_b16_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x, C, HW,
                      (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
 extern "C" int avsep_b16_to_f32(const void* x, int32_t N, int32_t C, int32_t HW, float* out, avsep_stream_t stream) {
-  if (!x || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_to_f32_kernel, b16_convert_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream,
+  const GluePlan pl = b16_convert_plan(N, C, HW);
+  if (!x || !out || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(b16_to_f32_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream,
                      (const u32x4*)x, C, HW, out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
 
 // ---- elementwise passes: grid (slot chunks, C/16, image slices) ---------------------------------------------------------------
+enum { B16_SLOT, B16_SLOT_IMAGES };
+// the grid over HW positions per image, whatever image they belong to (an input, a pooled or an upsampled map)
 static GluePlan b16_grid(int N, int C, long long HW) {
   const int gx = (int)min((HW * 2 + 255) / 256, (long long)32);
   int gz = N;
   const long long want = 4096;                        // enough workgroups for 256 CUs without one per image on big batches
   if ((long long)gx * (C / 16) * gz > want) gz = (int)max(1LL, want / ((long long)gx * (C / 16)));
   if (gz > N) gz = N;
-  return GluePlan{gz < N ? "slot,images" : "slot", dim3(gx, C / 16, gz)};
+  return GluePlan{gz < N ? B16_SLOT_IMAGES : B16_SLOT, dim3(gx, C / 16, gz)};
+}
+// a pass over a B16 image [N, C, HW]
+static GluePlan b16_slot_plan(int N, int C, long long HW) {
+  return b16_dims_ok(N, C, HW) ? b16_grid(N, C, HW) : glue_refused();
+}
+// the 3x3 / stride-2 pools over a B16 image [N, C, H, W]: a pass over the pooled map, or (the backward apply) over the input
+static GluePlan b16_pool_plan(int N, int C, int H, int W, bool pooled) {
+  if (H <= 0 || W <= 0 || !b16_dims_ok(N, C, (long long)H * W)) return glue_refused();
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  return b16_grid(N, C, pooled ? (long long)Ho * Wo : (long long)H * W);
 }
 
 // z = act(scale*y + shift [+ res_scale*res + res_shift | + res])
@@ -181,10 +196,11 @@ __global__ __launch_bounds__(256) void b16_affine_act_kernel(const u32x4* __rest
 extern "C" int avsep_b16_affine_act(const void* y, const float* scale, const float* shift, const void* residual,
                                     const float* res_scale, const float* res_shift, int32_t act, int32_t N, int32_t C, int32_t HW,
                                     void* z, avsep_stream_t stream) {
-  if (!y || !z || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
+  const GluePlan pl = b16_slot_plan(N, C, HW);
+  if (!y || !z || pl.refused()) return AVSEP_ERR_ARG;
   if ((scale == nullptr) != (shift == nullptr) || (res_scale == nullptr) != (res_shift == nullptr)) return AVSEP_ERR_ARG;
   if (act != AVSEP_ACT_NONE && act != AVSEP_ACT_RELU && act != AVSEP_ACT_LRELU02) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_affine_act_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y, scale, shift,
+  hipLaunchKernelGGL(b16_affine_act_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y, scale, shift,
                      (const u32x4*)residual, res_scale, res_shift, act, N, C, HW, (u32x4*)z);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -237,11 +253,12 @@ extern "C" int avsep_b16_affine_act_bwd(const void* dz, const void* dz2, const v
                                         const void* residual, const float* res_scale, const float* res_shift, const void* add,
                                         const float* mean, const float* invstd, int32_t act, int32_t N, int32_t C, int32_t HW,
                                         void* out, double* bstats, avsep_stream_t stream) {
-  if (!dz || !y || (!out && !bstats) || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
+  const GluePlan pl = b16_slot_plan(N, C, HW);
+  if (!dz || !y || (!out && !bstats) || pl.refused()) return AVSEP_ERR_ARG;
   if ((scale == nullptr) != (shift == nullptr) || (res_scale == nullptr) != (res_shift == nullptr)) return AVSEP_ERR_ARG;
   if (bstats && (!mean || !invstd)) return AVSEP_ERR_ARG;
   if (act != AVSEP_ACT_NONE && act != AVSEP_ACT_RELU && act != AVSEP_ACT_LRELU02) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_affine_act_bwd_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
+  hipLaunchKernelGGL(b16_affine_act_bwd_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
                      (const u32x4*)dz2, (const u32x4*)y, scale, shift, (const u32x4*)residual, res_scale, res_shift,
                      (const u32x4*)add, mean, invstd, act, N, C, HW, (u32x4*)out, bstats);
   AVSEP_LAUNCH_CHECK();
@@ -268,8 +285,9 @@ __global__ __launch_bounds__(256) void b16_bn_bwd_apply_kernel(const u32x4* __re
 }
 extern "C" int avsep_b16_bn_bwd_apply(const void* dz, const void* y, const float* pqr, int32_t N, int32_t C, int32_t HW, void* out,
                                       avsep_stream_t stream) {
-  if (!dz || !y || !pqr || !out || !b16_dims_ok(N, C, HW)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_bn_bwd_apply_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
+  const GluePlan pl = b16_slot_plan(N, C, HW);
+  if (!dz || !y || !pqr || !out || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(b16_bn_bwd_apply_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)dz,
                      (const u32x4*)y, pqr, N, C, HW, (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -298,8 +316,10 @@ __global__ void b16_sum_finish_kernel(const double* acc, int C, float* out) {
 }
 // acc: 2*C zeroed doubles of workspace
 int b16_channel_sum(const void* x, int N, int C, int HW, double* acc, float* out, hipStream_t st) {
+  const GluePlan pl = b16_slot_plan(N, C, HW);
+  if (pl.refused()) return AVSEP_ERR_ARG;
   if (hipMemsetAsync(acc, 0, (size_t)2 * C * sizeof(double), st) != hipSuccess) return AVSEP_ERR_LAUNCH;
-  hipLaunchKernelGGL(b16_channel_sum_kernel, b16_grid(N, C, HW).grid, dim3(256), 0, st, (const u32x4*)x, N, C, HW, acc);
+  hipLaunchKernelGGL(b16_channel_sum_kernel, pl.grid, dim3(256), 0, st, (const u32x4*)x, N, C, HW, acc);
   hipLaunchKernelGGL(b16_sum_finish_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, acc, C, out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -345,15 +365,22 @@ __global__ __launch_bounds__(256) void b16_relu_up2x_fwd_kernel(const u32x4* __r
     }
   }
 }
+// two B16 sources [N, C0 | C1, H, W] (C1 = 0: one source) whose images fit grid.z and whose hi-res slots fit 32-bit indices
+static bool b16_up2x_dims_ok(int N, int C0, int C1, int H, int W) {
+  return N > 0 && N <= 65535 && C0 > 0 && C0 % 16 == 0 && C1 >= 0 && C1 % 16 == 0 && H > 0 && W > 0 &&
+         (long long)H * W < (1LL << 27);
+}
+static GluePlan b16_relu_up2x_fwd_plan(int N, int C0, int C1, int H, int W) {
+  return b16_up2x_dims_ok(N, C0, C1, H, W) ? b16_grid(N, C0 + C1, 4LL * H * W) : glue_refused();
+}
 extern "C" int avsep_b16_relu_up2x_fwd(const void* x0, const void* x1, const float* sc0, const float* sh0, const float* sc1,
                                        const float* sh1, int32_t N, int32_t C0, int32_t C1, int32_t H, int32_t W, void* out,
                                        avsep_stream_t stream) {
-  if (!x0 || !out || N <= 0 || N > 65535 || C0 <= 0 || C0 % 16 || C1 < 0 || C1 % 16 || (C1 > 0 && !x1) || H <= 0 || W <= 0 ||
-      (long long)H * W >= (1LL << 27))
-    return AVSEP_ERR_ARG;
+  const GluePlan pl = b16_relu_up2x_fwd_plan(N, C0, C1, H, W);
+  if (!x0 || !out || (C1 > 0 && !x1) || pl.refused()) return AVSEP_ERR_ARG;
   if ((sc0 == nullptr) != (sh0 == nullptr) || (sc1 == nullptr) != (sh1 == nullptr)) return AVSEP_ERR_ARG;
   const float rh = H > 1 ? (float)(H - 1) / (float)(2 * H - 1) : 0.f, rw = W > 1 ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
-  hipLaunchKernelGGL(b16_relu_up2x_fwd_kernel, b16_grid(N, C0 + C1, 4LL * H * W).grid, dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(b16_relu_up2x_fwd_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream,
                      (const u32x4*)x0, (const u32x4*)x1, sc0, sh0, sc1, sh1, N, C0, C1, H, W, rh, rw, (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -484,22 +511,26 @@ __global__ __launch_bounds__(256) void b16_relu_up2x_bwd_kernel(const u32x4* __r
   }
   if (!first && bstats1) b16_block_stats(s1, s2, cbs, C1, bstats1);
 }
+// grid (tiles, (C0 + C1)/16, image slices): 8192 workgroups at the most once there are several images; arg[0] = tiles per row
+static GluePlan b16_relu_up2x_bwd_plan(int N, int C0, int C1, int H, int W) {
+  if (!b16_up2x_dims_ok(N, C0, C1, H, W)) return glue_refused();
+  const int tx = cdiv(W, B16U_TW), tyc = cdiv(H, B16U_TH), CB = (C0 + C1) / 16;
+  int gz = N;
+  if ((long long)tx * tyc * CB * gz > 8192) gz = (int)max(1LL, 8192LL / ((long long)tx * tyc * CB));
+  return GluePlan{0, dim3(tx * tyc, CB, gz), {tx, 0}};
+}
 extern "C" int avsep_b16_relu_up2x_bwd(const void* x0, const void* x1, const float* sc0, const float* sh0, const float* sc1,
                                        const float* sh1, int32_t N, int32_t C0, int32_t C1, int32_t H, int32_t W, const void* dout,
                                        void* g0, void* g1, const float* mean1, const float* invstd1, double* bstats1, int32_t acc0,
                                        avsep_stream_t stream) {
-  if (!x0 || !dout || !g0 || N <= 0 || N > 65535 || C0 <= 0 || C0 % 16 || C1 < 0 || C1 % 16 || (C1 > 0 && (!x1 || !g1)) ||
-      H <= 0 || W <= 0 || (long long)H * W >= (1LL << 27))
-    return AVSEP_ERR_ARG;
+  const GluePlan pl = b16_relu_up2x_bwd_plan(N, C0, C1, H, W);
+  if (!x0 || !dout || !g0 || (C1 > 0 && (!x1 || !g1)) || pl.refused()) return AVSEP_ERR_ARG;
   if ((sc0 == nullptr) != (sh0 == nullptr) || (sc1 == nullptr) != (sh1 == nullptr)) return AVSEP_ERR_ARG;
   if (bstats1 && (!mean1 || !invstd1 || C1 == 0)) return AVSEP_ERR_ARG;
   const float rh = H > 1 ? (float)(H - 1) / (float)(2 * H - 1) : 0.f, rw = W > 1 ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
-  const int tx = cdiv(W, B16U_TW), tyc = cdiv(H, B16U_TH), CB = (C0 + C1) / 16;
-  int gz = N;
-  if ((long long)tx * tyc * CB * gz > 8192) gz = (int)max(1LL, 8192LL / ((long long)tx * tyc * CB));
-  hipLaunchKernelGGL(b16_relu_up2x_bwd_kernel, dim3(tx * tyc, CB, gz), dim3(256), 0, (hipStream_t)stream, (const u32x4*)x0,
+  hipLaunchKernelGGL(b16_relu_up2x_bwd_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)x0,
                      (const u32x4*)x1, sc0, sh0, sc1, sh1, N, C0, C1, H, W, rh, rw, (const u32x4*)dout, (u32x4*)g0, (u32x4*)g1,
-                     mean1, invstd1, bstats1, acc0, tx);
+                     mean1, invstd1, bstats1, acc0, pl.arg[0]);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -547,10 +578,11 @@ __global__ __launch_bounds__(256) void b16_maxpool_fwd_kernel(const u32x4* __res
 }
 extern "C" int avsep_b16_maxpool3x3s2_fwd(const void* y, const float* scale, const float* shift, int32_t act, int32_t N, int32_t C,
                                           int32_t H, int32_t W, void* z, void* idx, avsep_stream_t stream) {
-  if (!y || !z || H <= 0 || W <= 0 || !b16_dims_ok(N, C, (long long)H * W)) return AVSEP_ERR_ARG;
+  const GluePlan pl = b16_pool_plan(N, C, H, W, true);
+  if (!y || !z || pl.refused()) return AVSEP_ERR_ARG;
   if ((scale == nullptr) != (shift == nullptr)) return AVSEP_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(b16_maxpool_fwd_kernel, b16_grid(N, C, (long long)Ho * Wo).grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y,
+  hipLaunchKernelGGL(b16_maxpool_fwd_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)y,
                      scale, shift, act, N, C, H, W, Ho, Wo, (u32x4*)z, (uint2*)idx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -644,16 +676,17 @@ extern "C" int avsep_b16_maxpool_bn_relu_bwd(const void* g, const void* g2, cons
                                              const float* shift, const float* mean, const float* invstd, const float* pqr,
                                              int32_t N, int32_t C, int32_t H, int32_t W, double* bstats, void* dy, int32_t dy_f32,
                                              avsep_stream_t stream) {
-  if (!g || !idx || !y || !scale || !shift || H <= 0 || W <= 0 || !b16_dims_ok(N, C, (long long)H * W)) return AVSEP_ERR_ARG;
+  const GluePlan pl = b16_pool_plan(N, C, H, W, dy == nullptr);
+  if (!g || !idx || !y || !scale || !shift || pl.refused()) return AVSEP_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   if (!dy) {                        // pass 1
     if (!bstats || !mean || !invstd) return AVSEP_ERR_ARG;
-    hipLaunchKernelGGL(b16_maxpool_bwd_stats_kernel, b16_grid(N, C, (long long)Ho * Wo).grid, dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(b16_maxpool_bwd_stats_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream,
                        (const u32x4*)g, (const u32x4*)g2, (const uint2*)idx, (const u32x4*)y, scale, shift, mean, invstd, N, C, H, W,
                        Ho, Wo, bstats);
   } else {                          // pass 2
     if (!pqr) return AVSEP_ERR_ARG;
-    hipLaunchKernelGGL(b16_maxpool_bwd_apply_kernel, b16_grid(N, C, (long long)H * W).grid, dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(b16_maxpool_bwd_apply_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream,
                        (const u32x4*)g, (const u32x4*)g2, (const uint2*)idx, (const u32x4*)y, scale, shift, pqr, N, C, H, W, Ho, Wo,
                        dy_f32 ? nullptr : (u32x4*)dy, dy_f32 ? (float*)dy : nullptr);
   }
@@ -687,13 +720,17 @@ __global__ __launch_bounds__(256) void b16_space_to_depth2_kernel(const float* _
     xs[i] = b16_pack8(v);
   }
 }
-static GluePlan b16_space_to_depth2_plan(long long total) {
-  return GluePlan{"flat", dim3((int)min((total + 255) / 256, (long long)262144))};
+// one thread per 8-channel slot of the output (4C <= 16: the phase channels fill one block)
+static GluePlan b16_space_to_depth2_plan(int N, int C, int H, int W) {
+  if (N <= 0 || C <= 0 || C > 4 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return glue_refused();
+  const long long total = (long long)N * (H / 2 + 3) * (W / 2 + 3) * 2;
+  return GluePlan{0, dim3((int)min((total + 255) / 256, (long long)262144))};
 }
 extern "C" int avsep_b16_space_to_depth2(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, void* xs, avsep_stream_t stream) {
-  if (!x || !xs || N <= 0 || C <= 0 || 4 * C > 16 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return AVSEP_ERR_ARG;
+  const GluePlan pl = b16_space_to_depth2_plan(N, C, H, W);
+  if (!x || !xs || pl.refused()) return AVSEP_ERR_ARG;
   const long long total = (long long)N * (H / 2 + 3) * (W / 2 + 3) * 2;
-  hipLaunchKernelGGL(b16_space_to_depth2_kernel, b16_space_to_depth2_plan(total).grid, dim3(256), 0,
+  hipLaunchKernelGGL(b16_space_to_depth2_kernel, pl.grid, dim3(256), 0,
                      (hipStream_t)stream, x, C, H, W, total, (u32x4*)xs);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -734,14 +771,28 @@ __global__ __launch_bounds__(256) void b16_grid_pack_kernel(const void* __restri
   }
   out[((long long)cb * HG * WG + pos) * 2 + half] = q;
 }
+// N images [C, H, W] at pitch (PY, PX), GX per row, inside one grid image [C, HG, WG] with 32-bit slot indices
+static bool grid_image_ok(int N, int C, int H, int W, int GX, int PY, int PX, int HG, int WG) {
+  return N > 0 && C > 0 && C % 16 == 0 && H > 0 && W > 0 && GX > 0 && PY >= H && PX >= W && HG > 0 && WG > 0 && HG % PY == 0 &&
+         WG == GX * PX && (long long)(HG / PY) * GX >= N && (long long)HG * WG < (1LL << 27);
+}
+// a thread per slot of the grid image (pack) or of the batch's images (unpack); grid (slot chunks, C/16)
+static GluePlan b16_grid_pack_plan(int N, int C, int H, int W, int GX, int PY, int PX, int HG, int WG) {
+  if (!grid_image_ok(N, C, H, W, GX, PY, PX, HG, WG)) return glue_refused();
+  return GluePlan{0, dim3(cdiv(HG * WG * 2, 256), C / 16)};
+}
+static GluePlan grid_unpack_plan(int N, int C, int H, int W, int GX, int PY, int PX, int HG, int WG) {
+  if (!grid_image_ok(N, C, H, W, GX, PY, PX, HG, WG) || (long long)N * H * W >= (1LL << 27)) return glue_refused();
+  return GluePlan{0, dim3(cdiv(N * H * W * 2, 256), C / 16)};
+}
 extern "C" int avsep_b16_grid_pack(const void* x, int32_t xfmt, int32_t N, int32_t C, int32_t H, int32_t W, int32_t GX, int32_t PY,
                                    int32_t PX, int32_t HG, int32_t WG, const float* scale, const float* shift, int32_t act, void* out,
                                    avsep_stream_t stream) {
-  if (!x || !out || (xfmt != AVSEP_FMT_F32 && xfmt != AVSEP_FMT_B16) || N <= 0 || C <= 0 || C % 16 || H <= 0 || W <= 0 || GX <= 0 ||
-      PY < H || PX < W || HG <= 0 || WG <= 0 || HG % PY || WG != GX * PX || (long long)(HG / PY) * GX < N ||
-      (long long)HG * WG >= (1LL << 27) || (scale == nullptr) != (shift == nullptr) || act < 0 || act > 2)
+  const GluePlan pl = b16_grid_pack_plan(N, C, H, W, GX, PY, PX, HG, WG);
+  if (!x || !out || (xfmt != AVSEP_FMT_F32 && xfmt != AVSEP_FMT_B16) || pl.refused() ||
+      (scale == nullptr) != (shift == nullptr) || act < 0 || act > 2)
     return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(b16_grid_pack_kernel, dim3(cdiv(HG * WG * 2, 256), C / 16), dim3(256), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(b16_grid_pack_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x,
                      (int)(xfmt == AVSEP_FMT_F32), N, C, H, W, GX, PY, PX, HG, WG, scale, shift, act, (u32x4*)out);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -779,33 +830,37 @@ __global__ __launch_bounds__(256) void grid_unpack_kernel(const float* __restric
 }
 extern "C" int avsep_grid_unpack(const float* grid, int32_t N, int32_t C, int32_t H, int32_t W, int32_t GX, int32_t PY, int32_t PX,
                                  int32_t HG, int32_t WG, void* out, int32_t ofmt, double* stats, avsep_stream_t stream) {
-  if (!grid || !out || (ofmt != AVSEP_FMT_F32 && ofmt != AVSEP_FMT_B16) || N <= 0 || C <= 0 || C % 16 || H <= 0 || W <= 0 || GX <= 0 ||
-      PY < H || PX < W || HG <= 0 || WG <= 0 || HG % PY || WG != GX * PX || (long long)(HG / PY) * GX < N ||
-      (long long)HG * WG >= (1LL << 27) || (long long)N * H * W >= (1LL << 27))
-    return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(grid_unpack_kernel, dim3(cdiv(N * H * W * 2, 256), C / 16), dim3(256), 0, (hipStream_t)stream, grid, N, C, H, W, GX,
+  const GluePlan pl = grid_unpack_plan(N, C, H, W, GX, PY, PX, HG, WG);
+  if (!grid || !out || (ofmt != AVSEP_FMT_F32 && ofmt != AVSEP_FMT_B16) || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(grid_unpack_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, grid, N, C, H, W, GX,
                      PY, PX, HG, WG, out, (int)(ofmt == AVSEP_FMT_F32), stats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
 
-// ---- launch plans of the launchers above, for avsep_glue_plan (ops.hip) ---------------------------------------------------------------
-bool b16_glue_plan(const char* op, int N, int C, int H, int W, int aux, GluePlan* out) {
-  (void)aux;
-  auto is = [&](const char* name) { return strcmp(op, name) == 0; };
-  const long long HW = (long long)H * W;
-  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (is("b16_space_to_depth2")) {
-    if (4 * C > 16 || (H & 1) || (W & 1)) return false;
-    *out = b16_space_to_depth2_plan((long long)N * (H / 2 + 3) * (W / 2 + 3) * 2);
-    return true;
-  }
-  if (!b16_dims_ok(N, C, HW)) return false;
-  if (is("f32_to_b16") || is("b16_to_f32") || is("bn_bwd_apply_to_b16")) *out = b16_convert_plan(N, C, (int)HW);
-  else if (is("b16_affine_act") || is("b16_affine_act_bwd") || is("b16_bn_bwd_apply") || is("b16_channel_sum") ||
-           is("b16_maxpool_bwd_apply"))
-    *out = b16_grid(N, C, HW);
-  else if (is("b16_maxpool_fwd") || is("b16_maxpool_bwd_stats")) *out = b16_grid(N, C, (long long)Ho * Wo);
-  else return false;
-  return true;
+// ---- this file's rows of avsep_glue_plan (common.h, ops.hip): form names in the order of the plan's enum -------------------------------
+static GluePlan convert_query(int N, int C, int H, int W, int) { return b16_convert_plan(N, C, (long long)H * W); }
+static GluePlan slot_query(int N, int C, int H, int W, int) { return b16_slot_plan(N, C, (long long)H * W); }
+static GluePlan pooled_query(int N, int C, int H, int W, int) { return b16_pool_plan(N, C, H, W, true); }
+#define SLOT_FORMS {"slot", "slot,images"}
+static const GluePlanRow glue_rows[] = {
+    {"f32_to_b16", {"position"}, convert_query},
+    {"b16_to_f32", {"position"}, convert_query},
+    {"bn_bwd_apply_to_b16", {"position"}, convert_query},
+    {"b16_affine_act", SLOT_FORMS, slot_query},
+    {"b16_affine_act_bwd", SLOT_FORMS, slot_query},
+    {"b16_bn_bwd_apply", SLOT_FORMS, slot_query},
+    {"b16_channel_sum", SLOT_FORMS, slot_query},
+    {"b16_maxpool_fwd", SLOT_FORMS, pooled_query},
+    {"b16_maxpool_bwd_stats", SLOT_FORMS, pooled_query},
+    {"b16_maxpool_bwd_apply", SLOT_FORMS, [](int N, int C, int H, int W, int) { return b16_pool_plan(N, C, H, W, false); }},
+    // the decoder glue: C = C0 + C1 with C0 = aux
+    {"b16_relu_up2x_fwd", SLOT_FORMS, [](int N, int C, int H, int W, int C0) { return b16_relu_up2x_fwd_plan(N, C0, C - C0, H, W); }},
+    {"b16_relu_up2x_bwd", {"tile"}, [](int N, int C, int H, int W, int C0) { return b16_relu_up2x_bwd_plan(N, C0, C - C0, H, W); }},
+    {"b16_space_to_depth2", {"flat"}, [](int N, int C, int H, int W, int) { return b16_space_to_depth2_plan(N, C, H, W); }},
+};
+#undef SLOT_FORMS
+const GluePlanRow* b16_glue_rows(int* count) {
+  *count = (int)(sizeof(glue_rows) / sizeof(glue_rows[0]));
+  return glue_rows;
 }

@@ -15,11 +15,26 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
-// Launch plan of a glue kernel (ops.hip, b16.hip): the kernel form a launcher picks for a shape and its grid.  Every launcher
-// takes both from its *_plan function, and avsep_glue_plan reports the same answer on the host.
-struct GluePlan { const char* form; dim3 grid; };
-// b16.hip's share of avsep_glue_plan: false when `op` is none of its launchers or the shape is one its launcher refuses
-bool b16_glue_plan(const char* op, int N, int C, int H, int W, int aux, GluePlan* out);
+// Launch plan of a glue kernel (ops.hip, b16.hip): what a launcher's *_plan function decides for a shape, and nothing else
+// decides it: whether the shape is taken at all, the kernel form (the op's own enum; refused when negative), the grid, and
+// the kernel arguments that are grid arithmetic too (the decoder glue's log2 widths and tiles per row; 0 elsewhere).  A
+// launcher checks its pointers, calls its plan, returns AVSEP_ERR_ARG on refusal and switches on the form.
+struct GluePlan {
+  int form;
+  dim3 grid;
+  int arg[2];
+  bool refused() const { return form < 0; }
+};
+static inline GluePlan glue_refused() { return GluePlan{-1, dim3(0, 0, 0), {0, 0}}; }
+// avsep_glue_plan (ops.hip) is a lookup in rows of this kind: the op's name, the names of its forms in enum order, and the
+// adaptor from the query's (N, C, H, W, aux) to the arguments of the plan function the launcher calls.  An adaptor restates
+// how the five integers map to an entry point's arguments and guards nothing.
+struct GluePlanRow {
+  const char* op;
+  const char* forms[3];
+  GluePlan (*plan)(int N, int C, int H, int W, int aux);
+};
+const GluePlanRow* b16_glue_rows(int* count);     // b16.hip's rows
 // The Winograd kernels load x / dY through buffer resources of num_records = 0xfffffff0 with 32-bit byte offsets.  A tensor of
 // `elems` floats whose resource base lies `shift` elements before its first element is addressable as a whole when the byte
 // offset of its last element, plus 4, stays within num_records; beyond it a valid element loads as 0 or wraps round.
@@ -74,6 +89,20 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+// BatchNorm sums of a 256-thread workgroup that works on ONE channel: the threads' partial sums (s1, s2) are added over each
+// wave in fp64, over the four waves through LDS, and thread 0 issues one pair of fp64 atomics at stats[c] and stats[C + c].
+// Every thread of the workgroup must call it (it holds a barrier).
+__device__ __forceinline__ void block_stats_add(double s1, double s2, int c, int C, double* stats) {
+  s1 = wave_sum_d(s1);
+  s2 = wave_sum_d(s2);
+  __shared__ double sh[8];
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = s1; sh[4 + (threadIdx.x >> 6)] = s2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(&stats[c], sh[0] + sh[1] + sh[2] + sh[3]);
+    atomicAdd(&stats[C + c], sh[4] + sh[5] + sh[6] + sh[7]);
+  }
 }
 // sum within each 32-lane half of the wave
 __device__ __forceinline__ float half_sum(float v) {

@@ -28,27 +28,22 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
   }
   ds += s;
   dq += q;
-  ds = wave_sum_d(ds);
-  dq = wave_sum_d(dq);
-  __shared__ double sh[8];
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = ds; sh[4 + (threadIdx.x >> 6)] = dq; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(&stats[c], sh[0] + sh[1] + sh[2] + sh[3]);
-    atomicAdd(&stats[C + c], sh[4] + sh[5] + sh[6] + sh[7]);
-  }
+  block_stats_add(ds, dq, c, C, stats);
 }
 
-static GluePlan channel_stats_plan(int N, int C, int HW) {
+// (HW: whatever an int32 argument can carry; the plan query computes it as H * W)
+static GluePlan channel_stats_plan(int N, int C, long long HW) {
+  if (N <= 0 || C <= 0 || HW <= 0 || HW > 0x7fffffffLL) return glue_refused();
   long long total = (long long)N * HW;
   int chunks = (int)min((long long)cdiv(2048, C), (total + 4095) / 4096);
   if (chunks < 1) chunks = 1;
-  return GluePlan{"chunks", dim3(C, chunks)};
+  return GluePlan{0, dim3(C, chunks)};
 }
 extern "C" int avsep_channel_stats(const float* x, int32_t N, int32_t C, int32_t HW, double* stats,
                                    avsep_stream_t stream) {
-  if (!x || !stats || N <= 0 || C <= 0 || HW <= 0) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(channel_stats_kernel, channel_stats_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, x, N, C, HW, stats);
+  const GluePlan pl = channel_stats_plan(N, C, HW);
+  if (!x || !stats || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(channel_stats_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x, N, C, HW, stats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -153,16 +148,22 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   }
 }
 
-// (the kernel itself takes the 16-byte form when HW % 4 == 0)
-static GluePlan bn_bwd_apply_plan(int N, int C, int HW) {
+// forms of bn_bwd_apply and affine_act: one kernel each, which takes the 16-byte path itself when HW % 4 == 0
+enum { FORM_VEC4, FORM_SCALAR };
+// their grid (x, C, N): C and N must fit grid.y and grid.z
+static bool plane_grid_ok(int N, int C, long long HW) {
+  return N > 0 && N <= 65535 && C > 0 && C <= 65535 && HW > 0 && HW <= 0x7fffffffLL;
+}
+static GluePlan bn_bwd_apply_plan(int N, int C, long long HW) {
+  if (!plane_grid_ok(N, C, HW)) return glue_refused();
   int gx = min(cdiv(HW, 1024), 64);
-  return GluePlan{(HW & 3) == 0 ? "vec4" : "scalar", dim3(gx, C, N)};
+  return GluePlan{(HW & 3) == 0 ? FORM_VEC4 : FORM_SCALAR, dim3(gx, C, N)};
 }
 extern "C" int avsep_bn_bwd_apply(const float* dz, const float* y, const float* pqr, int32_t N, int32_t C, int32_t HW,
                                   float* dy, avsep_stream_t stream) {
-  if (!dz || !y || !pqr || !dy || N <= 0 || C <= 0 || HW <= 0) return AVSEP_ERR_ARG;
-  if (C > 65535 || N > 65535) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, bn_bwd_apply_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, dz, y, pqr, C, HW, dy);
+  const GluePlan pl = bn_bwd_apply_plan(N, C, HW);
+  if (!dz || !y || !pqr || !dy || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, y, pqr, C, HW, dy);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -199,16 +200,18 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
   }
 }
 
-static GluePlan affine_act_plan(int N, int C, int HW) {
+static GluePlan affine_act_plan(int N, int C, long long HW) {
+  if (!plane_grid_ok(N, C, HW)) return glue_refused();
   int gx = min(cdiv(HW, (HW & 3) == 0 ? 1024 : 256), 64);
-  return GluePlan{(HW & 3) == 0 ? "vec4" : "scalar", dim3(gx, C, N)};
+  return GluePlan{(HW & 3) == 0 ? FORM_VEC4 : FORM_SCALAR, dim3(gx, C, N)};
 }
 extern "C" int avsep_affine_act(const float* y, const float* scale, const float* shift, const float* residual,
                                 const float* res_scale, const float* res_shift, int32_t act, int32_t N, int32_t C,
                                 int32_t HW, float* z, avsep_stream_t stream) {
-  if (!y || !z || N <= 0 || C <= 0 || HW <= 0 || C > 65535 || N > 65535) return AVSEP_ERR_ARG;
+  const GluePlan pl = affine_act_plan(N, C, HW);
+  if (!y || !z || pl.refused()) return AVSEP_ERR_ARG;
   if ((res_scale == nullptr) != (res_shift == nullptr)) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(affine_act_kernel, affine_act_plan(N, C, HW).grid, dim3(256), 0, (hipStream_t)stream, y, scale, shift, residual,
+  hipLaunchKernelGGL(affine_act_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, y, scale, shift, residual,
                      res_scale, res_shift, act, C, HW, z);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -259,39 +262,34 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const float* __rest
     }
     *reinterpret_cast<fv*>(out + o) = gv;
   }
-  if (bstats) {
-    double d1 = wave_sum_d((double)s1), d2 = wave_sum_d((double)s2);
-    __shared__ double sh2[8];
-    if ((threadIdx.x & 63) == 0) { sh2[threadIdx.x >> 6] = d1; sh2[4 + (threadIdx.x >> 6)] = d2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      atomicAdd(&bstats[c], sh2[0] + sh2[1] + sh2[2] + sh2[3]);
-      atomicAdd(&bstats[C + c], sh2[4] + sh2[5] + sh2[6] + sh2[7]);
-    }
-  }
+  if (bstats) block_stats_add((double)s1, (double)s2, c, C, bstats);
 }
 
-static GluePlan affine_act_bwd_plan(int N, int C, int HW) {
+enum { AFFINE_BWD_V4, AFFINE_BWD_V1 };
+static GluePlan affine_act_bwd_plan(int N, int C, long long HW) {
   long long total = (long long)N * HW;
+  if (N <= 0 || C <= 0 || HW <= 0 || HW > 0x7fffffffLL || total > 0x7fffffffLL) return glue_refused();   // the kernel indexes (n, hw) in 32 bits
   int chunks = (int)min((long long)cdiv(2048, C), (total + 2047) / 2048);
   if (chunks < 1) chunks = 1;
-  return GluePlan{(HW & 3) == 0 ? "v4" : "v1", dim3(C, chunks)};
+  return GluePlan{(HW & 3) == 0 ? AFFINE_BWD_V4 : AFFINE_BWD_V1, dim3(C, chunks)};
 }
 extern "C" int avsep_affine_act_bwd(const float* dz, const float* dz2, const float* y, const float* scale, const float* shift,
                                     const float* residual, const float* res_scale, const float* res_shift,
                                     const float* add, const float* mean, const float* invstd, int32_t act, int32_t N,
                                     int32_t C, int32_t HW, float* dz_pre, double* bstats, avsep_stream_t stream) {
-  if (!dz || !y || !dz_pre || N <= 0 || C <= 0 || HW <= 0) return AVSEP_ERR_ARG;
-  if (bstats && (!mean || !invstd)) return AVSEP_ERR_ARG;
-  long long total = (long long)N * HW;
-  if (total > 0x7fffffffLL) return AVSEP_ERR_ARG;
   const GluePlan pl = affine_act_bwd_plan(N, C, HW);
-  if (pl.form[1] == '4')
-    hipLaunchKernelGGL(affine_act_bwd_kernel<4>, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
-                       residual, res_scale, res_shift, add, mean, invstd, act, N, C, HW, dz_pre, bstats);
-  else
-    hipLaunchKernelGGL(affine_act_bwd_kernel<1>, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
-                       residual, res_scale, res_shift, add, mean, invstd, act, N, C, HW, dz_pre, bstats);
+  if (!dz || !y || !dz_pre || pl.refused()) return AVSEP_ERR_ARG;
+  if (bstats && (!mean || !invstd)) return AVSEP_ERR_ARG;
+  switch (pl.form) {
+    case AFFINE_BWD_V4:
+      hipLaunchKernelGGL(affine_act_bwd_kernel<4>, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
+                         residual, res_scale, res_shift, add, mean, invstd, act, N, C, HW, dz_pre, bstats);
+      break;
+    case AFFINE_BWD_V1:
+      hipLaunchKernelGGL(affine_act_bwd_kernel<1>, pl.grid, dim3(256), 0, (hipStream_t)stream, dz, dz2, y, scale, shift,
+                         residual, res_scale, res_shift, add, mean, invstd, act, N, C, HW, dz_pre, bstats);
+      break;
+  }
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -549,7 +547,7 @@ __global__ __launch_bounds__(256) void relu_up2x_bwd_sweep_kernel(CatArgs a, con
       atomicAdd(&bstats1[cs], d1);
       atomicAdd(&bstats1[a.C1 + cs], d2);
     }
-  } else if (stats) {
+  } else if (stats) {                                    // (block_stats_add in place: through the helper this kernel's code differs)
     const double d1 = wave_sum_d((double)s1), d2 = wave_sum_d((double)s2);
     __shared__ double sh2[8];
     if ((threadIdx.x & 63) == 0) { sh2[threadIdx.x >> 6] = d1; sh2[4 + (threadIdx.x >> 6)] = d2; }
@@ -561,14 +559,6 @@ __global__ __launch_bounds__(256) void relu_up2x_bwd_sweep_kernel(CatArgs a, con
   }
 }
 
-// log2 of the lanes per low-res row (W/2) when the static-pair kernels apply, else -1
-static int up2x_pair_lw(const avsep_cat_desc* d) {
-  if (d->bcast0 || d->bcast1 || d->W < 4 || d->W > 128 || (d->W & (d->W - 1)) || d->H < 2) return -1;
-  int lw = 0;
-  while ((2 << lw) < d->W) ++lw;
-  return lw;
-}
-
 static CatArgs make_cat(const avsep_cat_desc* d) {
   CatArgs a{};
   a.N = d->N; a.C0 = d->C0; a.C1 = d->C1; a.H = d->H; a.W = d->W; a.b0 = d->bcast0; a.b1 = d->bcast1;
@@ -577,40 +567,56 @@ static CatArgs make_cat(const avsep_cat_desc* d) {
   a.rw = (float)(d->W - 1) / (float)(2 * d->W - 1);
   return a;
 }
-static int check_cat(const avsep_cat_desc* d) {
-  if (!d || d->N <= 0 || d->C0 <= 0 || d->C1 < 0 || d->H <= 0 || d->W <= 0 || !d->x0) return AVSEP_ERR_ARG;
-  if (d->C1 > 0 && !d->x1) return AVSEP_ERR_ARG;
-  return AVSEP_OK;
+// the descriptor's pointers and channel split; its shape [N, C0 + C1, H, W] is the plans' to judge
+static bool cat_ok(const avsep_cat_desc* d) {
+  return d && d->C0 > 0 && d->C1 >= 0 && d->x0 && (d->C1 == 0 || d->x1);
 }
 
-extern "C" int avsep_relu_up2x_fwd(const avsep_cat_desc* d, float* out, avsep_stream_t stream) {
-  int rc = check_cat(d);
-  if (rc || !out) return AVSEP_ERR_ARG;
-  CatArgs a = make_cat(d);
-  long long planes = (long long)d->N * (d->C0 + d->C1);
-  if (planes > 0x7fffffffLL || 2 * d->H > 65535) return AVSEP_ERR_ARG;
-  const int plw = up2x_pair_lw(d);
+// log2 of the lanes per low-res row (W/2) when the static-pair kernels apply, else -1
+static int up2x_pair_lw(int H, int W, bool bcast) {
+  if (bcast || W < 4 || W > 128 || (W & (W - 1)) || H < 2) return -1;
+  int lw = 0;
+  while ((2 << lw) < W) ++lw;
+  return lw;
+}
+// [N, C, H, W]: the low-res shape, C = C0 + C1; bcast: a source is an [N, C] vector.  arg[0] = log2 of the block's columns
+enum { UP2X_FWD_PAIR, UP2X_FWD_4, UP2X_FWD_GENERIC };
+static GluePlan relu_up2x_fwd_plan(int N, int C, int H, int W, bool bcast) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return glue_refused();
+  const long long planes = (long long)N * C;
+  if (planes > 0x7fffffffLL || 2 * H > 65535) return glue_refused();
+  const int plw = up2x_pair_lw(H, W, bcast);
   if (plw >= 0 && planes <= 32768LL * 65535) {
     // planes over (y, z): [64, 1024, 16, 16] sources are 65536 planes, one more than grid.y holds (they fell back to the
     // generic kernel: 1.9 TB/s)
     const unsigned gy = (unsigned)(planes < 32768 ? planes : 32768), gz = (unsigned)cdiv(planes, gy);
-    hipLaunchKernelGGL(relu_up2x_fwd_pair_kernel, dim3(cdiv((long long)(d->H + 1) << plw, 256), gy, gz), dim3(256), 0,
-                       (hipStream_t)stream, a, out, plw);
-    AVSEP_LAUNCH_CHECK();
-    return AVSEP_OK;
+    return GluePlan{UP2X_FWD_PAIR, dim3(cdiv((long long)(H + 1) << plw, 256), gy, gz), {plw, 0}};
   }
-  if (!d->bcast0 && !d->bcast1 && d->W >= 8) {              // Wo % 4 == 0: four outputs per thread, 16-byte stores
+  if (!bcast && W >= 8) {                                   // Wo % 4 == 0: four outputs per thread, 16-byte stores
     int l4 = 6;
-    while (l4 > 2 && (1 << (l4 - 1)) >= d->W / 2) --l4;
-    hipLaunchKernelGGL(relu_up2x_fwd4_kernel, dim3(cdiv(d->W / 2, 1 << l4), cdiv(2 * d->H, 256 >> l4), (unsigned)planes),
-                       dim3(256), 0, (hipStream_t)stream, a, out, l4);
-    AVSEP_LAUNCH_CHECK();
-    return AVSEP_OK;
+    while (l4 > 2 && (1 << (l4 - 1)) >= W / 2) --l4;
+    return GluePlan{UP2X_FWD_4, dim3(cdiv(W / 2, 1 << l4), cdiv(2 * H, 256 >> l4), (unsigned)planes), {l4, 0}};
   }
   int lw = 8;
-  while (lw > 2 && (1 << (lw - 1)) >= 2 * d->W) --lw;      // smallest power of two >= Wo, capped at 256
-  hipLaunchKernelGGL(relu_up2x_fwd_kernel, dim3(cdiv(2 * d->W, 1 << lw), cdiv(2 * d->H, 256 >> lw), (unsigned)planes),
-                     dim3(256), 0, (hipStream_t)stream, a, out, lw);
+  while (lw > 2 && (1 << (lw - 1)) >= 2 * W) --lw;         // smallest power of two >= Wo, capped at 256
+  return GluePlan{UP2X_FWD_GENERIC, dim3(cdiv(2 * W, 1 << lw), cdiv(2 * H, 256 >> lw), (unsigned)planes), {lw, 0}};
+}
+extern "C" int avsep_relu_up2x_fwd(const avsep_cat_desc* d, float* out, avsep_stream_t stream) {
+  if (!cat_ok(d) || !out) return AVSEP_ERR_ARG;
+  const GluePlan pl = relu_up2x_fwd_plan(d->N, d->C0 + d->C1, d->H, d->W, d->bcast0 || d->bcast1);
+  if (pl.refused()) return AVSEP_ERR_ARG;
+  CatArgs a = make_cat(d);
+  switch (pl.form) {
+    case UP2X_FWD_PAIR:
+      hipLaunchKernelGGL(relu_up2x_fwd_pair_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, a, out, pl.arg[0]);
+      break;
+    case UP2X_FWD_4:
+      hipLaunchKernelGGL(relu_up2x_fwd4_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, a, out, pl.arg[0]);
+      break;
+    case UP2X_FWD_GENERIC:
+      hipLaunchKernelGGL(relu_up2x_fwd_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, a, out, pl.arg[0]);
+      break;
+  }
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -709,54 +715,58 @@ __global__ __launch_bounds__(256) void relu_up2x_bwd_kernel(CatArgs a, const flo
       }
     }
   }
-  if (!first && bstats1) {
-    double d1 = wave_sum_d((double)s1), d2 = wave_sum_d((double)s2);
-    __shared__ double sh2[8];
-    if ((threadIdx.x & 63) == 0) { sh2[threadIdx.x >> 6] = d1; sh2[4 + (threadIdx.x >> 6)] = d2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      atomicAdd(&bstats1[cs], sh2[0] + sh2[1] + sh2[2] + sh2[3]);
-      atomicAdd(&bstats1[a.C1 + cs], sh2[4] + sh2[5] + sh2[6] + sh2[7]);
-    }
-  }
+  if (!first && bstats1) block_stats_add((double)s1, (double)s2, cs, a.C1, bstats1);
 }
 
-extern "C" int avsep_relu_up2x_bwd(const avsep_cat_desc* d, const float* dout, float* g0, float* g1,
-                                   const float* mean1, const float* invstd1, double* bstats1, int32_t acc0,
-                                   avsep_stream_t stream) {
-  int rc = check_cat(d);
-  if (rc || !dout) return AVSEP_ERR_ARG;
-  if (bstats1 && (!mean1 || !invstd1 || d->bcast1 || !g1)) return AVSEP_ERR_ARG;
-  CatArgs a = make_cat(d);
-  int C = d->C0 + d->C1;
-  const int plw = up2x_pair_lw(d);
+// shape and bcast as in relu_up2x_fwd_plan.  sweep forms: arg = {log2 lanes per low-res row, log2 threads per plane};
+// tile: arg[0] = tiles per row
+enum { UP2X_BWD_SWEEP_PLANES, UP2X_BWD_SWEEP, UP2X_BWD_TILE };
+static GluePlan relu_up2x_bwd_plan(int N, int C, int H, int W, bool bcast) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return glue_refused();
+  const int plw = up2x_pair_lw(H, W, bcast);
   // (tiny planes: one block and one pair of atomics per plane would cost more than the LDS-tiled kernel's batch slices;
   // 16x16 planes — the [64, 1024, 32, 32] gradient of u4's input — ran at 1.2 TB/s on the tiled kernel)
-  const long long planes = (long long)d->N * C;
-  if (plw >= 0 && d->H >= 8 && planes <= 32768LL * 65535) {
-    const int chunks = cdiv(d->H, UPB_R), tp = chunks << plw;                  // threads per plane
+  const long long planes = (long long)N * C;
+  if (plw >= 0 && H >= 8 && planes <= 32768LL * 65535) {
+    const int chunks = cdiv(H, UPB_R), tp = chunks << plw;                     // threads per plane
     if (tp <= 64 && (chunks & (chunks - 1)) == 0) {                            // several planes per block
       int tp_log = 0;
       while ((1 << tp_log) < tp) ++tp_log;
       const long long groups = cdiv(planes, 256 >> tp_log);
       const unsigned gy = (unsigned)(groups < 32768 ? groups : 32768), gz = (unsigned)cdiv(groups, gy);
-      hipLaunchKernelGGL(relu_up2x_bwd_sweep_kernel<true>, dim3(1, gy, gz), dim3(256), 0, (hipStream_t)stream, a, dout, g0, g1, mean1,
-                         invstd1, bstats1, acc0, plw, tp_log);
-      AVSEP_LAUNCH_CHECK();
-      return AVSEP_OK;
+      return GluePlan{UP2X_BWD_SWEEP_PLANES, dim3(1, gy, gz), {plw, tp_log}};
     }
     const unsigned gy = (unsigned)(planes < 32768 ? planes : 32768), gz = (unsigned)cdiv(planes, gy);
-    hipLaunchKernelGGL(relu_up2x_bwd_sweep_kernel<false>, dim3(cdiv((long long)tp, 256), gy, gz),
-                       dim3(256), 0, (hipStream_t)stream, a, dout, g0, g1, mean1, invstd1, bstats1, acc0, plw, 0);
-    AVSEP_LAUNCH_CHECK();
-    return AVSEP_OK;
+    return GluePlan{UP2X_BWD_SWEEP, dim3(cdiv((long long)tp, 256), gy, gz), {plw, 0}};
   }
-  int tilesX = cdiv(d->W, UB_TW), tiles = tilesX * cdiv(d->H, UB_TH);
-  int chunks = min(cdiv(4096, C * tiles), d->N);   // batch slices: enough blocks to fill the chip, few atomics
+  if (C > 65535) return glue_refused();            // grid.y
+  int tilesX = cdiv(W, UB_TW), tiles = tilesX * cdiv(H, UB_TH);
+  int chunks = min(cdiv(4096, C * tiles), N);      // batch slices: enough blocks to fill the chip, few atomics
   if (chunks < 1) chunks = 1;
-  if (C > 65535) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(relu_up2x_bwd_kernel, dim3(tiles, C, chunks), dim3(256), 0, (hipStream_t)stream, a, dout, g0, g1,
-                     mean1, invstd1, bstats1, acc0, tilesX);
+  return GluePlan{UP2X_BWD_TILE, dim3(tiles, C, chunks), {tilesX, 0}};
+}
+extern "C" int avsep_relu_up2x_bwd(const avsep_cat_desc* d, const float* dout, float* g0, float* g1,
+                                   const float* mean1, const float* invstd1, double* bstats1, int32_t acc0,
+                                   avsep_stream_t stream) {
+  if (!cat_ok(d) || !dout) return AVSEP_ERR_ARG;
+  if (bstats1 && (!mean1 || !invstd1 || d->bcast1 || !g1)) return AVSEP_ERR_ARG;
+  const GluePlan pl = relu_up2x_bwd_plan(d->N, d->C0 + d->C1, d->H, d->W, d->bcast0 || d->bcast1);
+  if (pl.refused()) return AVSEP_ERR_ARG;
+  CatArgs a = make_cat(d);
+  switch (pl.form) {
+    case UP2X_BWD_SWEEP_PLANES:
+      hipLaunchKernelGGL(relu_up2x_bwd_sweep_kernel<true>, pl.grid, dim3(256), 0, (hipStream_t)stream, a, dout, g0, g1, mean1,
+                         invstd1, bstats1, acc0, pl.arg[0], pl.arg[1]);
+      break;
+    case UP2X_BWD_SWEEP:
+      hipLaunchKernelGGL(relu_up2x_bwd_sweep_kernel<false>, pl.grid, dim3(256), 0, (hipStream_t)stream, a, dout, g0, g1, mean1,
+                         invstd1, bstats1, acc0, pl.arg[0], 0);
+      break;
+    case UP2X_BWD_TILE:
+      hipLaunchKernelGGL(relu_up2x_bwd_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, a, dout, g0, g1, mean1, invstd1,
+                         bstats1, acc0, pl.arg[0]);
+      break;
+  }
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -1028,27 +1038,32 @@ __global__ __launch_bounds__(256) void maxpool_fwd4_kernel(const float* __restri
   if (idx) *reinterpret_cast<int4*>(idx + o) = make_int4(bi[0], bi[1], bi[2], bi[3]);
 }
 
-static GluePlan maxpool_fwd_plan(long long NC, int H, int W) {
+// NC planes of H x W, C channels per image (NC: whatever an int32 argument can carry)
+enum { MAXPOOL_FWD_4, MAXPOOL_FWD_GENERIC };
+static GluePlan maxpool_fwd_plan(int C, long long NC, int H, int W) {
+  if (NC <= 0 || NC > 0x7fffffffLL || H <= 0 || W <= 0 || C <= 0 || NC % C) return glue_refused();
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   if ((W & 7) == 0 && (H & 1) == 0 && NC <= 65535 && (long long)H * W < 0x7fffffffLL)
-    return GluePlan{"fwd4", dim3(cdiv(Ho * (Wo >> 2), 256), (unsigned)NC)};
+    return GluePlan{MAXPOOL_FWD_4, dim3(cdiv(Ho * (Wo >> 2), 256), (unsigned)NC)};
   long long total = NC * Ho * Wo;
-  return GluePlan{"generic", dim3((int)min((total + 255) / 256, (long long)65536))};
+  return GluePlan{MAXPOOL_FWD_GENERIC, dim3((int)min((total + 255) / 256, (long long)65536))};
 }
 extern "C" int avsep_maxpool3x3s2_fwd(const float* x, const float* scale, const float* shift, int32_t act, int32_t C,
                                       int32_t NC, int32_t H, int32_t W, float* y, int32_t* idx, avsep_stream_t stream) {
-  if (!x || !y || NC <= 0 || H <= 0 || W <= 0 || C <= 0 || NC % C) return AVSEP_ERR_ARG;
+  const GluePlan pl = maxpool_fwd_plan(C, NC, H, W);
+  if (!x || !y || pl.refused()) return AVSEP_ERR_ARG;
   if ((scale == nullptr) != (shift == nullptr)) return AVSEP_ERR_ARG;
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  const GluePlan pl = maxpool_fwd_plan(NC, H, W);
-  if (pl.form[3] == '4') {
-    hipLaunchKernelGGL(maxpool_fwd4_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x, scale, shift, act,
-                       C, H, W, Ho, Wo, y, idx);
-    AVSEP_LAUNCH_CHECK();
-    return AVSEP_OK;
+  switch (pl.form) {
+    case MAXPOOL_FWD_4:
+      hipLaunchKernelGGL(maxpool_fwd4_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x, scale, shift, act,
+                         C, H, W, Ho, Wo, y, idx);
+      break;
+    case MAXPOOL_FWD_GENERIC:
+      hipLaunchKernelGGL(maxpool_fwd_kernel, pl.grid, dim3(256), 0,
+                         (hipStream_t)stream, x, scale, shift, act, C, NC, H, W, Ho, Wo, y, idx);
+      break;
   }
-  hipLaunchKernelGGL(maxpool_fwd_kernel, pl.grid, dim3(256), 0,
-                     (hipStream_t)stream, x, scale, shift, act, C, NC, H, W, Ho, Wo, y, idx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }
@@ -1072,14 +1087,16 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
   }
 }
 static GluePlan maxpool_bwd_plan(long long NC, int H, int W) {
+  if (NC <= 0 || NC > 0x7fffffffLL || H <= 0 || W <= 0) return glue_refused();
   long long total = NC * H * W;
-  return GluePlan{"gather", dim3((int)min((total + 255) / 256, (long long)65536))};
+  return GluePlan{0, dim3((int)min((total + 255) / 256, (long long)65536))};
 }
 extern "C" int avsep_maxpool3x3s2_bwd(const float* dy, const int32_t* idx, int32_t NC, int32_t H, int32_t W, float* dx,
                                       avsep_stream_t stream) {
-  if (!dy || !idx || !dx || NC <= 0 || H <= 0 || W <= 0) return AVSEP_ERR_ARG;
+  const GluePlan pl = maxpool_bwd_plan(NC, H, W);
+  if (!dy || !idx || !dx || pl.refused()) return AVSEP_ERR_ARG;
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(maxpool_bwd_kernel, maxpool_bwd_plan(NC, H, W).grid, dim3(256), 0,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, pl.grid, dim3(256), 0,
                      (hipStream_t)stream, dy, idx, NC, H, W, Ho, Wo, dx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1110,17 +1127,19 @@ __global__ __launch_bounds__(256) void space_to_depth2_kernel(const float* __res
     }
   }
 }
-static GluePlan space_to_depth2_plan(int N, int H, int W, int Cp) {
+static GluePlan space_to_depth2_plan(int N, int C, int H, int W, int Cp) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Cp < 4 * (long long)C) return glue_refused();
+  if ((long long)N * Cp > 0x7fffffffLL || (long long)H * W > 0x3fffffffLL) return glue_refused();
   const int per = (H / 2 + 3) * (W / 2 + 3), gx = (per + 255) / 256 < 16 ? (per + 255) / 256 : 16;
   const int planes = N * Cp;
-  return GluePlan{"planes", dim3(gx, planes < 65535 ? planes : 65535)};
+  return GluePlan{0, dim3(gx, planes < 65535 ? planes : 65535)};
 }
 extern "C" int avsep_space_to_depth2(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t Cp, float* xs,
                                      avsep_stream_t stream) {
-  if (!x || !xs || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Cp < 4 * C) return AVSEP_ERR_ARG;
-  if ((long long)N * Cp > 0x7fffffffLL || (long long)H * W > 0x3fffffffLL) return AVSEP_ERR_ARG;
+  const GluePlan pl = space_to_depth2_plan(N, C, H, W, Cp);
+  if (!x || !xs || pl.refused()) return AVSEP_ERR_ARG;
   const int planes = N * Cp;
-  hipLaunchKernelGGL(space_to_depth2_kernel, space_to_depth2_plan(N, H, W, Cp).grid, dim3(256), 0, (hipStream_t)stream, x, C, Cp,
+  hipLaunchKernelGGL(space_to_depth2_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x, C, Cp,
                      H, W, planes, xs);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1153,14 +1172,7 @@ __global__ __launch_bounds__(256) void maxpool_bn_relu_bwd_stats_kernel(const fl
       s2 = fmaf(gv, (yv - mu) * is, s2);
     }
   }
-  double d1 = wave_sum_d((double)s1), d2 = wave_sum_d((double)s2);
-  __shared__ double sh_[8];
-  if ((threadIdx.x & 63) == 0) { sh_[threadIdx.x >> 6] = d1; sh_[4 + (threadIdx.x >> 6)] = d2; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(&bstats[c], sh_[0] + sh_[1] + sh_[2] + sh_[3]);
-    atomicAdd(&bstats[C + c], sh_[4] + sh_[5] + sh_[6] + sh_[7]);
-  }
+  block_stats_add((double)s1, (double)s2, c, C, bstats);
 }
 // pass 2: dy[i] = p * ([pre > 0] * sum_{windows that chose i} g) + q * y[i] + r
 // One (n, c) plane per blockIdx.y (per-channel constants in scalar registers, 32-bit indexing); a thread owns the pixel
@@ -1261,26 +1273,32 @@ __global__ __launch_bounds__(256) void maxpool_bn_relu_bwd_apply1_kernel(const f
     dy[i] = fmaf(pqr[c], s, fmaf(pqr[C + c], yv, pqr[2 * C + c]));
   }
 }
-static GluePlan maxpool_bn_relu_bwd_stats_plan(int N, int C) { return GluePlan{"plane", dim3(C, N)}; }
+static GluePlan maxpool_bn_relu_bwd_stats_plan(int N, int C, int H, int W) {
+  if (N <= 0 || N > 65535 || C <= 0 || H <= 0 || W <= 0) return glue_refused();
+  return GluePlan{0, dim3(C, N)};
+}
+enum { POOL_BWD_APPLY_4, POOL_BWD_APPLY_PAIR, POOL_BWD_APPLY_1 };
 static GluePlan maxpool_bn_relu_bwd_apply_plan(int N, int C, int H, int W) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return glue_refused();
   const long long total = (long long)N * C * H * W;
   if ((W & 3) == 0 && (long long)N * C <= 65535 && (long long)H * W < 0x7fffffffLL) {
     const int per = H * (W / 4), gx = (per + 255) / 256 < 64 ? (per + 255) / 256 : 64;
-    return GluePlan{"apply4", dim3(gx, N * C)};
+    return GluePlan{POOL_BWD_APPLY_4, dim3(gx, N * C)};
   }
   if ((W & 1) == 0 && (long long)N * C <= 65535 && (long long)H * W < 0x7fffffffLL) {
     const int per = H * (W / 2), gx = (per + 255) / 256 < 64 ? (per + 255) / 256 : 64;
-    return GluePlan{"pair", dim3(gx, N * C)};
+    return GluePlan{POOL_BWD_APPLY_PAIR, dim3(gx, N * C)};
   }
-  return GluePlan{"apply1", dim3((int)min((total + 255) / 256, (long long)262144))};
+  return GluePlan{POOL_BWD_APPLY_1, dim3((int)min((total + 255) / 256, (long long)262144))};
 }
 extern "C" int avsep_maxpool_bn_relu_bwd_stats(const float* g, const int32_t* idx, const float* y, const float* scale,
                                                const float* shift, const float* mean, const float* invstd, int32_t N, int32_t C,
                                                int32_t H, int32_t W, double* bstats, avsep_stream_t stream) {
   if (!g || !idx || !y || !scale || !shift || !mean || !invstd || !bstats) return AVSEP_ERR_ARG;
-  if (N <= 0 || N > 65535 || C <= 0 || H <= 0 || W <= 0) return AVSEP_ERR_ARG;
+  const GluePlan pl = maxpool_bn_relu_bwd_stats_plan(N, C, H, W);
+  if (pl.refused()) return AVSEP_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(maxpool_bn_relu_bwd_stats_kernel, maxpool_bn_relu_bwd_stats_plan(N, C).grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale, shift,
+  hipLaunchKernelGGL(maxpool_bn_relu_bwd_stats_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale, shift,
                      mean, invstd, C, H * W, Ho * Wo, bstats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1288,18 +1306,22 @@ extern "C" int avsep_maxpool_bn_relu_bwd_stats(const float* g, const int32_t* id
 extern "C" int avsep_maxpool_bn_relu_bwd_apply(const float* g, const int32_t* idx, const float* y, const float* scale,
                                                const float* shift, const float* pqr, int32_t N, int32_t C, int32_t H, int32_t W,
                                                float* dy, avsep_stream_t stream) {
-  if (!g || !idx || !y || !scale || !shift || !pqr || !dy || N <= 0 || C <= 0 || H <= 0 || W <= 0) return AVSEP_ERR_ARG;
-  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const GluePlan pl = maxpool_bn_relu_bwd_apply_plan(N, C, H, W);
-  if (pl.form[0] == 'a' && pl.form[5] == '4') {
-    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply4_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
-                       shift, pqr, C, H, W, Ho, Wo, dy);
-  } else if (pl.form[0] == 'p') {
-    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
-                       shift, pqr, C, H, W, Ho, Wo, dy);
-  } else {
-    hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply1_kernel, pl.grid, dim3(256), 0,
-                       (hipStream_t)stream, g, idx, y, scale, shift, pqr, C, N * C, H, W, Ho, Wo, dy);
+  if (!g || !idx || !y || !scale || !shift || !pqr || !dy || pl.refused()) return AVSEP_ERR_ARG;
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  switch (pl.form) {
+    case POOL_BWD_APPLY_4:
+      hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply4_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
+                         shift, pqr, C, H, W, Ho, Wo, dy);
+      break;
+    case POOL_BWD_APPLY_PAIR:
+      hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, g, idx, y, scale,
+                         shift, pqr, C, H, W, Ho, Wo, dy);
+      break;
+    case POOL_BWD_APPLY_1:
+      hipLaunchKernelGGL(maxpool_bn_relu_bwd_apply1_kernel, pl.grid, dim3(256), 0,
+                         (hipStream_t)stream, g, idx, y, scale, shift, pqr, C, N * C, H, W, Ho, Wo, dy);
+      break;
   }
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1317,12 +1339,18 @@ __global__ __launch_bounds__(256) void temporal_mean_fwd_kernel(const float* __r
 }
 // one element per thread and pass, grid-stride beyond `cap` workgroups (temporal mean: 65536, SGD: 16384)
 static GluePlan flat_plan(long long total, long long cap) {
-  return GluePlan{"flat", dim3((int)min((total + 255) / 256, cap))};
+  return GluePlan{0, dim3((int)min((total + 255) / 256, cap))};
+}
+// CHW: whatever an int32 argument can carry
+static GluePlan temporal_mean_plan(int B, int T, long long CHW, bool bwd) {
+  if (B <= 0 || T <= 0 || CHW <= 0 || CHW > 0x7fffffffLL) return glue_refused();
+  return flat_plan(bwd ? (long long)B * T * CHW : (long long)B * CHW, 65536);
 }
 extern "C" int avsep_temporal_mean_fwd(const float* x, int32_t B, int32_t T, int32_t CHW, float* y,
                                        avsep_stream_t stream) {
-  if (!x || !y || B <= 0 || T <= 0 || CHW <= 0) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(temporal_mean_fwd_kernel, flat_plan((long long)B * CHW, 65536).grid, dim3(256), 0,
+  const GluePlan pl = temporal_mean_plan(B, T, CHW, false);
+  if (!x || !y || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(temporal_mean_fwd_kernel, pl.grid, dim3(256), 0,
                      (hipStream_t)stream, x, B, T, (long long)CHW, y);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1338,8 +1366,9 @@ __global__ __launch_bounds__(256) void temporal_mean_bwd_kernel(const float* __r
 }
 extern "C" int avsep_temporal_mean_bwd(const float* dy, int32_t B, int32_t T, int32_t CHW, float* dx,
                                        avsep_stream_t stream) {
-  if (!dy || !dx || B <= 0 || T <= 0 || CHW <= 0) return AVSEP_ERR_ARG;
-  hipLaunchKernelGGL(temporal_mean_bwd_kernel, flat_plan((long long)B * T * CHW, 65536).grid, dim3(256), 0,
+  const GluePlan pl = temporal_mean_plan(B, T, CHW, true);
+  if (!dy || !dx || pl.refused()) return AVSEP_ERR_ARG;
+  hipLaunchKernelGGL(temporal_mean_bwd_kernel, pl.grid, dim3(256), 0,
                      (hipStream_t)stream, dy, B, T, (long long)CHW, dx);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
@@ -1528,35 +1557,40 @@ extern "C" int avsep_sdr_sums(const float* est, const float* ref, int32_t R, int
   return AVSEP_OK;
 }
 
+// ops.hip's rows of avsep_glue_plan (common.h): form names in the order of the plan's enum
+static const GluePlanRow ops_glue_rows[] = {
+    {"channel_stats", {"chunks"}, [](int N, int C, int H, int W, int) { return channel_stats_plan(N, C, (long long)H * W); }},
+    {"bn_bwd_apply", {"vec4", "scalar"}, [](int N, int C, int H, int W, int) { return bn_bwd_apply_plan(N, C, (long long)H * W); }},
+    {"affine_act", {"vec4", "scalar"}, [](int N, int C, int H, int W, int) { return affine_act_plan(N, C, (long long)H * W); }},
+    {"affine_act_bwd", {"v4", "v1"}, [](int N, int C, int H, int W, int) { return affine_act_bwd_plan(N, C, (long long)H * W); }},
+    {"relu_up2x_fwd", {"pair", "fwd4", "generic"}, [](int N, int C, int H, int W, int aux) { return relu_up2x_fwd_plan(N, C, H, W, aux != 0); }},
+    {"relu_up2x_bwd", {"sweep,planes", "sweep", "tile"}, [](int N, int C, int H, int W, int aux) { return relu_up2x_bwd_plan(N, C, H, W, aux != 0); }},
+    {"maxpool_fwd", {"fwd4", "generic"}, [](int N, int C, int H, int W, int) { return maxpool_fwd_plan(C, (long long)N * C, H, W); }},
+    {"maxpool_bwd", {"gather"}, [](int N, int C, int H, int W, int) { return maxpool_bwd_plan((long long)N * C, H, W); }},
+    {"maxpool_bn_relu_bwd_stats", {"plane"}, [](int N, int C, int H, int W, int) { return maxpool_bn_relu_bwd_stats_plan(N, C, H, W); }},
+    {"maxpool_bn_relu_bwd_apply", {"apply4", "pair", "apply1"}, [](int N, int C, int H, int W, int) { return maxpool_bn_relu_bwd_apply_plan(N, C, H, W); }},
+    {"space_to_depth2", {"planes"}, [](int N, int C, int H, int W, int Cp) { return space_to_depth2_plan(N, C, H, W, Cp); }},
+    {"temporal_mean_fwd", {"flat"}, [](int B, int C, int H, int W, int T) { return temporal_mean_plan(B, T, (long long)C * H * W, false); }},
+    {"temporal_mean_bwd", {"flat"}, [](int B, int C, int H, int W, int T) { return temporal_mean_plan(B, T, (long long)C * H * W, true); }},
+    {"sgd", {"flat"}, [](int N, int C, int H, int W, int) { return flat_plan((long long)N * C * ((long long)H * W), 16384); }},
+};
+
 // the launch plan of a glue launcher, from the function the launcher itself calls (include/avsep.h)
 extern "C" int avsep_glue_plan(const char* op, int32_t N, int32_t C, int32_t H, int32_t W, int32_t aux, char* form, size_t cap,
                                int32_t grid[3]) {
   if (!op || !form || !grid || cap < 32 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || aux < 0) return AVSEP_ERR_ARG;
-  const long long HWl = (long long)H * W, NC = (long long)N * C;
-  const int HW = (int)HWl;
-  const bool hw_ok = HWl <= 0x7fffffffLL, zgrid_ok = C <= 65535 && N <= 65535;
-  GluePlan p{nullptr, dim3(0, 0, 0)};
-  auto is = [&](const char* name) { return strcmp(op, name) == 0; };
-  if (is("channel_stats")) { if (hw_ok) p = channel_stats_plan(N, C, HW); }
-  else if (is("bn_bwd_apply")) { if (hw_ok && zgrid_ok) p = bn_bwd_apply_plan(N, C, HW); }
-  else if (is("affine_act")) { if (hw_ok && zgrid_ok) p = affine_act_plan(N, C, HW); }
-  else if (is("affine_act_bwd")) { if (hw_ok && N * HWl <= 0x7fffffffLL) p = affine_act_bwd_plan(N, C, HW); }
-  else if (is("maxpool_fwd")) { if (NC <= 0x7fffffffLL) p = maxpool_fwd_plan(NC, H, W); }
-  else if (is("maxpool_bwd")) { if (NC <= 0x7fffffffLL) p = maxpool_bwd_plan(NC, H, W); }
-  else if (is("maxpool_bn_relu_bwd_stats")) { if (N <= 65535) p = maxpool_bn_relu_bwd_stats_plan(N, C); }
-  else if (is("maxpool_bn_relu_bwd_apply")) p = maxpool_bn_relu_bwd_apply_plan(N, C, H, W);
-  else if (is("space_to_depth2")) {
-    if (!(H & 1) && !(W & 1) && aux >= 4 * (long long)C && (long long)N * aux <= 0x7fffffffLL && HWl <= 0x3fffffffLL)
-      p = space_to_depth2_plan(N, H, W, aux);
-  }
-  else if (is("temporal_mean_fwd")) { if (aux > 0 && C * HWl <= 0x7fffffffLL) p = flat_plan(N * (C * HWl), 65536); }
-  else if (is("temporal_mean_bwd")) { if (aux > 0 && C * HWl <= 0x7fffffffLL) p = flat_plan(N * (long long)aux * (C * HWl), 65536); }
-  else if (is("sgd")) p = flat_plan(NC * HWl, 16384);
-  else if (!b16_glue_plan(op, N, C, H, W, aux, &p)) return AVSEP_ERR_ARG;
-  if (!p.form) return AVSEP_ERR_ARG;
-  snprintf(form, cap, "%s", p.form);
-  grid[0] = (int32_t)p.grid.x; grid[1] = (int32_t)p.grid.y; grid[2] = (int32_t)p.grid.z;
-  return AVSEP_OK;
+  int counts[2] = {(int)(sizeof(ops_glue_rows) / sizeof(ops_glue_rows[0])), 0};
+  const GluePlanRow* const tables[2] = {ops_glue_rows, b16_glue_rows(&counts[1])};
+  for (int t = 0; t < 2; ++t)
+    for (const GluePlanRow* r = tables[t]; r < tables[t] + counts[t]; ++r) {
+      if (strcmp(op, r->op)) continue;
+      const GluePlan p = r->plan(N, C, H, W, aux);
+      if (p.refused()) return AVSEP_ERR_ARG;
+      snprintf(form, cap, "%s", r->forms[p.form]);
+      grid[0] = (int32_t)p.grid.x; grid[1] = (int32_t)p.grid.y; grid[2] = (int32_t)p.grid.z;
+      return AVSEP_OK;
+    }
+  return AVSEP_ERR_ARG;
 }
 
 extern "C" int avsep_version(void) { return 101; }

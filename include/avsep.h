@@ -62,8 +62,12 @@ const char* avsep_strerror(int code);
  *   space_to_depth2                 aux = Cp
  *   temporal_mean_fwd, temporal_mean_bwd    B = N, T = aux, CHW = C * H * W
  *   sgd                             n = N * C * H * W
+ *   relu_up2x_fwd, relu_up2x_bwd    the descriptor's low-resolution [N, C0 + C1, H, W]; aux = 1 when a source is a broadcast
+ *                                   vector (bcast0 or bcast1), else 0
+ *   b16_relu_up2x_fwd, b16_relu_up2x_bwd    low-resolution [N, C0 + C1, H, W] with C0 = aux
  * `form` (cap >= 32 bytes) receives the form's name, grid[3] the grid.  AVSEP_ERR_ARG for an unknown op or a shape the
- * launcher refuses. */
+ * launcher refuses: a launcher accepts or refuses a shape, and picks form and grid, in that one function and nowhere else.
+ * (avsep_b16_grid_pack and avsep_grid_unpack plan the same way but are no op here: their geometry is nine integers.) */
 int avsep_glue_plan(const char* op, int32_t N, int32_t C, int32_t H, int32_t W, int32_t aux, char* form, size_t cap,
                     int32_t grid[3]);
 

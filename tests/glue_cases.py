@@ -23,6 +23,11 @@ Forms and thresholds (csrc/ops.hip, csrc/b16.hip), 256-thread workgroups through
   the B16 elementwise kernels, pools and channel sum   "slot": grid (gx = min(ceil(2*HW/256), 32), C/16, N) |
                      "slot,images": gz = 4096 / (gx * C/16) < N once gx * C/16 * N > 4096 (image-stride loop)
   b16_space_to_depth2   "flat": min(.., 262144)
+  relu_up2x_fwd      "pair" | "fwd4" | "generic";   relu_up2x_bwd   "sweep,planes" | "sweep" | "tile"
+  b16_relu_up2x_fwd  "slot" | "slot,images";        b16_relu_up2x_bwd   "tile"
+                     (the decoder glue: no sweep rows here yet; form and grid are pinned by DECODER in test_glue_plans_host.py)
+A launcher accepts or refuses a shape, and picks form and grid, in its *_plan function alone; avsep_glue_plan looks the op up in
+one table and calls that function, so a refusal here is the launcher's.
 
 Not reached (the size limit of a test's largest tensor is 2^25 elements):
   channel_stats, a flush followed by a remainder (>= 65 terms on a thread): needs 2048 * 16385 = 33 556 480 elements

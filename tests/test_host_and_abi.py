@@ -32,6 +32,53 @@ def test_library_exports_every_declared_symbol():
     L = P.lib.load()
     assert L.avsep_arch() == b"gfx950" and L.avsep_version() >= 100
     assert L.avsep_strerror(-1).startswith(b"invalid argument")
+    # ... and with the declared types, class by class
+    protos = _header_prototypes(hdr)
+    assert set(protos) == declared and len(protos) >= 100
+    lib_m = P.lib
+    descs = {"avsep_conv_desc": lib_m.ConvDesc, "avsep_cat_desc": lib_m.CatDesc, "avsep_act_bwd": lib_m.ActBwd}
+
+    def c_class(decl):
+        """class of a C parameter or return type: its name and qualifiers dropped"""
+        t = re.sub(r"\bconst\b", " ", decl)
+        is_ptr = "*" in t or "[" in t
+        t = re.sub(r"\[.*?\]", " ", t).replace("*", " ").split()
+        base = t[0] if t[0] not in ("unsigned", "struct") else " ".join(t[:2])
+        if is_ptr:
+            return base if base in descs else ("char*" if base == "char" else "pointer")
+        return {"int": "int", "int32_t": "int", "int64_t": "int64", "size_t": "size", "float": "float", "double": "double",
+                "avsep_stream_t": "pointer"}[base]
+
+    def ctypes_class(t):
+        for name, struct in descs.items():
+            if t is ctypes.POINTER(struct):
+                return name
+        if t is ctypes.c_char_p:
+            return "char*"
+        if t is ctypes.c_void_p or (hasattr(t, "_type_") and not isinstance(t._type_, str)):      # void* or POINTER(...)
+            return "pointer"
+        return {ctypes.c_int: "int", ctypes.c_int32: "int", ctypes.c_int64: "int64", ctypes.c_size_t: "size",
+                ctypes.c_float: "float", ctypes.c_double: "double"}[t]
+
+    assert ctypes.c_int64 is not ctypes.c_size_t and ctypes.c_int is not ctypes.c_int64       # the classes are distinct types here
+    for name, (ret, params) in sorted(protos.items()):
+        restype, argtypes = lib_m.SIGNATURES[name]
+        assert ctypes_class(restype) == c_class(ret), (name, ret, restype)
+        assert [ctypes_class(t) for t in argtypes] == [c_class(p) for p in params], (name, params, argtypes)
+
+
+def _header_prototypes(hdr):
+    """{name: (return type, [parameter declarations])} of every prototype of include/avsep.h (comments already stripped)"""
+    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)                       # preprocessor lines
+    hdr = re.sub(r'extern\s+"C"\s*\{', "", hdr)
+    hdr = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", hdr, flags=re.S)
+    hdr = re.sub(r"typedef[^;{]*;", "", hdr)
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(avsep_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr):
+        params = params.strip()
+        assert name not in out, name
+        out[name] = (ret.strip(), [] if params in ("", "void") else [p.strip() for p in params.split(",")])
+    return out
 
 
 def test_library_reads_no_environment_variable():
