@@ -1105,6 +1105,34 @@ def true_peak(x, taps, os):
     return peaks
 
 
+FRAMES_MAX_T = 65535              # frames per launch of avsep_frames_prepare (a grid dimension)
+
+
+def frames_prepare(frames, tables, size, S, crop, flip, return_u8=False):
+    """avsep_frames_prepare (include/avsep.h): frames uint8 [T,H,W,3] on the GPU, as frames.check_stack passes them (frames.prepare
+    is the caller and checks there); tables = (hcoef int32 [w,kh], hbound int32
+    [w,2], vcoef int32 [h,kv], vbound int32 [h,2], lut f32 [256,3]) on the frames' device (frames.Plan.on); size (w, h), crop
+    (i, j), flip -> f32 [T,3,S,S]; with return_u8 also the cropped pixels uint8 [T,S,S,3].  Stacks of more than 65535 frames
+    are cut into several launches."""
+    lib.require_gpu(frames)
+    T, H, W, _ = frames.shape
+    hcoef, hbound, vcoef, vbound, lut = tables
+    (w, h), S = size, int(S)
+    want = ((hcoef, torch.int32, (w, hcoef.shape[-1])), (hbound, torch.int32, (w, 2)), (vcoef, torch.int32, (h, vcoef.shape[-1])),
+            (vbound, torch.int32, (h, 2)), (lut, torch.float32, (256, 3)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != frames.device or not t.is_contiguous():
+            raise lib.AvsepError(f"frames_prepare: a table must be {dtype} {shape} on {frames.device}, got {_got(t)}")
+    out = _f32((T, 3, S, S), frames)
+    u8 = torch.empty((T, S, S, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
+    for a in range(0, T, FRAMES_MAX_T):
+        n = min(FRAMES_MAX_T, T - a)
+        call("avsep_frames_prepare", ptr(frames[a:a + n]), n, H, W, ptr(hcoef), ptr(hbound), w, hcoef.shape[1], ptr(vcoef), ptr(vbound),
+             h, vcoef.shape[1], S, int(crop[0]), int(crop[1]), int(bool(flip)), ptr(lut), ptr(out[a:a + n]),
+             ptr(u8[a:a + n]) if return_u8 else None)
+    return (out, u8) if return_u8 else out
+
+
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 

@@ -104,6 +104,7 @@ SIGNATURES = {
     "avsep_loudness_energies": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "avsep_true_peak_workspace_bytes": (_Z, [_I, _I]),
     "avsep_true_peak": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "avsep_frames_prepare": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

@@ -24,7 +24,7 @@ import torch
 from . import kernels as K
 from . import lib
 from .lib import AvsepError
-from .separate import FOUT, WIDTH, frame_columns, load_nets, open_recording, plan_windows, trunk_features
+from .separate import FOUT, WIDTH, frame_columns, is_shot, load_nets, open_recording, plan_windows, trunk_features
 
 
 def jet_table():
@@ -57,6 +57,9 @@ def localise(nets, wav, frames, frame_times, args, stride_frames=128, batch=16, 
     nets: (net_sound, net_frame), both in eval() (else AvsepError).  wav [L] on the GPU, L >= args.stft_frame.  frames: list
     of C = args.num_mix tensors [T,3,H,W] (ImageNet-normalised floats), or a one-element list = duet (num_mix 2 only): the
     same feature map feeds both sources and, as inference.NetWrapper.forward_av, img_activation is not applied to it.
+    A frame tensor may be uint8 [T,H,W,3] instead, RGB frames as shot: they are prepared on the GPU at args.imgSize
+    (``frames.prepare``, dataset.VideoTransform's validation form bit for bit) and the overlays are drawn over the prepared
+    frames.
     frame_times [T]: seconds from the start of wav.  fusion_type hidsep / CoLoc_Sel (their maps are the same); MixVis:
     NotImplementedError; pooled visual features (args.not_pool_vis): AvsepError.
 
@@ -84,8 +87,9 @@ def localise(nets, wav, frames, frame_times, args, stride_frames=128, batch=16, 
     T = frames[0].shape[0]
     for n, fr in enumerate(frames):
         lib.require_gpu(fr)
-        if fr.dim() != 4 or fr.shape[1] != 3 or tuple(fr.shape) != tuple(frames[0].shape):
-            raise AvsepError(f"frames[{n}] must be [T,3,H,W] like frames[0], got {tuple(fr.shape)}")
+        if fr.dim() != 4 or fr.shape[3 if is_shot(fr) else 1] != 3 or tuple(fr.shape) != tuple(frames[0].shape) \
+                or fr.dtype != frames[0].dtype:
+            raise AvsepError(f"frames[{n}] must be [T,3,H,W] (or uint8 [T,H,W,3]) like frames[0], got {fr.dtype} {tuple(fr.shape)}")
     times = torch.as_tensor(frame_times).reshape(-1)
     if T < 1 or times.numel() != T:
         raise AvsepError(f"localise needs one time per video frame: {T} frames, {times.numel()} times")
@@ -99,6 +103,14 @@ def localise(nets, wav, frames, frame_times, args, stride_frames=128, batch=16, 
         starts_t = torch.tensor(starts, dtype=torch.int32, device=dev)
         _, logm = K.window_prepare(mag, starts_t, FOUT, WIDTH)
         x = net_sound.bottleneck(logm, batch)                                                      # [K, D, Fq, Tq]
+        if is_shot(frames[0]):                                                                     # the overlays need every prepared frame
+            from . import frames as FR
+            if getattr(args, "imgSize", None) is None:
+                raise AvsepError("uint8 frames are prepared at args.imgSize, which these args do not have")
+            for fr in frames:
+                FR.check_stack(fr, "localise")
+            shot = FR.plan(frames[0].shape[1], frames[0].shape[2], args.imgSize)
+            frames = [torch.cat([FR.prepare(fr[i:i + batch], shot) for i in range(0, T, batch)], 0) for fr in frames]
         frames = [fr.float().contiguous() for fr in frames]
         feats = [_frame_features(net_frame, fr, args, batch, act=not duet) for fr in frames]
         if feats[0].shape[1] != x.shape[1] // Cn:
@@ -125,7 +137,8 @@ def build_parser():
     p.add_argument("--wav", required=True, help="mixture, a WAV file (16-, 24- or 32-bit PCM or 32-bit float) at any sample rate "
                                                 "(resampled to --audRate on the GPU)")
     p.add_argument("--frames", nargs="+", required=True,
-                   help="one .npy [T,3,H,W] (normalised floats) per source; ONE file with --num_mix 2 is a duet")
+                   help="one .npy [T,3,H,W] (normalised floats) per source; ONE file with --num_mix 2 is a duet.  Frames as shot: "
+                        "a uint8 .npy [T,H,W,3], or a folder of .jpg / .png files in name order, prepared on the GPU at --imgSize")
     p.add_argument("--fps", type=float, required=True, help="video frames per second of the .npy stacks")
     p.add_argument("--frame_offset", type=float, default=0.0, help="time of the first video frame, seconds from the WAV's start")
     p.add_argument("--out", default="localised", help="output directory (maps.npy, overlay_source<c>.npy)")
@@ -157,7 +170,8 @@ def cli(argv=None):
     wav = open_recording(args, "localisation")[1]      # frame times are in seconds: only the input side needs the model's rate
     dev = wav.device
     nets = load_nets(args, dev)
-    frames = [torch.from_numpy(np.load(path)).float().to(dev) for path in args.frames]
+    from . import frames as FR
+    frames = [fr.to(dev) if is_shot(fr) else fr.float().to(dev) for fr in (FR.load_stack(path) for path in args.frames)]
     times = args.frame_offset + torch.arange(frames[0].shape[0], dtype=torch.float64) / args.fps
     out = localise(nets, wav, frames, times, args, stride_frames=args.window_stride,
                    batch=args.window_batch, alpha=args.alpha)

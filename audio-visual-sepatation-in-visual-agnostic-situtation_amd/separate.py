@@ -130,13 +130,26 @@ def frames_of_windows(frame_times, starts, rate, hop, width=WIDTH):
     return torch.from_numpy(np.stack([first, count], 1).astype(np.int32))
 
 
-def trunk_features(net_frame, fr, batch, dev, pool, activation=None):
+def is_shot(fr):
+    """Frames as shot: a uint8 tensor, [T,H,W,3] RGB (prepared frames are floats [T,3,H,W])."""
+    return torch.is_tensor(fr) and fr.dtype == torch.uint8
+
+
+def trunk_features(net_frame, fr, batch, dev, pool, activation=None, img_size=None):
     """fr [T,3,H,W] through the visual trunk, ``batch`` frames at a time (each batch is moved to ``dev``, as float32) ->
     the features of all T frames, concatenated.  activation: applied to every batch's features (img_activation); None
-    leaves it out.  The one trunk loop of ``separate_long`` (frames and clips) and of ``localise``."""
-    parts = []
+    leaves it out.  fr uint8 [T,H,W,3], frames as shot: every batch goes to ``dev`` as the bytes it is and is prepared there
+    (``frames.prepare``, the validation form at ``img_size``, which is then required).  The one trunk loop of
+    ``separate_long`` (frames and clips) and of ``localise``."""
+    parts, shot = [], None
+    if is_shot(fr):
+        from . import frames as FR
+        if img_size is None:
+            raise AvsepError("uint8 frames are prepared at args.imgSize, which these args do not have")
+        shot = FR.plan(FR.check_stack(fr, "separate_long / localise")[1], fr.shape[2], img_size)
     for i in range(0, fr.shape[0], batch):
-        f = net_frame.forward(fr[i:i + batch].to(dev).float().contiguous(), pool=pool)
+        x = fr[i:i + batch].to(dev)
+        f = net_frame.forward(x.float().contiguous() if shot is None else FR.prepare(x.contiguous(), shot), pool=pool)
         parts.append(f if activation is None else activate(f, activation))
     return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
@@ -147,9 +160,14 @@ def _visual_features(net_frame, frames, args, Kw, batch, act=True):
     feats = []
     for n, fr in enumerate(frames):
         if fr.dim() != 4 or fr.shape[0] not in (1, Kw):
-            raise AvsepError(f"frames[{n}] must be [1,3,H,W] or [{Kw},3,H,W] (one per window), got {tuple(fr.shape)}")
+            raise AvsepError(f"frames[{n}] must be [1,3,H,W] or [{Kw},3,H,W] (one per window; uint8 frames as shot: "
+                             f"[1,H,W,3] or [{Kw},H,W,3]), got {tuple(fr.shape)}")
+        if is_shot(fr) != is_shot(frames[0]):
+            raise AvsepError(f"frames must be of one kind, all uint8 as shot or all prepared floats; frames[{n}] is {fr.dtype}, "
+                             f"frames[0] {frames[0].dtype}")
         lib.require_gpu(fr)
-        feats.append(trunk_features(net_frame, fr, batch, fr.device, args.not_pool_vis, args.img_activation if act else None))
+        feats.append(trunk_features(net_frame, fr, batch, fr.device, args.not_pool_vis, args.img_activation if act else None,
+                                    getattr(args, "imgSize", None)))
     return feats
 
 
@@ -165,9 +183,10 @@ def _clip_features(net_frame, frames, frame_times, starts, args, batch, dev, act
     times = torch.as_tensor(frame_times, dtype=torch.float64).reshape(-1)
     T = frames[0].shape[0] if torch.is_tensor(frames[0]) and frames[0].dim() == 4 else 0
     for n, fr in enumerate(frames):
-        if not torch.is_tensor(fr) or fr.dim() != 4 or fr.shape[1] != 3 or tuple(fr.shape) != tuple(frames[0].shape):
-            what = tuple(fr.shape) if torch.is_tensor(fr) else type(fr).__name__
-            raise AvsepError(f"with frame_times, frames[{n}] must be [T,3,H,W] like frames[0], got {what}")
+        if not torch.is_tensor(fr) or fr.dim() != 4 or fr.shape[3 if is_shot(fr) else 1] != 3 \
+                or tuple(fr.shape) != tuple(frames[0].shape) or fr.dtype != frames[0].dtype:
+            what = f"{fr.dtype} {tuple(fr.shape)}" if torch.is_tensor(fr) else type(fr).__name__
+            raise AvsepError(f"with frame_times, frames[{n}] must be [T,3,H,W] (or uint8 [T,H,W,3]) like frames[0], got {what}")
     if T < 1 or times.numel() != T:
         raise AvsepError(f"separate_long needs one time per video frame: {T} frames, {times.numel()} times")
     try:
@@ -176,7 +195,8 @@ def _clip_features(net_frame, frames, frame_times, starts, args, batch, dev, act
         raise AvsepError(f"separate_long(frame_times=...): {e}") from e
     feats = []
     for fr in frames:
-        w = K.window_reduce(trunk_features(net_frame, fr, batch, dev, False).float().contiguous(), ranges, "mean")
+        w = K.window_reduce(trunk_features(net_frame, fr, batch, dev, False, None, getattr(args, "imgSize", None)).float().contiguous(),
+                            ranges, "mean")
         feats.append(activate(w, args.img_activation) if act else w)
     return feats
 
@@ -285,6 +305,11 @@ def separate_long(nets, wav, frames, args, use_vis=True, stride_frames=128, batc
     recording: its feature map is computed once and broadcast over the windows) or [K,3,H,W] (one frame per window,
     K = len(plan_windows(F, stride_frames))); ignored for use_vis=False.  Activations and ``pool`` as in
     inference.NetWrapper.forward_av.  ``fusion_type == 'MixVis'`` is not provided: NotImplementedError.
+
+    Wherever a frame tensor is a float [T,3,H,W] it may be uint8 [T,H,W,3] instead, RGB frames as shot, of any size: they are
+    resized, cropped and normalised on the GPU as dataset.VideoTransform's validation form does at args.imgSize
+    (``frames.prepare``, bit for bit), batch by batch inside the trunk loop, so a clip on the host goes up as bytes.  Float
+    frames take the path they always took.
 
     A one-element frames list with num_mix == 2 is a duet (one camera, two players), in any of the frame forms: the one feature
     tensor feeds both sources and, as in inference.NetWrapper and localise, img_activation is not applied to it.  With the same
@@ -503,7 +528,9 @@ def build_parser():
                    help="one gain for all sources that brings the mixture to LUFS (-70 ... 0) integrated loudness; "
                         "with --peak the ceiling wins")
     p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]; with --fps a "
-                                                           "stack [T,3,H,W], and ONE stack with --num_mix 2 is a duet")
+                                                           "stack [T,3,H,W], and ONE stack with --num_mix 2 is a duet.  Frames as "
+                                                           "shot: a uint8 .npy [H,W,3] or [T,H,W,3], or a folder of .jpg / .png "
+                                                           "files in name order, prepared on the GPU at --imgSize")
     p.add_argument("--fps", type=float, default=None, help="video frames per second of the .npy stacks (needs the spatial visual "
                                                            "features of --not_pool_vis)")
     p.add_argument("--frame_offset", type=float, default=0.0, help="time of the first video frame, seconds from the WAV's start")
@@ -637,8 +664,11 @@ def cli(argv=None):
     out_fmt = {"file": "s24" if info.fmt == "s32" else info.fmt}.get(args.out_format, args.out_format)
     nets = load_nets(args, dev)
     frames, times = [], None
+    from . import frames as FR
     for path in args.frames:
-        fr = torch.from_numpy(np.load(path)).float()
+        fr = FR.load_stack(path)                     # uint8 [T,H,W,3]: frames as shot, prepared on the GPU batch by batch
+        if not is_shot(fr):
+            fr = fr.float()
         if args.fps is not None:                     # a clip stays on the host: the trunk takes it up batch by batch
             if fr.dim() != 4:
                 raise SystemExit(f"{path}: with --fps every .npy is a stack [T,3,H,W], this one is {tuple(fr.shape)}")

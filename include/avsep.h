@@ -713,6 +713,25 @@ size_t avsep_true_peak_workspace_bytes(int32_t R, int32_t L);
 int avsep_true_peak(const float* x, const double* taps, int32_t R, int32_t L, int32_t os, double* peaks, void* ws, size_t ws_bytes,
                     avsep_stream_t stream);
 
+/* ---- Frames as shot (csrc/frames.hip; avsep_amd/frames.py): uint8 RGB frames [T][H][W][3] -> out f32 [T][3][S][S], bit for bit
+ * dataset.VideoTransform: Pillow's 8-bit bicubic resize to (w, h), the crop of S x S at (crop_i, crop_j) of the resized image
+ * (rows, columns; either may be negative or reach past the image: pixels outside it are 0), the left-right flip, and
+ * (v / 255 - mean) / std.  All floating-point arithmetic is the host's: the kernel is handed, in DEVICE memory,
+ *   hcoef int32 [w][kh], hbound int32 [w][2]: per column of the resized image its kh fixed-point weights (22 fractional bits,
+ *     those past the count are 0) and (first input column, count); vcoef [h][kv], vbound [h][2] likewise for the rows.
+ *     kh = 2 * ceil(2 * max(W / w, 1)) + 1 and kv = 2 * ceil(2 * max(H / h, 1)) + 1, Pillow's, each at most 81 (a downscale of
+ *     up to 20); an axis that keeps its size has the identity table.  first and count are clamped to the input, so a wrong
+ *     table gives wrong pixels and never an access outside `frames`.
+ *   lut f32 [256][3]: the normalised value of every byte value per channel.
+ * Horizontal pass: mid = clip((2^21 + sum_k hcoef[x][k] * frames[.., first + k, c]) >> 22, 0, 255) in int32 with an arithmetic
+ * shift, rounded to uint8; vertical pass: the same rule over mid.  out[t][c][y][x'] = lut[v][c] with v the cropped pixel and
+ * x' = S - 1 - x under flip.  out_u8 (or NULL): uint8 [T][S][S][3], the pixels v themselves, after crop and flip.
+ * 1 <= T <= 65535, 1 <= H, W, h, w <= 4096, 8 <= S <= 1024, |crop_i|, |crop_j| <= 4096, flip 0 | 1; `frames` may start at any
+ * byte.  Anything else, or a null pointer other than out_u8, is AVSEP_ERR_ARG before any launch. */
+int avsep_frames_prepare(const uint8_t* frames, int32_t T, int32_t H, int32_t W, const int32_t* hcoef, const int32_t* hbound, int32_t w,
+                         int32_t kh, const int32_t* vcoef, const int32_t* vbound, int32_t h, int32_t kv, int32_t S, int32_t crop_i,
+                         int32_t crop_j, int32_t flip, const float* lut, float* out, uint8_t* out_u8, avsep_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
