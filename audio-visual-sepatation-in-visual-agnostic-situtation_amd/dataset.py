@@ -69,26 +69,41 @@ def _resize_size(w, h, size, max_size):
     return (new_short, new_long) if w <= h else (new_long, new_short)
 
 
+def draw_crop_flip(w, h, img_size, train):
+    """The one statement of a clip's crop and flip draws, for a first frame resized to w x h -> ((i, j) | None, flip).
+    Training form: randint(0, h - S), randint(0, w - S) (neither when the frame is S x S already), then random() for the flip,
+    in this order; a frame smaller than the crop raises randint's ValueError.  Validation form: no draw, (None, False): every
+    frame takes its own centre."""
+    if not train:
+        return None, False
+    if w == img_size and h == img_size:
+        i = j = 0
+    else:
+        i = random.randint(0, h - img_size)
+        j = random.randint(0, w - img_size)
+    return (i, j), random.random() < 0.5
+
+
 class VideoTransform:
     """The reference's Compose of video_transforms (one crop / flip decision per clip, shared by its frames)."""
 
     def __init__(self, img_size, train, max_size=448):
         self.img_size, self.train, self.max_size = img_size, train, max_size
 
+    def resized_size(self, w, h):
+        """The size a w x h frame is resized to, (w', h')."""
+        return _resize_size(w, h, int(self.img_size * 1.1) if self.train else self.img_size, self.max_size)
+
     def __call__(self, frames):
         from PIL import Image
-        size = int(self.img_size * 1.1) if self.train else self.img_size
-        frames = [f.resize(_resize_size(f.size[0], f.size[1], size, self.max_size), Image.BICUBIC) for f in frames]
+        frames = [f.resize(self.resized_size(f.size[0], f.size[1]), Image.BICUBIC) for f in frames]
         th = tw = self.img_size
         w, h = frames[0].size
+        crop, flip = draw_crop_flip(w, h, self.img_size, self.train)
         if self.train:
-            if w == tw and h == th:
-                i = j = 0
-            else:
-                i = random.randint(0, h - th)
-                j = random.randint(0, w - tw)
+            i, j = crop
             frames = [f.crop((j, i, j + tw, i + th)) for f in frames]
-            if random.random() < 0.5:
+            if flip:
                 frames = [f.transpose(Image.FLIP_LEFT_RIGHT) for f in frames]
         else:
             out = []
@@ -106,9 +121,11 @@ class VideoTransform:
 
 # ------------------------------------------------------------------------------------------ dataset
 class MUSICMixDataset(torch.utils.data.Dataset):
-    def __init__(self, csv_path, params, split="val", debug=False, seed=None, random_sample=False, vis_data=False):
+    def __init__(self, csv_path, params, split="val", debug=False, seed=None, random_sample=False, vis_data=False,
+                 raw_frames=False):
         p = params
         self.debug = debug
+        self.raw_frames = bool(raw_frames)     # items carry the decoded uint8 frames and the draws: to_device prepares them on the GPU
         self.num_frames, self.imgSize, self.stride_frames = p["num_frames"], p["imgSize"], p["stride_frames"]
         self.one_frame = p["one_frame"]
         if p.get("load_clips"):
@@ -237,16 +254,29 @@ class MUSICMixDataset(torch.utils.data.Dataset):
         return [os.path.join(fpath, "{:06d}.jpg".format(center_idx + (i - self.num_frames // 2) * self.stride_frames))
                 for i in range(self.num_frames)], center_idx
 
-    def _load_frames(self, paths):
+    @staticmethod
+    def _open_frames(paths):
         from PIL import Image
-        return self.vid_transform([Image.open(p).convert("RGB") for p in paths])
+        return [Image.open(p).convert("RGB") for p in paths]
+
+    def _load_frames(self, paths):
+        return self.vid_transform(self._open_frames(paths))
+
+    def _load_raw_frames(self, paths):
+        """The clip as decoded, with the draws VideoTransform would make for it, in its order -> (uint8 [bytes]: the frames
+        [H,W,3] back to back, int32 [T,2] their (H, W), crop (i, j) | None, flip)."""
+        arrays = [np.asarray(f, dtype=np.uint8) for f in self._open_frames(paths)]
+        H, W = arrays[0].shape[:2]
+        crop, flip = draw_crop_flip(*self.vid_transform.resized_size(W, H), self.imgSize, self.vid_transform.train)
+        pixels = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays]))
+        return pixels, torch.tensor([a.shape[:2] for a in arrays], dtype=torch.int32), crop, flip
 
     def get_frames(self, infos, center_times):
         frames, shifts = [], []
         for n in range(self.num_mix):
             paths, center_idx = self.frame_paths(infos[n], center_times[n])
             shifts.append(center_times[n] - center_idx / float(infos[n][3]))
-            frames.append(self._load_frames(paths))
+            frames.append(self._load_raw_frames(paths) if self.raw_frames else self._load_frames(paths))
         return frames, shifts
 
     # ---- music.py:240-252
@@ -263,8 +293,16 @@ class MUSICMixDataset(torch.utils.data.Dataset):
         audios, mixture, center_times = self.get_audios(infos)
         frames, _ = self.get_frames(infos, center_times)
         name, cls = self.get_ids_labels(infos, index, center_times)
-        return {"infos": infos, "audios": [torch.from_numpy(a) for a in audios], "audio_mix": torch.from_numpy(mixture),
-                "frames": frames, "id": name, "class": cls}
+        item = {"infos": infos, "audios": [torch.from_numpy(a) for a in audios], "audio_mix": torch.from_numpy(mixture),
+                "id": name, "class": cls}
+        if not self.raw_frames:
+            item["frames"] = frames
+            return item
+        # per source: the decoded pixels, the frames' shapes and the clip's draws (RAW_KEYS); no "frames" until to_device
+        item.update({"frames_u8": [f[0] for f in frames], "frame_shapes": [f[1] for f in frames],
+                     "frame_crops": [f[2] for f in frames], "frame_flips": [f[3] for f in frames],
+                     "imgSize": self.imgSize, "split": self.split})
+        return item
 
 
 # ------------------------------------------------------------------------------------------ hand-off
@@ -277,21 +315,52 @@ def _stack(ts):
 
 def collate(samples):
     """default_collate's layout for this dict (lists of per-source tensors stay lists; `infos` transposed like
-    default_collate does for nested lists of strings).  GPU-free: safe in forked workers."""
+    default_collate does for nested lists of strings).  GPU-free: safe in forked workers.
+    A batch of raw items (MUSICMixDataset(raw_frames=True)) has, instead of "frames", with N sources, B items, T frames:
+      "frames_u8"     uint8 [bytes]: every frame [H,W,3] back to back, in the order source, item, time;
+      "frame_shapes"  int32 [N,B,T,2]: (H, W) of every frame;
+      "frame_crops"   int32 [N,B,2]: the clips' drawn corners (i, j), or None in the validation form (every frame its centre);
+      "frame_flips"   bool [N,B];
+      "imgSize" int and "split" str, as the dataset has them.
+    ``to_device`` turns these into "frames"."""
     N = len(samples[0]["audios"])
-    return {"audios": [_stack([s["audios"][n] for s in samples]) for n in range(N)],
-            "audio_mix": _stack([s["audio_mix"] for s in samples]),
-            "frames": [_stack([s["frames"][n] for s in samples]) for n in range(N)],
-            "id": [s["id"] for s in samples], "class": torch.stack([s["class"] for s in samples], 0),
-            "infos": [[[s["infos"][n][k] for s in samples] for k in range(len(samples[0]["infos"][n]))] for n in range(N)]}
+    out = {"audios": [_stack([s["audios"][n] for s in samples]) for n in range(N)],
+           "audio_mix": _stack([s["audio_mix"] for s in samples]),
+           "id": [s["id"] for s in samples], "class": torch.stack([s["class"] for s in samples], 0),
+           "infos": [[[s["infos"][n][k] for s in samples] for k in range(len(samples[0]["infos"][n]))] for n in range(N)]}
+    if "frames_u8" not in samples[0]:
+        out["frames"] = [_stack([s["frames"][n] for s in samples]) for n in range(N)]
+        return out
+    out["frames_u8"] = torch.cat([s["frames_u8"][n] for n in range(N) for s in samples])
+    out["frame_shapes"] = torch.stack([torch.stack([s["frame_shapes"][n] for s in samples]) for n in range(N)])
+    crops = [[s["frame_crops"][n] for s in samples] for n in range(N)]
+    out["frame_crops"] = None if crops[0][0] is None else torch.tensor(crops, dtype=torch.int32)
+    out["frame_flips"] = torch.tensor([[s["frame_flips"][n] for s in samples] for n in range(N)], dtype=torch.bool)
+    out["imgSize"], out["split"] = samples[0]["imgSize"], samples[0]["split"]
+    return out
+
+
+def _prepare_raw(batch, device):
+    """The "frames" of a raw batch: one upload of the bytes, one launch for every source -> N tensors [B,3,T,S,S]."""
+    from . import frames as F
+    N, B, T, _ = batch["frame_shapes"].shape
+    train, crops = batch["split"] == "train", batch["frame_crops"]
+    per_clip = [None] * (N * B) if crops is None else [tuple(c) for c in crops.reshape(N * B, 2).tolist()]
+    plan = F.plan_batch(batch["frame_shapes"].reshape(-1, 2).tolist(), batch["imgSize"], train=train,
+                        crops=[c for c in per_clip for _ in range(T)],
+                        flips=[f for f in batch["frame_flips"].reshape(-1).tolist() for _ in range(T)], layout=(N * B, T))
+    out = F.prepare_batch(batch["frames_u8"].to(device, non_blocking=True), plan)
+    return list(out.view(N, B, 3, T, plan.img_size, plan.img_size).unbind(0))
 
 
 def to_device(batch, device):
-    """Asynchronous H2D of the tensors of a collated batch (pinned source -> non_blocking copies on the current stream)."""
+    """Asynchronous H2D of the tensors of a collated batch (pinned source -> non_blocking copies on the current stream).  A raw
+    batch (``collate``) uploads its bytes and gets its "frames" from the GPU (frames.prepare_batch), bit for bit what the
+    workers' VideoTransform would have made of them."""
     mv = lambda t: t.to(device, non_blocking=True)      # noqa: E731
     out = dict(batch)
     out["audios"] = [mv(t) for t in batch["audios"]]
-    out["frames"] = [mv(t) for t in batch["frames"]]
+    out["frames"] = _prepare_raw(batch, device) if "frames_u8" in batch else [mv(t) for t in batch["frames"]]
     out["audio_mix"] = mv(batch["audio_mix"])
     return out
 

@@ -1133,6 +1133,34 @@ def frames_prepare(frames, tables, size, S, crop, flip, return_u8=False):
     return (out, u8) if return_u8 else out
 
 
+def frames_batch_plan(rows, S, pixel_bytes, table_words, out_floats, plane):
+    """avsep_frames_batch_plan (include/avsep.h; host only, no GPU): rows = a NumPy array of dtype np.dtype(lib.FramesRow),
+    at most 65535 of them -> (grid y, LDS bytes, smallest tile height); the rows' launch sizing is filled in in place.
+    AvsepError for anything the library refuses."""
+    launch = (C.c_int32 * 3)()
+    rc = lib.load().avsep_frames_batch_plan(rows.ctypes.data_as(C.POINTER(lib.FramesRow)), len(rows), int(S), int(pixel_bytes),
+                                            int(table_words), int(out_floats), int(plane), launch)
+    if rc != 0:
+        raise lib.AvsepError(f"avsep_frames_batch_plan refused {len(rows)} frames at S = {S}: a size, crop, tap count or a pixel, "
+                             f"table or output range outside its buffer ({rc})")
+    return tuple(launch)
+
+
+def frames_prepare_batch(pixels, rows, tables, lut, S, out, plane, grid_y, lds_bytes):
+    """avsep_frames_prepare_batch (include/avsep.h): pixels uint8 [bytes], rows uint8 [n * sizeof(avsep_frames_row)] (the planned
+    rows), tables int32 [words], lut f32 [256,3] and out f32, all on one GPU; one launch for n <= 65535 frames."""
+    lib.require_gpu(pixels)
+    n = rows.numel() // C.sizeof(lib.FramesRow)
+    for t, dtype in ((pixels, torch.uint8), (rows, torch.uint8), (tables, torch.int32), (lut, torch.float32), (out, torch.float32)):
+        if t.dtype != dtype or t.device != pixels.device or not t.is_contiguous():
+            raise lib.AvsepError(f"frames_prepare_batch: a buffer must be {dtype}, contiguous, on {pixels.device}, got {_got(t)}")
+    if rows.numel() != n * C.sizeof(lib.FramesRow) or tuple(lut.shape) != (256, 3):
+        raise lib.AvsepError(f"frames_prepare_batch: {rows.numel()} bytes of rows, look-up table {tuple(lut.shape)}")
+    call("avsep_frames_prepare_batch", ptr(pixels), pixels.numel(), ptr(rows), n, ptr(tables), tables.numel(), int(S), ptr(lut),
+         ptr(out), out.numel(), int(plane), int(grid_y), int(lds_bytes))
+    return out
+
+
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 

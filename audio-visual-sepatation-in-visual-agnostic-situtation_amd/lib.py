@@ -41,8 +41,17 @@ class CatDesc(C.Structure):
                [(n, C.c_void_p) for n in "x0 x1 scale0 shift0 scale1 shift1".split()]
 
 
+class FramesRow(C.Structure):
+    """avsep_frames_row (include/avsep.h): one frame of avsep_frames_prepare_batch.  np.dtype(FramesRow) is the layout of a
+    table of rows on the host and, byte for byte, on the device."""
+    _fields_ = [("pix_off", C.c_int64), ("out_off", C.c_int64)] + \
+               [(n, C.c_int32) for n in "H W w h kh kv hcoef hbound vcoef vbound crop_i crop_j flip TR max_cols in_bytes mid_rows "
+                                        "reserved".split()]
+
+
 _P, _I, _F, _D, _Z = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t
 _CD, _KD = C.POINTER(ConvDesc), C.POINTER(CatDesc)
+_L = C.c_int64
 
 # name -> (restype, argtypes); one entry per prototype in include/avsep.h
 SIGNATURES = {
@@ -105,6 +114,8 @@ SIGNATURES = {
     "avsep_true_peak_workspace_bytes": (_Z, [_I, _I]),
     "avsep_true_peak": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "avsep_frames_prepare": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "avsep_frames_batch_plan": (C.c_int, [C.POINTER(FramesRow), _I, _I, _L, _L, _L, _L, C.POINTER(C.c_int32)]),
+    "avsep_frames_prepare_batch": (C.c_int, [_P, _L, _P, _I, _P, _L, _I, _P, _P, _L, _L, _I, _I, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

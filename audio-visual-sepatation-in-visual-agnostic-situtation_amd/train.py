@@ -121,7 +121,9 @@ def main(args):
         optimizer = create_optimizer(nets, args, world_size=world)
     torch.manual_seed(args.seed + 1 + rank)                        # rank-local data order and AO swaps
 
-    loader_val = dataset.make_loader(args.list_val, args, "val", args.batch_size, False, workers=min(4, args.workers))
+    # --gpu_frames: the workers hand the frames as decoded and to_device prepares them in one launch (frames.prepare_batch)
+    raw = {"raw_frames": True} if getattr(args, "gpu_frames", False) else {}
+    loader_val = dataset.make_loader(args.list_val, args, "val", args.batch_size, False, workers=min(4, args.workers), **raw)
     history = new_history()
     start_i = 0
     if args.load_ckpt:
@@ -142,8 +144,8 @@ def main(args):
         evaluate(wrapper, loader_val, history, 0, args, False, device, world)
         print("Evaluation Done!")
         return history
-    av = _Cycle(dataset.make_loader(args.av_list_train, args, "train", args.batch_size, True, workers=args.workers))
-    ao = _Cycle(dataset.make_loader(args.ao_list_train, args, "train", args.batch_size, True, workers=args.workers, seed=10))
+    av = _Cycle(dataset.make_loader(args.av_list_train, args, "train", args.batch_size, True, workers=args.workers, **raw))
+    ao = _Cycle(dataset.make_loader(args.ao_list_train, args, "train", args.batch_size, True, workers=args.workers, seed=10, **raw))
 
     err_total = err_av = err_ao = match_sum = 0.0
     av_count = ao_count = 0
@@ -199,8 +201,19 @@ def main(args):
     return history
 
 
+def own_flags(argv=None):
+    """The flags of this command line that the reference's flag table (arguments.py) does not have -> (namespace, the rest)."""
+    import argparse
+    own = argparse.ArgumentParser(add_help=False)
+    own.add_argument("--gpu_frames", action="store_true",
+                     help="loader workers decode only; resize, crop, flip and normalisation run on the GPU, one launch per batch")
+    return own.parse_known_args(argv)
+
+
 def cli(argv=None):
+    own, argv = own_flags(argv)
     args = ArgParser().parse_train_arguments(argv)
+    args.gpu_frames = own.gpu_frames
     print("Model ID: {}".format(args.id))
     args.ckpt = os.path.join(args.ckpt, args.id)                   # main.py:776-791
     three_stage = getattr(args, "train_steps", None) is not None

@@ -732,6 +732,38 @@ int avsep_frames_prepare(const uint8_t* frames, int32_t T, int32_t H, int32_t W,
                          int32_t kh, const int32_t* vcoef, const int32_t* vbound, int32_t h, int32_t kv, int32_t S, int32_t crop_i,
                          int32_t crop_j, int32_t flip, const float* lut, float* out, uint8_t* out_u8, avsep_stream_t stream);
 
+/* Frames of many sizes in one launch (the training loader: B x N clips, each with its own size, crop and flip).  `pixels` is one
+ * uint8 DEVICE buffer of pixel_bytes bytes that holds the n RGB frames back to back, each [H][W][3] and starting at any byte;
+ * `tables` one int32 DEVICE buffer of table_words words that holds the coefficient and bound tables of every axis pair the
+ * batch has, in the layout above (frames of one axis pair share them).  One row per frame says where everything is: */
+typedef struct avsep_frames_row {
+  int64_t pix_off;                          /* the frame's first byte in `pixels` */
+  int64_t out_off;                          /* the first float of its channel 0 in `out` */
+  int32_t H, W, w, h, kh, kv;               /* as for avsep_frames_prepare */
+  int32_t hcoef, hbound, vcoef, vbound;     /* word offsets of the four tables in `tables` */
+  int32_t crop_i, crop_j, flip;
+  int32_t TR, max_cols, in_bytes, mid_rows; /* launch sizing: written by avsep_frames_batch_plan, never by the caller */
+  int32_t reserved;
+} avsep_frames_row;
+/* Frame r writes out[out_off + c * plane + y * S + x'], c = 0 .. 2: plane = S*S and out_off = r*3*S*S give [n][3][S][S];
+ * plane = T*S*S and out_off = (b*3*T + t)*S*S give the loader's [B][3][T][S][S].
+ * avsep_frames_batch_plan (host only, nothing is launched): checks n HOST rows against the limits of avsep_frames_prepare
+ * (sides, S, kh / kv as the sizes imply and <= 81, crop, flip), every pixel range inside pixel_bytes, every table range inside
+ * table_words and every output range out_off + 2*plane + S*S inside out_floats (plane >= S*S); fills in the rows' launch
+ * sizing and returns launch[0] = grid y (S over the smallest tile height of the batch), launch[1] = dynamic LDS bytes (the
+ * largest any frame needs), launch[2] = that smallest tile height.  1 <= n <= 65535.  On AVSEP_ERR_ARG the rows' sizing fields
+ * are unspecified.
+ * avsep_frames_prepare_batch: rows = the planned rows in DEVICE memory, grid_y and lds_bytes = the plan's answer.  The kernel
+ * does not trust the device rows with addresses: every offset, count and size it reads is clamped or checked against
+ * pixel_bytes, table_words, out_floats and lds_bytes, so a wrong row gives wrong pixels or an untouched output, never an
+ * access outside a buffer.  A null pointer, n outside 1 .. 65535, S outside 8 .. 1024, plane < S*S, out_floats < 2*plane + S*S,
+ * grid_y outside ceil(S/32) .. S or lds_bytes outside 3072 .. 54400 is AVSEP_ERR_ARG before any launch. */
+int avsep_frames_batch_plan(avsep_frames_row* rows, int32_t n, int32_t S, int64_t pixel_bytes, int64_t table_words,
+                            int64_t out_floats, int64_t plane, int32_t* launch);
+int avsep_frames_prepare_batch(const uint8_t* pixels, int64_t pixel_bytes, const avsep_frames_row* rows, int32_t n,
+                               const int32_t* tables, int64_t table_words, int32_t S, const float* lut, float* out,
+                               int64_t out_floats, int64_t plane, int32_t grid_y, int32_t lds_bytes, avsep_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
