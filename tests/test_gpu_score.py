@@ -20,8 +20,10 @@ CASES = [(2, 1, 3000, 16, 1000, 500),        # overlapping windows
          (3, 1, 2500, 32, 800, 400),         # three sources
          (3, 2, 2200, 8, 700, 700),          # six rows and six right-hand sides
          (2, 2, 6000, 512, 6000, 6000),      # the 2048-unknown limit, one window
-         (2, 2, 4453, 16, 1453, 1000)]       # two 2048-sample chunks of the correlation kernel and an odd remainder of 357:
+         (2, 2, 4453, 16, 1453, 1000),       # two 2048-sample chunks of the correlation kernel and an odd remainder of 357:
 #                                              windows start inside a chunk (1000, 3000) and the last one ends exactly at L
+         (2, 2, 2500, 13, 900, 450),         # flen no multiple of 8: discarded lags and zero-padded taps
+         (3, 1, 2300, 24, 700, 700)]         # three groups of 8 lags: 64 of the correlation kernel's 256 threads idle
 
 
 def _score():
