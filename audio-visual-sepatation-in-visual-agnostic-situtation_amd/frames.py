@@ -25,7 +25,7 @@ import torch
 
 from . import dataset
 from . import kernels as K
-from .lib import AvsepError, FramesRow
+from .lib import AvsepError, FramesRow, got
 
 MAX_SIDE = 4096
 MIN_SIZE, MAX_SIZE = 8, 1024
@@ -164,9 +164,8 @@ def check_stack(frames, who="frames.prepare"):
     """frames must be a uint8 tensor [T,H,W,3], contiguous, T >= 1 -> its shape."""
     if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 \
             or frames.shape[0] < 1 or not frames.is_contiguous():
-        got = f"{frames.dtype} {tuple(frames.shape)}" + ("" if frames.is_contiguous() else ", not contiguous") \
-            if torch.is_tensor(frames) else type(frames).__name__
-        raise AvsepError(f"{who} takes uint8 RGB frames [T,H,W,3], contiguous, T >= 1; got {got}")
+        loose = ", not contiguous" if torch.is_tensor(frames) and not frames.is_contiguous() else ""
+        raise AvsepError(f"{who} takes uint8 RGB frames [T,H,W,3], contiguous, T >= 1; got {got(frames)}{loose}")
     return tuple(frames.shape)
 
 
@@ -270,9 +269,8 @@ def prepare_batch(pixels_u8, batch_plan):
         raise AvsepError(f"frames.prepare_batch takes a plan of frames.plan_batch, got {type(batch_plan).__name__}")
     if not torch.is_tensor(pixels_u8) or pixels_u8.dtype != torch.uint8 or pixels_u8.dim() != 1 or not pixels_u8.is_contiguous() \
             or pixels_u8.numel() != batch_plan.pixel_bytes:
-        got = f"{pixels_u8.dtype} {tuple(pixels_u8.shape)}" if torch.is_tensor(pixels_u8) else type(pixels_u8).__name__
         raise AvsepError(f"frames.prepare_batch takes the plan's {batch_plan.pixel_bytes} bytes as one contiguous uint8 tensor "
-                         f"[bytes]; got {got}")
+                         f"[bytes]; got {got(pixels_u8)}")
     K.lib.require_gpu(pixels_u8)
     dev = pixels_u8.device
     tables, lut = batch_plan.packed.on(dev)

@@ -1,7 +1,10 @@
 """Tensor-level wrappers over the C ABI (one Python function per entry point of include/avsep.h).
 
-Only shape bookkeeping and output allocation happen here; all arithmetic is in
-libavsep_gfx950.so.  Tensors are dense fp32 NCHW on the current cuda device.
+Only shape bookkeeping, output allocation and operand checks happen here; all arithmetic is in
+libavsep_gfx950.so.  Tensors are dense and live on a cuda device: activations are fp32 NCHW or
+B16 images (bfloat16 [N, C/16, H, W, 16], see "storage formats" below), the conv wrappers
+convert between the two at a kernel's door, and the audio, frame and scoring entry points take
+the dtypes their docstrings name (uint8 file bytes, int32 tables, float64 sums).
 """
 import ctypes as C
 import os
@@ -53,31 +56,43 @@ def _b16(shape_nchw, like):
     return torch.empty((N, Cc // 16, H, W, 16), dtype=torch.bfloat16, device=like.device)
 
 
-def empty_as(t):
-    return torch.empty_like(t)
+class _Mark:
+    """Where and when something was built that another HIP stream may read later: the one body of the host layer's
+    multi-stream rule (the twin cache, the pack cache and the BatchNorm order of fork_streams).  `_Mark(t)` is made right
+    after the launches that build it, on the current stream of t's device; a host tensor leaves an empty mark."""
+    __slots__ = ("event", "stream")
+
+    def __init__(self, t):
+        self.event = self.stream = None
+        if t.is_cuda:
+            self.event, self.stream = torch.cuda.Event(), torch.cuda.current_stream(t.device)
+            self.event.record(self.stream)
+
+    def reach(self, *tensors):
+        """Order the current stream behind the mark if it is another one than the producer's, and keep the memory of
+        `tensors` from being handed out again before this stream is done with it."""
+        if self.event is None:
+            return
+        cur = torch.cuda.current_stream(self.stream.device)
+        if cur != self.stream:
+            cur.wait_event(self.event)
+            for t in tensors:
+                t.record_stream(cur)
 
 
 def _twin_hit(t):
-    """The remembered other-format twin of `t` if it is current.  A twin built on another stream (two passes that share a
-    tensor run on forked streams) is waited for, and its memory is kept until this stream is done with it."""
+    """The remembered other-format twin of `t` if it is current (two passes that share a tensor may run on forked streams)."""
     twin = getattr(t, "_avsep_twin", None)
     if twin is None or twin[1] != t._version:
         return None
-    if twin[2] is not None:
-        cur = torch.cuda.current_stream(t.device)
-        if cur != twin[3]:
-            cur.wait_event(twin[2])
-            twin[0].record_stream(cur)
+    twin[2].reach(twin[0])
     return twin[0]
 
 
 def _twin_set(t, out):
-    ev = st = None
-    if t.is_cuda:
-        ev, st = torch.cuda.Event(), torch.cuda.current_stream(t.device)
-        ev.record()
-    t._avsep_twin = (out, t._version, ev, st)
-    out._avsep_twin = (t, out._version, ev, st)
+    mark = _Mark(t)
+    t._avsep_twin = (out, t._version, mark)
+    out._avsep_twin = (t, out._version, mark)
 
 
 def to_b16(t):
@@ -117,13 +132,9 @@ def b16_ok(c):
     return c % 16 == 0
 
 
-# Activations between the bf16 kernels are kept as B16 images when the arithmetic mode is bf16 (set_precision).  The module
-# attribute exists for A/B measurements from a script (False: fp32 NCHW tensors, converted at every bf16 kernel's door).
-b16_activations = True
-
-
 def want_b16(c=16):
-    return _precision == 1 and b16_activations and b16_ok(c)
+    """Activations between the bf16 kernels are kept as B16 images when the arithmetic mode is bf16 (set_precision)."""
+    return _precision == 1 and b16_ok(c)
 
 
 # bf16 mode: weight gradients of the <= 8x8 maps (the deep U-Net levels) run over ONE grid image of the whole batch instead of
@@ -207,6 +218,9 @@ class pack_scope:
         return False
 
 
+CONV_MODES = {"fwd": 0, "dgrad": 1, "wgrad": 2}     # the `mode` of the avsep_conv_* queries
+
+
 def out_size(h, k, s, p, d):
     return (h + 2 * p - d * (k - 1) - 1) // s + 1
 
@@ -277,21 +291,14 @@ class Conv:
                    d.plan_n, bool(d.scale0), bool(d.scale1), d.act0, d.act1, d.algo, d.tune)
             hit = _pack_cache.get(key)
             if hit is not None:
-                if hit[2] is not None and torch.cuda.current_stream() != hit[3]:
-                    cur = torch.cuda.current_stream()
-                    cur.wait_event(hit[2])           # packed on another stream (fork_streams): order behind it ...
-                    hit[0].record_stream(cur)        # ... and keep its memory from being reused before this stream is done
+                hit[2].reach(hit[0])         # streams may share the cache (fork_streams, and the backward of such passes)
                 return hit[0]
         n = lib.load().avsep_conv_packed_floats(ref, mode)
         out = _f32((n,), w)
         call("avsep_conv_pack_weights", ref, ptr(w), ptr(out), mode)
         if key is not None:
-            ev = None
-            if out.is_cuda:                  # streams may share the cache (fork_streams, and the backward of such passes):
-                ev = torch.cuda.Event()      # remember where and when the image was built
-                ev.record()
             # holding `w` keeps a temporary weight tensor's address from being reused
-            _pack_cache[key] = (out, w, ev, torch.cuda.current_stream() if ev is not None else None)
+            _pack_cache[key] = (out, w, _Mark(out))
         return out
 
     def _grid_geometry(self, mode=2):
@@ -300,7 +307,7 @@ class Conv:
         4x4 / stride 2 / pad 1, the forward (mode 0) of 4x4 / stride 2 / pad 1.  None otherwise."""
         if mode not in (0, 2):
             return None
-        key = (mode, grid_small_maps, b16_activations)
+        key = (mode, grid_small_maps)
         memo = self.__dict__.setdefault("_grid_memo", {})
         hit = memo.get(key, 0)
         if hit != 0:
@@ -310,7 +317,7 @@ class Conv:
 
     def _grid_geometry_of(self, mode):
         d = self.d
-        if not (grid_small_maps and d.prec == 1 and b16_activations and self.keep[1] is None and not d.up2x and d.dil == 1 and
+        if not (grid_small_maps and d.prec == 1 and self.keep[1] is None and not d.up2x and d.dil == 1 and
                 self.N >= 2 and b16_ok(self.Cin) and b16_ok(self.Cout) and max(self.H, self.W) <= 8):
             return None
         geo = (self.KH, self.KW, d.stride, d.pad)
@@ -416,10 +423,10 @@ class Conv:
     def kernel_name(self, mode, with_stats=True):
         """Kernel family the library dispatches this call to (mode: "fwd" | "dgrad" | "wgrad")."""
         ref = self.ref
-        g = self._grid_geometry({"fwd": 0, "wgrad": 2}.get(mode, 1))
+        g = self._grid_geometry(CONV_MODES[mode])
         if g is not None:                            # the call runs on the grid image of the batch
             ref = C.byref(self._grid_desc(g))
-        return lib.load().avsep_conv_kernel_name(ref, {"fwd": 0, "dgrad": 1, "wgrad": 2}[mode], int(with_stats)).decode()
+        return lib.load().avsep_conv_kernel_name(ref, CONV_MODES[mode], int(with_stats)).decode()
 
     def kernel_variant(self, mode, with_stats=True, plan_n=None):
         """Family + the grid-size dependent launch decisions (tile shape, workgroup size, split-K) of this call; with
@@ -429,7 +436,7 @@ class Conv:
             d = ConvDesc.from_buffer_copy(self.d)
             d.plan_n = plan_n
         buf = C.create_string_buffer(128)
-        rc = lib.load().avsep_conv_kernel_variant(C.byref(d), {"fwd": 0, "dgrad": 1, "wgrad": 2}[mode], int(with_stats), buf, 128)
+        rc = lib.load().avsep_conv_kernel_variant(C.byref(d), CONV_MODES[mode], int(with_stats), buf, 128)
         if rc != 0:
             raise lib.AvsepError(f"avsep_conv_kernel_variant failed ({rc})")
         return buf.value.decode()
@@ -533,7 +540,7 @@ class fork_streams:
         return False
 
 
-_order = None      # fork_streams: running_mean.data_ptr() -> (event of the last update, its stream)
+_order = None      # fork_streams: running_mean.data_ptr() -> _Mark of the last update
 
 
 def bn_finalize(stats, count, gamma, beta, rmean, rvar, momentum, eps, training, like, num_batches_tracked=None, updates=1):
@@ -542,15 +549,13 @@ def bn_finalize(stats, count, gamma, beta, rmean, rvar, momentum, eps, training,
     ordered = _order is not None and training and rmean is not None
     if ordered:
         last = _order.get(rmean.data_ptr())
-        if last is not None and last[1] != torch.cuda.current_stream():
-            torch.cuda.current_stream().wait_event(last[0])
+        if last is not None:
+            last.reach()
     call("avsep_bn_finalize", ptr(stats), float(count), ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
          float(momentum), float(eps), Cc, int(training), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]),
          ptr(num_batches_tracked), int(updates))
     if ordered:
-        ev = torch.cuda.Event()
-        ev.record()
-        _order[rmean.data_ptr()] = (ev, torch.cuda.current_stream())
+        _order[rmean.data_ptr()] = _Mark(rmean)
     return out
 
 
@@ -756,8 +761,7 @@ def window_reduce_check(ranges, T):
     1 <= K <= 65535 and, for every row, count >= 1, 0 <= first and first + count <= T.  AvsepError otherwise."""
     if not torch.is_tensor(ranges) or ranges.is_cuda or ranges.dtype != torch.int32 or ranges.dim() != 2 or ranges.shape[1] != 2 \
             or not 1 <= ranges.shape[0] <= 65535:
-        what = f"{ranges.dtype} {tuple(ranges.shape)} on {ranges.device}" if torch.is_tensor(ranges) else type(ranges).__name__
-        raise lib.AvsepError(f"window_reduce takes ranges as int32 [K,2] (first, count) on the CPU with K in 1 ... 65535, got {what}")
+        raise lib.AvsepError(f"window_reduce takes ranges as int32 [K,2] (first, count) on the CPU with K in 1 ... 65535, got {lib.got(ranges)}")
     r = ranges.to(torch.int64)
     bad = (r[:, 1] < 1) | (r[:, 0] < 0) | (r[:, 0] + r[:, 1] > int(T))
     if bool(bad.any()):
@@ -773,8 +777,7 @@ def window_reduce(f, ranges, op="mean"):
     if op not in WINDOW_REDUCE_OPS:
         raise lib.AvsepError(f"window_reduce takes op 'mean' or 'max', got {op!r}")
     if not torch.is_tensor(f) or f.dtype != torch.float32 or f.dim() < 1 or f.numel() < 1 or not f.is_contiguous():
-        what = f"{f.dtype} {tuple(f.shape)}" if torch.is_tensor(f) else type(f).__name__
-        raise lib.AvsepError(f"window_reduce takes f as a contiguous float32 tensor [T, ...] with T >= 1, got {what}")
+        raise lib.AvsepError(f"window_reduce takes f as a contiguous float32 tensor [T, ...] with T >= 1, got {lib.got(f)}")
     T = f.shape[0]
     window_reduce_check(ranges, T)
     lib.require_gpu(f)
@@ -900,8 +903,7 @@ def _sample_format(what, fmt, out=False):
 def raw_frames(what, raw, C, nbytes):
     """The frame count of raw uint8 [L*C*nbytes] (a file's data chunk, from any byte address)."""
     if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() % (C * nbytes):
-        got = f"{raw.dtype} {tuple(raw.shape)}" if torch.is_tensor(raw) else type(raw).__name__
-        raise lib.AvsepError(f"{what} takes raw frames as uint8 [L*{C}*{nbytes}], got {got}")
+        raise lib.AvsepError(f"{what} takes raw frames as uint8 [L*{C}*{nbytes}], got {lib.got(raw)}")
     return raw.numel() // (C * nbytes)
 
 
@@ -910,8 +912,7 @@ def _raw_out(what, out, n, device):
     if out is None:
         return torch.empty((n,), dtype=torch.uint8, device=device)
     if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (n,) or not out.is_contiguous() or out.device != device:
-        got = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else type(out).__name__
-        raise lib.AvsepError(f"{what}: out is contiguous uint8 [{n}] on {device}, got {got}")
+        raise lib.AvsepError(f"{what}: out is contiguous uint8 [{n}] on {device}, got {lib.got(out)}")
     return out
 
 
@@ -989,10 +990,6 @@ BAND_MAX_ROWS = 8
 BAND_MAX_HOP = 4096
 
 
-def _got(t):
-    return f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
-
-
 def band_gains(stem_mag, mix_mag, lo_bin=None):
     """avsep_band_gains (include/avsep.h): stem_mag f32 [N,G,bins,F], mix_mag f32 [G,bins,F] -> f32 [N,G,F], per frame the share
     of the mixture's RMS amplitude every source holds over the bins [lo_bin, bins), at most 1; ``lo_bin`` defaults to
@@ -1000,7 +997,7 @@ def band_gains(stem_mag, mix_mag, lo_bin=None):
     if not torch.is_tensor(stem_mag) or not torch.is_tensor(mix_mag) or stem_mag.dtype != torch.float32 or stem_mag.dim() != 4 \
             or mix_mag.dtype != torch.float32 or tuple(mix_mag.shape) != tuple(stem_mag.shape[1:]) or mix_mag.device != stem_mag.device:
         raise lib.AvsepError(f"band_gains takes stem_mag float32 [N,G,bins,F] and mix_mag float32 [G,bins,F] on one device, got "
-                             f"{_got(stem_mag)} and {_got(mix_mag)}")
+                             f"{lib.got(stem_mag)} and {lib.got(mix_mag)}")
     lib.require_gpu(stem_mag)
     N, G, bins, F = stem_mag.shape
     if not (1 <= N <= BAND_MAX_SOURCES and 1 <= G <= BAND_MAX_ROWS and F >= 1):
@@ -1023,7 +1020,7 @@ def band_extend(stems, low, file, gains, filt, up, down, hop):
     for name, t, nd in (("stems", stems, 3), ("low", low, 2), ("file", file, 2), ("gains", gains, 3)):
         if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != nd:
             raise lib.AvsepError(f"band_extend takes {name} as float32 with {nd} dimensions (stems [N,G,Lm], low [G,Ll], file [G,Lf], "
-                                 f"gains [N,G,F]), got {_got(t)}")
+                                 f"gains [N,G,F]), got {lib.got(t)}")
     lib.require_gpu(stems)
     lib.require_gpu(filt)
     N, G, Lm = stems.shape
@@ -1062,8 +1059,7 @@ TRUE_PEAK_TAPS = 21               # rows of avsep_true_peak's polyphase table
 
 def _level_rows(what, x):
     if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or not 1 <= x.shape[0] <= 65535 or x.shape[1] < 1:
-        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
-        raise lib.AvsepError(f"{what} takes float32 rows [R,L] with 1 <= R <= 65535 and L >= 1, got {got}")
+        raise lib.AvsepError(f"{what} takes float32 rows [R,L] with 1 <= R <= 65535 and L >= 1, got {lib.got(x)}")
     return x.shape
 
 
@@ -1094,8 +1090,7 @@ def true_peak(x, taps, os):
     if isinstance(os, bool) or os not in (1, 2, 4) or os * L >= 2 ** 31:
         raise lib.AvsepError(f"true_peak oversamples by 1, 2 or 4 with os * L < 2^31, got os={os!r} L={L}")
     if not torch.is_tensor(taps) or taps.dtype != torch.float64 or tuple(taps.shape) != (TRUE_PEAK_TAPS, os) or taps.device != x.device:
-        got = f"{taps.dtype} {tuple(taps.shape)} on {taps.device}" if torch.is_tensor(taps) else type(taps).__name__
-        raise lib.AvsepError(f"true_peak: the table of os={os} is float64 [{TRUE_PEAK_TAPS},{os}] on {x.device}, got {got}")
+        raise lib.AvsepError(f"true_peak: the table of os={os} is float64 [{TRUE_PEAK_TAPS},{os}] on {x.device}, got {lib.got(taps)}")
     lib.require_gpu(x)
     x, taps = x.contiguous(), taps.contiguous()
     nbytes = lib.load().avsep_true_peak_workspace_bytes(R, L)
@@ -1122,7 +1117,7 @@ def frames_prepare(frames, tables, size, S, crop, flip, return_u8=False):
             (vbound, torch.int32, (h, 2)), (lut, torch.float32, (256, 3)))
     for t, dtype, shape in want:
         if t.dtype != dtype or tuple(t.shape) != shape or t.device != frames.device or not t.is_contiguous():
-            raise lib.AvsepError(f"frames_prepare: a table must be {dtype} {shape} on {frames.device}, got {_got(t)}")
+            raise lib.AvsepError(f"frames_prepare: a table must be {dtype} {shape} on {frames.device}, got {lib.got(t)}")
     out = _f32((T, 3, S, S), frames)
     u8 = torch.empty((T, S, S, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
     for a in range(0, T, FRAMES_MAX_T):
@@ -1153,7 +1148,7 @@ def frames_prepare_batch(pixels, rows, tables, lut, S, out, plane, grid_y, lds_b
     n = rows.numel() // C.sizeof(lib.FramesRow)
     for t, dtype in ((pixels, torch.uint8), (rows, torch.uint8), (tables, torch.int32), (lut, torch.float32), (out, torch.float32)):
         if t.dtype != dtype or t.device != pixels.device or not t.is_contiguous():
-            raise lib.AvsepError(f"frames_prepare_batch: a buffer must be {dtype}, contiguous, on {pixels.device}, got {_got(t)}")
+            raise lib.AvsepError(f"frames_prepare_batch: a buffer must be {dtype}, contiguous, on {pixels.device}, got {lib.got(t)}")
     if rows.numel() != n * C.sizeof(lib.FramesRow) or tuple(lut.shape) != (256, 3):
         raise lib.AvsepError(f"frames_prepare_batch: {rows.numel()} bytes of rows, look-up table {tuple(lut.shape)}")
     call("avsep_frames_prepare_batch", ptr(pixels), pixels.numel(), ptr(rows), n, ptr(tables), tables.numel(), int(S), ptr(lut),
@@ -1179,7 +1174,7 @@ def localise_maps(x, win, vs, att):
     best = torch.empty((T,), dtype=torch.int32, device=x.device)
     scores = _f32((T, 2 if Cn == 2 else 6), x)
     call("avsep_localise_maps", ptr(x), ptr(win), _ptr_array(vs), T, Kw, Cn, D, x.shape[2] * x.shape[3], h * w,
-         {"cos": 0, "sig": 1}[att], ptr(maps), ptr(best), ptr(scores))
+         lib.ATT_BY_NAME[att], ptr(maps), ptr(best), ptr(scores))
     return maps, best, scores
 
 

@@ -152,8 +152,7 @@ def measure(x, rate, weights=None):
     (``channel_weights`` by default).  A NaN or an infinity in a row raises AvsepError naming the programme and channel."""
     rate = _check_rate(rate)
     if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() not in (2, 3) or x.shape[-1] < 1 or x.shape[-2] < 1:
-        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
-        raise AvsepError(f"measure takes float32 [P,C,L] or [C,L], got {got}")
+        raise AvsepError(f"measure takes float32 [P,C,L] or [C,L], got {lib.got(x)}")
     if x.dim() == 2:
         x = x[None]
     P, C, L = x.shape

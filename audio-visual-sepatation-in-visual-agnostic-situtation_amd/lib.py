@@ -16,6 +16,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_SIGMOID, ACT_TANH, ACT_SOFTMAX2 = range(6)
 ACT_BY_NAME = {"no": ACT_NONE, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "tanh": ACT_TANH,
                "softmax": ACT_SOFTMAX2}
 LOSS_BY_NAME = {"bce": 0, "l1": 1, "l2": 2}
+ATT_BY_NAME = {"cos": 0, "sig": 1}
 # avsep_conv_desc.algo: kernel families a call must not use (include/avsep.h AVSEP_ALGO_NO_*)
 ALGO_NO = {"winograd": 1, "winograd_wgrad": 2, "flat": 4, "misc_patch": 8, "bf16_kernels": 16, "smallci_wgrad": 32, "winograd4": 64}
 
@@ -202,6 +203,11 @@ def call(name, *args):
     rc = getattr(lib, name)(*args, stream())
     if rc != 0:
         raise AvsepError(f"{name} failed: {lib.avsep_strerror(rc).decode()} ({rc})")
+
+
+def got(t):
+    """What a refused operand was, for the error message."""
+    return f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
 
 
 def require_gpu(t):

@@ -15,9 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import lib
-from ..lib import call, ptr
-
-_ATT = {"cos": 0, "sig": 1}
+from ..lib import ATT_BY_NAME as _ATT, call, ptr
 
 
 def _pool(t):

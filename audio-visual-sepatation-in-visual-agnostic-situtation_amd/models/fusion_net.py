@@ -11,10 +11,10 @@ import torch
 import torch.nn as nn
 
 from .. import lib
-from ..lib import call, ptr
+from ..kernels import _ptr_array
+from ..lib import ATT_BY_NAME as _ATT, call, ptr
 
 _KIND = {"hidsep": 0, "CoLoc_Sel": 1, "MixVis": 2}
-_ATT = {"cos": 0, "sig": 1}
 
 
 class _FusionBase(nn.Module):
@@ -35,11 +35,7 @@ class _FusionBase(nn.Module):
     # tensor keeps 2*D channels, so the U-Net's parameter shapes do not depend on C), all C! permutations in itertools
     # order, first maximum wins.  One launch forward, one backward (avsep_fusion_n_*), like the two-source kernels.
     num_src = 2
-
-    @staticmethod
-    def _ptr_array(tensors):
-        import ctypes
-        return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+    _ptr_array = staticmethod(_ptr_array)
 
     def _run_forward_n(self, x, vs, draws):
         B, D, Fq, T = x.shape

@@ -113,8 +113,7 @@ def band_extend(stems, low, file_rows, gains, rate_model, rate_file, hop):
         raise AvsepError(f"band_extend adds what a file holds above the model's band: the file's rate ({rate_file} Hz) has to "
                          f"exceed the model's ({rate_model} Hz)")
     if not torch.is_tensor(stems) or stems.dim() != 3:
-        got = f"{stems.dtype} {tuple(stems.shape)}" if torch.is_tensor(stems) else type(stems).__name__
-        raise AvsepError(f"band_extend takes stems as float32 [N,G,Lm], got {got}")
+        raise AvsepError(f"band_extend takes stems as float32 [N,G,Lm], got {lib.got(stems)}")
     lib.require_gpu(stems)
     _check_length(stems.shape[-1], up, down)
     return K.band_extend(stems, low, file_rows, gains, filter_table(up, down, stems.device), up, down, hop)
@@ -161,8 +160,7 @@ def join_frames(x, rate_in, rate_out, fmt, out=None):
     if fmt not in K.SAMPLE_OUT_FORMATS:
         raise AvsepError(f"join_frames writes the sample formats {', '.join(K.SAMPLE_OUT_FORMATS)}, got {fmt!r}")
     if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2:
-        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
-        raise AvsepError(f"join_frames takes float32 [C,L], got {got}")
+        raise AvsepError(f"join_frames takes float32 [C,L], got {lib.got(x)}")
     if not 1 <= x.shape[0] <= MAX_KEPT_CHANNELS:
         raise AvsepError(f"join_frames writes 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {x.shape[0]}")
     up, down = check_rates(rate_in, rate_out)
@@ -201,8 +199,7 @@ def join_pcm(x, rate_in, rate_out):
     """x: f32 [C,L] on the GPU, 1 <= C <= 8 -> interleaved int16 [Lout,C] at rate_out: join_frames(.., 's16') as a typed
     tensor; column c is resample(x[c], .., out_s16=True)."""
     if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2:
-        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
-        raise AvsepError(f"join_pcm takes float32 [C,L], got {got}")
+        raise AvsepError(f"join_pcm takes float32 [C,L], got {lib.got(x)}")
     if not 1 <= x.shape[0] <= MAX_KEPT_CHANNELS:
         raise AvsepError(f"join_pcm writes 1 to {MAX_KEPT_CHANNELS} channels (up to 7.1), got {x.shape[0]}")
     return join_frames(x, rate_in, rate_out, "s16").view(torch.int16).reshape(-1, x.shape[0])

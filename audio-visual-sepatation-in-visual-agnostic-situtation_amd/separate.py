@@ -185,8 +185,8 @@ def _clip_features(net_frame, frames, frame_times, starts, args, batch, dev, act
     for n, fr in enumerate(frames):
         if not torch.is_tensor(fr) or fr.dim() != 4 or fr.shape[3 if is_shot(fr) else 1] != 3 \
                 or tuple(fr.shape) != tuple(frames[0].shape) or fr.dtype != frames[0].dtype:
-            what = f"{fr.dtype} {tuple(fr.shape)}" if torch.is_tensor(fr) else type(fr).__name__
-            raise AvsepError(f"with frame_times, frames[{n}] must be [T,3,H,W] (or uint8 [T,H,W,3]) like frames[0], got {what}")
+            raise AvsepError(f"with frame_times, frames[{n}] must be [T,3,H,W] (or uint8 [T,H,W,3]) like frames[0], "
+                             f"got {lib.got(fr)}")
     if T < 1 or times.numel() != T:
         raise AvsepError(f"separate_long needs one time per video frame: {T} frames, {times.numel()} times")
     try:
@@ -223,9 +223,8 @@ def _check_inputs(nets, wav, frames, args, use_vis, channels, return_maps):
     if channels is not None:
         if not torch.is_tensor(channels) or channels.dtype != torch.float32 or channels.dim() != 2 or channels.shape[0] < 1 \
                 or channels.shape[1] != wav.numel() or channels.device != wav.device:
-            what = f"{channels.dtype} {tuple(channels.shape)} on {channels.device}" if torch.is_tensor(channels) else type(channels).__name__
             raise AvsepError(f"separate_long takes channels as float32 [C,{wav.numel()}] on {wav.device} (the recording's "
-                             f"channels, as long as wav), got {what}")
+                             f"channels, as long as wav), got {lib.got(channels)}")
     if net_sound.training or (use_vis and net_frame.training):
         raise AvsepError("separate_long needs the nets in eval(): call .eval() on both before separating")
     if use_vis:

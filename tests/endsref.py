@@ -26,6 +26,8 @@ import math
 
 import torch
 
+from recipes import cdiv, f32
+
 F64 = torch.float64
 U = 2.0 ** -24
 FN = 4
@@ -33,18 +35,9 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, ACT_SOFTMAX = 0, 1, 3, 4, 5
 BCE, L1, L2 = 0, 1, 2
 
 
-def f32(v):
-    """The fp32 value of a constant of the kernels, as float."""
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
 EPS_COS = f32(1e-8)           # FUS_EPS, FN_EPS, ATT_EPS
 EPS_MIX = f32(1e-10)
 BCE_FLOOR = f32(1e-12)
-
-
-def cdiv(a, b):
-    return -(-a // b)
 
 
 # k per launcher: the fp32 roundings on the longest path (a math function: FN), with the source lines they were counted from

@@ -40,6 +40,8 @@ Not reached (the size limit of a test's largest tensor is 2^25 elements):
 """
 import ctypes
 
+from recipes import cdiv, out_hw
+
 BIG = 2 ** 24 + 1000
 SIZE_LIMIT = 2 ** 25
 
@@ -172,14 +174,6 @@ def plan(L, op, dims, aux=0):
     rc = L.avsep_glue_plan(op.encode(), *dims, aux, form, 64, grid)
     assert rc == 0, (op, dims, aux, rc)
     return form.value.decode(), tuple(grid)
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def out_hw(h):
-    return (h + 2 - 3) // 2 + 1
 
 
 def loops(op, dims, aux, form, grid):

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import convref as R
+from recipes import f32, out_hw
 
 F64 = torch.float64
 ACT_NONE, ACT_RELU, ACT_LRELU02 = R.ACT_NONE, R.ACT_RELU, R.ACT_LRELU02
@@ -45,10 +46,6 @@ def blocked_to_nchw(t):
 def nchw_to_blocked(t):
     N, Cc, H, W = t.shape
     return t.view(N, Cc // 16, 16, H, W).permute(0, 1, 3, 4, 2).contiguous()
-
-
-def out_hw(h):
-    return (h + 2 - 3) // 2 + 1
 
 
 # ---- BatchNorm pieces ---------------------------------------------------------------------------------------------------------
@@ -231,11 +228,6 @@ def temporal_mean(x, B, T):
 def temporal_mean_bwd(dy, B, T):
     d = dy.to(F64).reshape(B, 1, -1).expand(B, T, -1) / T
     return d, d.abs()
-
-
-def f32(v):
-    """The fp32 value of a Python scalar, as the C ABI receives it."""
-    return float(torch.tensor(v, dtype=torch.float32))
 
 
 def sgd(p, g, buf, lr, momentum, weight_decay, grad_scale, first):

@@ -15,6 +15,7 @@ import numpy as np
 
 import mwf_ref as M
 import mwf_tv_ref as T
+from recipes import cdiv
 
 U = 2.0 ** -24
 FLT_MIN = M.FLT_MIN
@@ -22,10 +23,6 @@ BLOCK, CHUNK, WAVES = 256, 2048, 4                  # MWF_BLOCK, MWF_CHUNK, MWF_
 FN = 4                                              # a math function at 2 ulp (sincosf, sqrtf, atan2f), in U
 SQRT2 = math.sqrt(2.0)
 f32, f64 = np.float32, np.float64
-
-
-def cdiv(a, b):
-    return -(-a // b)
 
 
 def chunks(F):

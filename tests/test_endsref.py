@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 import ends_cases as S
 import endsref as E
+from recipes import lib as _lib
 
 F64 = torch.float64
 TOL = 1e-11
@@ -366,11 +367,6 @@ def test_gate_rejects_one_zeroed_slice_of_the_fusion_backward():
 
 # ---- argument rejections that return before any launch ----------------------------------------------------------------------------
 DUMMY = 256          # a non-null address: these calls only check that it is set
-
-
-def _lib():
-    import avsep_amd
-    return avsep_amd.lib.load()
 
 
 def test_launchers_reject_bad_arguments_before_launching():

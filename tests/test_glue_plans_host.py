@@ -9,11 +9,7 @@ import torch
 
 import glue_cases as S
 import glueref as G
-
-
-def _lib():
-    import avsep_amd
-    return avsep_amd.lib.load()
+from recipes import lib as _lib
 
 
 @pytest.mark.parametrize("row", S.SWEEP, ids=lambda r: f"{r[0]}-{S.case_id(r)}")

@@ -4,8 +4,6 @@ csrc/resample.hip, separate_long(channels=...) and --channels keep of avsep_amd/
 Every comparison is torch.equal / equal bytes against the same result composed from the entry points that were there
 before: the new kernels share their arithmetic (one __device__ body per file), so identity is derived, not a tolerance.
 The values of those older entry points are held to float64 restatements in test_gpu_longform.py and test_gpu_resample.py."""
-import argparse
-import itertools
 import math
 
 import numpy as np
@@ -15,85 +13,15 @@ import torch
 import avsep_amd as P
 from avsep_amd import resample as RS
 from avsep_amd import separate as S
+from recipes import (args as _args, file_bytes as _bytes, nets as _nets, random_perms as _random_perms,
+                     small_nets as _small_nets, starts_t as _starts_t, tone_mix as _tone_mix,
+                     tone_mix_stereo as _tone_mix_stereo, write_pcm as _write_pcm)
 
 pytestmark = pytest.mark.gpu
 
 W = 256            # frames per window
 FOUT = 256         # warped bins
 FIN = 512          # linear bins of the 1022-point STFT
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# helpers (the recipes of test_gpu_longform.py and test_gpu_resample.py)
-# ---------------------------------------------------------------------------------------------------------------------
-def _starts_t(starts, dev):
-    return torch.tensor(starts, dtype=torch.int32, device=dev)
-
-
-def _random_perms(Kw, N, seed):
-    cands = list(itertools.permutations(range(N)))
-    g = torch.Generator().manual_seed(seed)
-    return [list(cands[i]) for i in torch.randint(0, len(cands), (Kw,), generator=g).tolist()]
-
-
-def _tone_mix(L, seed, rate=11025):
-    """A deterministic mixture with spectral structure: drifting partials plus a little noise, |x| < 1."""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.arange(L, dtype=torch.float64) / rate
-    x = torch.zeros(L, dtype=torch.float64)
-    for f0, a, v in ((220.0, 0.25, 0.3), (523.25, 0.2, 0.11), (1318.5, 0.12, 0.05), (3200.0, 0.06, 0.7)):
-        x += a * torch.sin(2 * np.pi * f0 * t * (1 + 0.01 * torch.sin(2 * np.pi * v * t)))
-    x += 0.02 * torch.randn(L, generator=g, dtype=torch.float64)
-    return x.float()
-
-
-def _args(**kw):
-    a = argparse.Namespace(num_mix=2, log_freq=1, binary_mask=1, mask_thres=0.5, output_activation="sigmoid",
-                           img_activation="relu", not_pool_vis=False, fusion_type="hidsep", stft_frame=1022, stft_hop=256,
-                           stft_pad_mode="reflect")
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
-
-
-def _small_nets(dev, seed):
-    """The unet5 / ngf 8 + ResnetDilated(fc_dim=32) pair of test_gpu_longform.py, wide init, eval mode."""
-    from oracle import nets as O
-    torch.manual_seed(seed)
-    gen = torch.Generator().manual_seed(seed)
-    osnd = O.Unet(fc_dim=2, num_downs=5, ngf=8, fusion_type="hidsep", att_type="sig")
-    O.wide_init(osnd, gen)
-    ofrm = O.VisualNet(fc_dim=32, pool_type="maxpool", dilate_scale=16)
-    snd = P.models.Unet(fc_dim=2, num_downs=5, ngf=8, fusion_type="hidsep", att_type="sig")
-    frm = P.models.ResnetDilated(None, fc_dim=32, pool_type="maxpool")
-    snd.load_state_dict(osnd.state_dict()); frm.load_state_dict(ofrm.state_dict())
-    return (snd.to(dev).eval(), frm.to(dev).eval()), gen
-
-
-def _tone_mix_stereo(Ln, rate, seed):
-    """A deterministic stereo mixture with spectral structure below the model's Nyquist, int16 [Ln, 2]; the partials are
-    panned differently, so the two channels are not copies of each other."""
-    g = np.random.default_rng(seed)
-    t = np.arange(Ln, dtype=np.float64) / rate
-    ch = []
-    for pan in (0.8, 0.3):
-        x = np.zeros(Ln)
-        for f0, a, v in ((220.0, 0.25, 0.3), (523.25, 0.2, 0.11), (1318.5, 0.12, 0.05), (3200.0, 0.06, 0.7)):
-            x += a * (pan if f0 < 1000 else 1 - pan) * np.sin(2 * np.pi * f0 * t * (1 + 0.01 * np.sin(2 * np.pi * v * t)))
-        ch.append(x + 0.02 * g.standard_normal(Ln))
-    return np.clip(np.rint(np.stack(ch, 1) * 32768.0), -32768, 32767).astype(np.int16)
-
-
-def _write_pcm(path, pcm, rate):
-    import wave
-    with wave.open(path, "wb") as w:
-        w.setnchannels(pcm.shape[1]); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(pcm.astype("<i2").tobytes())
-
-
-def _bytes(path):
-    with open(str(path), "rb") as f:
-        return f.read()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -276,14 +204,6 @@ def cli_case(tmp_path_factory):
              "--fusion_type", "hidsep", "--att_type", "sig", "--weights_sound", str(d / "sound.pth"),
              "--weights_frame", str(d / "frame.pth"), "--binary_mask", "0"]                       # ratio masks: never silent
     return d, flags, [str(d / f"one{n}.npy") for n in range(2)]
-
-
-def _nets(args, dev):
-    mb = P.ModelBuilder()
-    frm = mb.build_frame(arch=args.arch_frame, fc_dim=args.vis_channels, pool_type=args.img_pool, weights=args.weights_frame)
-    snd = mb.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, weights=args.weights_sound,
-                         fusion_type=args.fusion_type, att_type=args.att_type)
-    return snd.to(dev).eval(), frm.to(dev).eval()
 
 
 def test_cli_keeps_the_channels_of_a_48k_stereo_file(dev, cli_case, tmp_path, capsys):

@@ -14,6 +14,7 @@ from avsep_amd import separate as S
 from oracle import inference as OI
 
 import clip_ref as R
+from recipes import args as _args, tone_mix as _tone_mix
 import test_gpu_longform as LF
 
 pytestmark = pytest.mark.gpu
@@ -132,7 +133,7 @@ TOL = 3e-4          # the mask bound of test_separate_long_masks_vs_oracle_nets 
 @pytest.fixture(scope="module")
 def clip(dev):
     nets, onets, gen = LF._small_nets(dev, 3)
-    wav = LF._tone_mix(HOP * (FR - 1) + 17, 6)                                  # 16 s
+    wav = _tone_mix(HOP * (FR - 1) + 17, 6)                                  # 16 s
     with torch.no_grad():
         mag = P.kernels.Stft(dev, 1022, 256, "reflect").stft(wav.to(dev)[None])[0][0].cpu()
     assert mag.shape == (LF.FIN, FR)
@@ -167,7 +168,7 @@ def _oracle(c, which, duet=False):
 
 def _run(c, dev, frames, times, args=None, **kw):
     with torch.no_grad():
-        return S.separate_long(c.nets, c.wav.to(dev), frames, args or LF._args(audRate=RATE), True, STRIDE, batch=BATCH,
+        return S.separate_long(c.nets, c.wav.to(dev), frames, args or _args(audRate=RATE), True, STRIDE, batch=BATCH,
                                return_masks=True, frame_times=times, **kw)
 
 
@@ -200,7 +201,7 @@ def test_clip_form_masks_vs_oracle_nets(clip, dev):
     assert_close(on_cpu["maps"], ref_maps, TOL, "attention maps")                # the bound test_inference_wrapper_vs_oracle holds maps to
     # one shared frame per source is another separation
     with torch.no_grad():
-        first = S.separate_long(c.nets, c.wav.to(dev), [s[:1].to(dev) for s in c.stacks], LF._args(audRate=RATE), True, STRIDE,
+        first = S.separate_long(c.nets, c.wav.to(dev), [s[:1].to(dev) for s in c.stacks], _args(audRate=RATE), True, STRIDE,
                                 batch=BATCH, return_masks=True)
     moved = rel_err(first["masks"], on_cpu["masks"])
     print(f"clip form vs the first frame alone: max|d|/max {moved:.3e}")
@@ -229,16 +230,16 @@ def test_clip_form_refusals(clip, dev):
     with pytest.raises(E):
         _run(c, dev, [c.stacks[0], c.stacks[1][:5]], c.times)                   # stacks of equal shape
     with pytest.raises(E):
-        _run(c, dev, c.stacks[:1], c.times, args=LF._args(audRate=RATE, num_mix=3))      # a duet has two sources
+        _run(c, dev, c.stacks[:1], c.times, args=_args(audRate=RATE, num_mix=3))      # a duet has two sources
     with pytest.raises(E):
-        _run(c, dev, c.stacks, c.times, args=LF._args(audRate=RATE, not_pool_vis=True), return_maps=True)
+        _run(c, dev, c.stacks, c.times, args=_args(audRate=RATE, not_pool_vis=True), return_maps=True)
     with pytest.raises(E, match="pooled"):
-        _run(c, dev, c.stacks, c.times, args=LF._args(audRate=RATE, not_pool_vis=True))      # the fusion takes maps only
+        _run(c, dev, c.stacks, c.times, args=_args(audRate=RATE, not_pool_vis=True))      # the fusion takes maps only
     with pytest.raises(E):
         with torch.no_grad():
-            S.separate_long(c.nets, c.wav.to(dev), None, LF._args(audRate=RATE), False, STRIDE, return_maps=True)
+            S.separate_long(c.nets, c.wav.to(dev), None, _args(audRate=RATE), False, STRIDE, return_maps=True)
     with pytest.raises(NotImplementedError):
-        _run(c, dev, c.stacks, c.times, args=LF._args(audRate=RATE, fusion_type="MixVis"))
+        _run(c, dev, c.stacks, c.times, args=_args(audRate=RATE, fusion_type="MixVis"))
 
 
 @pytest.mark.parametrize("pool_type,op", [("maxpool", "max"), ("avgpool", "mean")])
@@ -275,7 +276,7 @@ def test_duet_clip_masks_alignment_and_maps(clip, dev):
     _, _, feats, _ = _oracle(c, "times", duet=True)
     fed = types.SimpleNamespace(forward=lambda x, pool: x)                      # the window-mean features go in as they are
     with torch.no_grad():
-        ref = OI.forward((c.onets[0], fed), (LF.ref_slices(c.mag, c.starts), None), [feats[0]], LF._args(audRate=RATE), True)
+        ref = OI.forward((c.onets[0], fed), (LF.ref_slices(c.mag, c.starts), None), [feats[0]], _args(audRate=RATE), True)
     masks = out["masks"].cpu()
     for n in range(2):
         print(f"duet mask {n}: max|d|/max|ref| {rel_err(masks[:, n:n + 1], ref['pred_masks'][n]):.3e}")
@@ -299,7 +300,7 @@ def test_duet_clip_masks_alignment_and_maps(clip, dev):
 
 def test_duet_in_the_old_frame_forms_runs(clip, dev):
     c = clip
-    args = LF._args()
+    args = _args()
     with torch.no_grad():
         one = S.separate_long(c.nets, c.wav.to(dev), [c.stacks[0][:1].to(dev)], args, True, STRIDE, return_masks=True, return_maps=True)
         per = S.separate_long(c.nets, c.wav.to(dev), [c.stacks[0][:5].to(dev)], args, True, STRIDE, return_masks=True)
@@ -326,12 +327,12 @@ def test_duet_in_the_old_frame_forms_runs(clip, dev):
         two = S.separate_long(c.nets, c.wav.to(dev), [c.stacks[0][:1].to(dev)] * 2, args, True, STRIDE, return_masks=True)
     assert rel_err(one["masks"], two["masks"]) > TOL
     with pytest.raises(P.lib.AvsepError):
-        S.separate_long(c.nets, c.wav.to(dev), [c.stacks[0][:1].to(dev)], LF._args(num_mix=3), True, STRIDE)
+        S.separate_long(c.nets, c.wav.to(dev), [c.stacks[0][:1].to(dev)], _args(num_mix=3), True, STRIDE)
 
 
 def test_frame_times_none_is_the_earlier_path(clip, dev):
     c = clip
-    args = LF._args()
+    args = _args()
     wav = c.wav.to(dev)
     for frames in ([s[:1].to(dev) for s in c.stacks], [s[:5].to(dev) for s in c.stacks]):
         with torch.no_grad():
@@ -354,7 +355,7 @@ def test_cli_separates_with_clips_and_writes_maps(dev, tmp_path):
     torch.save(snd.state_dict(), str(tmp_path / "sound.pth"))
     torch.save(frm.state_dict(), str(tmp_path / "frame.pth"))
     L = 30000
-    S.write_wav(str(tmp_path / "mix.wav"), LF._tone_mix(L, 8).numpy(), RATE)
+    S.write_wav(str(tmp_path / "mix.wav"), _tone_mix(L, 8).numpy(), RATE)
     g = torch.Generator().manual_seed(3)
     paths = []
     for n in range(2):

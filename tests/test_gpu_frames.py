@@ -17,6 +17,7 @@ from avsep_amd import separate as S
 
 import frames_ref as R
 import test_frames_host as FH
+from recipes import args as _args, tone_mix as _tone_mix
 import test_gpu_longform as LF
 
 pytestmark = pytest.mark.gpu
@@ -155,13 +156,13 @@ def _floats(u8):
 @pytest.fixture(scope="module")
 def pipe(dev):
     nets, _, _ = LF._small_nets(dev, 5)
-    wav = LF._tone_mix(HOP * (FRAMES - 1) + 9, 2).to(dev)
+    wav = _tone_mix(HOP * (FRAMES - 1) + 9, 2).to(dev)
     starts = S.plan_windows(FRAMES, STRIDE)
     assert len(starts) == 3
     g = np.random.default_rng(11)
     shot = [torch.from_numpy(g.integers(0, 256, (7, H0, W0, 3), dtype=np.uint8)) for _ in range(2)]
     return types.SimpleNamespace(nets=nets, wav=wav, K=len(starts), shot=shot, prepared=[_floats(s) for s in shot],
-                                 times=torch.arange(7, dtype=torch.float64) * 1.3, args=LF._args(audRate=RATE, imgSize=IMG))
+                                 times=torch.arange(7, dtype=torch.float64) * 1.3, args=_args(audRate=RATE, imgSize=IMG))
 
 
 def _both(c, pick, **kw):
@@ -211,7 +212,7 @@ def test_separate_long_refuses_mixed_and_sizeless_uint8_frames(pipe, dev):
     with pytest.raises(E, match="one kind"):
         S.separate_long(c.nets, c.wav, [c.shot[0][:1].to(dev), c.prepared[1][:1].to(dev)], c.args, True, STRIDE)
     with pytest.raises(E, match="imgSize"):
-        S.separate_long(c.nets, c.wav, [s[:1].to(dev) for s in c.shot], LF._args(audRate=RATE), True, STRIDE)
+        S.separate_long(c.nets, c.wav, [s[:1].to(dev) for s in c.shot], _args(audRate=RATE), True, STRIDE)
     with pytest.raises(E):
         S.separate_long(c.nets, c.wav, [s[:1, :, :, :2].to(dev) for s in c.shot], c.args, True, STRIDE)
 
@@ -242,7 +243,7 @@ def test_cli_takes_a_folder_of_pngs_and_a_uint8_npy(dev, tmp_path):
     frm = mb.build_frame(arch="resnet18dilated", fc_dim=256, pool_type="maxpool")
     torch.save(snd.state_dict(), str(tmp_path / "sound.pth"))
     torch.save(frm.state_dict(), str(tmp_path / "frame.pth"))
-    S.write_wav(str(tmp_path / "mix.wav"), LF._tone_mix(30000, 8).numpy(), RATE)
+    S.write_wav(str(tmp_path / "mix.wav"), _tone_mix(30000, 8).numpy(), RATE)
     g = np.random.default_rng(3)
     forms = {"png": [], "u8": [], "f32": []}
     for n in range(2):

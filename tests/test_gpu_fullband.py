@@ -33,8 +33,9 @@ from avsep_amd import wavio
 
 import fullband_ref as FB
 import resample_ref as R
+from recipes import (args as _args, file_bytes as _bytes, nets as _nets, small_nets as _small_nets, tone_mix as _tone_mix,
+                     tone_mix_stereo as _tone_mix_stereo, write_pcm as _write_pcm)
 from test_gpu_levels import _check_figures
-from test_gpu_channels import _args, _bytes, _nets, _small_nets, _tone_mix, _tone_mix_stereo, _write_pcm
 from test_gpu_resample import _rows
 
 pytestmark = pytest.mark.gpu

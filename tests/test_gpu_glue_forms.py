@@ -21,6 +21,7 @@ import convref as R
 import glue_cases as S
 import glue_inputs as I
 import glueref as G
+from recipes import pkg as _pkg
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
@@ -83,11 +84,6 @@ K = {
     # `(float)acc[c]`
     "b16_channel_sum": lambda terms: terms + 6,    # measured: slot 0.033, slot,images 0.026
 }
-
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
 
 
 def _id(row):

@@ -16,6 +16,7 @@ import torch
 
 import convref
 from conftest import assert_close
+from recipes import pkg as _pkg
 
 TOL = 2e-5
 IGEMM = {"fwd": "igemm_kernel<fwd>", "dgrad": "igemm_kernel<dgrad>", "wgrad": "igemm_kernel<wgrad>"}
@@ -44,11 +45,6 @@ CASES = {
     "halo_1x1s2_layer2": ((2, 64, 56, 56, 128, 1, 2, 0, 1), None, RAW, HALO),
     "halo_1x1s2_ragged": ((2, 32, 12, 40, 48, 1, 2, 0, 1), None, RAW, HALO),
 }
-
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
 
 
 def _dgrad_into_nan(K, cv, wp, dy, misalign=False):

@@ -17,6 +17,7 @@ from avsep_amd import wavio as W
 from avsep_amd.lib import AvsepError
 
 import levels_ref as REF
+from recipes import file_bytes as _bytes, nets as _nets, tone_mix_panned as _tone_mix
 
 pytestmark = pytest.mark.gpu
 
@@ -205,18 +206,6 @@ def test_measure_weights_and_the_lfe(dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # separate
 # ---------------------------------------------------------------------------------------------------------------------
-def _tone_mix(Ln, rate, seed, pans=(0.8, 0.3)):
-    g = np.random.default_rng(seed)
-    t = np.arange(Ln, dtype=np.float64) / rate
-    ch = []
-    for pan in pans:
-        x = np.zeros(Ln)
-        for f0, a, v in ((220.0, 0.25, 0.3), (523.25, 0.2, 0.11), (1318.5, 0.12, 0.05), (3200.0, 0.06, 0.7)):
-            x += a * (pan if f0 < 1000 else 1 - pan) * np.sin(2 * np.pi * f0 * t * (1 + 0.01 * np.sin(2 * np.pi * v * t)))
-        ch.append(x + 0.02 * g.standard_normal(Ln))
-    return np.stack(ch, 1)
-
-
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
     """A tiny random-weight model saved as a checkpoint; a 2 s 48 kHz stereo mixture as a 16-bit file and, eight times as hot
@@ -245,21 +234,8 @@ def case(tmp_path_factory):
     return d, flags
 
 
-def _nets(args, dev):
-    mb = P.ModelBuilder()
-    frm = mb.build_frame(arch=args.arch_frame, fc_dim=args.vis_channels, pool_type=args.img_pool, weights=args.weights_frame)
-    snd = mb.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, weights=args.weights_sound,
-                         fusion_type=args.fusion_type, att_type=args.att_type)
-    return snd.to(dev).eval(), frm.to(dev).eval()
-
-
 def _frames(args, dev):
     return [torch.from_numpy(np.load(p)).float()[None].to(dev) for p in args.frames]
-
-
-def _bytes(path):
-    with open(str(path), "rb") as f:
-        return f.read()
 
 
 def _read_rows(path, dev):

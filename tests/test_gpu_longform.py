@@ -1,8 +1,5 @@
 """gpu: long-form separation (csrc/longform.hip, avsep_amd/separate.py) against restatements written here from
 torch.nn.functional.grid_sample on the oracle's warpgrid, float64 blending and the oracle STFT — never the code under test."""
-import argparse
-import itertools
-
 import numpy as np
 import pytest
 import torch
@@ -13,6 +10,7 @@ from conftest import assert_close
 import avsep_amd as P
 from avsep_amd import separate as S
 from oracle import step as OS, stft as OST
+from recipes import args as _args, random_perms as _random_perms, starts_t as _starts_t, tone_mix as _tone_mix
 
 pytestmark = pytest.mark.gpu
 
@@ -66,36 +64,6 @@ def ref_agreement(masks, starts):
             for j in range(N):
                 D[k, i, j] = (m[k, i, :, d:] - m[k + 1, j, :, :W - d]).abs().sum()
     return D
-
-
-def _starts_t(starts, dev):
-    return torch.tensor(starts, dtype=torch.int32, device=dev)
-
-
-def _random_perms(Kw, N, seed):
-    cands = list(itertools.permutations(range(N)))
-    g = torch.Generator().manual_seed(seed)
-    return [list(cands[i]) for i in torch.randint(0, len(cands), (Kw,), generator=g).tolist()]
-
-
-def _tone_mix(L, seed, rate=11025):
-    """A deterministic mixture with spectral structure: drifting partials plus a little noise, |x| < 1."""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.arange(L, dtype=torch.float64) / rate
-    x = torch.zeros(L, dtype=torch.float64)
-    for f0, a, v in ((220.0, 0.25, 0.3), (523.25, 0.2, 0.11), (1318.5, 0.12, 0.05), (3200.0, 0.06, 0.7)):
-        x += a * torch.sin(2 * np.pi * f0 * t * (1 + 0.01 * torch.sin(2 * np.pi * v * t)))
-    x += 0.02 * torch.randn(L, generator=g, dtype=torch.float64)
-    return x.float()
-
-
-def _args(**kw):
-    a = argparse.Namespace(num_mix=2, log_freq=1, binary_mask=1, mask_thres=0.5, output_activation="sigmoid",
-                           img_activation="relu", not_pool_vis=False, fusion_type="hidsep", stft_frame=1022, stft_hop=256,
-                           stft_pad_mode="reflect")
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
 
 
 def _small_nets(dev, seed):

@@ -9,13 +9,9 @@ import pytest
 import torch
 
 from conftest import assert_close, rel_err
+from recipes import pkg as _pkg
 
 pytestmark = pytest.mark.gpu
-
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
 
 
 def _load_unet(P, G, tag, downs, ngf, ftype, att, dev, **kw):

@@ -18,8 +18,6 @@ divides the windowed sum by the window-sum-square, so a sample moves by at most
     G * e,   G = max_n sum_m w[n - m hop] / sum_m w[n - m hop]^2   (periodic Hann, 1022 / 256: G = 1.34, computed below),
 and the clamp to [-1, 1] moves nothing further apart.  With e = BOUND_Y * max|Y_ref| that is the bound used; the iSTFT
 kernel's own rounding is common to both sides up to a term four orders below it."""
-import argparse
-
 import numpy as np
 import pytest
 import torch
@@ -28,6 +26,8 @@ import avsep_amd as P
 from avsep_amd import separate as S
 
 import mwf_ref as M
+from recipes import (args as _args, file_bytes as _bytes, istft_gain as _istft_gain, small_nets as _small_nets,
+                     tones as _tones)
 
 pytestmark = pytest.mark.gpu
 
@@ -153,54 +153,12 @@ def test_mwf_raises_the_sdr_of_panned_sources_as_the_restatement_does(dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # separate_long(wiener=...)
 # ---------------------------------------------------------------------------------------------------------------------
-def _args(**kw):
-    a = argparse.Namespace(num_mix=2, log_freq=1, binary_mask=1, mask_thres=0.5, output_activation="sigmoid",
-                           img_activation="relu", not_pool_vis=False, fusion_type="hidsep", stft_frame=1022, stft_hop=256,
-                           stft_pad_mode="reflect")
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
-
-
-def _small_nets(dev, seed):
-    """The unet5 / ngf 8 + ResnetDilated(fc_dim=32) pair of test_gpu_channels.py, wide init, eval mode."""
-    from oracle import nets as O
-    torch.manual_seed(seed)
-    gen = torch.Generator().manual_seed(seed)
-    osnd = O.Unet(fc_dim=2, num_downs=5, ngf=8, fusion_type="hidsep", att_type="sig")
-    O.wide_init(osnd, gen)
-    ofrm = O.VisualNet(fc_dim=32, pool_type="maxpool", dilate_scale=16)
-    snd = P.models.Unet(fc_dim=2, num_downs=5, ngf=8, fusion_type="hidsep", att_type="sig")
-    frm = P.models.ResnetDilated(None, fc_dim=32, pool_type="maxpool")
-    snd.load_state_dict(osnd.state_dict()); frm.load_state_dict(ofrm.state_dict())
-    return (snd.to(dev).eval(), frm.to(dev).eval()), gen
-
-
-def _tones(Ln, partials, seed, rate=11025):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.arange(Ln, dtype=torch.float64) / rate
-    x = torch.zeros(Ln, dtype=torch.float64)
-    for f0, a, v in partials:
-        x += a * torch.sin(2 * np.pi * f0 * t * (1 + 0.01 * torch.sin(2 * np.pi * v * t)))
-    return (x + 0.01 * torch.randn(Ln, generator=g, dtype=torch.float64)).float()
-
-
 def _stereo(Ln):
     """Two instruments at two places: a is mostly left, b mostly right.  -> (down-mix [Ln], channels [2, Ln])."""
     a = _tones(Ln, ((220.0, 0.25, 0.3), (523.25, 0.2, 0.11)), 1)
     b = _tones(Ln, ((1318.5, 0.2, 0.05), (3200.0, 0.1, 0.7)), 2)
     ch = torch.stack([0.9 * a + 0.3 * b, 0.35 * a + 0.8 * b])
     return ch.mean(0), ch
-
-
-def _istft_gain(n_fft, hop, frames):
-    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft)
-    s1, s2 = np.zeros(n_fft + hop * (frames - 1)), np.zeros(n_fft + hop * (frames - 1))
-    for m in range(frames):
-        s1[m * hop:m * hop + n_fft] += w
-        s2[m * hop:m * hop + n_fft] += w * w
-    keep = slice(n_fft // 2, len(s1) - n_fft // 2)
-    return float((s1[keep] / s2[keep]).max())
 
 
 def test_separate_long_with_wiener(dev):
@@ -244,11 +202,6 @@ def test_separate_long_with_wiener(dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # command line
 # ---------------------------------------------------------------------------------------------------------------------
-def _bytes(path):
-    with open(str(path), "rb") as f:
-        return f.read()
-
-
 def test_cli_wiener(dev, tmp_path, capsys):
     """A stereo 16-bit file at the model's rate: --wiener 0 writes the bytes --channels keep writes, --wiener 1 stereo files
     of the same length that differ from them."""

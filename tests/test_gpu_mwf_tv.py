@@ -22,7 +22,8 @@ from avsep_amd.lib import AvsepError
 
 import mwf_ref as M
 import mwf_tv_ref as T
-from test_gpu_mwf import _args, _bytes, _complex, _cov_np, _dev, _istft_gain, _small_nets, _stereo
+from recipes import args as _args, file_bytes as _bytes, istft_gain as _istft_gain, small_nets as _small_nets
+from test_gpu_mwf import _complex, _cov_np, _dev, _stereo
 
 pytestmark = pytest.mark.gpu
 

@@ -7,13 +7,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import assert_close
+from recipes import pkg as _pkg
 
 pytestmark = pytest.mark.gpu
-
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
 
 
 CONV_CASES = [

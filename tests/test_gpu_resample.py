@@ -16,6 +16,7 @@ from avsep_amd import resample as RS
 from avsep_amd import separate as S
 
 import resample_ref as R
+from recipes import file_bytes as _bytes, nets as _nets, tone_mix_stereo as _tone_mix_stereo, write_pcm as _write_pcm
 
 pytestmark = pytest.mark.gpu
 
@@ -185,26 +186,6 @@ def test_wrapper_refusals(dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # 5. command lines
 # ---------------------------------------------------------------------------------------------------------------------
-def _tone_mix_stereo(Ln, rate, seed):
-    """A deterministic stereo mixture with spectral structure below the model's Nyquist, int16 [Ln, 2]."""
-    g = np.random.default_rng(seed)
-    t = np.arange(Ln, dtype=np.float64) / rate
-    ch = []
-    for pan in (0.8, 0.3):
-        x = np.zeros(Ln)
-        for f0, a, v in ((220.0, 0.25, 0.3), (523.25, 0.2, 0.11), (1318.5, 0.12, 0.05), (3200.0, 0.06, 0.7)):
-            x += a * (pan if f0 < 1000 else 1 - pan) * np.sin(2 * np.pi * f0 * t * (1 + 0.01 * np.sin(2 * np.pi * v * t)))
-        ch.append(x + 0.02 * g.standard_normal(Ln))
-    return np.clip(np.rint(np.stack(ch, 1) * 32768.0), -32768, 32767).astype(np.int16)
-
-
-def _write_pcm(path, pcm, rate):
-    import wave
-    with wave.open(path, "wb") as w:
-        w.setnchannels(pcm.shape[1]); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(pcm.astype("<i2").tobytes())
-
-
 @pytest.fixture(scope="module")
 def cli_case(tmp_path_factory):
     """Small nets saved as a checkpoint, a 3 s 48 kHz stereo mix, its 11 025 Hz twin and two frame stacks."""
@@ -228,19 +209,6 @@ def cli_case(tmp_path_factory):
              "--fusion_type", "hidsep", "--att_type", "sig", "--weights_sound", str(d / "sound.pth"),
              "--weights_frame", str(d / "frame.pth")]
     return d, flags, stacks, [str(d / f"one{n}.npy") for n in range(2)]
-
-
-def _nets(args, dev):
-    mb = P.ModelBuilder()
-    frm = mb.build_frame(arch=args.arch_frame, fc_dim=args.vis_channels, pool_type=args.img_pool, weights=args.weights_frame)
-    snd = mb.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, weights=args.weights_sound,
-                         fusion_type=args.fusion_type, att_type=args.att_type)
-    return snd.to(dev).eval(), frm.to(dev).eval()
-
-
-def _bytes(path):
-    with open(str(path), "rb") as f:
-        return f.read()
 
 
 def test_separate_cli_takes_a_48k_stereo_file_and_answers_at_48k(dev, cli_case, tmp_path):

@@ -21,6 +21,7 @@ from avsep_amd import separate as S
 from avsep_amd import wavio as W
 
 import sample_formats_ref as F
+from recipes import file_bytes as _bytes, nets as _nets, tone_mix_panned as _tone_mix
 
 pytestmark = pytest.mark.gpu
 
@@ -225,19 +226,6 @@ def test_wrapper_refusals(dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. command lines
 # ---------------------------------------------------------------------------------------------------------------------
-def _tone_mix(Ln, rate, seed, pans=(0.8, 0.3)):
-    """A deterministic mixture with spectral structure below the model's Nyquist, float64 [Ln, len(pans)]."""
-    g = np.random.default_rng(seed)
-    t = np.arange(Ln, dtype=np.float64) / rate
-    ch = []
-    for pan in pans:
-        x = np.zeros(Ln)
-        for f0, a, v in ((220.0, 0.25, 0.3), (523.25, 0.2, 0.11), (1318.5, 0.12, 0.05), (3200.0, 0.06, 0.7)):
-            x += a * (pan if f0 < 1000 else 1 - pan) * np.sin(2 * np.pi * f0 * t * (1 + 0.01 * np.sin(2 * np.pi * v * t)))
-        ch.append(x + 0.02 * g.standard_normal(Ln))
-    return np.stack(ch, 1)
-
-
 @pytest.fixture(scope="module")
 def cli_case(tmp_path_factory):
     """Small nets saved as a checkpoint; a 2 s 48 kHz stereo mix as a 16-bit file and as the 24-bit file whose samples are
@@ -265,19 +253,6 @@ def cli_case(tmp_path_factory):
              "--weights_frame", str(d / "frame.pth"), "--frames", *ones, "--binary_mask", "0"]
     out16 = S.cli(["--wav", str(d / "mix16.wav"), "--out", str(d / "out16"), *flags])
     return d, flags, pcm, out16
-
-
-def _nets(args, dev):
-    mb = P.ModelBuilder()
-    frm = mb.build_frame(arch=args.arch_frame, fc_dim=args.vis_channels, pool_type=args.img_pool, weights=args.weights_frame)
-    snd = mb.build_sound(arch=args.arch_sound, fc_dim=args.num_channels, weights=args.weights_sound,
-                         fusion_type=args.fusion_type, att_type=args.att_type)
-    return snd.to(dev).eval(), frm.to(dev).eval()
-
-
-def _bytes(path):
-    with open(str(path), "rb") as f:
-        return f.read()
 
 
 def test_separate_cli_hears_a_24_bit_file_as_its_16_bit_twin(dev, cli_case, tmp_path):

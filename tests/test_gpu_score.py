@@ -9,6 +9,7 @@ import torch
 
 import score_ref as SR
 from conftest import assert_close
+from recipes import score as _score
 
 pytestmark = pytest.mark.gpu
 NAMES = ("sdr", "isr", "sir", "sar")
@@ -24,11 +25,6 @@ CASES = [(2, 1, 3000, 16, 1000, 500),        # overlapping windows
 #                                              windows start inside a chunk (1000, 3000) and the last one ends exactly at L
          (2, 2, 2500, 13, 900, 450),         # flen no multiple of 8: discarded lags and zero-padded taps
          (3, 1, 2300, 24, 700, 700)]         # three groups of 8 lags: 64 of the correlation kernel's 256 threads idle
-
-
-def _score():
-    from avsep_amd import score
-    return score
 
 
 def make_inputs(S, C, L, seed):

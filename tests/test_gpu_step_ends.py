@@ -17,15 +17,11 @@ import torch
 
 import ends_cases as S
 import endsref as E
+from recipes import pkg as _pkg
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
 _TABLE = {}          # (launcher, form) -> [rows, worst ratio, excluded elements]
-
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
 
 
 def _id(row):

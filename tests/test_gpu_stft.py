@@ -17,13 +17,9 @@ import torch
 
 import stft_cases as SC
 import stftref as SR
+from recipes import pkg as _pkg
 
 ERR_ARG, ERR_LAUNCH, ERR_WORKSPACE = -1, -2, -3
-
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
 
 
 def _plan(dev, n_fft, hop, mode, cache={}):

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import assert_close
+from recipes import pkg as _pkg
 
 pytestmark = pytest.mark.gpu
 MARGIN = 4e-5
@@ -34,11 +35,6 @@ def _grads(VH, mod):
         def __getitem__(self, p):
             return self.d[p]
     return G(mod)
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
-
 
 def _nudge(pre, bias, margin=MARGIN):
     """Shift bias[c] (a BatchNorm beta: the batch statistics do not see it) until no element of the pre-activation

@@ -7,12 +7,9 @@ import re
 import pytest
 import torch
 
+from recipes import pkg as _pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _pkg():
-    import avsep_amd
-    return avsep_amd
 
 
 def test_library_exports_every_declared_symbol():
@@ -447,3 +444,144 @@ def test_storage_format_helpers_and_conversion_cache_host_logic():
     finally:
         K.call, K.ptr = orig_call, orig_ptr
         K.set_precision("f32")
+
+
+def test_stream_marks_of_twin_pack_and_batchnorm_order_host_logic():
+    """kernels._Mark, the one body of "built on one stream, read on another", at its three sites without a GPU:
+    torch.cuda.Event and torch.cuda.current_stream are recording fakes and a device tensor is stood in for by an object
+    with what kernels.py reads of one.  Per site: one event, recorded where the thing is built; a consumer on the same
+    stream does nothing; a consumer on another stream waits once for that event and record_stream()s exactly the cached
+    tensor (none for the BatchNorm order); a host tensor creates no event; a stale version / changed key never reaches
+    the old mark."""
+    P = _pkg()
+    K = P.kernels
+    log = []
+
+    class Stream:
+        device = "gpu"
+
+        def wait_event(self, ev):
+            log.append(("wait", self, ev))
+
+    class Event:
+        def __init__(self):
+            log.append(("event", self))
+
+        def record(self, stream=None):
+            log.append(("record", self, stream or current[0]))
+
+    class Dev:
+        is_cuda, device = True, "gpu"
+
+        def __init__(self, shape=(4,), dtype=torch.float32):
+            self.shape, self.dtype, self._version = shape, dtype, 0
+
+        def data_ptr(self):
+            return id(self)
+
+        def numel(self):
+            return 4
+
+        def __getitem__(self, i):
+            return self
+
+        def record_stream(self, stream):
+            log.append(("keep", self, stream))
+
+    class FakeLib:
+        def avsep_conv_packed_floats(self, ref, mode):
+            return 4
+    s0, s1 = Stream(), Stream()
+    current = [s0]
+
+    def since(n):
+        return [e for e in log[n:] if e[0] != "call"]
+
+    def built(n, stream):
+        """the entries since n are one new event, recorded on `stream`, and nothing else -> that event"""
+        got = since(n)
+        assert len(got) == 2 and got[0][0] == "event" and got[1] == ("record", got[0][1], stream), got
+        return got[0][1]
+    orig = (K.call, K.ptr, K._f32, K._b16, K.lib.load, K.torch.cuda.Event, K.torch.cuda.current_stream)
+    K.call, K.ptr, K.lib.load = (lambda name, *a: log.append(("call", name))), (lambda t: 0), (lambda: FakeLib())
+    K._f32 = lambda shape, like: Dev(shape) if like.is_cuda else orig[2](shape, like)
+    K._b16 = lambda s, like: Dev((s[0], s[1] // 16, s[2], s[3], 16), torch.bfloat16) if like.is_cuda else orig[3](s, like)
+    K.torch.cuda.Event, K.torch.cuda.current_stream = Event, (lambda device=None: current[0])
+    try:
+        # ---- the twin cache: one mark for both entries of the pair, the twin handed out is the tensor protected
+        x = Dev((2, 32, 5, 7))
+        b = K.to_b16(x)
+        ev = built(0, s0)
+        n = len(log)
+        assert K.to_b16(x) is b and K.to_f32(b) is x and since(n) == []                    # (a)
+        current[0] = s1
+        assert K.to_b16(x) is b and since(n) == [("wait", s1, ev), ("keep", b, s1)]         # (b)
+        n = len(log)
+        assert K.to_f32(b) is x and since(n) == [("wait", s1, ev), ("keep", x, s1)]
+        x._version += 1                                                                    # (d): rebuilt, on s1
+        n = len(log)
+        assert K.to_b16(x) is not b and built(n, s1) is not ev
+        h = torch.zeros(1, 16, 2, 2)                                                       # (c)
+        current[0], n = s0, len(log)
+        hb = K.to_b16(h)
+        current[0] = s1
+        assert K.to_b16(h) is hb and K.to_f32(hb) is h and since(n) == []
+        # ---- the pack cache: the packed image is protected, the weight is only held
+        cv = K.Conv.__new__(K.Conv)
+        cv.d, cv.ref = P.lib.ConvDesc(), None
+        w = Dev()
+        with K.pack_scope():
+            current[0], n = s0, len(log)
+            a = cv.pack(w, 0)
+            ev = built(n, s0)
+            assert K._pack_cache and all(e[1] is w for e in K._pack_cache.values())
+            n = len(log)
+            assert cv.pack(w, 0) is a and since(n) == []                                   # (a)
+            current[0] = s1
+            assert cv.pack(w, 0) is a and since(n) == [("wait", s1, ev), ("keep", a, s1)]   # (b)
+            w._version += 1                                                                # (d)
+            n = len(log)
+            assert cv.pack(w, 0) is not a and built(n, s1) is not ev
+            hw = torch.zeros(4)                                                            # (c)
+            current[0], n = s0, len(log)
+            ha = cv.pack(hw, 0)
+            current[0] = s1
+            assert cv.pack(hw, 0) is ha and since(n) == []
+        # ---- the BatchNorm order of fork_streams: reach the previous update before the launch, mark after it, keep nothing
+        gamma, rmean = Dev(), Dev()
+
+        def finalize(rm, training=True, like=gamma):
+            K.bn_finalize(None, 8, like, None, rm, None, 0.1, 1e-5, training, like)
+        launch = ("call", "avsep_bn_finalize")
+        current[0], n = s0, len(log)
+        finalize(rmean)                                                                    # outside fork_streams: no order
+        with K.fork_streams():
+            finalize(rmean, training=False)
+            finalize(None)
+            assert log[n:] == [launch] * 3
+            n = len(log)
+            finalize(rmean)
+            assert log[n] == launch
+            built(n, s0)
+            n = len(log)
+            finalize(rmean)                                                                # (a)
+            assert log[n] == launch
+            ev = built(n, s0)
+            current[0], n = s1, len(log)
+            finalize(rmean)                                                                # (b)
+            assert log[n:n + 2] == [("wait", s1, ev), launch]
+            built(n + 1, s1)
+            assert not [e for e in log[n:] if e[0] == "keep"]
+            n = len(log)
+            finalize(Dev())                                                                # (d): other buffers, no wait
+            assert log[n] == launch
+            built(n, s1)
+            n = len(log)
+            hg, hr = torch.ones(4), torch.zeros(4)                                         # (c)
+            finalize(hr, like=hg)
+            current[0] = s0
+            finalize(hr, like=hg)
+            assert log[n:] == [launch] * 2
+        assert K._order is None
+    finally:
+        K.call, K.ptr, K._f32, K._b16, K.lib.load, K.torch.cuda.Event, K.torch.cuda.current_stream = orig

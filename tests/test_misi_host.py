@@ -14,6 +14,7 @@ from avsep_amd import separate as S
 from avsep_amd.lib import AvsepError
 
 import misi_ref as M
+from recipes import no_gpu_call as _no_gpu_call
 
 MAX_ITERS = S.MAX_PHASE_ITERS          # the feature's own constant: without the feature this file does not even import
 
@@ -30,15 +31,6 @@ def test_cli_phase_iters_flag():
         with pytest.raises(SystemExit) as e:
             S.parse_args(base + ["--phase_iters", bad])
         assert "--phase_iters" in str(e.value)
-
-
-def _no_gpu_call(monkeypatch):
-    """Any kernel call from here on fails the test: the refusals below come from the argument checks."""
-    def boom(*a, **k):
-        raise AssertionError("reached the GPU path")
-    monkeypatch.setattr(avsep_amd.lib, "call", boom)
-    monkeypatch.setattr(avsep_amd.kernels, "call", boom)
-    monkeypatch.setattr(avsep_amd.lib, "require_gpu", boom)
 
 
 def test_separate_long_refuses_phase_iters_out_of_range(monkeypatch):

@@ -12,6 +12,7 @@ from avsep_amd import separate as S
 from avsep_amd.lib import AvsepError
 
 import mwf_ref as M
+from recipes import no_gpu_call as _no_gpu_call
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -32,15 +33,6 @@ def test_cli_wiener_flag():
     for bad in ("9", "-1"):
         with pytest.raises(SystemExit):
             S.parse_args(["--wav", "mix.wav", "--audio_only", "--channels", "keep", "--wiener", bad])
-
-
-def _no_gpu_call(monkeypatch):
-    """Any kernel call from here on fails the test: the refusals below come from the argument checks."""
-    def boom(*a, **k):
-        raise AssertionError("reached the GPU path")
-    monkeypatch.setattr(avsep_amd.lib, "call", boom)
-    monkeypatch.setattr(avsep_amd.kernels, "call", boom)
-    monkeypatch.setattr(avsep_amd.lib, "require_gpu", boom)
 
 
 def test_separate_long_refuses_wiener_without_channels_and_out_of_range(monkeypatch):

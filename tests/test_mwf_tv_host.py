@@ -13,6 +13,7 @@ from avsep_amd.lib import AvsepError
 
 import mwf_ref as M
 import mwf_tv_ref as T
+from recipes import no_gpu_call as _no_gpu_call
 
 BAD_SPANS = (63, 96, 4160, -64, -1, 32, 1)
 
@@ -36,15 +37,6 @@ def test_cli_wiener_span_flag():
         with pytest.raises(SystemExit) as e:
             S.parse_args(base + ["--channels", "keep", "--wiener", "1", "--wiener_span", str(bad)])
         assert "multiple of 64" in str(e.value), bad
-
-
-def _no_gpu_call(monkeypatch):
-    """Any kernel call from here on fails the test: the refusals below come from the argument checks."""
-    def boom(*a, **k):
-        raise AssertionError("reached the GPU path")
-    monkeypatch.setattr(avsep_amd.lib, "call", boom)
-    monkeypatch.setattr(avsep_amd.kernels, "call", boom)
-    monkeypatch.setattr(avsep_amd.lib, "require_gpu", boom)
 
 
 def test_separate_long_refuses_bad_spans_before_touching_the_gpu(monkeypatch):

@@ -5,11 +5,7 @@ import numpy as np
 import pytest
 
 import score_ref as SR
-
-
-def _score():
-    from avsep_amd import score
-    return score
+from recipes import score as _score
 
 
 # ---- window planning and the permutation rule (restatement and package agree) ------------------------------------------------------
