@@ -1,5 +1,6 @@
 // Stem levels (include/avsep.h): the two measurements of ITU-R BS.1770-4 that need every sample of a stem, taken where the
-// stems lie just before they are encoded.  Neither writes a waveform.
+// stems lie just before they are encoded (neither writes a waveform), and the linked look-ahead limiter that keeps them under
+// a true-peak ceiling there (avsep_limiter, at the end of this file: the meter's oversampler is its detector).
 //
 // avsep_loudness_energies: the K-weighting is a cascade of two biquads, a serial recurrence in time.  It is also a linear
 // system with four state values (two per section, transposed direct form II), so a row is cut into PIECES that run in
@@ -320,25 +321,25 @@ __device__ __forceinline__ void tp_block_max(double a, double b, double* out) {
   }
 }
 
-// grid (tiles, R).  Input position q in [0, L) carries the outputs m = q * OS + p: pos = m + 10 * OS, phase p, newest sample
-// n0 = q + 10, so u[m] = sum_i x[q + 10 - i] * taps[i][p].  part [R][tiles][2] = the tile's (sample peak, oversampled peak).
+constexpr int TP_LDS = TP_TILE + 2 * TP_HALF + (TP_TILE + 2 * TP_HALF) / TP_PER + 1;   // doubles of a staged tile
+
+// The oversampler, shared by the meter (tp_tile_kernel) and the limiter's detector (lim_detect_kernel).  The workgroup stages
+// the tile of the row xr [L] that starts at q0, with its halo, as doubles; after the barrier every lane reads the samples its
+// TP_PER consecutive positions touch once (xs; position k's own sample is xs[k + TP_HALF]) and makes all OS phases of them.
+// Input position q in [0, L) carries the outputs m = q * OS + p: pos = m + 10 * OS, phase p, newest sample n0 = q + 10, so
+// acc[k][p] = u[m] = sum_i x[q + 10 - i] * taps[i][p], i ascending.
 template <int OS>
-__global__ __launch_bounds__(TP_BLOCK) void tp_tile_kernel(const float* __restrict__ x, const double* __restrict__ taps, int L,
-                                                           double* __restrict__ part) {
-  __shared__ double s_x[TP_TILE + 2 * TP_HALF + (TP_TILE + 2 * TP_HALF) / TP_PER + 1];
+__device__ __forceinline__ void tp_oversample(const float* __restrict__ xr, const double* __restrict__ taps, int L, long long q0,
+                                              double* s_x, double xs[TP_WIN], double acc[TP_PER][OS]) {
   const int tid = threadIdx.x;
-  const long long q0 = (long long)blockIdx.x * TP_TILE;
-  const float* xr = x + (long long)blockIdx.y * L;
   for (int s = tid; s < TP_TILE + 2 * TP_HALF; s += TP_BLOCK) {
     const long long n = q0 - TP_HALF + s;
     s_x[tp_slot(s)] = (n >= 0 && n < L) ? (double)xr[n] : 0.0;
   }
   __syncthreads();
   // the lane's window: the samples its TP_PER consecutive positions touch, read from LDS once
-  double xs[TP_WIN];
 #pragma unroll
   for (int j = 0; j < TP_WIN; ++j) xs[j] = s_x[tp_slot(tid * TP_PER + j)];
-  double acc[TP_PER][OS];
 #pragma unroll
   for (int k = 0; k < TP_PER; ++k)
 #pragma unroll
@@ -352,6 +353,17 @@ __global__ __launch_bounds__(TP_BLOCK) void tp_tile_kernel(const float* __restri
       for (int k = 0; k < TP_PER; ++k) acc[k][p] = fma(xs[k + 2 * TP_HALF - i], c, acc[k][p]);
     }
   }
+}
+
+// grid (tiles, R).  part [R][tiles][2] = the tile's (sample peak, oversampled peak).
+template <int OS>
+__global__ __launch_bounds__(TP_BLOCK) void tp_tile_kernel(const float* __restrict__ x, const double* __restrict__ taps, int L,
+                                                           double* __restrict__ part) {
+  __shared__ double s_x[TP_LDS];
+  const int tid = threadIdx.x;
+  const long long q0 = (long long)blockIdx.x * TP_TILE;
+  double xs[TP_WIN], acc[TP_PER][OS];
+  tp_oversample<OS>(x + (long long)blockIdx.y * L, taps, L, q0, s_x, xs, acc);
   double ps = 0.0, pu = 0.0;
 #pragma unroll
   for (int k = 0; k < TP_PER; ++k) {
@@ -400,6 +412,238 @@ extern "C" int avsep_true_peak(const float* x, const double* taps, int32_t R, in
     hipLaunchKernelGGL(tp_tile_kernel<4>, grid, dim3(TP_BLOCK), 0, st, x, taps, L, part);
   AVSEP_LAUNCH_CHECK();
   hipLaunchKernelGGL(tp_row_kernel, dim3(R), dim3(TP_BLOCK), 0, st, (const double*)part, tiles, peaks);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// linked look-ahead limiter (include/avsep.h states the definition)
+// ---------------------------------------------------------------------------------------------------------------------
+// Three launches over tiles of TP_TILE samples of a programme, grid (tiles, P):
+//   lim_detect_kernel: the C rows of the tile go through tp_oversample one after the other, every lane keeps the running
+//     maximum of its TP_PER positions in registers; r goes to the workspace [P][L], the tile's largest p to its partials.
+//   lim_apply_kernel: stages r on [t0 - 2A, t0 + TP_TILE + 2A) in LDS (1 outside the row; the allocation follows A, so a
+//     short look-ahead keeps several workgroups on a CU), takes the sliding minimum of width 2A + 1 in place by doubling
+//     (m_2k[s] = min(m_k[s], m_k[s + k]); the last step joins two windows of the largest power of two), smooths 1 - h with w
+//     in ascending k (every lane eight consecutive positions: one LDS read per eight fma, the weights are wave-uniform),
+//     hands g to the workgroup through LDS and then walks the C rows with coalesced loads and stores.  A tile whose staged
+//     r are all 1 skips minimum and sum: g = 1 - 0 there whatever the order.
+//   lim_stats_kernel: a programme's partials to stats.
+constexpr int LIM_MAX_A = 2048;
+constexpr int LIM_MAX_C = 64;
+constexpr int LIM_PAD = 16;                      // staged slots past the envelope that the unrolled sum touches with weight 0
+
+static size_t lim_lds_doubles(int A) {
+  const int n = TP_TILE + 4 * A + LIM_PAD;
+  return (size_t)n + n / TP_PER + 1;
+}
+
+// r [P][L]; part [P][tiles][3]: slot 0 = the tile's largest p
+template <int OS>
+__global__ __launch_bounds__(TP_BLOCK) void lim_detect_kernel(const float* __restrict__ x, const double* __restrict__ taps, int C, int L,
+                                                              double G, double ceiling, double* __restrict__ r,
+                                                              double* __restrict__ part) {
+  __shared__ double s_x[TP_LDS];
+  const int tid = threadIdx.x;
+  const long long q0 = (long long)blockIdx.x * TP_TILE;
+  const float* xp = x + (long long)blockIdx.y * C * L;
+  double pk[TP_PER];
+#pragma unroll
+  for (int k = 0; k < TP_PER; ++k) pk[k] = 0.0;
+  for (int c = 0; c < C; ++c) {
+    if (c) __syncthreads();                      // every lane has read its window of the previous row
+    double xs[TP_WIN], acc[TP_PER][OS];
+    tp_oversample<OS>(xp + (long long)c * L, taps, L, q0, s_x, xs, acc);
+#pragma unroll
+    for (int k = 0; k < TP_PER; ++k) {
+      pk[k] = fmax(pk[k], tp_abs(xs[k + TP_HALF]));
+#pragma unroll
+      for (int p = 0; p < OS; ++p) pk[k] = fmax(pk[k], tp_abs(acc[k][p]));
+    }
+  }
+  double* rr = r + (long long)blockIdx.y * L;
+  double top = 0.0;
+#pragma unroll
+  for (int k = 0; k < TP_PER; ++k) {
+    const long long n = q0 + tid * TP_PER + k;
+    if (n >= L) continue;
+    top = fmax(top, pk[k]);
+    rr[n] = fmin(1.0, ceiling / (G * pk[k]));    // p = 0: c / 0 = +inf, so 1; p = +inf: 0
+  }
+  double out[2] = {0.0, 0.0};
+  tp_block_max(top, 0.0, out);
+  if (tid == 0) part[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3] = out[0];
+}
+
+// y may be x: a sample is read and written by the same lane.  part slots 1, 2 = the tile's smallest g, its count of g < 1.
+__global__ __launch_bounds__(TP_BLOCK) void lim_apply_kernel(const float* x, const double* __restrict__ r, const double* __restrict__ w,
+                                                             int C, int L, int A, double G, float* y, double* __restrict__ gain,
+                                                             double* __restrict__ part) {
+  extern __shared__ double s_m[];                // lim_lds_doubles(A)
+  __shared__ double s_min[TP_BLOCK / 64];
+  __shared__ int s_cnt[TP_BLOCK / 64];
+  const int tid = threadIdx.x;
+  const long long t0 = (long long)blockIdx.x * TP_TILE;
+  const int n = TP_TILE + 4 * A, W = 2 * A + 1, reach = TP_TILE + 2 * A;
+  const double* rr = r + (long long)blockIdx.y * L;
+  int touched = 0;
+  for (int s = tid; s < n + LIM_PAD; s += TP_BLOCK) {
+    const long long idx = t0 - 2 * A + s;
+    const double v = (s < n && idx >= 0 && idx < L) ? rr[idx] : 1.0;
+    touched |= (v != 1.0) ? 1 : 0;
+    s_m[tp_slot(s)] = v;
+  }
+  double g[TP_PER];                              // of the positions t0 + tid * TP_PER + i
+#pragma unroll
+  for (int i = 0; i < TP_PER; ++i) g[i] = 1.0;
+  if (__syncthreads_or(touched)) {               // the same answer in every lane: the barriers below are met by all
+    // m_k[s] = min of the staged r over [s, s + k), valid where s + k <= n.  A pass reads a chunk, waits, writes it: a later
+    // chunk reads only slots that no earlier chunk has written.
+    int k = 1;
+    for (; 2 * k <= W; k *= 2) {
+      for (int base = 0; base + 2 * k <= n; base += TP_TILE) {
+        double v[TP_PER];
+#pragma unroll
+        for (int i = 0; i < TP_PER; ++i) {
+          const int s = base + i * TP_BLOCK + tid;
+          v[i] = (s + 2 * k <= n) ? fmin(s_m[tp_slot(s)], s_m[tp_slot(s + k)]) : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < TP_PER; ++i) {
+          const int s = base + i * TP_BLOCK + tid;
+          if (s + 2 * k <= n) s_m[tp_slot(s)] = v[i];
+        }
+      }
+      __syncthreads();
+    }
+    // h[t0 - A + s] = min(m_k[s], m_k[s + W - k]) for s in [0, reach); the slot gets the reduction 1 - h
+    const int rest = W - k;
+    for (int base = 0; base < reach; base += TP_TILE) {
+      double v[TP_PER];
+#pragma unroll
+      for (int i = 0; i < TP_PER; ++i) {
+        const int s = base + i * TP_BLOCK + tid;
+        v[i] = (s < reach) ? 1.0 - fmin(s_m[tp_slot(s)], s_m[tp_slot(s + rest)]) : 0.0;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < TP_PER; ++i) {
+        const int s = base + i * TP_BLOCK + tid;
+        if (s < reach) s_m[tp_slot(s)] = v[i];
+      }
+    }
+    __syncthreads();
+    // g[q] = 1 - sum_{kk = 0 .. 2A} w[kk] * d[q + kk].  Slot j = i + kk of the lane serves its eight positions i with the weights
+    // w[j - i]; those before w's start and past its end are 0, and the slots from `reach` on hold finite values in [0, 1].
+    double acc[TP_PER], wp[TP_PER];
+#pragma unroll
+    for (int i = 0; i < TP_PER; ++i) acc[i] = 0.0, wp[i] = 0.0;
+    for (int jb = 0; jb < 2 * A + TP_PER; jb += TP_PER) {
+      double wc[TP_PER];
+#pragma unroll
+      for (int u = 0; u < TP_PER; ++u) wc[u] = (jb + u < W) ? w[jb + u] : 0.0;
+#pragma unroll
+      for (int u = 0; u < TP_PER; ++u) {
+        const double d = s_m[tp_slot(tid * TP_PER + jb + u)];
+#pragma unroll
+        for (int i = 0; i < TP_PER; ++i) acc[i] = fma(u >= i ? wc[u - i] : wp[TP_PER + u - i], d, acc[i]);
+      }
+#pragma unroll
+      for (int u = 0; u < TP_PER; ++u) wp[u] = wc[u];
+    }
+#pragma unroll
+    for (int i = 0; i < TP_PER; ++i) g[i] = 1.0 - acc[i];
+    __syncthreads();                             // every lane has read its reductions: the slots are free for g
+  }
+  double gmin = (double)INFINITY;
+  int cnt = 0;
+#pragma unroll
+  for (int i = 0; i < TP_PER; ++i) {
+    s_m[tid * TP_PER + i] = g[i];
+    if (t0 + tid * TP_PER + i >= L) continue;
+    gmin = fmin(gmin, g[i]);
+    cnt += g[i] < 1.0 ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) gmin = fmin(gmin, __shfl_xor(gmin, o, 64)), cnt += __shfl_xor(cnt, o, 64);
+  if ((tid & 63) == 0) s_min[tid >> 6] = gmin, s_cnt[tid >> 6] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int v = 1; v < TP_BLOCK / 64; ++v) gmin = fmin(gmin, s_min[v]), cnt += s_cnt[v];
+    double* p = part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+    p[1] = gmin, p[2] = (double)cnt;
+  }
+  double gg[TP_PER];
+#pragma unroll
+  for (int i = 0; i < TP_PER; ++i) {
+    const int q = i * TP_BLOCK + tid;
+    const double v = s_m[q];
+    if (gain && t0 + q < L) gain[(long long)blockIdx.y * L + t0 + q] = v;
+    gg[i] = G * v;
+  }
+  for (int c = 0; c < C; ++c) {
+    const long long row = ((long long)blockIdx.y * C + c) * L;
+#pragma unroll
+    for (int i = 0; i < TP_PER; ++i) {
+      const long long q = t0 + i * TP_BLOCK + tid;
+      if (q < L) y[row + q] = (float)((double)x[row + q] * gg[i]);
+    }
+  }
+}
+
+// grid (P): maximum, minimum and the sum of integer counts (exact in float64, so order-free) over the programme's tiles
+__global__ __launch_bounds__(TP_BLOCK) void lim_stats_kernel(const double* __restrict__ part, int tiles, double* __restrict__ stats) {
+  __shared__ double s_r[3][TP_BLOCK / 64];
+  const double* p = part + (long long)blockIdx.x * tiles * 3;
+  double a = 0.0, b = (double)INFINITY, c = 0.0;
+  for (int t = threadIdx.x; t < tiles; t += TP_BLOCK) a = fmax(a, p[3 * t]), b = fmin(b, p[3 * t + 1]), c += p[3 * t + 2];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a = fmax(a, __shfl_xor(a, o, 64)), b = fmin(b, __shfl_xor(b, o, 64)), c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) s_r[0][threadIdx.x >> 6] = a, s_r[1][threadIdx.x >> 6] = b, s_r[2][threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int v = 1; v < TP_BLOCK / 64; ++v) a = fmax(a, s_r[0][v]), b = fmin(b, s_r[1][v]), c += s_r[2][v];
+    stats[3 * blockIdx.x] = a, stats[3 * blockIdx.x + 1] = b, stats[3 * blockIdx.x + 2] = c;
+  }
+}
+
+static bool lim_shape_ok(int P, int C, int L) { return P >= 1 && P <= 65535 && C >= 1 && C <= LIM_MAX_C && L >= 1; }
+
+// doubles: r [P][L], the partials [P][tiles][3]
+static size_t lim_ws_doubles(int P, int L) { return (size_t)P * ((size_t)L + 3 * (size_t)cdiv(L, TP_TILE)); }
+
+extern "C" size_t avsep_limiter_workspace_bytes(int32_t P, int32_t C, int32_t L) {
+  return lim_shape_ok(P, C, L) ? lim_ws_doubles(P, L) * sizeof(double) : 0;
+}
+
+extern "C" int avsep_limiter(const float* x, const double* taps, const double* w, int32_t P, int32_t C, int32_t L, int32_t os, int32_t A,
+                             double pre_gain, double ceiling, float* y, double* gain, double* stats, void* ws, size_t ws_bytes,
+                             avsep_stream_t stream) {
+  if (!x || !taps || !w || !y || !stats || !ws || !lim_shape_ok(P, C, L) || !tp_shape_ok(1, L, os)) return AVSEP_ERR_ARG;
+  if (A < 1 || A > LIM_MAX_A || !isfinite(pre_gain) || !(pre_gain > 0.0) || !(ceiling > 0.0 && ceiling <= 1.0)) return AVSEP_ERR_ARG;
+  if (ws_bytes < lim_ws_doubles(P, L) * sizeof(double)) return AVSEP_ERR_WORKSPACE;
+  const int tiles = cdiv(L, TP_TILE);
+  const dim3 grid(tiles, P);
+  const hipStream_t st = (hipStream_t)stream;
+  double* r = (double*)ws;
+  double* part = r + (size_t)P * L;
+  const size_t lds = lim_lds_doubles(A) * sizeof(double);
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)lim_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return AVSEP_ERR_LAUNCH;
+  if (os == 1)
+    hipLaunchKernelGGL(lim_detect_kernel<1>, grid, dim3(TP_BLOCK), 0, st, x, taps, C, L, pre_gain, ceiling, r, part);
+  else if (os == 2)
+    hipLaunchKernelGGL(lim_detect_kernel<2>, grid, dim3(TP_BLOCK), 0, st, x, taps, C, L, pre_gain, ceiling, r, part);
+  else
+    hipLaunchKernelGGL(lim_detect_kernel<4>, grid, dim3(TP_BLOCK), 0, st, x, taps, C, L, pre_gain, ceiling, r, part);
+  AVSEP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lim_apply_kernel, grid, dim3(TP_BLOCK), lds, st, x, (const double*)r, w, C, L, A, pre_gain, y, gain, part);
+  AVSEP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lim_stats_kernel, dim3(P), dim3(TP_BLOCK), 0, st, (const double*)part, tiles, stats);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }

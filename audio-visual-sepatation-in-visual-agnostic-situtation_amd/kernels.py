@@ -1100,6 +1100,44 @@ def true_peak(x, taps, os):
     return peaks
 
 
+LIMITER_MAX_A = 2048              # the longest half-width avsep_limiter takes, samples
+LIMITER_MAX_C = 64                # rows of a programme
+
+
+def limiter(x, taps, w, os, pre_gain, ceiling, return_gain=False, out=None):
+    """avsep_limiter (include/avsep.h): x f32 [P,C,L], P programmes of C linked rows; taps f64 [21, os] and w f64 [2A+1]
+    (the smoothing weights, symmetric, sum 1) on x's device; pre_gain > 0, 0 < ceiling <= 1 (linear) -> (y f32 [P,C,L],
+    gain f64 [P,L] or None, stats f64 [P,3] on the GPU: the largest detector value, the smallest gain, the count of gains
+    below 1).  out: where y goes (x itself is allowed)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 3 or not 1 <= x.shape[0] <= 65535 or \
+            not 1 <= x.shape[1] <= LIMITER_MAX_C or x.shape[2] < 1:
+        raise lib.AvsepError(f"limiter takes float32 [P,C,L] with 1 <= P <= 65535, 1 <= C <= {LIMITER_MAX_C} and L >= 1, got {lib.got(x)}")
+    P, C, L = x.shape
+    if isinstance(os, bool) or os not in (1, 2, 4) or os * L >= 2 ** 31:
+        raise lib.AvsepError(f"limiter oversamples by 1, 2 or 4 with os * L < 2^31, got os={os!r} L={L}")
+    if not torch.is_tensor(taps) or taps.dtype != torch.float64 or tuple(taps.shape) != (TRUE_PEAK_TAPS, os) or taps.device != x.device:
+        raise lib.AvsepError(f"limiter: the table of os={os} is float64 [{TRUE_PEAK_TAPS},{os}] on {x.device}, got {lib.got(taps)}")
+    if not torch.is_tensor(w) or w.dtype != torch.float64 or w.dim() != 1 or w.shape[0] % 2 != 1 or \
+            not 3 <= w.shape[0] <= 2 * LIMITER_MAX_A + 1 or w.device != x.device:
+        raise lib.AvsepError(f"limiter: the weights are float64 [2A+1] with 1 <= A <= {LIMITER_MAX_A} on {x.device}, got {lib.got(w)}")
+    pre_gain, ceiling = float(pre_gain), float(ceiling)
+    if not (np.isfinite(pre_gain) and pre_gain > 0.0 and 0.0 < ceiling <= 1.0):
+        raise lib.AvsepError(f"limiter takes a finite pre_gain > 0 and 0 < ceiling <= 1, got pre_gain={pre_gain} ceiling={ceiling}")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device
+                            or not out.is_contiguous()):
+        raise lib.AvsepError(f"limiter: out is dense float32 {tuple(x.shape)} on {x.device}, got {lib.got(out)}")
+    lib.require_gpu(x)
+    x, taps, w = x.contiguous(), taps.contiguous(), w.contiguous()
+    y = torch.empty_like(x) if out is None else out
+    gain = torch.empty((P, L), dtype=torch.float64, device=x.device) if return_gain else None
+    stats = torch.empty((P, 3), dtype=torch.float64, device=x.device)
+    nbytes = lib.load().avsep_limiter_workspace_bytes(P, C, L)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
+    call("avsep_limiter", ptr(x), ptr(taps), ptr(w), P, C, L, int(os), w.shape[0] // 2, pre_gain, ceiling, ptr(y), ptr(gain),
+         ptr(stats), ptr(ws), nbytes)
+    return y, gain, stats
+
+
 FRAMES_MAX_T = 65535              # frames per launch of avsep_frames_prepare (a grid dimension)
 
 

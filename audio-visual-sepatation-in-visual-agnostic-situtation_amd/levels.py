@@ -8,9 +8,12 @@ host (``loudness_from_energies``), because a gate is a data-dependent selection 
 
     measure(x, rate)          -> integrated / momentary-max / short-term-max LUFS, true and sample peak, the energies
     output_gain(...)          -> the ONE gain that brings a run to a loudness and keeps its largest true peak under a ceiling
+    limit(x, rate, dbtp, ...) -> the rows under a true-peak ceiling by ONE look-ahead gain curve per programme (avsep_limiter:
+                                 the meter's oversampler as the detector, a hold and a raised-cosine smoothing, all on the GPU)
 
 CLI: ``python -m avsep_amd.levels a.wav b.wav ... [--json out.json]`` prints the five figures of every file (any format and
-rate wavio.py reads, up to eight channels).
+rate wavio.py reads, up to eight channels); ``python -m avsep_amd.levels in.wav --limit DBTP --out out.wav [--limit_lookahead
+MS]`` writes the file limited to DBTP in its own format, its channels linked, and prints the figures before and after.
 """
 import json
 import math
@@ -204,6 +207,82 @@ def scaled(m, gain):
     return out
 
 
+def limiter_plan(rate, lookahead_ms):
+    """-> (A, w): the limiter's half-width in samples, max(1, round(rate * ms / 1000)), and its smoothing weights, float64
+    [2A + 1]: w[k + A] = (1 + cos(pi k / (A + 1))) / sum for k = -A .. A (symmetric, sum 1)."""
+    rate = _check_rate(rate)
+    try:
+        ms = float(lookahead_ms)
+    except (TypeError, ValueError):
+        ms = math.nan
+    if not (math.isfinite(ms) and ms > 0.0):
+        raise AvsepError(f"the limiter's look-ahead is a finite time > 0 in milliseconds, got {lookahead_ms!r}")
+    A = max(1, int(round(rate * ms / 1000.0)))
+    if A > K.LIMITER_MAX_A:
+        raise AvsepError(f"the limiter looks ahead by at most {K.LIMITER_MAX_A} samples ({1000.0 * K.LIMITER_MAX_A / rate:.2f} ms at "
+                         f"{rate} Hz), {ms} ms are {A}")
+    k = np.arange(-A, A + 1, dtype=np.float64)
+    w = 1.0 + np.cos(np.pi * k / (A + 1))
+    return A, w / w.sum()
+
+
+def limit(x, rate, ceiling_db, gain=1.0, lookahead_ms=5.0, trim=True, return_gain=False):
+    """The linked look-ahead true-peak limiter (avsep_limiter, include/avsep.h).  x: f32 [P, C, L] on the GPU, P
+    programmes of C rows (or [C, L], one programme) at ``rate``; every row of a programme gets the SAME gain curve: the
+    pre-gain ``gain`` everywhere, turned down around the peaks only, so that no sample of gain * x passes the ceiling
+    ``ceiling_db`` (dBTP, <= 0) where the oversampled detector sees it.  -> (y like x, info); info holds CPU float64 [P]
+    tensors: "peak_in" (the programme's largest true peak, linear, the pre-gain included), "min_gain" (the curve's lowest
+    value, the pre-gain not included), "limited_share" (the share of samples whose gain is below 1), "trim" (linear).
+    trim: the curve moves a row's inter-sample peaks, so y is measured with avsep_true_peak and a programme whose true peak
+    still passes the ceiling is multiplied by ceiling / true peak (1: nothing to do).  return_gain: info["gain"] is the
+    curve, f64 [P, L] on the GPU, without pre-gain and trim.  A NaN or an infinity raises AvsepError naming the programme."""
+    rate = _check_rate(rate)
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() not in (2, 3) or x.shape[-1] < 1 or x.shape[-2] < 1:
+        raise AvsepError(f"limit takes float32 [P,C,L] or [C,L], got {lib.got(x)}")
+    single = x.dim() == 2
+    if single:
+        x = x[None]
+    P, C, L = x.shape
+    if not 1 <= P <= 65535 or C > K.LIMITER_MAX_C or P * C > 65535:
+        raise AvsepError(f"limit takes up to 65535 rows in one call and up to {K.LIMITER_MAX_C} rows per programme, got {P} x {C}")
+    try:
+        ceiling_db, gain = float(ceiling_db), float(gain)
+    except (TypeError, ValueError):
+        raise AvsepError(f"limit takes a ceiling in dBTP and a linear pre-gain, got {ceiling_db!r} and {gain!r}")
+    if not (math.isfinite(ceiling_db) and ceiling_db <= 0.0):
+        raise AvsepError(f"limit takes a finite ceiling of at most 0 dBTP, got {ceiling_db}")
+    if not (math.isfinite(gain) and gain > 0.0):
+        raise AvsepError(f"limit takes a finite pre-gain > 0, got {gain}")
+    _, w = limiter_plan(rate, lookahead_ms)          # refused before the device is looked at
+    lib.require_gpu(x)
+    c = 10.0 ** (ceiling_db / 20.0)
+    os, taps = peak_table(rate, x.device)
+    w = torch.from_numpy(w).to(taps.device)          # at most 32 KiB a call: nothing is kept on the device
+    y, curve, stats = K.limiter(x, taps, w, os, gain, c, return_gain=return_gain)
+    after = K.true_peak(y.reshape(P * C, L), taps, os)[:, 1].reshape(P, C).amax(1) if trim else None
+    stats = stats.cpu()
+    bad = torch.nonzero(~torch.isfinite(stats[:, 0]))
+    if bad.numel():
+        raise AvsepError(f"limit: programme {bad[0, 0].item()} holds a NaN or an infinity: it has no level")
+    info = {"peak_in": stats[:, 0] * gain, "min_gain": stats[:, 1].contiguous(), "limited_share": stats[:, 2] / L,
+            "trim": torch.ones(P, dtype=torch.float64)}
+    if trim:
+        after = after.cpu()
+        for p in torch.nonzero(after > c)[:, 0].tolist():
+            info["trim"][p] = c / after[p].item()
+            y[p] = (y[p].double() * info["trim"][p].item()).float()       # one f32 rounding per sample
+    if return_gain:
+        info["gain"] = curve
+    return (y[0] if single else y), info
+
+
+def limiter_figures(info, ceiling_db, lookahead_ms, p=0):
+    """The "limiter" block of levels.json from programme p of ``limit``'s info (-inf and +inf: None)."""
+    return {"ceiling_dbtp": float(ceiling_db), "lookahead_ms": float(lookahead_ms),
+            "max_reduction_db": _json_number(max(0.0, -_db(info["min_gain"][p]))), "limited_share": float(info["limited_share"][p]),
+            "trim_db": _json_number(_db(info["trim"][p]))}
+
+
 def _db(v):
     v = float(v)
     return 20.0 * math.log10(v) if v > 0.0 else -math.inf
@@ -222,10 +301,14 @@ def figures(m, p=0):
             "sample_peak_dbfs": [_json_number(_db(v)) for v in m["sample_peak"][p]]}
 
 
-def report(rate, gain, limited_by, mixture, stems):
-    """What ``separate`` writes as levels.json: mixture, stems: ``measure`` results (one programme; one per source) AFTER the gain."""
-    return {"rate": int(rate), "gain_db": _db(gain), "limited_by": limited_by, "mixture": figures(mixture),
-            "sources": [figures(stems, n) for n in range(stems["integrated"].shape[0])]}
+def report(rate, gain, limited_by, mixture, stems, limiter=None):
+    """What ``separate`` writes as levels.json: mixture, stems: ``measure`` results (one programme; one per source) AFTER the gain
+    (and after the limiter: ``limiter`` is then ``limiter_figures``' block and ``gain`` the limiter's pre-gain)."""
+    out = {"rate": int(rate), "gain_db": _db(gain), "limited_by": limited_by, "mixture": figures(mixture),
+           "sources": [figures(stems, n) for n in range(stems["integrated"].shape[0])]}
+    if limiter is not None:
+        out["limiter"] = dict(limiter)
+    return out
 
 
 def _line(name, f):
@@ -248,15 +331,62 @@ def measure_file(path, device):
     return info, measure(rows, info.rate)
 
 
+def _limit_file(args, dev):
+    """``--limit``: one file in, the same file under the ceiling out (its own rate, channels and sample format; a 32-bit PCM
+    file is written as 24-bit, as ``separate`` writes it)."""
+    from . import wavio
+    path = args.wavs[0]
+    raw, info = wavio.read_frames(path)
+    if info.channels > R.MAX_KEPT_CHANNELS:
+        raise AvsepError(f"{path}: levels are measured for up to {R.MAX_KEPT_CHANNELS} channels, this file has {info.channels}")
+    _check_rate(info.rate)
+    limiter_plan(info.rate, args.limit_lookahead)
+    rows = R.split_frames(torch.from_numpy(raw).to(dev), info.fmt, info.channels, info.rate, info.rate)[1:]
+    before = measure(rows, info.rate)
+    y, lim = limit(rows, info.rate, args.limit, lookahead_ms=args.limit_lookahead)
+    fmt = "s24" if info.fmt == "s32" else info.fmt
+    wavio.write_frames(args.out, R.join_frames(y.contiguous(), info.rate, info.rate, fmt).cpu().numpy(), info.rate, info.channels, fmt)
+    after = measure(y, info.rate)
+    out = {"input": dict(figures(before), rate=info.rate, channels=info.channels), "output": figures(after),
+           "limiter": limiter_figures(lim, args.limit, args.limit_lookahead)}
+    print(_line(path, out["input"]))
+    print(_line(args.out, out["output"]))
+    f = out["limiter"]
+    most = "to silence" if f["max_reduction_db"] is None else f"by up to {f['max_reduction_db']:.2f} dB"
+    print(f"limiter at {f['ceiling_dbtp']:.2f} dBTP, look-ahead {f['lookahead_ms']:g} ms: {100.0 * f['limited_share']:.2f} % of the "
+          f"samples turned down, {most}; trim {f['trim_db']:.4f} dB")
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    return out
+
+
 def cli(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="BS.1770-4 loudness and true peak of WAV files, measured on the GPU.")
     ap.add_argument("wavs", nargs="+", help="WAV files (16-, 24- or 32-bit PCM or 32-bit float, any rate from 8 to 192 kHz)")
     ap.add_argument("--json", default=None, help="also write the figures to this file")
+    ap.add_argument("--limit", type=float, default=None, metavar="DBTP",
+                    help="limit the ONE input file to this true-peak ceiling (<= 0) with a look-ahead limiter, its channels "
+                         "linked, and write it to --out in the file's own format")
+    ap.add_argument("--limit_lookahead", type=float, default=5.0, metavar="MS", help="with --limit: the look-ahead, milliseconds")
+    ap.add_argument("--out", default=None, help="with --limit: the file to write")
     args = ap.parse_args(argv)
+    if args.limit is not None:
+        if len(args.wavs) != 1 or not args.out:
+            raise SystemExit("--limit takes exactly one input file and --out OUT.wav")
+        if not args.limit <= 0.0 or math.isinf(args.limit):
+            raise SystemExit(f"--limit takes a finite true-peak ceiling of at most 0 dBTP, got {args.limit}")
+    elif args.out:
+        raise SystemExit("--out is where --limit writes: it needs --limit DBTP")
     if not torch.cuda.is_available():
         raise AvsepError("levels are measured on an MI355X; there is no CPU fallback")
     dev = torch.device("cuda", 0)
+    if args.limit is not None:
+        try:
+            return _limit_file(args, dev)
+        except AvsepError as e:
+            raise SystemExit(str(e))
     out = {}
     for path in args.wavs:
         try:

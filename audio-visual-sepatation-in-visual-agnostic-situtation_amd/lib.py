@@ -114,6 +114,8 @@ SIGNATURES = {
     "avsep_loudness_energies": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "avsep_true_peak_workspace_bytes": (_Z, [_I, _I]),
     "avsep_true_peak": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "avsep_limiter_workspace_bytes": (_Z, [_I, _I, _I]),
+    "avsep_limiter": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _Z, _P]),
     "avsep_frames_prepare": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avsep_frames_batch_plan": (C.c_int, [C.POINTER(FramesRow), _I, _I, _L, _L, _L, _L, C.POINTER(C.c_int32)]),
     "avsep_frames_prepare_batch": (C.c_int, [_P, _L, _P, _I, _P, _L, _I, _P, _P, _L, _L, _I, _I, _P]),

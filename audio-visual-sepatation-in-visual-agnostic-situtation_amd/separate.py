@@ -38,6 +38,7 @@ the frames that fall into it (``frames_of_windows``, ``avsep_window_reduce``): w
 fusion.  One frame list for two sources is a duet, one camera on both players.
 """
 import itertools
+import math
 import os
 import wave
 
@@ -526,6 +527,12 @@ def build_parser():
     p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                    help="one gain for all sources that brings the mixture to LUFS (-70 ... 0) integrated loudness; "
                         "with --peak the ceiling wins")
+    p.add_argument("--limit", type=float, default=None, metavar="DBTP",
+                   help="a linked look-ahead true-peak limiter in place of the clip: ONE gain curve for all sources and channels "
+                        "that turns the level down around the peaks only, so that no true peak exceeds DBTP (<= 0) and "
+                        "--loudness is reached elsewhere (not with --peak)")
+    p.add_argument("--limit_lookahead", type=float, default=5.0, metavar="MS",
+                   help="with --limit: the limiter's look-ahead in milliseconds (default 5; at most 2048 samples at the output rate)")
     p.add_argument("--frames", nargs="*", default=[], help="one .npy per source: [3,H,W], [1,3,H,W] or [K,3,H,W]; with --fps a "
                                                            "stack [T,3,H,W], and ONE stack with --num_mix 2 is a duet.  Frames as "
                                                            "shot: a uint8 .npy [H,W,3] or [T,H,W,3], or a folder of .jpg / .png "
@@ -575,6 +582,17 @@ def parse_args(argv=None):
         raise SystemExit(f"--peak takes a true-peak ceiling of at most 0 dBTP, got {args.peak}")
     if args.loudness is not None and not -70.0 <= args.loudness <= 0.0:
         raise SystemExit(f"--loudness takes a target in -70 ... 0 LUFS, got {args.loudness}")
+    if args.limit is not None:
+        from . import levels as LV
+        if not args.limit <= 0.0 or math.isinf(args.limit):
+            raise SystemExit(f"--limit takes a finite true-peak ceiling of at most 0 dBTP, got {args.limit}")
+        if args.peak is not None:
+            raise SystemExit("--limit and --peak both set the ceiling: pass one of them (--peak: one gain for the whole run; "
+                             "--limit: a gain curve around the peaks)")
+        try:                                         # at the rate the sources are written at if it is known, else at the lowest
+            LV.limiter_plan(args.audRate if args.out_rate == "model" else LV.MIN_RATE, args.limit_lookahead)
+        except AvsepError as e:
+            raise SystemExit(f"--limit_lookahead: {e}")
     return args
 
 
@@ -602,6 +620,11 @@ def open_recording(args, what, keep=False, levels=False):
         measured_rate = info.rate if args.out_rate == "file" else args.audRate
         if not LV.MIN_RATE <= measured_rate <= LV.MAX_RATE:
             raise SystemExit(f"{args.wav}: levels are measured at {LV.MIN_RATE} ... {LV.MAX_RATE} Hz, the sources are written at {measured_rate} Hz")
+        if args.limit is not None:
+            try:
+                LV.limiter_plan(measured_rate, args.limit_lookahead)
+            except AvsepError as e:
+                raise SystemExit(f"{args.wav}: --limit_lookahead: {e}")
     if not torch.cuda.is_available():
         raise AvsepError(f"{what} runs on an MI355X; there is no CPU fallback")
     # the raw frames go up; down-mix (and with keep every channel beside it), conversion and filter are one kernel
@@ -654,10 +677,29 @@ def write_stems(out_dir, rows, rate_in, rate_out, fmt):
                            rate_out, r.shape[0], fmt)
 
 
+def limit_rows(rows, mix, rate, gain, args):
+    """--limit: the stems ``rows`` f32 [N, C, L] go through levels.limit as ONE programme of N*C rows at the pre-gain ``gain``;
+    the mixture ``mix`` f32 [Cm, Lmix] gets the same curve and the same trim in float64 (past the stems' end, where there is
+    nothing to limit, the pre-gain and the trim alone) -> (rows, mix, the "limiter" block of levels.json)."""
+    from . import levels as LV
+    N, Cc, Lr = rows.shape
+    try:
+        y, info = LV.limit(rows.reshape(1, N * Cc, Lr), rate, args.limit, gain=gain, lookahead_ms=args.limit_lookahead,
+                           return_gain=True)
+    except AvsepError as e:
+        raise SystemExit(f"{args.wav}: {e}")
+    flat = gain * float(info["trim"][0])
+    n = min(Lr, mix.shape[1])
+    curve = torch.full((mix.shape[1],), flat, dtype=torch.float64, device=mix.device)
+    curve[:n] = info["gain"][0, :n] * flat
+    mix = (mix.double() * curve).float()
+    return y.reshape(N, Cc, Lr), mix, LV.limiter_figures(info, args.limit, args.limit_lookahead)
+
+
 def cli(argv=None):
     args = parse_args(argv)
     keep = args.channels == "keep"
-    levelled = args.peak is not None or args.loudness is not None
+    levelled = args.peak is not None or args.loudness is not None or args.limit is not None
     info, wav, channels = open_recording(args, "separation", keep, levels=args.levels or levelled)
     rate, dev = info.rate, wav.device
     out_fmt = {"file": "s24" if info.fmt == "s32" else info.fmt}.get(args.out_format, args.out_format)
@@ -701,10 +743,16 @@ def cli(argv=None):
                 gain, limited_by = LV.output_gain(m_mix["integrated"][0], m_stems["true_peak"], args.loudness, args.peak)
             except AvsepError as e:
                 raise SystemExit(f"{args.wav}: {e}")
-            if gain != 1.0:                          # both meters are linear: the figures after the gain follow from those before
+            limiter = None
+            if args.limit is not None:               # one programme of all N*C rows: one curve, so the stems still sum to the mixture
+                rows, mix, limiter = limit_rows(rows, mix, out_rate, gain, args)
+                m_stems, m_mix = LV.measure(rows, out_rate), LV.measure(mix, out_rate)     # not linear: measured again
+                if limiter["limited_share"] > 0.0:
+                    limited_by = "limiter"
+            elif gain != 1.0:                        # both meters are linear: the figures after the gain follow from those before
                 rows = rows * gain
                 m_stems, m_mix = LV.scaled(m_stems, gain), LV.scaled(m_mix, gain)
-            report = LV.report(out_rate, gain, limited_by, m_mix, m_stems)
+            report = LV.report(out_rate, gain, limited_by, m_mix, m_stems, limiter)
         if levelled or full:                         # written from the rows; else from the model-rate stems, resampled by the join
             stems, rate_in = rows, out_rate
     write_stems(args.out, stems, rate_in, out_rate, out_fmt)
@@ -715,6 +763,10 @@ def cli(argv=None):
     kept = f", {channels.shape[0]} channel{'s' if channels.shape[0] != 1 else ''} each" if keep else ""
     if report is not None and report["limited_by"]:
         kept += f", gain {report['gain_db']:+.2f} dB (limited by {report['limited_by']})"
+        if report["limited_by"] == "limiter":
+            lim = report["limiter"]
+            most = "to silence" if lim["max_reduction_db"] is None else f"by up to {lim['max_reduction_db']:.2f} dB"
+            kept += f", limiter at {lim['ceiling_dbtp']:.2f} dBTP: {100.0 * lim['limited_share']:.2f} % of the samples turned down, {most}"
     if args.wiener:
         kept += f", multichannel Wiener filter x{args.wiener}"
         if args.wiener_span:

@@ -713,6 +713,32 @@ size_t avsep_true_peak_workspace_bytes(int32_t R, int32_t L);
 int avsep_true_peak(const float* x, const double* taps, int32_t R, int32_t L, int32_t os, double* peaks, void* ws, size_t ws_bytes,
                     avsep_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Linked look-ahead true-peak limiter (csrc/levels.hip; avsep_amd/levels.py limit): x f32 [P][C][L] in device memory, P
+ * programmes of C rows; ONE gain curve per programme, applied to all of its rows, so that stems keep their balance and sum
+ * to the limited mixture as well as they summed to the mixture.  taps and os are avsep_true_peak's; w f64 [2A + 1] in DEVICE
+ * memory, w[k + A] = (1 + cos(pi k / (A + 1))) / sum for k = -A .. A (symmetric, sum 1, built by the caller); G = pre_gain,
+ * c = ceiling (linear).  Per programme, float64 throughout:
+ *   1 detector  p[n] = max over the C rows of max(|x[n]|, |u[os*n + q]|, q = 0 .. os-1), u avsep_true_peak's oversampled row
+ *               (one device function serves both: max_n p[n] is bit for bit the programme's largest true peak).
+ *   2 required  r[n] = min(1, c / (G * p[n])) for 0 <= n < L, 1 outside; p = 0 gives 1.
+ *   3 hold      h[j] = min of r over |i - j| <= A, for -A <= j < L + A: the envelope reaches A samples past both ends.
+ *   4 smooth    g[n] = 1 - sum_{k = -A .. A, ascending} w[k + A] * (1 - h[n + k]): an untouched stretch gives exactly 1.
+ *   5 apply     y[row][n] = the f32 nearest to the float64 product x[row][n] * (G * g[n]).
+ * Every h[n + k] is a minimum over a window that holds n, so in exact arithmetic g[n] <= r[n] and |y[n]| <= c: the gain never
+ * rises above what the oversampled detector asks for at n.  (The TRUE peak of y may still pass c a little, because the
+ * modulation moves the inter-sample peaks: the caller measures y and trims.)
+ * y may be x itself.  gain: f64 [P][L] or NULL.  stats f64 [P][3]: max_n p[n] (not scaled by G; +inf when a sample of the
+ * programme is NaN or infinite), min_n g[n], the number of n with g[n] < 1.  No atomics; the reductions are a maximum, a
+ * minimum and a count of integers (order-free) and the sum of step 4 runs in ascending k: a programme gives the same bits
+ * alone, inside a batch and on a second call.  1 <= P <= 65535, 1 <= C <= 64, 1 <= L, os*L < 2^31, os in {1, 2, 4},
+ * 1 <= A <= 2048, pre_gain finite and > 0, 0 < ceiling <= 1.  Anything outside these limits or a null pointer (but gain) is
+ * AVSEP_ERR_ARG before any launch (the workspace query returns 0); ws: the query's bytes, else AVSEP_ERR_WORKSPACE. */
+size_t avsep_limiter_workspace_bytes(int32_t P, int32_t C, int32_t L);
+int avsep_limiter(const float* x, const double* taps, const double* w, int32_t P, int32_t C, int32_t L, int32_t os, int32_t A,
+                  double pre_gain, double ceiling, float* y, double* gain, double* stats, void* ws, size_t ws_bytes,
+                  avsep_stream_t stream);
+
 /* ---- Frames as shot (csrc/frames.hip; avsep_amd/frames.py): uint8 RGB frames [T][H][W][3] -> out f32 [T][3][S][S], bit for bit
  * dataset.VideoTransform: Pillow's 8-bit bicubic resize to (w, h), the crop of S x S at (crop_i, crop_j) of the resized image
  * (rows, columns; either may be negative or reach past the image: pixels outside it are 0), the left-right flip, and
