@@ -1231,6 +1231,46 @@ def heatmap_overlay(maps, frames, table, alpha256):
     return out
 
 
+SPEC_REDUCE = {"max": 0, "mean": 1}
+
+
+def spec_image(mag, mask=None, thres=None, cell=1, reduce="max", log=True, scale=200.0, table=None, out=None):
+    """mag [R,F,T] fp32 (mask: the same shape, or None) -> uint8 [R,F,W,3] with a uint8 [256,3] RGB ``table`` on the device,
+    [R,F,W,1] (the level itself) without; W = ceil(T / cell).  One launch (``avsep_spec_image``, include/avsep.h): per pixel
+    the max / mean over a cell of mag * m, m = 1 | mask > thres | mask, then log10(c + 1) * scale or c * scale, saturated at
+    255 and truncated; image row 0 is the highest frequency row.  out: a dense uint8 tensor of that shape to write into."""
+    if not torch.is_tensor(mag) or mag.dim() != 3 or mag.dtype != torch.float32 or mag.numel() == 0:
+        raise lib.AvsepError(f"spec_image takes a float32 magnitude [R,F,T], got {lib.got(mag)}")
+    if mask is not None and (not torch.is_tensor(mask) or mask.shape != mag.shape or mask.dtype != torch.float32
+                             or mask.device != mag.device):
+        raise lib.AvsepError(f"spec_image: the mask must be float32 {tuple(mag.shape)} beside the magnitude, got {lib.got(mask)}")
+    if thres is not None and (mask is None or thres != thres):
+        raise lib.AvsepError("spec_image: a threshold is a number and needs a mask (None: the mask value itself)")
+    if isinstance(cell, bool) or not isinstance(cell, int) or cell < 1:
+        raise lib.AvsepError(f"spec_image: cell is a whole number of frames >= 1, got {cell!r}")
+    if reduce not in SPEC_REDUCE:
+        raise lib.AvsepError(f"spec_image: reduce is 'max' or 'mean', got {reduce!r}")
+    if not float(scale) == float(scale):
+        raise lib.AvsepError("spec_image: scale is a number")
+    if table is not None and (not torch.is_tensor(table) or tuple(table.shape) != (256, 3) or table.dtype != torch.uint8
+                              or table.device != mag.device):
+        raise lib.AvsepError(f"spec_image: the colour table is uint8 [256,3] beside the magnitude, got {lib.got(table)}")
+    R, F, T = mag.shape
+    shape = (R, F, -(-T // cell), 3 if table is not None else 1)
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.uint8
+                            or out.device != mag.device or not out.is_contiguous()):
+        raise lib.AvsepError(f"spec_image: out must be a dense uint8 {shape} beside the magnitude, got {lib.got(out)}")
+    lib.require_gpu(mag)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=mag.device)
+    mag = mag.contiguous()                               # dense copies of strided views: bound to names that outlive the launch
+    mask = None if mask is None else mask.contiguous()
+    call("avsep_spec_image", ptr(mag), ptr(mask),
+         float("nan") if thres is None else float(thres), R, F, T, cell, SPEC_REDUCE[reduce], int(bool(log)), float(scale),
+         ptr(table), ptr(out))
+    return out
+
+
 def sgd_momentum_(p, g, buf, lr, momentum, weight_decay, grad_scale, first):
     call("avsep_sgd_momentum", ptr(p), ptr(g), ptr(buf), p.numel(), float(lr), float(momentum),
          float(weight_decay), float(grad_scale), int(first))

@@ -105,6 +105,7 @@ SIGNATURES = {
     "avsep_misi": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "avsep_localise_maps": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avsep_heatmap_overlay": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "avsep_spec_image": (C.c_int, [_P, _P, _F, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "avsep_resample_poly": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_resample_split": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "avsep_resample_join": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -542,6 +542,11 @@ def build_parser():
     p.add_argument("--frame_offset", type=float, default=0.0, help="time of the first video frame, seconds from the WAV's start")
     p.add_argument("--maps", action="store_true", help="also write the attention map of every window and source to <out>/maps.npy "
                                                        "(needs the spatial visual features of --not_pool_vis)")
+    p.add_argument("--report", action="store_true",
+                   help="also write <out>/report.html with mix.png, source<n>.png (mask x mixture magnitude) and mask<n>.png, "
+                        "rendered on the GPU (needs Pillow)")
+    p.add_argument("--report_width", type=int, default=2048, metavar="PX",
+                   help="with --report: the pictures are at most PX pixels wide; ceil(frames / PX) STFT frames share a column")
     p.add_argument("--out", default="separated", help="output directory (source<n>.wav)")
     p.add_argument("--audio_only", action="store_true", help="no frames: audio-only branch with aligned windows")
     p.add_argument("--window_stride", type=int, default=128, help="STFT frames between window starts (<= 256)")
@@ -576,6 +581,8 @@ def parse_args(argv=None):
         raise SystemExit(f"--wiener_span takes 0 or a multiple of 64 frames in {K.MWF_MIN_SPAN} ... {K.MWF_MAX_SPAN}, got {args.wiener_span}")
     if args.wiener_span and not args.wiener:
         raise SystemExit("--wiener_span is the span of the Wiener filter's covariances: it needs --wiener K with K >= 1")
+    if args.report_width < 1:
+        raise SystemExit(f"--report_width takes a positive number of pixels, got {args.report_width}")
     if args.band == "full" and args.out_rate == "model":
         raise SystemExit("--band full adds what the file holds above the model's band: it cannot be written at --out_rate model")
     if args.peak is not None and not args.peak <= 0.0:
@@ -723,7 +730,7 @@ def cli(argv=None):
                         stride_frames=args.window_stride, batch=args.window_batch, channels=channels, wiener=args.wiener,
                         phase_iters=args.phase_iters, clamp=not (levelled or full), wiener_span=args.wiener_span,
                         **({"band_gains": True} if full else {}), **({"frame_times": times} if times is not None else {}),
-                        **({"return_maps": True} if args.maps else {}))
+                        **({"return_maps": True} if args.maps else {}), **({"return_masks": True} if args.report else {}))
     os.makedirs(args.out, exist_ok=True)
     if args.maps:
         np.save(os.path.join(args.out, "maps.npy"), out["maps"].cpu().numpy())
@@ -756,6 +763,9 @@ def cli(argv=None):
         if levelled or full:                         # written from the rows; else from the model-rate stems, resampled by the join
             stems, rate_in = rows, out_rate
     write_stems(args.out, stems, rate_in, out_rate, out_fmt)
+    if args.report:                                  # after the stems: the page offers them beside their pictures
+        from . import visuals
+        visuals.report(args.out, wav, out["lin_masks"], args, args.report_width, title=os.path.basename(args.wav))
     if report is not None:
         import json
         with open(os.path.join(args.out, "levels.json"), "w") as f:

@@ -15,7 +15,8 @@ Same flags, same schedule and same bookkeeping as the reference:
 
 Different on purpose: one process per GPU (torch.distributed + RCCL; each rank draws its own shard of every global
 batch) instead of nn.DataParallel; batches carry waveforms and the STFT runs on the GPU; the metrics (SI-SDR and
-BSS-eval SDR / SIR / SAR, evaluate.py + bss_eval.py) are computed on the device; no HTML visualisation.
+BSS-eval SDR / SIR / SAR, evaluate.py + bss_eval.py) are computed on the device; the HTML visualisation of the first
+`--num_vis` validation items is off unless `--visuals` is passed (visuals.py: images rendered on the GPU, no videos).
 """
 import os
 import random
@@ -58,18 +59,27 @@ def new_history():
 
 
 def evaluate(wrapper, loader, history, itera, args, use_vis, device, world=1):
-    """main.py:421-503 without the visualisation: mean loss / match loss / SI-SDR / SDR over the validation list."""
+    """main.py:421-503: mean loss / match loss / SI-SDR / SDR over the validation list.  With args.vis (--visuals) rank 0
+    also writes the pictures, sounds and page of its first args.num_vis items under args.vis/av or args.vis/ao (visuals.py)."""
     print("Evaluating at {} iterations...".format(itera))
     wrapper.eval()
+    rank = torch.distributed.get_rank() if world > 1 and torch.distributed.is_initialized() else 0
+    vis_rows = [] if getattr(args, "vis", None) and rank == 0 else None
     tot = torch.zeros(7, dtype=torch.float64, device=device)      # loss, match, si_sdr, sdr, sir, sar, batches
     with torch.no_grad():
         for host in loader:
             batch = dataset.to_device(host, device)
             err, outputs = wrapper.forward(batch, args, use_vis)
             m = ev.calc_metrics(batch, outputs, args, wrapper.stft_plan)
+            if vis_rows is not None and len(vis_rows) < args.num_vis:
+                from . import visuals
+                visuals.output_visuals(vis_rows, batch, outputs, args, m, use_vis, wrapper.stft_plan)
             match = outputs["match_loss"].mean() if use_vis else err.new_zeros(())
             tot += torch.stack([err.mean().double(), match.double(), m["si_sdr_mean"].double(), m["sdr_mean"].double(),
                                 m["sir_mean"].double(), m["sar_mean"].double(), tot.new_ones(())])
+    if vis_rows is not None:
+        from . import visuals
+        print("Visualisation: {}".format(visuals.write_index(vis_rows, args, use_vis)))
     if world > 1:
         import torch.distributed as dist
         dist.all_reduce(tot)
@@ -207,6 +217,9 @@ def own_flags(argv=None):
     own = argparse.ArgumentParser(add_help=False)
     own.add_argument("--gpu_frames", action="store_true",
                      help="loader workers decode only; resize, crop, flip and normalisation run on the GPU, one launch per batch")
+    own.add_argument("--visuals", action="store_true",
+                     help="every evaluation also writes the pictures, sounds and index.html of its first --num_vis validation "
+                          "items under <ckpt>/<id>/visualization/av and .../ao (needs Pillow)")
     return own.parse_known_args(argv)
 
 
@@ -216,6 +229,8 @@ def cli(argv=None):
     args.gpu_frames = own.gpu_frames
     print("Model ID: {}".format(args.id))
     args.ckpt = os.path.join(args.ckpt, args.id)                   # main.py:776-791
+    if own.visuals:
+        args.vis = os.path.join(args.ckpt, "visualization")
     three_stage = getattr(args, "train_steps", None) is not None
     paths = None
     if args.mode == "train":

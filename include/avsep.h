@@ -586,6 +586,32 @@ int avsep_heatmap_overlay(const float* maps, const float* const* frames, const u
                           int32_t w, int32_t H, int32_t W, int32_t alpha256, uint8_t* out, avsep_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Evaluation visuals (csrc/visuals.hip): the spectrogram, weight and mask images of a whole batch as image bytes.
+ * ------------------------------------------------------------------------- */
+/* One launch for R images (replaces, per image, utils.py:90-98 magnitude2heatmap, the mask product of main.py:367-369, the
+ * clip of main.py:375-376 and the [::-1] row flips of main.py:358-386, all NumPy / OpenCV on the host).
+ * mag: [R, F, T] fp32; mask_or_null: [R, F, T] fp32; thres: a NaN means "no threshold"; cell >= 1 frames per image column;
+ * reduce: 0 max / 1 mean; log: 0 / 1; table_or_null: 256 x 3 uint8 RGB colours on the device.
+ * out: uint8 [R, F, W, ch], W = ceil(T / cell), ch = 3 with a table and 1 (the level itself) without.  Per pixel (r, f, w):
+ *   1. the source row is F - 1 - f: low frequencies end up at the bottom of the picture.
+ *   2. over the frames t in [w*cell, min((w+1)*cell, T)): p = mag[t] * m(t), ONE fp32 multiply, with m = 1 without a mask,
+ *      (mask > thres ? 1 : 0) with a threshold, the mask value without one.
+ *   3. c = max of p (a NaN stays, as in numpy.max), or the mean: an fp32 sum in a fixed order divided by the number of frames
+ *      actually in the cell.  The order is the frame order for cell <= 32; beyond that lane l of a wave sums frames l, l + 64,
+ *      ... in that order and the 64 lane sums meet in a butterfly (xor 32, 16, ... 1).
+ *   4. v = log ? log10f(c + 1) * scale : c * scale;  level = v > 255 ? 255 : trunc(v); a negative v and a NaN give level 0
+ *      (the reference's astype(uint8) would wrap them).
+ *   5. the pixel is table[level], or level.
+ * cell = 1, log = 1, scale = 200 with the JET table is magnitude2heatmap followed by the BGR->RGB and row flips; log = 0,
+ * scale = 100 the weight image; log = 0, scale = 255 without a table is clip(mask, 0, 1) * 255 truncated.
+ * No atomics; a second call gives the same bytes.  Every offset is formed in 64 bits; the work is strided over a bounded
+ * grid.  A null mag / out, R, F or T <= 0, cell < 1, reduce or log outside {0, 1} and R * F > 2^31 - 1 are AVSEP_ERR_ARG
+ * before any launch. */
+int avsep_spec_image(const float* mag, const float* mask_or_null, float thres, int32_t R, int32_t F, int32_t T, int32_t cell,
+                     int32_t reduce, int32_t log, float scale, const uint8_t* table_or_null, uint8_t* out,
+                     avsep_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Sample-rate conversion (csrc/resample.hip): a rational polyphase FIR resampler, so that a WAV file at any rate goes in
  * and the separated sources come out at the file's own rate.  up = rate_out / g, down = rate_in / g, g = gcd; both in
  * [1, 1280] (8 ... 96 kHz to and from 11 025 Hz; the worst cases are 441/1280 and 147/1280).
