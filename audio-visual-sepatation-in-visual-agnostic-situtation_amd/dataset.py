@@ -122,10 +122,13 @@ class VideoTransform:
 # ------------------------------------------------------------------------------------------ dataset
 class MUSICMixDataset(torch.utils.data.Dataset):
     def __init__(self, csv_path, params, split="val", debug=False, seed=None, random_sample=False, vis_data=False,
-                 raw_frames=False):
+                 raw_frames=False, jpeg_bytes=False):
         p = params
         self.debug = debug
         self.raw_frames = bool(raw_frames)     # items carry the decoded uint8 frames and the draws: to_device prepares them on the GPU
+        self.jpeg_bytes = bool(jpeg_bytes)     # ... the files' bytes instead of the decoded frames: to_device decodes them too (jpeg.decode)
+        if self.jpeg_bytes and not self.raw_frames:
+            raise ValueError("MUSICMixDataset(jpeg_bytes=True) is a form of raw_frames=True: pass both")
         self.num_frames, self.imgSize, self.stride_frames = p["num_frames"], p["imgSize"], p["stride_frames"]
         self.one_frame = p["one_frame"]
         if p.get("load_clips"):
@@ -271,12 +274,41 @@ class MUSICMixDataset(torch.utils.data.Dataset):
         pixels = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays]))
         return pixels, torch.tensor([a.shape[:2] for a in arrays], dtype=torch.int32), crop, flip
 
+    def _load_jpeg_frames(self, paths):
+        """The clip as it lies in its files, with the same draws in the same order -> (uint8 [bytes]: the files back to back,
+        int64 [T] their lengths, int32 [T,2] the frames' (H, W), crop, flip, [(t, uint8 pixels [H*W*3])] for the files the GPU
+        decoder refuses (jpeg.probe), decoded here as ``_open_frames`` decodes them)."""
+        from . import jpeg
+        files, shapes, fallback = [], [], []
+        for t, path in enumerate(paths):
+            with open(path, "rb") as f:
+                files.append(f.read())
+            try:
+                info = jpeg.probe(files[-1])
+                shapes.append((info.H, info.W))
+            except jpeg.Unsupported:
+                a = np.asarray(self._open_frames([path])[0], dtype=np.uint8)
+                shapes.append(a.shape[:2])
+                fallback.append((t, torch.from_numpy(a.reshape(-1).copy())))
+        H, W = shapes[0]
+        crop, flip = draw_crop_flip(*self.vid_transform.resized_size(W, H), self.imgSize, self.vid_transform.train)
+        data = torch.from_numpy(np.frombuffer(b"".join(files), dtype=np.uint8).copy())
+        return (data, torch.tensor([len(f) for f in files], dtype=torch.int64), torch.tensor(shapes, dtype=torch.int32), crop, flip,
+                fallback)
+
+    def _load_raw(self, paths):
+        """One clip of a raw item, in one form for both kinds: (data, lengths | None, shapes, crop, flip, fallback)."""
+        if self.jpeg_bytes:
+            return self._load_jpeg_frames(paths)
+        pixels, shapes, crop, flip = self._load_raw_frames(paths)
+        return pixels, None, shapes, crop, flip, []
+
     def get_frames(self, infos, center_times):
         frames, shifts = [], []
         for n in range(self.num_mix):
             paths, center_idx = self.frame_paths(infos[n], center_times[n])
             shifts.append(center_times[n] - center_idx / float(infos[n][3]))
-            frames.append(self._load_raw_frames(paths) if self.raw_frames else self._load_frames(paths))
+            frames.append(self._load_raw(paths) if self.raw_frames else self._load_frames(paths))
         return frames, shifts
 
     # ---- music.py:240-252
@@ -299,9 +331,11 @@ class MUSICMixDataset(torch.utils.data.Dataset):
             item["frames"] = frames
             return item
         # per source: the decoded pixels, the frames' shapes and the clip's draws (RAW_KEYS); no "frames" until to_device
-        item.update({"frames_u8": [f[0] for f in frames], "frame_shapes": [f[1] for f in frames],
-                     "frame_crops": [f[2] for f in frames], "frame_flips": [f[3] for f in frames],
+        item.update({"frames_jpeg" if self.jpeg_bytes else "frames_u8": [f[0] for f in frames], "frame_shapes": [f[2] for f in frames],
+                     "frame_crops": [f[3] for f in frames], "frame_flips": [f[4] for f in frames],
                      "imgSize": self.imgSize, "split": self.split})
+        if self.jpeg_bytes:
+            item.update({"frame_bytes": [f[1] for f in frames], "frames_fallback": [f[5] for f in frames]})
         return item
 
 
@@ -322,22 +356,53 @@ def collate(samples):
       "frame_crops"   int32 [N,B,2]: the clips' drawn corners (i, j), or None in the validation form (every frame its centre);
       "frame_flips"   bool [N,B];
       "imgSize" int and "split" str, as the dataset has them.
+    A batch of MUSICMixDataset(raw_frames=True, jpeg_bytes=True) has, instead of "frames_u8":
+      "frames_jpeg"    uint8 [bytes]: every frame's file back to back, in the same order;
+      "frame_bytes"    int64 [N,B,T]: the files' lengths;
+      "fallback_index" int64 [k] and "fallback_u8" uint8 [bytes]: the frames (n * B + b) * T + t whose files the GPU decoder
+                       refuses, ascending, and their pixels [H,W,3] as the worker decoded them, back to back.
     ``to_device`` turns these into "frames"."""
     N = len(samples[0]["audios"])
     out = {"audios": [_stack([s["audios"][n] for s in samples]) for n in range(N)],
            "audio_mix": _stack([s["audio_mix"] for s in samples]),
            "id": [s["id"] for s in samples], "class": torch.stack([s["class"] for s in samples], 0),
            "infos": [[[s["infos"][n][k] for s in samples] for k in range(len(samples[0]["infos"][n]))] for n in range(N)]}
-    if "frames_u8" not in samples[0]:
+    if "frames_u8" not in samples[0] and "frames_jpeg" not in samples[0]:
         out["frames"] = [_stack([s["frames"][n] for s in samples]) for n in range(N)]
         return out
-    out["frames_u8"] = torch.cat([s["frames_u8"][n] for n in range(N) for s in samples])
+    if "frames_jpeg" in samples[0]:
+        out["frames_jpeg"] = torch.cat([s["frames_jpeg"][n] for n in range(N) for s in samples])
+        out["frame_bytes"] = torch.stack([torch.stack([s["frame_bytes"][n] for s in samples]) for n in range(N)])
+        B, T = len(samples), out["frame_bytes"].shape[2]
+        late = [((n * B + b) * T + t, px) for n in range(N) for b, s in enumerate(samples) for t, px in s["frames_fallback"][n]]
+        out["fallback_index"] = torch.tensor([i for i, _ in late], dtype=torch.int64)
+        out["fallback_u8"] = torch.cat([px for _, px in late]) if late else torch.zeros(0, dtype=torch.uint8)
+    else:
+        out["frames_u8"] = torch.cat([s["frames_u8"][n] for n in range(N) for s in samples])
     out["frame_shapes"] = torch.stack([torch.stack([s["frame_shapes"][n] for s in samples]) for n in range(N)])
     crops = [[s["frame_crops"][n] for s in samples] for n in range(N)]
     out["frame_crops"] = None if crops[0][0] is None else torch.tensor(crops, dtype=torch.int32)
     out["frame_flips"] = torch.tensor([[s["frame_flips"][n] for s in samples] for n in range(N)], dtype=torch.bool)
     out["imgSize"], out["split"] = samples[0]["imgSize"], samples[0]["split"]
     return out
+
+
+def _decode_jpeg(batch, device):
+    """The pixel buffer of a batch of files: decoded on the GPU (jpeg.decode), the workers' fallback pixels dropped into their
+    slots -> uint8 [bytes] on the device, what "frames_u8" holds in a batch without jpeg_bytes."""
+    from . import jpeg
+    data, ends = batch["frames_jpeg"].numpy(), np.cumsum(batch["frame_bytes"].reshape(-1).numpy())
+    files = [data[a:b].tobytes() for a, b in zip(np.concatenate([[0], ends[:-1]]), ends)]
+    shapes = batch["frame_shapes"].reshape(-1, 2).tolist()
+    decoded, at = {}, 0
+    for i in batch["fallback_index"].tolist():
+        n = shapes[i][0] * shapes[i][1] * 3
+        decoded[i] = batch["fallback_u8"][at:at + n].numpy().reshape(shapes[i][0], shapes[i][1], 3)
+        at += n
+    pixels, got = jpeg.decode(files, device, decoded=decoded)
+    if [list(s) for s in got] != shapes:
+        raise ValueError("the frames' sizes changed between the workers' probe and the decode")
+    return pixels
 
 
 def _prepare_raw(batch, device):
@@ -349,7 +414,11 @@ def _prepare_raw(batch, device):
     plan = F.plan_batch(batch["frame_shapes"].reshape(-1, 2).tolist(), batch["imgSize"], train=train,
                         crops=[c for c in per_clip for _ in range(T)],
                         flips=[f for f in batch["frame_flips"].reshape(-1).tolist() for _ in range(T)], layout=(N * B, T))
-    out = F.prepare_batch(batch["frames_u8"].to(device, non_blocking=True), plan)
+    if "frames_jpeg" in batch:
+        pixels = _decode_jpeg(batch, device)
+    else:
+        pixels = batch["frames_u8"].to(device, non_blocking=True)
+    out = F.prepare_batch(pixels, plan)
     return list(out.view(N, B, 3, T, plan.img_size, plan.img_size).unbind(0))
 
 
@@ -360,7 +429,7 @@ def to_device(batch, device):
     mv = lambda t: t.to(device, non_blocking=True)      # noqa: E731
     out = dict(batch)
     out["audios"] = [mv(t) for t in batch["audios"]]
-    out["frames"] = _prepare_raw(batch, device) if "frames_u8" in batch else [mv(t) for t in batch["frames"]]
+    out["frames"] = _prepare_raw(batch, device) if "frames_u8" in batch or "frames_jpeg" in batch else [mv(t) for t in batch["frames"]]
     out["audio_mix"] = mv(batch["audio_mix"])
     return out
 

@@ -1194,6 +1194,53 @@ def frames_prepare_batch(pixels, rows, tables, lut, S, out, plane, grid_y, lds_b
     return out
 
 
+def jpeg_plan_check(images, segments, nbytes, table_words, pixel_bytes, ws_blocks):
+    """avsep_jpeg_plan_check (include/avsep.h; host only, no GPU): images and segments = NumPy arrays of dtype
+    np.dtype(lib.JpegImage) and np.dtype(lib.JpegSegment), the rows of one chunk.  AvsepError for anything the library refuses."""
+    images, segments = np.ascontiguousarray(images), np.ascontiguousarray(segments)
+    rc = lib.load().avsep_jpeg_plan_check(images.ctypes.data, len(images), segments.ctypes.data, len(segments), int(nbytes),
+                                          int(table_words), int(pixel_bytes), int(ws_blocks))
+    if rc != 0:
+        raise lib.AvsepError(f"avsep_jpeg_plan_check refused {len(images)} images in {len(segments)} segments: a size, sampling "
+                             f"form or MCU count outside the limits, or a byte, block, table or pixel range outside its buffer ({rc})")
+
+
+def _jpeg_buffers(who, first, typed):
+    lib.require_gpu(first)
+    for t, dtype in typed:
+        if not torch.is_tensor(t) or t.dtype != dtype or t.device != first.device or not t.is_contiguous() or t.dim() != 1:
+            raise lib.AvsepError(f"{who}: a buffer must be {dtype} [n], contiguous, on {first.device}, got {lib.got(t)}")
+
+
+def jpeg_entropy(data, images, segments, tables, coef, ws_blocks, status):
+    """avsep_jpeg_entropy (include/avsep.h): data uint8 [bytes], images / segments uint8 (the checked rows of one chunk), tables
+    int32 [words], coef int16 [>= 64 * ws_blocks], status int32 [images] (zeroed), all on one GPU.  coef[:64 * ws_blocks] is
+    zeroed and filled; a lane that stops sets its image's status word."""
+    _jpeg_buffers("jpeg_entropy", data, ((data, torch.uint8), (images, torch.uint8), (segments, torch.uint8), (tables, torch.int32),
+                                         (coef, torch.int16), (status, torch.int32)))
+    n, ns = images.numel() // C.sizeof(lib.JpegImage), segments.numel() // C.sizeof(lib.JpegSegment)
+    if images.numel() != n * C.sizeof(lib.JpegImage) or segments.numel() != ns * C.sizeof(lib.JpegSegment) or status.numel() != n \
+            or coef.numel() < 64 * int(ws_blocks):
+        raise lib.AvsepError(f"jpeg_entropy: {images.numel()} bytes of image rows, {segments.numel()} of segment rows, "
+                             f"{status.numel()} status words, {coef.numel()} coefficients for {ws_blocks} blocks")
+    call("avsep_jpeg_entropy", ptr(data), data.numel(), ptr(images), n, ptr(segments), ns, ptr(tables), tables.numel(), ptr(coef),
+         int(ws_blocks), ptr(status))
+
+
+def jpeg_pixels(coef, planes, ws_blocks, images, max_blocks, max_pixels, tables, status, pixels):
+    """avsep_jpeg_pixels (include/avsep.h): the coefficients of one chunk -> planes uint8 [>= 64 * ws_blocks] -> the chunk's
+    frames in pixels uint8 [bytes]; images whose status word is set are skipped."""
+    _jpeg_buffers("jpeg_pixels", coef, ((coef, torch.int16), (planes, torch.uint8), (images, torch.uint8), (tables, torch.int32),
+                                        (status, torch.int32), (pixels, torch.uint8)))
+    n = images.numel() // C.sizeof(lib.JpegImage)
+    if images.numel() != n * C.sizeof(lib.JpegImage) or status.numel() != n or coef.numel() < 64 * int(ws_blocks) \
+            or planes.numel() < 64 * int(ws_blocks):
+        raise lib.AvsepError(f"jpeg_pixels: {images.numel()} bytes of image rows, {status.numel()} status words, {coef.numel()} "
+                             f"coefficients and {planes.numel()} plane bytes for {ws_blocks} blocks")
+    call("avsep_jpeg_pixels", ptr(coef), ptr(planes), int(ws_blocks), ptr(images), n, int(max_blocks), int(max_pixels), ptr(tables),
+         tables.numel(), ptr(status), ptr(pixels), pixels.numel())
+
+
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 

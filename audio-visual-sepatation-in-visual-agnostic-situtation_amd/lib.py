@@ -50,6 +50,18 @@ class FramesRow(C.Structure):
                                         "reserved".split()]
 
 
+class JpegImage(C.Structure):
+    """avsep_jpeg_image (include/avsep.h): one image of avsep_jpeg_entropy / avsep_jpeg_pixels; np.dtype(JpegImage) is the
+    layout of a table of rows on the host and on the device."""
+    _fields_ = [("pix_off", C.c_int64), ("block0", C.c_int64)] + [(n, C.c_int32) for n in "H W ncomp hs vs mcux mcuy".split()] + \
+               [(n, C.c_int32 * 3) for n in "quant dc ac".split()] + [("restart", C.c_int32), ("reserved", C.c_int32)]
+
+
+class JpegSegment(C.Structure):
+    """avsep_jpeg_segment (include/avsep.h): one entropy-coded segment."""
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64)] + [(n, C.c_int32) for n in "image mcu0 mcus reserved".split()]
+
+
 _P, _I, _F, _D, _Z = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t
 _CD, _KD = C.POINTER(ConvDesc), C.POINTER(CatDesc)
 _L = C.c_int64
@@ -120,6 +132,9 @@ SIGNATURES = {
     "avsep_frames_prepare": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avsep_frames_batch_plan": (C.c_int, [C.POINTER(FramesRow), _I, _I, _L, _L, _L, _L, C.POINTER(C.c_int32)]),
     "avsep_frames_prepare_batch": (C.c_int, [_P, _L, _P, _I, _P, _L, _I, _P, _P, _L, _L, _I, _I, _P]),
+    "avsep_jpeg_plan_check": (C.c_int, [_P, _I, _P, _I, _L, _L, _L, _L]),
+    "avsep_jpeg_entropy": (C.c_int, [_P, _L, _P, _I, _P, _I, _P, _L, _P, _L, _P, _P]),
+    "avsep_jpeg_pixels": (C.c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _L, _P, _P, _L, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

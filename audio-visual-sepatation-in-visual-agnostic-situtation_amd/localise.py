@@ -140,6 +140,9 @@ def build_parser():
                    help="one .npy [T,3,H,W] (normalised floats) per source; ONE file with --num_mix 2 is a duet.  Frames as shot: "
                         "a uint8 .npy [T,H,W,3], or a folder of .jpg / .png files in name order, prepared on the GPU at --imgSize")
     p.add_argument("--fps", type=float, required=True, help="video frames per second of the .npy stacks")
+    p.add_argument("--gpu_decode", action="store_true",
+                   help="decode the .jpg / .jpeg files of a --frames folder on the GPU (baseline JPEGs; anything else, .png included, "
+                        "is read through Pillow as without the flag): the same pixels, without the one-core decode")
     p.add_argument("--frame_offset", type=float, default=0.0, help="time of the first video frame, seconds from the WAV's start")
     p.add_argument("--out", default="localised", help="output directory (maps.npy, overlay_source<c>.npy)")
     p.add_argument("--png", action="store_true", help="also write one PNG per frame and source (needs Pillow)")
@@ -171,7 +174,7 @@ def cli(argv=None):
     dev = wav.device
     nets = load_nets(args, dev)
     from . import frames as FR
-    frames = [fr.to(dev) if is_shot(fr) else fr.float().to(dev) for fr in (FR.load_stack(path) for path in args.frames)]
+    frames = [fr.to(dev) if is_shot(fr) else fr.float().to(dev) for fr in (FR.load_stack(path, dev if args.gpu_decode else None) for path in args.frames)]
     times = args.frame_offset + torch.arange(frames[0].shape[0], dtype=torch.float64) / args.fps
     out = localise(nets, wav, frames, times, args, stride_frames=args.window_stride,
                    batch=args.window_batch, alpha=args.alpha)

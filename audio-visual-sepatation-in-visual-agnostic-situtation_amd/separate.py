@@ -537,6 +537,9 @@ def build_parser():
                                                            "stack [T,3,H,W], and ONE stack with --num_mix 2 is a duet.  Frames as "
                                                            "shot: a uint8 .npy [H,W,3] or [T,H,W,3], or a folder of .jpg / .png "
                                                            "files in name order, prepared on the GPU at --imgSize")
+    p.add_argument("--gpu_decode", action="store_true",
+                   help="decode the .jpg / .jpeg files of a --frames folder on the GPU (baseline JPEGs; anything else, .png included, "
+                        "is read through Pillow as without the flag): the same pixels, without the one-core decode")
     p.add_argument("--fps", type=float, default=None, help="video frames per second of the .npy stacks (needs the spatial visual "
                                                            "features of --not_pool_vis)")
     p.add_argument("--frame_offset", type=float, default=0.0, help="time of the first video frame, seconds from the WAV's start")
@@ -714,7 +717,7 @@ def cli(argv=None):
     frames, times = [], None
     from . import frames as FR
     for path in args.frames:
-        fr = FR.load_stack(path)                     # uint8 [T,H,W,3]: frames as shot, prepared on the GPU batch by batch
+        fr = FR.load_stack(path, dev if args.gpu_decode else None)       # uint8 [T,H,W,3]: frames as shot, prepared on the GPU batch by batch
         if not is_shot(fr):
             fr = fr.float()
         if args.fps is not None:                     # a clip stays on the host: the trunk takes it up batch by batch

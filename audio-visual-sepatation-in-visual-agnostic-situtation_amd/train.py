@@ -132,7 +132,10 @@ def main(args):
     torch.manual_seed(args.seed + 1 + rank)                        # rank-local data order and AO swaps
 
     # --gpu_frames: the workers hand the frames as decoded and to_device prepares them in one launch (frames.prepare_batch)
+    # --gpu_decode with it: they hand the files' bytes, and to_device decodes them first (jpeg.decode)
     raw = {"raw_frames": True} if getattr(args, "gpu_frames", False) else {}
+    if getattr(args, "gpu_decode", False):
+        raw["jpeg_bytes"] = True
     loader_val = dataset.make_loader(args.list_val, args, "val", args.batch_size, False, workers=min(4, args.workers), **raw)
     history = new_history()
     start_i = 0
@@ -217,6 +220,9 @@ def own_flags(argv=None):
     own = argparse.ArgumentParser(add_help=False)
     own.add_argument("--gpu_frames", action="store_true",
                      help="loader workers decode only; resize, crop, flip and normalisation run on the GPU, one launch per batch")
+    own.add_argument("--gpu_decode", action="store_true",
+                     help="with --gpu_frames: the workers read the frame files and do not decode them; baseline JPEGs are decoded on "
+                          "the GPU, bit for bit Pillow's pixels (anything else is decoded by Pillow in the worker, as without it)")
     own.add_argument("--visuals", action="store_true",
                      help="every evaluation also writes the pictures, sounds and index.html of its first --num_vis validation "
                           "items under <ckpt>/<id>/visualization/av and .../ao (needs Pillow)")
@@ -226,7 +232,9 @@ def own_flags(argv=None):
 def cli(argv=None):
     own, argv = own_flags(argv)
     args = ArgParser().parse_train_arguments(argv)
-    args.gpu_frames = own.gpu_frames
+    args.gpu_frames, args.gpu_decode = own.gpu_frames, own.gpu_decode
+    if own.gpu_decode and not own.gpu_frames:
+        raise SystemExit("--gpu_decode is a form of --gpu_frames: pass both")
     print("Model ID: {}".format(args.id))
     args.ckpt = os.path.join(args.ckpt, args.id)                   # main.py:776-791
     if own.visuals:

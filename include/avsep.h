@@ -816,6 +816,58 @@ int avsep_frames_prepare_batch(const uint8_t* pixels, int64_t pixel_bytes, const
                                const int32_t* tables, int64_t table_words, int32_t S, const float* lut, float* out,
                                int64_t out_floats, int64_t plane, int32_t grid_y, int32_t lds_bytes, avsep_stream_t stream);
 
+/* ---- Baseline JPEG frames (csrc/jpeg.hip, csrc/jpeg_parts.h; avsep_amd/jpeg.py): SOF0, 8 bit, Huffman, one interleaved scan,
+ * grey or YCbCr with luma sampling 1x1, 2x1 or 2x2 -> uint8 RGB [H][W][3], bit for bit libjpeg-turbo's default decoder (islow
+ * inverse DCT, fancy upsampling), which is what Pillow gives.  The host reads the markers and hands over, in DEVICE memory,
+ *   bytes  uint8 [nbytes]: the entropy-coded bytes of the images back to back (stuffed FF 00 still in them);
+ *   tables int32 [table_words]: quantisation tables (64 words, NATURAL order) and Huffman tables (546 words: look[256] =
+ *     (length << 8) | value by the next 8 bits, 0 = a longer code; maxcode[17] by length, -1 = none; valoff[17], a code's value
+ *     is values[valoff[length] + code]; values[256]) anywhere in it, shared by the images that have them;
+ *   one row per image and one per entropy-coded segment (a file without restart intervals is one segment): */
+typedef struct avsep_jpeg_image {
+  int64_t pix_off;                          /* the image's first byte in `pixels` */
+  int64_t block0;                           /* its first block in the coefficient workspace (64 int16 per block) */
+  int32_t H, W, ncomp;                      /* 1 <= H, W <= 16384; ncomp 1 | 3 */
+  int32_t hs, vs;                           /* luma sampling: (1,1), (2,1) or (2,2); (1,1) with one component */
+  int32_t mcux, mcuy;                       /* MCUs across and down: ceil(W / (8 hs)), ceil(H / (8 vs)) */
+  int32_t quant[3], dc[3], ac[3];           /* word offsets in `tables`, per component */
+  int32_t restart;                          /* MCUs per restart interval, 0 = none */
+  int32_t reserved;
+} avsep_jpeg_image;
+typedef struct avsep_jpeg_segment {
+  int64_t begin, end;                       /* its bytes: bytes[begin .. end) */
+  int32_t image;                            /* row of `images` */
+  int32_t mcu0, mcus;                       /* first MCU and MCU count */
+  int32_t reserved;
+} avsep_jpeg_segment;
+/* An image's blocks lie component after component, each [blocks down][blocks across], the luma plane mcuy*vs x mcux*hs blocks
+ * and each chroma plane mcuy x mcux; a block is 64 coefficients in natural order.
+ * avsep_jpeg_plan_check (host only, nothing is launched): every HOST row against the limits above and against the buffer
+ *   sizes: pixel range inside pixel_bytes, blocks inside ws_blocks, tables inside table_words, segment bytes inside nbytes,
+ *   segment MCUs inside the image and matching its restart interval.  AVSEP_ERR_ARG on the first row that fails.
+ * avsep_jpeg_entropy: zeroes coef[0 .. 64 ws_blocks) and decodes one segment per lane into it.  A lane trusts neither the
+ *   rows nor the stream: a read outside [begin, end) (status bit 1), no code within 16 bits (2), a DC size above 11 (4), a
+ *   coefficient index past 63 (8), a marker inside the segment (16), a block outside the segment's blocks (32), a table outside
+ *   `tables` (64), |coefficient x quantiser| above AVSEP_JPEG_MAX_COEF (128), a row outside its limits (256) or bytes left over
+ *   after the last block (512) stops the lane and ORs the bit into status[image]; no check reads or writes out of range.
+ *   status: int32 [n_images], zeroed by the caller.  Every segment gets a wavefront of its own: lanes of one wavefront that
+ *   walk different streams pay for each other's branches (DESIGN §32 has the measurement).
+ * avsep_jpeg_pixels: coefficients -> planes (uint8, 64 per block, the workspace's block order) -> pixels.  Images whose status
+ *   is not 0 are skipped: their pixels are left as they were.  max_blocks, max_pixels: the most any one image has (the grids).
+ * AVSEP_JPEG_MAX_COEF: below it no value of either inverse DCT pass can leave int32; equality with the int64
+ *   recipe is claimed up to it, and with libjpeg-turbo for what an encoder makes of 8-bit pixels.
+ * A null pointer, a count < 1, a size < 1, or coef or planes off a 16-byte boundary in avsep_jpeg_pixels (its lanes move whole
+ * rows of a block) is AVSEP_ERR_ARG before any launch. */
+#define AVSEP_JPEG_MAX_COEF 1173
+int avsep_jpeg_plan_check(const avsep_jpeg_image* images, int32_t n_images, const avsep_jpeg_segment* segments, int32_t n_segments,
+                          int64_t nbytes, int64_t table_words, int64_t pixel_bytes, int64_t ws_blocks);
+int avsep_jpeg_entropy(const uint8_t* bytes, int64_t nbytes, const avsep_jpeg_image* images, int32_t n_images,
+                       const avsep_jpeg_segment* segments, int32_t n_segments, const int32_t* tables, int64_t table_words,
+                       int16_t* coef, int64_t ws_blocks, int32_t* status, avsep_stream_t stream);
+int avsep_jpeg_pixels(const int16_t* coef, uint8_t* planes, int64_t ws_blocks, const avsep_jpeg_image* images, int32_t n_images,
+                      int32_t max_blocks, int32_t max_pixels, const int32_t* tables, int64_t table_words, const int32_t* status,
+                      uint8_t* pixels, int64_t pixel_bytes, avsep_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles

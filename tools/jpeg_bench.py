@@ -1,0 +1,216 @@
+"""The GPU JPEG decoder (csrc/jpeg.hip, avsep_amd/jpeg.py) on cuda:0, beside Pillow on one core.  The files are made here with
+Pillow from seeded synthetic pictures (nothing is downloaded): 360 x 640, 4:2:0, quality 75, without restart intervals, as ffmpeg
+writes the MUSIC frames.
+
+  (a) one loader batch, --files (384) files in one plan: jpeg.plan on the host, the upload of bytes, rows and tables, the entropy
+      stage and the pixel stage, each between device events (median of --reps after warm-up), per batch and per frame; the
+      result checked against Pillow on --check files;
+  (b) Pillow (Image.open(..).convert("RGB")) on one CPU core over --cpu-files of the same files, per file;
+  (c) one clip, --clip (4 800) files (the batch's files repeated in order): jpeg.decode end to end (plan, upload, every chunk, the
+      status read), a host clock around a device synchronise;
+  (d) the loader at the train_MUSIC shape (tools/loader_bench.py's dataset): ds[i] on one core, to_device of a batch and the
+      one-worker loader rate, for --gpu_frames alone (the parent commit's path, unchanged) and with --gpu_decode, in the same run.
+Prints each figure as it is measured and writes --out (default profiles/jpeg_bench.json); the last line is one JSON object.
+Usage: python tools/jpeg_bench.py [--files 384] [--clip 4800] [--reps 10] [--sections batch,pillow,clip,loader] [--out FILE]"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import avsep_amd as P  # noqa: E402,F401
+from avsep_amd import dataset as D  # noqa: E402
+from avsep_amd import jpeg  # noqa: E402
+from avsep_amd import kernels as K  # noqa: E402
+from loader_bench import event_ms, loader_flags, spread, sync_ms, write_dataset  # noqa: E402
+
+H, W = 360, 640
+
+
+def make_files(n):
+    """n seeded pictures with smooth structure and grain, as JPEG bytes."""
+    from PIL import Image
+    rs, out = np.random.RandomState(0), []
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    for i in range(n):
+        ph = rs.rand(3, 2) * 6.28
+        img = np.stack([127 + 100 * np.sin(xx / (20 + 9 * c) + ph[c, 0] + i / 9) * np.cos(yy / (15 + 7 * c) + ph[c, 1]) for c in range(3)], 2)
+        img += rs.randn(H, W, 3) * 12
+        b = io.BytesIO()
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(b, "JPEG", quality=75, subsampling=2)
+        out.append(b.getvalue())
+    return out
+
+
+def pillow(data):
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)
+
+
+def batch_rows(o, dev, files, result):
+    t0 = time.perf_counter()
+    p = jpeg.plan(files)
+    plan_ms = (time.perf_counter() - t0) * 1e3
+    n = len(p.images)
+    assert not p.fallback and n == len(files)
+    host = [torch.from_numpy(p.bytes).pin_memory(), torch.from_numpy(p.tables).pin_memory(),
+            torch.from_numpy(p.images.view(np.uint8)).pin_memory()] + [torch.from_numpy(ch.segs.view(np.uint8)).pin_memory() for ch in p.chunks]
+    up = event_ms(lambda: [t.to(dev, non_blocking=True) for t in host], o.reps)
+    data, tables, images, *segs = [t.to(dev) for t in host]
+    blocks = max(ch.blocks for ch in p.chunks)
+    coef = torch.empty(blocks * 64, dtype=torch.int16, device=dev)
+    planes = torch.empty(blocks * 64, dtype=torch.uint8, device=dev)
+    pixels = torch.empty(p.pixel_bytes, dtype=torch.uint8, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    size = jpeg.IMAGE.itemsize
+
+    def entropy():
+        for ch, sg in zip(p.chunks, segs):
+            K.jpeg_entropy(data, images[ch.a * size:ch.b * size], sg, tables, coef, ch.blocks, status[ch.a:ch.b])
+
+    def both():
+        for ch, sg in zip(p.chunks, segs):
+            rows, st = images[ch.a * size:ch.b * size], status[ch.a:ch.b]
+            K.jpeg_entropy(data, rows, sg, tables, coef, ch.blocks, st)
+            K.jpeg_pixels(coef, planes, ch.blocks, rows, ch.max_blocks, ch.max_pixels, tables, st, pixels)
+
+    ent_ms = event_ms(entropy, o.reps, warmup=1)
+    ent = statistics.median(ent_ms)
+    tot = statistics.median(event_ms(both, o.reps, warmup=1))
+    both()
+    torch.cuda.synchronize()
+    assert not status.any().item()
+    got = pixels.cpu().numpy()
+    same = all(np.array_equal(got[int(p.offsets[i]):int(p.offsets[i + 1])].reshape(H, W, 3), pillow(files[i])) for i in range(min(o.check, n)))
+    result["batch"] = {
+        "files": n, "chunks": len(p.chunks), "file_bytes_mean": sum(map(len, files)) / n, "entropy_bytes": int(len(p.bytes)),
+        "decoded_bytes": p.pixel_bytes, "workspace_bytes": blocks * 192, "plan_ms": plan_ms, "upload_ms": spread(up),
+        "entropy_ms": ent, "entropy_ms_spread": spread(ent_ms), "entropy_us_per_frame": 1e3 * ent / n, "entropy_and_pixels_ms": tot, "pixels_ms": tot - ent,
+        "pixels_us_per_frame": 1e3 * (tot - ent) / n, "equals_pillow": bool(same), "checked": min(o.check, n)}
+    r = result["batch"]
+    print(f"batch of {n} files ({r['file_bytes_mean'] / 1e3:.1f} KB each, {r['entropy_bytes'] / 1e6:.1f} MB up for {p.pixel_bytes / 1e6:.0f} MB "
+          f"decoded, {len(p.chunks)} chunk(s)): plan {plan_ms:.1f} ms on the host, upload {statistics.median(up):.2f} ms, entropy stage "
+          f"{ent:.2f} ms = {r['entropy_us_per_frame']:.0f} us per frame, pixel stage {r['pixels_ms']:.2f} ms = "
+          f"{r['pixels_us_per_frame']:.1f} us per frame (both stages {tot:.2f} ms, the difference); equal to Pillow on {r['checked']} files: "
+          f"{same}", flush=True)
+
+
+def pillow_row(o, files, result):
+    n = min(o.cpu_files, len(files))
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        pillow(files[0])
+        t0 = time.perf_counter()
+        for f in files[:n]:
+            pillow(f)
+        ms = (time.perf_counter() - t0) * 1e3
+    finally:
+        torch.set_num_threads(threads)
+    result["pillow_one_core"] = {"files": n, "ms_per_file": ms / n}
+    print(f"Pillow on one core: {ms / n:.2f} ms per file over {n} files", flush=True)
+
+
+def clip_row(o, dev, files, result):
+    clip = [files[i % len(files)] for i in range(o.clip)]
+    jpeg.decode(clip[:len(files)], dev)
+    ms = sync_ms(lambda: jpeg.decode(clip, dev), 2, warmup=0)
+    chunks = len(jpeg.plan(clip).chunks)
+    result["clip"] = {"files": o.clip, "chunks": chunks, "decode_ms": spread(ms), "ms_per_frame": statistics.median(ms) / o.clip}
+    print(f"clip of {o.clip} files, jpeg.decode end to end (plan, upload, {chunks} chunks, status read): {statistics.median(ms):.0f} ms = "
+          f"{statistics.median(ms) / o.clip:.3f} ms per frame", flush=True)
+
+
+def loader_rows(o, dev, result):
+    rows = {}
+    with tempfile.TemporaryDirectory() as root:
+        lst, _ = write_dataset(root)
+        a = loader_flags(repeat=max(1, (8 + o.batches) * o.batch // 11 + 1))
+        modes = (("gpu_frames", {}), ("gpu_frames_gpu_decode", {"jpeg_bytes": True}))
+        threads = torch.get_num_threads()
+        torch.set_num_threads(1)
+        try:
+            for mode, kw in modes:
+                ds = D.MUSICMixDataset(lst, vars(a), split="train", raw_frames=True, **kw)
+                ds[0]
+                t0 = time.perf_counter()
+                for i in range(o.items):
+                    ds[i]
+                rows[f"item_ms_{mode}"] = (time.perf_counter() - t0) * 1e3 / o.items
+                print(f"ds[i], {mode}: {rows[f'item_ms_{mode}']:.2f} ms per item on one core ({o.items} items)", flush=True)
+        finally:
+            torch.set_num_threads(threads)
+        outs = {}
+        for mode, kw in modes:
+            ds = D.MUSICMixDataset(lst, vars(a), split="train", raw_frames=True, **kw)
+            host = D.collate([ds[i % len(ds)] for i in range(o.batch)])
+            host = {k: (v.pin_memory() if torch.is_tensor(v) and v.numel() else v) for k, v in host.items()}
+            ms = sync_ms(lambda: D.to_device(host, dev), o.reps)
+            key = "frames_jpeg" if kw else "frames_u8"
+            rows[f"to_device_ms_{mode}"], rows[f"frame_bytes_up_{mode}"] = spread(ms), host[key].numel()
+            outs[mode] = D.to_device(host, dev)["frames"]
+            print(f"to_device, {mode}: {statistics.median(ms):.2f} ms for {o.batch} x 2 x 3 frames, {host[key].numel() / 1e6:.1f} MB of frames "
+                  f"up", flush=True)
+        rows["batches_equal"] = all(torch.equal(x, y) for x, y in zip(*outs.values()))
+        for mode, kw in modes:
+            loader = D.make_loader([lst], a, "train", o.batch, True, workers=1, raw_frames=True, **kw)
+            it = iter(loader)
+            for _ in range(3):
+                D.to_device(next(it), dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(o.batches):
+                D.to_device(next(it), dev)
+            torch.cuda.synchronize()
+            rows[f"loader_1_worker_mixtures_per_s_{mode}"] = o.batches * o.batch / (time.perf_counter() - t0)
+            del it, loader
+            print(f"loader, 1 worker, {mode}: {rows[f'loader_1_worker_mixtures_per_s_{mode}']:.0f} mixtures/s", flush=True)
+    result["loader"] = rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=384)
+    ap.add_argument("--clip", type=int, default=4800)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--check", type=int, default=16)
+    ap.add_argument("--cpu-files", type=int, default=96)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--items", type=int, default=24)
+    ap.add_argument("--batches", type=int, default=4)
+    ap.add_argument("--sections", type=lambda v: v.split(","), default=["batch", "pillow", "clip", "loader"])
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_bench.json"))
+    o = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("jpeg_bench measures on an MI355X; there is nothing to report without one")
+    dev = torch.device("cuda", 0)
+    torch.zeros(1, device=dev)
+    result = {"frame": [H, W], "quality": 75, "sampling": "4:2:0", "reps": o.reps}
+    files = make_files(o.files)
+    if "batch" in o.sections:
+        batch_rows(o, dev, files, result)
+    if "pillow" in o.sections:
+        pillow_row(o, files, result)
+    if "clip" in o.sections:
+        clip_row(o, dev, files, result)
+    if "loader" in o.sections:
+        loader_rows(o, dev, result)
+    result["command"] = "python tools/jpeg_bench.py"
+    os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
+    with open(o.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
