@@ -219,3 +219,44 @@ JP_HD void jp_idct_1d(const int d0, const int d1, const int d2, const int d3, co
   o[2] = (tmp12 + tmp1 + half) >> shift, o[5] = (tmp12 - tmp1 + half) >> shift;
   o[3] = (tmp13 + tmp0 + half) >> shift, o[4] = (tmp13 - tmp0 + half) >> shift;
 }
+
+// ---- the encoder (jpeg_enc.hip): what a row of avsep_jpeg_enc_image says, checked as jp_image_ok checks a decoder's row.
+// nblocks: all its blocks, the dummy ones included; nintervals: its restart intervals (1 without restarts).
+constexpr int JP_ENC_HUFF_WORDS = 256;       // by symbol: (code length << 16) | code, 0 = the table has no such symbol
+JP_HD bool jp_enc_image_ok(const avsep_jpeg_enc_image& im, long long* nblocks, long long* nintervals) {
+  if (im.H < 1 || im.H > JP_MAX_SIDE || im.W < 1 || im.W > JP_MAX_SIDE) return false;
+  if (im.ncomp != 1 && im.ncomp != 3) return false;
+  const bool form = im.ncomp == 1 ? (im.hs == 1 && im.vs == 1) : ((im.hs == 1 || im.hs == 2) && (im.vs == 1 || im.vs == 2) && im.vs <= im.hs);
+  if (!form) return false;
+  if (im.mcux != (im.W + 8 * im.hs - 1) / (8 * im.hs) || im.mcuy != (im.H + 8 * im.vs - 1) / (8 * im.vs)) return false;
+  if (im.restart < 0 || im.restart > 65535 || im.pix_off < 0 || im.block0 < 0 || im.interval0 < 0) return false;
+  const long long mcus = (long long)im.mcux * im.mcuy;
+  *nblocks = mcus * (im.hs * im.vs + im.ncomp - 1);
+  *nintervals = im.restart ? (mcus + im.restart - 1) / im.restart : 1;
+  return true;
+}
+
+// One pass of libjpeg's islow forward DCT over eight values, in place: CONST_BITS = 13, PASS1_BITS = 2.  The row pass
+// (second = false) leaves its results scaled up by 4, the column pass (second = true) takes that scaling out again, so a block
+// ends 8 times the true DCT.  Samples are 8 bit less 128: no value formed in either pass leaves int32.
+JP_HD void jp_fdct_1d(int* v, const bool second) {
+  const int t0 = v[0] + v[7], t7 = v[0] - v[7], t1 = v[1] + v[6], t6 = v[1] - v[6];
+  const int t2 = v[2] + v[5], t5 = v[2] - v[5], t3 = v[3] + v[4], t4 = v[3] - v[4];
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  const int n = second ? 15 : 11, half = 1 << (n - 1);
+  v[0] = second ? (t10 + t11 + 2) >> 2 : (t10 + t11) * 4;
+  v[4] = second ? (t10 - t11 + 2) >> 2 : (t10 - t11) * 4;
+  int z1 = (t12 + t13) * 4433;
+  v[2] = (z1 + t13 * 6270 + half) >> n;
+  v[6] = (z1 - t12 * 15137 + half) >> n;
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * 9633;
+  const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+  z1 *= -7373, z2 *= -20995;
+  z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+  v[7] = (a4 + z1 + z3 + half) >> n;
+  v[5] = (a5 + z2 + z4 + half) >> n;
+  v[3] = (a6 + z2 + z3 + half) >> n;
+  v[1] = (a7 + z1 + z4 + half) >> n;
+}

@@ -8,7 +8,10 @@ without restart intervals.  Anything else is *refused* by ``probe`` with a reaso
 is *flagged* in a status word, and both kinds of file are decoded by Pillow into their slot: ``decode`` returns Pillow's pixels
 for every input, and a file Pillow cannot read raises as it does there.
 
-The output layout is the one ``frames.plan_batch`` takes: every frame [H,W,3] uint8, back to back, in file order."""
+The output layout is the one ``frames.plan_batch`` takes: every frame [H,W,3] uint8, back to back, in file order.
+
+The way back (csrc/jpeg_enc.hip): ``encode`` writes uint8 pictures on the device as baseline JPEG files, byte for byte the files
+Pillow's ``save`` writes; ``encode_header`` / ``encode_plan`` / ``encode_launch`` are its parts.  See the second half of this file."""
 import io
 import os
 import struct
@@ -18,7 +21,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .lib import AvsepError, JpegImage, JpegSegment
+from .lib import AvsepError, JpegEncImage, JpegImage, JpegSegment, got
 
 IMAGE = np.dtype(JpegImage)          # include/avsep.h: avsep_jpeg_image
 SEGMENT = np.dtype(JpegSegment)      # include/avsep.h: avsep_jpeg_segment
@@ -411,3 +414,249 @@ def decode_stack(paths, device):
             raise SystemExit(f"{os.path.dirname(q)}: frames of unequal size: {os.path.basename(q)} is {s[0]} x {s[1]}, "
                              f"{os.path.basename(paths[0])} is {shapes[0][0]} x {shapes[0][1]}")
     return pixels.view(len(paths), shapes[0][0], shapes[0][1], 3)
+
+
+# ---- writing: uint8 pictures on the device -> baseline JPEG files, byte for byte what Pillow's save gives (csrc/jpeg_enc.hip;
+# include/avsep.h and DESIGN §33 have the rule)
+
+ENC_IMAGE = np.dtype(JpegEncImage)   # include/avsep.h: avsep_jpeg_enc_image
+ENC_HUFF_WORDS = 256                 # by symbol: (length << 16) | code (csrc/jpeg_parts.h: JP_ENC_HUFF_WORDS)
+MAX_ENC_IMAGES = 1 << 24             # images per chunk
+SAMPLING = {0: (1, 1), 1: (2, 1), 2: (2, 2), "4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+
+# ITU-T T.81 Annex K: the example quantisers (natural order) and the typical Huffman tables (counts by length, values)
+STD_QUANT = (np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51,
+                       87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120,
+                       101, 72, 92, 95, 98, 112, 100, 103, 99]),
+             np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99]
+                      + [99] * 36))
+STD_HUFFMAN = {
+    (0, 0): ([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], bytes(range(12))),
+    (0, 1): ([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0], bytes(range(12))),
+    (1, 0): ([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125], bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43"
+        "4445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2"
+        "b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    (1, 1): ([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119], bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a"
+        "434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9"
+        "aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
+}
+
+
+def quantisers(quality, chroma):
+    """The quantisation table of ``quality`` (1 .. 100) -> int [64], natural order: libjpeg's scaling of the Annex K table."""
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return np.clip((STD_QUANT[1 if chroma else 0] * scale + 50) // 100, 1, 255)
+
+
+def huffman_codes(counts, values):
+    """One Huffman table as the encoding kernels read it -> int32 [ENC_HUFF_WORDS]: by symbol, (length << 16) | code."""
+    w = np.zeros(ENC_HUFF_WORDS, dtype=np.int32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(int(counts[length - 1])):
+            w[values[k]] = (length << 16) | code
+            code, k = code + 1, k + 1
+        code <<= 1
+    return w
+
+
+def _encode_form(shape, quality, subsampling, restart_blocks, restart_rows):
+    """One picture's arguments, checked -> (H, W, components, hs, vs, MCUs across, MCUs down, restart interval in MCUs)."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+        raise AvsepError(f"jpeg.encode takes pictures [H,W] (grey) or [H,W,3] (RGB), got a shape of {shape}")
+    H, W = shape[:2]
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise AvsepError(f"jpeg.encode takes sides of 1 .. {MAX_SIDE}, got {H} x {W}")
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise AvsepError(f"jpeg.encode takes a quality of 1 .. 100, got {quality!r}")
+    if isinstance(subsampling, bool) or not isinstance(subsampling, (int, np.integer, str)) or subsampling not in SAMPLING:
+        raise AvsepError(f"jpeg.encode takes subsampling 0 / 1 / 2 or '4:4:4' / '4:2:2' / '4:2:0', got {subsampling!r}")
+    for name, v in (("restart_blocks", restart_blocks), ("restart_rows", restart_rows)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 65535:
+            raise AvsepError(f"jpeg.encode takes {name} of 0 .. 65535, got {v!r}")
+    ncomp = 1 if len(shape) == 2 else 3
+    hs, vs = SAMPLING[subsampling] if ncomp == 3 else (1, 1)
+    mcux, mcuy = -(-W // (8 * hs)), -(-H // (8 * vs))
+    restart = min(int(restart_rows) * mcux, 65535) if restart_rows else int(restart_blocks)      # rows win, as in libjpeg
+    return H, W, ncomp, hs, vs, mcux, mcuy, restart
+
+
+def _segment(marker, body):
+    return bytes([0xFF, marker]) + struct.pack(">H", len(body) + 2) + bytes(body)
+
+
+def encode_header(shape, quality=75, subsampling="4:2:0", restart_blocks=0, restart_rows=0):
+    """Everything of the file before its entropy-coded bytes, SOI up to and including SOS -> bytes.  Pure Python, no GPU."""
+    H, W, ncomp, hs, vs, _, _, restart = _encode_form(shape, quality, subsampling, restart_blocks, restart_rows)
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    for t in range(2 if ncomp == 3 else 1):
+        out += _segment(0xDB, bytes([t]) + bytes(int(v) for v in quantisers(int(quality), t)[ZIGZAG]))
+    comps = [(1, hs << 4 | vs, 0)] + ([(2, 0x11, 1), (3, 0x11, 1)] if ncomp == 3 else [])
+    out += _segment(0xC0, struct.pack(">BHHB", 8, H, W, ncomp) + b"".join(bytes(c) for c in comps))
+    for t in range(2 if ncomp == 3 else 1):
+        for cls in (0, 1):
+            counts, values = STD_HUFFMAN[(cls, t)]
+            out += _segment(0xC4, bytes([cls << 4 | t]) + bytes(counts) + values)
+    if restart:
+        out += _segment(0xDD, struct.pack(">H", restart))
+    scan = b"".join(bytes([c[0], c[2] << 4 | c[2]]) for c in comps)
+    return out + _segment(0xDA, bytes([ncomp]) + scan + bytes([0, 63, 0]))
+
+
+class EncodeChunk:
+    """The images [a, b) of an encoding plan that share one workspace: their rows (blocks and intervals count from 0 in the
+    chunk), and how many blocks and restart intervals they have."""
+
+    def __init__(self, a, b, images, blocks, intervals):
+        self.a, self.b, self.images, self.blocks, self.intervals = a, b, images, blocks, intervals
+
+
+class EncodePlan:
+    """What the encoding kernels read for a list of pictures: see ``encode_plan``."""
+
+    def __init__(self, shapes, forms, headers, chunks, tables, offsets, pixel_bytes):
+        self.shapes, self.forms, self.headers, self.chunks, self.tables = shapes, forms, headers, chunks, tables
+        self.offsets, self.pixel_bytes = offsets, pixel_bytes
+
+
+def _per_image(v, n, name):
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise AvsepError(f"jpeg.encode_plan: {len(v)} values of {name} for {n} pictures")
+        return list(v)
+    return [v] * n
+
+
+def encode_plan(shapes, quality=75, subsampling="4:2:0", restart_blocks=0, restart_rows=0, cap=WORKSPACE_CAP):
+    """Pack what the kernels read to encode pictures of ``shapes`` ((H, W) grey, (H, W, 3) RGB; uint8, back to back in one buffer)
+    -> EncodePlan.  quality, subsampling, restart_blocks and restart_rows are one value for all pictures or a list with one
+    per picture.
+    forms: per picture (H, W, components, hs, vs, MCUs across, MCUs down, restart interval); headers: its bytes up to SOS;
+    chunks: the pictures cut so that a chunk's coefficient workspace stays within ``cap`` bytes, each with its ENC_IMAGE rows;
+    tables: quantisers (64 words, natural order) and Huffman code tables (``huffman_codes``) in one int32 buffer;
+    offsets, pixel_bytes: every picture's first byte in the pixel buffer."""
+    shapes = [tuple(int(x) for x in s) for s in shapes]
+    n = len(shapes)
+    if n < 1:
+        raise AvsepError("jpeg.encode_plan takes at least one picture")
+    cap_blocks = int(cap) // BLOCK_BYTES
+    if cap_blocks < 1:
+        raise AvsepError(f"jpeg.encode_plan takes a workspace cap of at least {BLOCK_BYTES} bytes, got {cap!r}")
+    args = [_per_image(v, n, name) for v, name in ((quality, "quality"), (subsampling, "subsampling"),
+                                                   (restart_blocks, "restart_blocks"), (restart_rows, "restart_rows"))]
+    forms = [_encode_form(s, *a) for s, a in zip(shapes, zip(*args))]
+    headers = [encode_header(s, *a) for s, a in zip(shapes, zip(*args))]
+    offsets = np.concatenate([[0], np.cumsum([f[0] * f[1] * f[2] for f in forms], dtype=np.int64)])
+    parts, where, words = [], {}, 0
+
+    def table(key, make):
+        nonlocal words
+        if key not in where:
+            t = np.asarray(make(), dtype=np.int32)
+            where[key] = words
+            parts.append(t)
+            words += len(t)
+        return where[key]
+
+    blocks_of = [f[5] * f[6] * (f[3] * f[4] + f[2] - 1) for f in forms]
+    for i, nb in enumerate(blocks_of):
+        if nb > cap_blocks:
+            raise AvsepError(f"jpeg.encode_plan: picture {i} has {nb} blocks, more than the workspace cap of {cap_blocks}")
+    total = sum(blocks_of)
+    target = -(-total // max(1, -(-total // cap_blocks)))                      # chunks of about equal size, as in plan
+    rows = np.zeros(n, dtype=ENC_IMAGE)
+    chunks, a, block0, interval0 = [], 0, 0, 0
+    for r, (f, q) in enumerate(zip(forms, args[0])):
+        H, W, ncomp, hs, vs, mcux, mcuy, restart = f
+        if block0 and (block0 + blocks_of[r] > cap_blocks or block0 >= target or r - a >= MAX_ENC_IMAGES):
+            chunks.append(EncodeChunk(a, r, rows[a:r], block0, interval0))
+            a, block0, interval0 = r, 0, 0
+        row = rows[r]
+        row["pix_off"], row["block0"], row["interval0"], row["H"], row["W"], row["ncomp"] = offsets[r], block0, interval0, H, W, ncomp
+        row["hs"], row["vs"], row["mcux"], row["mcuy"], row["restart"] = hs, vs, mcux, mcuy, restart
+        for c in range(ncomp):
+            t = 0 if c == 0 else 1
+            row["quant"][c] = table(("q", int(q), t), lambda: quantisers(int(q), t))
+            row["dc"][c] = table(("h", 0, t), lambda: huffman_codes(*STD_HUFFMAN[(0, t)]))
+            row["ac"][c] = table(("h", 1, t), lambda: huffman_codes(*STD_HUFFMAN[(1, t)]))
+        block0 += blocks_of[r]
+        interval0 += -(-(mcux * mcuy) // restart) if restart else 1
+    chunks.append(EncodeChunk(a, n, rows[a:n], block0, interval0))
+    p = EncodePlan(shapes, forms, headers, chunks, np.concatenate(parts), offsets, int(offsets[-1]))
+    for ch in chunks:
+        K.jpeg_enc_plan_check(ch.images, p.pixel_bytes, len(p.tables), ch.blocks, ch.intervals)
+    return p
+
+
+def encode_launch(p, device, pixels, coef=None, bits=None, stream=None):
+    """Run an encoding plan on the current stream of ``device`` over ``pixels`` (uint8 [plan.pixel_bytes], the pictures back to
+    back) -> (outs, coef, bits, stream): outs = per chunk (out uint8 [bytes], sizes int64 [2 * images]: every image's first byte
+    and byte count in out), on the device; coef (int16, 64 per block), bits (int32, one per block) and stream (uint8, the
+    unstuffed bytes) as the last chunk left them.  coef, bits and stream, when given, are the buffers to use: 64 and 1 per block
+    of the largest chunk, and at least the largest chunk's unstuffed bytes rounded up to 4.  Two 8-byte totals per chunk are read
+    back, the sizes of the stream and of the output; nothing else."""
+    device = torch.device(device)
+    if not torch.is_tensor(pixels) or pixels.dtype != torch.uint8 or pixels.dim() != 1 or pixels.numel() != p.pixel_bytes \
+            or pixels.device.type != device.type:
+        raise AvsepError(f"jpeg.encode_launch takes pixels uint8 [{p.pixel_bytes}] on {device}, got {got(pixels)}")
+    device = pixels.device
+    tables = torch.from_numpy(p.tables).to(device, non_blocking=True)
+    blocks, intervals = max(ch.blocks for ch in p.chunks), max(ch.intervals for ch in p.chunks)
+    coef = torch.empty(blocks * 64, dtype=torch.int16, device=device) if coef is None else coef
+    bits = torch.empty(blocks, dtype=torch.int32, device=device) if bits is None else bits
+    i64 = lambda m: torch.empty(m, dtype=torch.int64, device=device)
+    i32 = lambda m: torch.empty(m, dtype=torch.int32, device=device)
+    pos, ivl_off, out_off, ff0, ivl_bytes, ivl_out = i64(blocks + 1), i64(intervals + 1), i64(intervals + 1), i64(intervals), \
+        i32(intervals), i32(intervals)
+    outs, own_stream = [], stream is None
+    for ch in p.chunks:
+        rows = torch.from_numpy(np.ascontiguousarray(ch.images).view(np.uint8)).to(device, non_blocking=True)
+        B, I = ch.blocks, ch.intervals
+        tiles = i64(-(-B // 256))
+        K.jpeg_enc_coef(pixels, rows, tables, coef, B)
+        K.jpeg_enc_count(coef, B, rows, I, tables, bits, pos, ivl_bytes, ivl_off, tiles)
+        nbytes = max(4, -(-int(ivl_off[I].item()) // 4) * 4)
+        if own_stream and (stream is None or stream.numel() < nbytes):
+            stream = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        if stream.numel() < nbytes:
+            raise AvsepError(f"jpeg.encode_launch: the stream buffer has {stream.numel()} bytes, the chunk's unstuffed stream {nbytes}")
+        groups = -(-nbytes // 64)
+        tiles = i64(max(-(-groups // 256), -(-I // 256)))
+        grp, ffpos = i32(groups), i64(groups + 1)
+        K.jpeg_enc_pack(coef, B, rows, I, tables, pos, ivl_off, stream[:nbytes], grp, ffpos, ff0, ivl_out, out_off, tiles)
+        out = torch.empty(int(out_off[I].item()), dtype=torch.uint8, device=device)
+        sizes = i64(2 * (ch.b - ch.a))
+        K.jpeg_enc_stuff(stream[:nbytes], rows, I, ivl_off, ffpos, ff0, out_off, out, sizes)
+        outs.append((out, sizes))
+    return outs, coef, bits, stream
+
+
+def encode(images, quality=75, subsampling="4:2:0", restart_blocks=0, restart_rows=0, cap=WORKSPACE_CAP):
+    """uint8 pictures on the GPU -> a list of ``bytes``, one JPEG file per picture, each byte for byte what
+    ``Image.fromarray(picture).save(f, "JPEG", quality=, subsampling=, restart_marker_blocks=, restart_marker_rows=)`` writes.
+    images: a list of tensors [H,W] (grey) or [H,W,3] (RGB), or one tensor [T,H,W] / [T,H,W,3].  The four settings are one
+    value for all pictures or a list with one per picture.  Everything else Pillow's save takes (optimize, progressive,
+    quality="keep", qtables, other modes) is not offered, and anything outside the limits raises: there is no fallback.  Only
+    the encoded bytes and their sizes cross to the host."""
+    if torch.is_tensor(images):
+        if images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[3] != 3):
+            raise AvsepError(f"jpeg.encode takes one tensor [T,H,W] or [T,H,W,3], got {got(images)}")
+        images = images.contiguous()
+    seq = list(images.unbind(0)) if torch.is_tensor(images) else list(images)
+    if not seq:
+        raise AvsepError("jpeg.encode takes at least one picture")
+    for t in seq:
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or t.device != seq[0].device:
+            raise AvsepError(f"jpeg.encode takes uint8 tensors on one GPU, got {got(t)}")
+    p = encode_plan([tuple(t.shape) for t in seq], quality, subsampling, restart_blocks, restart_rows, cap)
+    pixels = images.reshape(-1) if torch.is_tensor(images) else torch.cat([t.reshape(-1) for t in seq])
+    outs, _, _, _ = encode_launch(p, seq[0].device, pixels)
+    files = []
+    for ch, (out, sizes) in zip(p.chunks, outs):
+        out, sizes = out.cpu().numpy(), sizes.cpu().numpy().reshape(-1, 2)
+        for r, (at, n) in enumerate(sizes):
+            files.append(p.headers[ch.a + r] + out[int(at):int(at + n)].tobytes())
+    return files

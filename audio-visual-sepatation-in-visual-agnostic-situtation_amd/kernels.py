@@ -1241,6 +1241,79 @@ def jpeg_pixels(coef, planes, ws_blocks, images, max_blocks, max_pixels, tables,
          tables.numel(), ptr(status), ptr(pixels), pixels.numel())
 
 
+def jpeg_enc_plan_check(images, pixel_bytes, table_words, ws_blocks, n_intervals):
+    """avsep_jpeg_enc_plan_check (include/avsep.h; host only, no GPU): images = a NumPy array of dtype np.dtype(lib.JpegEncImage),
+    the rows of one chunk.  AvsepError for anything the library refuses."""
+    images = np.ascontiguousarray(images)
+    rc = lib.load().avsep_jpeg_enc_plan_check(images.ctypes.data, len(images), int(pixel_bytes), int(table_words), int(ws_blocks),
+                                              int(n_intervals))
+    if rc != 0:
+        raise lib.AvsepError(f"avsep_jpeg_enc_plan_check refused {len(images)} images: a size, sampling form, MCU count or restart "
+                             f"interval outside the limits, blocks or intervals that do not run on, or a pixel or table range outside "
+                             f"its buffer ({rc})")
+
+
+def _jpeg_enc_rows(who, images, sized):
+    """The row count of `images` (uint8); sized: (tensor, name, least elements)."""
+    n = images.numel() // C.sizeof(lib.JpegEncImage)
+    if n < 1 or images.numel() != n * C.sizeof(lib.JpegEncImage):
+        raise lib.AvsepError(f"{who}: {images.numel()} bytes of image rows")
+    for t, name, least in sized:
+        if t.numel() < least:
+            raise lib.AvsepError(f"{who}: {name} has {t.numel()} elements, {least} are needed")
+    return n
+
+
+def jpeg_enc_coef(pixels, images, tables, coef, ws_blocks):
+    """avsep_jpeg_enc_coef (include/avsep.h): pixels uint8 [bytes], images uint8 (the checked rows of one chunk), tables int32
+    [words] -> coef int16 [>= 64 * ws_blocks]: every block of the chunk, scan order, zig-zag inside."""
+    _jpeg_buffers("jpeg_enc_coef", pixels, ((pixels, torch.uint8), (images, torch.uint8), (tables, torch.int32), (coef, torch.int16)))
+    n = _jpeg_enc_rows("jpeg_enc_coef", images, ((coef, "coef", 64 * int(ws_blocks)),))
+    call("avsep_jpeg_enc_coef", ptr(pixels), pixels.numel(), ptr(images), n, ptr(tables), tables.numel(), ptr(coef), int(ws_blocks))
+
+
+def jpeg_enc_count(coef, ws_blocks, images, n_intervals, tables, bits, pos, ivl_bytes, ivl_off, tiles):
+    """avsep_jpeg_enc_count: coef -> bits int32 [ws_blocks], pos int64 [ws_blocks + 1], ivl_bytes int32 [n_intervals], ivl_off
+    int64 [n_intervals + 1]; tiles int64: scratch."""
+    _jpeg_buffers("jpeg_enc_count", coef, ((coef, torch.int16), (images, torch.uint8), (tables, torch.int32), (bits, torch.int32),
+                                           (pos, torch.int64), (ivl_bytes, torch.int32), (ivl_off, torch.int64), (tiles, torch.int64)))
+    B, I = int(ws_blocks), int(n_intervals)
+    n = _jpeg_enc_rows("jpeg_enc_count", images, ((coef, "coef", 64 * B), (bits, "bits", B), (pos, "pos", B + 1),
+                                                  (ivl_bytes, "ivl_bytes", I), (ivl_off, "ivl_off", I + 1)))
+    call("avsep_jpeg_enc_count", ptr(coef), B, ptr(images), n, I, ptr(tables), tables.numel(), ptr(bits), ptr(pos), ptr(ivl_bytes),
+         ptr(ivl_off), ptr(tiles), tiles.numel())
+
+
+def jpeg_enc_pack(coef, ws_blocks, images, n_intervals, tables, pos, ivl_off, stream_buf, groups, ffpos, ff0, ivl_out, out_off, tiles):
+    """avsep_jpeg_enc_pack: the blocks' bits -> stream_buf uint8 [a multiple of 4: the unstuffed stream], then the 0xFF counts:
+    groups int32 [ceil(bytes / 64)], ffpos int64 [groups + 1], ff0 int64 [n_intervals], ivl_out int32 [n_intervals], out_off int64
+    [n_intervals + 1]."""
+    _jpeg_buffers("jpeg_enc_pack", coef, ((coef, torch.int16), (images, torch.uint8), (tables, torch.int32), (pos, torch.int64),
+                                          (ivl_off, torch.int64), (stream_buf, torch.uint8), (groups, torch.int32), (ffpos, torch.int64),
+                                          (ff0, torch.int64), (ivl_out, torch.int32), (out_off, torch.int64), (tiles, torch.int64)))
+    B, I, G = int(ws_blocks), int(n_intervals), -(-stream_buf.numel() // 64)
+    n = _jpeg_enc_rows("jpeg_enc_pack", images, ((coef, "coef", 64 * B), (pos, "pos", B + 1), (ivl_off, "ivl_off", I + 1),
+                                                 (groups, "groups", G), (ffpos, "ffpos", G + 1), (ff0, "ff0", I), (ivl_out, "ivl_out", I),
+                                                 (out_off, "out_off", I + 1)))
+    call("avsep_jpeg_enc_pack", ptr(coef), B, ptr(images), n, I, ptr(tables), tables.numel(), ptr(pos), ptr(ivl_off), ptr(stream_buf),
+         stream_buf.numel(), ptr(groups), ptr(ffpos), ptr(ff0), ptr(ivl_out), ptr(out_off), ptr(tiles), tiles.numel())
+
+
+def jpeg_enc_stuff(stream_buf, images, n_intervals, ivl_off, ffpos, ff0, out_off, out, sizes):
+    """avsep_jpeg_enc_stuff: the unstuffed stream -> out uint8 [bytes]: per image its stuffed intervals, RSTn between them, EOI
+    at the end; sizes int64 [2 * images] = (first byte, bytes) of every image in out."""
+    _jpeg_buffers("jpeg_enc_stuff", stream_buf, ((stream_buf, torch.uint8), (images, torch.uint8), (ivl_off, torch.int64),
+                                                 (ffpos, torch.int64), (ff0, torch.int64), (out_off, torch.int64), (out, torch.uint8),
+                                                 (sizes, torch.int64)))
+    I, G = int(n_intervals), -(-stream_buf.numel() // 64)
+    n = _jpeg_enc_rows("jpeg_enc_stuff", images, ((ivl_off, "ivl_off", I + 1), (ffpos, "ffpos", G + 1), (ff0, "ff0", I),
+                                                  (out_off, "out_off", I + 1), (out, "out", 1)))
+    if sizes.numel() != 2 * n:
+        raise lib.AvsepError(f"jpeg_enc_stuff: {sizes.numel()} size words for {n} images")
+    call("avsep_jpeg_enc_stuff", ptr(stream_buf), stream_buf.numel(), ptr(images), n, I, ptr(ivl_off), ptr(ffpos), ptr(ff0), ptr(out_off),
+         ptr(out), out.numel(), ptr(sizes))
+
+
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 

@@ -62,6 +62,13 @@ class JpegSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64)] + [(n, C.c_int32) for n in "image mcu0 mcus reserved".split()]
 
 
+class JpegEncImage(C.Structure):
+    """avsep_jpeg_enc_image (include/avsep.h): one image of the avsep_jpeg_enc_* entry points."""
+    _fields_ = [("pix_off", C.c_int64), ("block0", C.c_int64), ("interval0", C.c_int64)] + \
+               [(n, C.c_int32) for n in "H W ncomp hs vs mcux mcuy".split()] + \
+               [(n, C.c_int32 * 3) for n in "quant dc ac".split()] + [("restart", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P, _I, _F, _D, _Z = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t
 _CD, _KD = C.POINTER(ConvDesc), C.POINTER(CatDesc)
 _L = C.c_int64
@@ -135,6 +142,11 @@ SIGNATURES = {
     "avsep_jpeg_plan_check": (C.c_int, [_P, _I, _P, _I, _L, _L, _L, _L]),
     "avsep_jpeg_entropy": (C.c_int, [_P, _L, _P, _I, _P, _I, _P, _L, _P, _L, _P, _P]),
     "avsep_jpeg_pixels": (C.c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _L, _P, _P, _L, _P]),
+    "avsep_jpeg_enc_plan_check": (C.c_int, [_P, _I, _L, _L, _L, _L]),
+    "avsep_jpeg_enc_coef": (C.c_int, [_P, _L, _P, _I, _P, _L, _P, _L, _P]),
+    "avsep_jpeg_enc_count": (C.c_int, [_P, _L, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P]),
+    "avsep_jpeg_enc_pack": (C.c_int, [_P, _L, _P, _I, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "avsep_jpeg_enc_stuff": (C.c_int, [_P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

@@ -127,6 +127,9 @@ def localise(nets, wav, frames, frame_times, args, stride_frames=128, batch=16, 
 # ---------------------------------------------------------------------------------------------------------------------
 # command line
 # ---------------------------------------------------------------------------------------------------------------------
+JPG_CHUNK = 512                  # frames per jpeg.encode call of --jpg
+
+
 def build_parser():
     from .arguments import ArgParser
     ap = ArgParser()
@@ -146,6 +149,9 @@ def build_parser():
     p.add_argument("--frame_offset", type=float, default=0.0, help="time of the first video frame, seconds from the WAV's start")
     p.add_argument("--out", default="localised", help="output directory (maps.npy, overlay_source<c>.npy)")
     p.add_argument("--png", action="store_true", help="also write one PNG per frame and source (needs Pillow)")
+    p.add_argument("--jpg", action="store_true",
+                   help="also write one JPEG per frame and source, encoded on the GPU: the file Pillow's save(f, 'JPEG', quality=Q) writes")
+    p.add_argument("--jpg_quality", type=int, default=90, help="quality of the --jpg files, 1 .. 100")
     p.add_argument("--alpha", type=float, default=0.4, help="weight of the heat map in the blend")
     p.add_argument("--window_stride", type=int, default=128, help="STFT frames between window starts (<= 256)")
     p.add_argument("--window_batch", type=int, default=16, help="windows / video frames per network pass")
@@ -163,6 +169,8 @@ def parse_args(argv=None):
         raise SystemExit("--fps must be positive")
     if not 0.0 <= args.alpha <= 1.0:
         raise SystemExit("--alpha must lie in [0, 1]")
+    if not 1 <= args.jpg_quality <= 100:
+        raise SystemExit("--jpg_quality must lie in [1, 100]")
     if not 1 <= args.window_stride <= WIDTH:
         raise SystemExit(f"--window_stride must lie in [1, {WIDTH}]")
     return args
@@ -191,6 +199,14 @@ def cli(argv=None):
         for c in range(overlays.shape[0]):
             for t in range(overlays.shape[1]):
                 Image.fromarray(overlays[c, t]).save(os.path.join(args.out, f"source{c}_frame{t:05d}.png"))
+    if args.jpg:
+        from . import jpeg
+        stack = out["overlays"]
+        for c in range(stack.shape[0]):
+            for t0 in range(0, stack.shape[1], JPG_CHUNK):                   # only the encoded bytes come back, a chunk at a time
+                for t, data in enumerate(jpeg.encode(stack[c, t0:t0 + JPG_CHUNK], quality=args.jpg_quality), t0):
+                    with open(os.path.join(args.out, f"source{c}_frame{t:05d}.jpg"), "wb") as f:
+                        f.write(data)
     print(f"{overlays.shape[1]} frames x {overlays.shape[0]} sources over {len(out['starts'])} windows -> {args.out}/")
     return out
 

@@ -226,13 +226,16 @@ def own_flags(argv=None):
     own.add_argument("--visuals", action="store_true",
                      help="every evaluation also writes the pictures, sounds and index.html of its first --num_vis validation "
                           "items under <ckpt>/<id>/visualization/av and .../ao (needs Pillow)")
+    own.add_argument("--gpu_encode", action="store_true",
+                     help="with --visuals: the .jpg images are encoded on the GPU in one call per batch, byte for byte the files "
+                          "Pillow writes (the frame strips stay PNG and stay with Pillow)")
     return own.parse_known_args(argv)
 
 
 def cli(argv=None):
     own, argv = own_flags(argv)
     args = ArgParser().parse_train_arguments(argv)
-    args.gpu_frames, args.gpu_decode = own.gpu_frames, own.gpu_decode
+    args.gpu_frames, args.gpu_decode, args.gpu_encode = own.gpu_frames, own.gpu_decode, own.gpu_encode
     if own.gpu_decode and not own.gpu_frames:
         raise SystemExit("--gpu_decode is a form of --gpu_frames: pass both")
     print("Model ID: {}".format(args.id))

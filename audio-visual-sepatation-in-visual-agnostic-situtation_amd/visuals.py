@@ -15,6 +15,8 @@ takes.  A batch of B items and N sources is a handful of launches, not 2 + 4N im
 ``output_visuals`` lays the files of the first ``num_vis`` validation items out as the reference does (one folder per item
 id under <vis>/av or <vis>/ao: .jpg images through Pillow, 24-bit .wav files through wavio), with one ``frames{n}.png``
 strip of the item's frames in place of the reference's ffmpeg videos; ``write_page`` writes the table that shows them.
+With ``args.gpu_encode`` (``train.py --gpu_encode``) the .jpg images stay on the device and ``jpeg.encode`` writes them in one
+call: the same bytes as Pillow's, and only those bytes cross to the host; the PNG strips stay with Pillow.
 
 ``report`` is the same picture for a recording of any length (``separate --report``): the mixture, every stem's share of it
 and every stitched mask at ``cell = ceil(frames / width)`` STFT frames per image column.
@@ -189,6 +191,7 @@ def output_visuals(vis_rows, batch, outputs, args, metrics, use_vis, stft_plan=N
     """main.py:290-418 for the items of one batch that still fit under ``args.num_vis``: their folders under
     <args.vis>/av (use_vis) or <args.vis>/ao, and one row per item appended to ``vis_rows`` for ``write_index``.
     metrics: evaluate.calc_metrics' result for the same batch ("pred_wavs" [N,B,L]; "sdr" / "sir" [B,N] where it has them).
+    args.gpu_encode (optional): the .jpg files are encoded on the GPU, byte for byte the files Pillow writes.
     Returns the number of items written."""
     Image = _pillow("output_visuals")
     mag_mix, phase = batch["mag_mix"], batch["phase_mix"]
@@ -203,7 +206,15 @@ def output_visuals(vis_rows, batch, outputs, args, metrics, use_vis, stft_plan=N
         mag = mag_mix.detach().float()[:todo, 0].contiguous()
         ph = phase.detach().float()[:todo, 0].contiguous()
         linear = linear_masks(outputs, args, mag.shape[1], todo)                # one un-warp for the pictures and the sounds
-        images = {k: v.cpu().numpy() for k, v in item_images(batch, outputs, args, todo, linear).items()}
+        images = item_images(batch, outputs, args, todo, linear)
+        if getattr(args, "gpu_encode", False):                                  # the .jpg files of all items in one encode
+            from . import jpeg
+            names = ["mix", "weight"] + [f"{kind}{n}" for n in range(1, N + 1) for kind in ("predamp", "gtamp", "predmask", "gtmask")]
+            files = jpeg.encode([images[k][j] for j in range(todo) for k in names])
+            jpgs = [dict(zip(names, files[j * len(names):(j + 1) * len(names)])) for j in range(todo)]
+        else:
+            images = {k: v.cpu().numpy() for k, v in images.items()}
+            jpgs = None
         plan = stft_plan or K.Stft(mag_mix.device, args.stft_frame, args.stft_hop, getattr(args, "stft_pad_mode", "reflect"))
         gt_mag = (mag[None] * linear[1].view(N, todo, *mag.shape[1:])).reshape(N * todo, *mag.shape[1:]).contiguous()
         waves = plan.istft(torch.cat([mag, gt_mag], 0), ph.repeat(N + 1, 1, 1)).clamp_(-1.0, 1.0)      # mix, then gt [N,todo]
@@ -214,8 +225,15 @@ def output_visuals(vis_rows, batch, outputs, args, metrics, use_vis, stft_plan=N
         os.makedirs(os.path.join(root, name), exist_ok=True)
         rel = lambda fn: name + "/" + fn                                        # noqa: E731
         full = lambda fn: os.path.join(root, name, fn)                          # noqa: E731
-        Image.fromarray(images["mix"][j]).save(full("mix.jpg"))
-        Image.fromarray(images["weight"][j]).save(full("weight.jpg"))
+
+        def save_jpg(key):
+            if jpgs is None:
+                Image.fromarray(images[key][j]).save(full(key + ".jpg"))
+            else:
+                with open(full(key + ".jpg"), "wb") as f:
+                    f.write(jpgs[j][key])
+        save_jpg("mix")
+        save_jpg("weight")
         _write_wav(full("mix.wav"), waves[j], args.audRate)
         text = [name]
         for key in ("sdr", "sir"):
@@ -224,7 +242,7 @@ def output_visuals(vis_rows, batch, outputs, args, metrics, use_vis, stft_plan=N
         row = [{"text": text}, {"image": rel("mix.jpg"), "audio": rel("mix.wav")}]
         for n in range(1, N + 1):
             for kind in ("predamp", "gtamp", "predmask", "gtmask"):
-                Image.fromarray(images[f"{kind}{n}"][j]).save(full(f"{kind}{n}.jpg"))
+                save_jpg(f"{kind}{n}")
             _write_wav(full(f"pred{n}.wav"), pred_wavs[n - 1, j], args.audRate)
             _write_wav(full(f"gt{n}.wav"), waves[n * todo + j], args.audRate)
             cell = {"text": "audio only"}

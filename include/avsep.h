@@ -868,6 +868,83 @@ int avsep_jpeg_pixels(const int16_t* coef, uint8_t* planes, int64_t ws_blocks, c
                       int32_t max_blocks, int32_t max_pixels, const int32_t* tables, int64_t table_words, const int32_t* status,
                       uint8_t* pixels, int64_t pixel_bytes, avsep_stream_t stream);
 
+/* ---- Baseline JPEG files written (csrc/jpeg_enc.hip, csrc/jpeg_parts.h; avsep_amd/jpeg.py: encode): uint8 [H][W] (grey, one
+ * component) or [H][W][3] (RGB -> YCbCr, three components) -> the entropy-coded bytes of a file, byte for byte what libjpeg-turbo's
+ * default encoder (Pillow's `save(f, "JPEG", quality=, subsampling=, restart_marker_blocks=)`) puts after its SOS segment, EOI
+ * included.  The markers before it are the host's (jpeg.encode_header).  THE RULE:
+ *   scope    luma sampling 1x1, 2x1 or 2x2, chroma 1x1; grey is 1x1.  quality 1 .. 100.  restart = MCUs per interval, 0 = none.
+ *   header   SOI, APP0 JFIF 1.01 (density 1:1, no units), one DQT per table (luma; chroma with three components), SOF0, the
+ *            DHTs (DC0, AC0 and with three components DC1, AC1: the Annex K tables), DRI only with restarts, SOS.
+ *            Quantisers: scale = 5000 / q for q < 50, else 200 - 2q; entry = clamp((std * scale + 50) / 100, 1, 255), zig-zag.
+ *   colour   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *            Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *            Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *   edges    a plane is replicated to the right to width_in_blocks * 8 * (hmax / h) columns and at the bottom to a multiple of
+ *            vmax rows, THEN downsampled (2x1: (a + b + bias) >> 1, bias 0,1,0,1.. along the output columns; 2x2:
+ *            (a + b + c + d + bias) >> 2, bias 1,2,1,2..), and only then replicated at the bottom to the MCU rows' height: a
+ *            sample is the downsampled value of source coordinates clamped to the picture, and below the downsampled plane's
+ *            ceil(H v / vmax) rows its last row again.  Blocks of
+ *            an MCU beyond the component's width_in_blocks = ceil(ceil(W h / hmax) / 8) or height_in_blocks are DUMMY blocks: all
+ *            AC zero, DC the quantised DC of the block before them in MCU order.
+ *   DCT      libjpeg's islow forward DCT of sample - 128, 13-bit constants: rows first, scaled up by 4; then columns with
+ *            rounded descales by 2 and 15; the result is 8 times the true DCT.
+ *   quantise (|d| + ((8 q) >> 1)) / (8 q), the sign restored.
+ *   entropy  one interleaved scan, MCUs in raster order, the luma blocks of an MCU in raster order inside it.  A DC difference
+ *            (to the component's previous block in the interval, 0 at its start) is its category's code and the extra bits; AC
+ *            values are run/size symbols with ZRL (0xF0) for runs above 15 and EOB (0x00) when zeros trail; a negative v of
+ *            size s is written as v + 2^s - 1.  Every 0xFF byte is followed by 0x00.  The last byte of every restart interval
+ *            and of the scan is padded with 1-bits; RSTn (n = 0 .. 7 in turn) stands between intervals, EOI at the end.
+ * In DEVICE memory: pixels (the images back to back, anywhere in it), tables int32 [table_words] (quantisers: 64 words, NATURAL
+ * order, 1 .. 255; Huffman codes: 256 words by symbol, (length << 16) | code, length <= 16, 0 = no such symbol), one row per image: */
+typedef struct avsep_jpeg_enc_image {
+  int64_t pix_off;                          /* the image's first byte in `pixels`: H*W bytes (one component) or H*W*3 */
+  int64_t block0;                           /* its first block in the workspace: the rows' blocks lie back to back from 0 */
+  int64_t interval0;                        /* its first restart interval: the rows' intervals count on from 0 */
+  int32_t H, W, ncomp;                      /* 1 <= H, W <= 16384; ncomp 1 | 3 */
+  int32_t hs, vs;                           /* luma sampling: (1,1), (2,1) or (2,2); (1,1) with one component */
+  int32_t mcux, mcuy;                       /* MCUs across and down: ceil(W / (8 hs)), ceil(H / (8 vs)) */
+  int32_t quant[3], dc[3], ac[3];           /* word offsets in `tables`, per component */
+  int32_t restart;                          /* MCUs per restart interval, 0 = none (one interval) */
+  int32_t reserved;
+} avsep_jpeg_enc_image;
+/* An image's blocks lie in SCAN order: MCU after MCU, in an MCU hs*vs luma blocks, then Cb, then Cr; a block is 64 int16 in
+ * ZIG-ZAG order; dummy blocks are there like any other.  Four stages on the caller's stream, none of which reads anything back
+ * (the caller copies the two totals it sizes the next buffer by):
+ * avsep_jpeg_enc_plan_check (host only): every HOST row against the limits, block0 and interval0 running on from 0 to ws_blocks
+ *   and n_intervals, pixel and table ranges inside their buffers.
+ * avsep_jpeg_enc_coef: pixels -> coef int16 [64 ws_blocks], one lane per block (16-byte aligned).
+ * avsep_jpeg_enc_count: bits int32 [ws_blocks] = every block's Huffman bits; pos int64 [ws_blocks + 1] = their running sum;
+ *   ivl_bytes int32 [n_intervals] = an interval's bytes before stuffing, ivl_off int64 [n_intervals + 1] their running sum:
+ *   ivl_off[n_intervals] is the size of the unstuffed stream.
+ * avsep_jpeg_enc_pack: zeroes stream_buf[0 .. stream_bytes) and every block writes its bits at its place, the last block of an
+ *   interval the 1-bit padding too; whole words are stored, the words a block shares with its neighbours are ORed in with an
+ *   integer atomicOr (the order does not show in the result).  stream_bytes: ivl_off[n_intervals] rounded up to a multiple of 4
+ *   (4-byte aligned).  Then groups int32 [ceil(stream_bytes / 64)] = the 0xFF bytes of every 64 bytes, ffpos int64 [groups + 1]
+ *   their running sum, ff0 int64 [n_intervals] = the 0xFF bytes before an interval, ivl_out int32 [n_intervals] = an interval's
+ *   bytes after stuffing plus its 2-byte marker, out_off int64 [n_intervals + 1] their running sum: out_off[n_intervals] is the
+ *   size of all output.
+ * avsep_jpeg_enc_stuff: out uint8 [out_bytes] = image after image the stuffed intervals with RSTn between them and EOI at the
+ *   end; sizes int64 [2 n_images] = (first byte, byte count) of every image in `out`.
+ * tiles int64 [tile_words]: scratch of the running sums, tile_words >= ceil(max(ws_blocks, n_intervals, groups) / 256).
+ * Grids are bounded and strided, offsets 64 bit.  Rows in device memory are checked again by every lane that reads one and
+ * every store is checked against its buffer's size: a wrong row gives wrong bytes, not an access outside a buffer.  A null
+ * pointer, a count or size < 1, ws_blocks above 2^32, n_images above 2^24, a misaligned coef or stream_buf, or scratch too
+ * small is AVSEP_ERR_ARG before any launch. */
+int avsep_jpeg_enc_plan_check(const avsep_jpeg_enc_image* images, int32_t n_images, int64_t pixel_bytes, int64_t table_words,
+                              int64_t ws_blocks, int64_t n_intervals);
+int avsep_jpeg_enc_coef(const uint8_t* pixels, int64_t pixel_bytes, const avsep_jpeg_enc_image* images, int32_t n_images,
+                        const int32_t* tables, int64_t table_words, int16_t* coef, int64_t ws_blocks, avsep_stream_t stream);
+int avsep_jpeg_enc_count(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_enc_image* images, int32_t n_images,
+                         int64_t n_intervals, const int32_t* tables, int64_t table_words, int32_t* bits, int64_t* pos,
+                         int32_t* ivl_bytes, int64_t* ivl_off, int64_t* tiles, int64_t tile_words, avsep_stream_t stream);
+int avsep_jpeg_enc_pack(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_enc_image* images, int32_t n_images,
+                        int64_t n_intervals, const int32_t* tables, int64_t table_words, const int64_t* pos, const int64_t* ivl_off,
+                        uint8_t* stream_buf, int64_t stream_bytes, int32_t* groups, int64_t* ffpos, int64_t* ff0, int32_t* ivl_out,
+                        int64_t* out_off, int64_t* tiles, int64_t tile_words, avsep_stream_t stream);
+int avsep_jpeg_enc_stuff(const uint8_t* stream_buf, int64_t stream_bytes, const avsep_jpeg_enc_image* images, int32_t n_images,
+                         int64_t n_intervals, const int64_t* ivl_off, const int64_t* ffpos, const int64_t* ff0,
+                         const int64_t* out_off, uint8_t* out, int64_t out_bytes, int64_t* sizes, avsep_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
