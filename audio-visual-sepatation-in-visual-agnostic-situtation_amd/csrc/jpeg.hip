@@ -29,8 +29,8 @@ __global__ __launch_bounds__(JP_BLOCK) void jpeg_idct_kernel(const int16_t* __re
   const int img = blockIdx.y;
   if (status[img] != 0) return;
   const avsep_jpeg_image im = images[img];
-  long long nblocks = 0;
-  if (!jp_image_ok(im, &nblocks) || !jp_inside(im.block0, nblocks, ws_blocks)) return;
+  long long nblocks = 0, nintervals = 0;
+  if (!jp_image_ok(im, &nblocks, &nintervals) || !jp_inside(im.block0, nblocks, ws_blocks)) return;
   const long long blk = (long long)blockIdx.x * JP_BLOCK + threadIdx.x;
   if (blk >= nblocks) return;
   const long long luma = (long long)im.mcux * im.mcuy * im.hs * im.vs;
@@ -107,8 +107,8 @@ __global__ __launch_bounds__(JP_BLOCK) void jpeg_colour_kernel(const uint8_t* __
   const int img = blockIdx.y;
   if (status[img] != 0) return;
   const avsep_jpeg_image im = images[img];
-  long long nblocks = 0;
-  if (!jp_image_ok(im, &nblocks) || !jp_inside(im.block0, nblocks, ws_blocks)) return;
+  long long nblocks = 0, nintervals = 0;
+  if (!jp_image_ok(im, &nblocks, &nintervals) || !jp_inside(im.block0, nblocks, ws_blocks)) return;
   if (!jp_inside(im.pix_off, (long long)im.H * im.W * 3, pixel_bytes)) return;
   const long long p = (long long)blockIdx.x * JP_BLOCK + threadIdx.x;
   if (p >= (long long)im.H * im.W) return;
@@ -133,14 +133,9 @@ extern "C" int avsep_jpeg_plan_check(const avsep_jpeg_image* images, int32_t n_i
   if (!images || !segments || n_images < 1 || n_segments < 1 || nbytes < 1 || table_words < 1 || pixel_bytes < 1 || ws_blocks < 1)
     return AVSEP_ERR_ARG;
   for (int i = 0; i < n_images; ++i) {
-    const avsep_jpeg_image& im = images[i];
-    long long nblocks = 0;
-    if (!jp_image_ok(im, &nblocks) || !jp_inside(im.block0, nblocks, ws_blocks)) return AVSEP_ERR_ARG;
-    if (!jp_inside(im.pix_off, (long long)im.H * im.W * 3, pixel_bytes)) return AVSEP_ERR_ARG;
-    for (int c = 0; c < im.ncomp; ++c)
-      if (!jp_inside(im.quant[c], JP_QUANT_WORDS, table_words) || !jp_inside(im.dc[c], JP_HUFF_WORDS, table_words) ||
-          !jp_inside(im.ac[c], JP_HUFF_WORDS, table_words))
-        return AVSEP_ERR_ARG;
+    long long nblocks = 0, nintervals = 0;
+    if (!jp_row_ok(images[i], 3, JP_HUFF_WORDS, pixel_bytes, table_words, &nblocks, &nintervals)) return AVSEP_ERR_ARG;
+    if (!jp_inside(images[i].block0, nblocks, ws_blocks)) return AVSEP_ERR_ARG;
   }
   for (int s = 0; s < n_segments; ++s) {
     const avsep_jpeg_segment& g = segments[s];

@@ -21,7 +21,7 @@ static inline int je_grid(long long n) {
 }
 
 // the row whose block0 (by_interval: interval0) is the last one <= key; the rows run on in both
-__device__ __forceinline__ int je_row_of(const avsep_jpeg_enc_image* __restrict__ images, int n, long long key, bool by_interval) {
+__device__ __forceinline__ int je_row_of(const avsep_jpeg_image* __restrict__ images, int n, long long key, bool by_interval) {
   int lo = 0, hi = n - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -34,15 +34,15 @@ __device__ __forceinline__ int je_row_of(const avsep_jpeg_enc_image* __restrict_
 
 // Block b of the workspace: its image's row (checked), and where it stands in it.
 struct JeWhere {
-  avsep_jpeg_enc_image im;
+  avsep_jpeg_image im;
   long long lb, mcu;                   // block and MCU inside the image
   int i, c, luma, per_mcu;             // block inside the MCU, its component, luma blocks and all blocks of an MCU
 };
-__device__ __forceinline__ bool je_where(const avsep_jpeg_enc_image* __restrict__ images, int n_images, long long ws_blocks, long long b,
+__device__ __forceinline__ bool je_where(const avsep_jpeg_image* __restrict__ images, int n_images, long long ws_blocks, long long b,
                                          JeWhere& w) {
   w.im = images[je_row_of(images, n_images, b, false)];
   long long nblocks = 0, nintervals = 0;
-  if (!jp_enc_image_ok(w.im, &nblocks, &nintervals) || !jp_inside(w.im.block0, nblocks, ws_blocks)) return false;
+  if (!jp_image_ok(w.im, &nblocks, &nintervals) || !jp_inside(w.im.block0, nblocks, ws_blocks)) return false;
   w.lb = b - w.im.block0;
   if (w.lb < 0 || w.lb >= nblocks) return false;
   w.luma = w.im.hs * w.im.vs, w.per_mcu = w.luma + w.im.ncomp - 1;
@@ -54,7 +54,7 @@ __device__ __forceinline__ bool je_where(const avsep_jpeg_enc_image* __restrict_
 
 // sample (y, x) of component c's plane, downsampled: source coordinates clamped to the picture, and rows below the downsampled
 // plane repeat its last row (include/avsep.h: edges)
-__device__ __forceinline__ int je_sample(const uint8_t* __restrict__ px, const avsep_jpeg_enc_image& im, int c, int y, int x) {
+__device__ __forceinline__ int je_sample(const uint8_t* __restrict__ px, const avsep_jpeg_image& im, int c, int y, int x) {
   if (im.ncomp == 1) return px[(long long)min(y, im.H - 1) * im.W + min(x, im.W - 1)];
   if (c == 0) {
     const uint8_t* p = px + ((long long)min(y, im.H - 1) * im.W + min(x, im.W - 1)) * 3;
@@ -75,13 +75,13 @@ __device__ __forceinline__ int je_sample(const uint8_t* __restrict__ px, const a
 
 // lane = one block: grid-strided over the workspace
 __global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_coef_kernel(const uint8_t* __restrict__ pixels, long long pixel_bytes,
-                                                                 const avsep_jpeg_enc_image* __restrict__ images, int n_images,
+                                                                 const avsep_jpeg_image* __restrict__ images, int n_images,
                                                                  const int32_t* __restrict__ tables, long long table_words,
                                                                  int16_t* __restrict__ coef, long long ws_blocks) {
   for (long long b = (long long)blockIdx.x * JE_BLOCK + threadIdx.x; b < ws_blocks; b += (long long)gridDim.x * JE_BLOCK) {
     JeWhere w;
     if (!je_where(images, n_images, ws_blocks, b, w)) continue;
-    const avsep_jpeg_enc_image& im = w.im;
+    const avsep_jpeg_image& im = w.im;
     if (!jp_inside(im.pix_off, (long long)im.H * im.W * im.ncomp, pixel_bytes)) continue;
     const int qoff = w.c == 0 ? im.quant[0] : (w.c == 1 ? im.quant[1] : im.quant[2]);
     if (!jp_inside(qoff, JP_QUANT_WORDS, table_words)) continue;
@@ -187,7 +187,7 @@ struct JeCode {
 };
 __device__ __forceinline__ bool je_code(const JeWhere& w, const int32_t* __restrict__ tables, long long table_words,
                                         const int16_t* __restrict__ coef, JeCode& k) {
-  const avsep_jpeg_enc_image& im = w.im;
+  const avsep_jpeg_image& im = w.im;
   const int doff = w.c == 0 ? im.dc[0] : (w.c == 1 ? im.dc[1] : im.dc[2]);
   const int aoff = w.c == 0 ? im.ac[0] : (w.c == 1 ? im.ac[1] : im.ac[2]);
   if (!jp_inside(doff, JP_ENC_HUFF_WORDS, table_words) || !jp_inside(aoff, JP_ENC_HUFF_WORDS, table_words)) return false;
@@ -214,7 +214,7 @@ struct JeCount {
 };
 
 __global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_count_kernel(const int16_t* __restrict__ coef, long long ws_blocks,
-                                                                  const avsep_jpeg_enc_image* __restrict__ images, int n_images,
+                                                                  const avsep_jpeg_image* __restrict__ images, int n_images,
                                                                   const int32_t* __restrict__ tables, long long table_words,
                                                                   int32_t* __restrict__ bits) {
   for (long long b = (long long)blockIdx.x * JE_BLOCK + threadIdx.x; b < ws_blocks; b += (long long)gridDim.x * JE_BLOCK) {
@@ -289,12 +289,12 @@ static int je_running_sum(const int32_t* in, long long n, long long* out, long l
 
 // Interval k of the batch: its image's row (checked) and its blocks [*b0, *b1) in the workspace; *local: its number in the image,
 // *count: the image's intervals, *row: the image.
-__device__ __forceinline__ bool je_interval(const avsep_jpeg_enc_image* __restrict__ images, int n_images, long long ws_blocks, long long k,
+__device__ __forceinline__ bool je_interval(const avsep_jpeg_image* __restrict__ images, int n_images, long long ws_blocks, long long k,
                                             long long* b0, long long* b1, long long* local, long long* count, int* row) {
   *row = je_row_of(images, n_images, k, true);
-  const avsep_jpeg_enc_image im = images[*row];
+  const avsep_jpeg_image im = images[*row];
   long long nblocks = 0;
-  if (!jp_enc_image_ok(im, &nblocks, count) || !jp_inside(im.block0, nblocks, ws_blocks)) return false;
+  if (!jp_image_ok(im, &nblocks, count) || !jp_inside(im.block0, nblocks, ws_blocks)) return false;
   *local = k - im.interval0;
   if (*local < 0 || *local >= *count) return false;
   const long long mcus = (long long)im.mcux * im.mcuy, per = im.restart ? im.restart : mcus;
@@ -305,7 +305,7 @@ __device__ __forceinline__ bool je_interval(const avsep_jpeg_enc_image* __restri
 }
 
 // lane = one interval: its bytes before stuffing
-__global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_interval_kernel(const avsep_jpeg_enc_image* __restrict__ images, int n_images,
+__global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_interval_kernel(const avsep_jpeg_image* __restrict__ images, int n_images,
                                                                      long long ws_blocks, long long n_intervals,
                                                                      const long long* __restrict__ pos, int32_t* __restrict__ ivl_bytes) {
   for (long long k = (long long)blockIdx.x * JE_BLOCK + threadIdx.x; k < n_intervals; k += (long long)gridDim.x * JE_BLOCK) {
@@ -347,7 +347,7 @@ struct JePack {
 };
 
 __global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_pack_kernel(const int16_t* __restrict__ coef, long long ws_blocks,
-                                                                 const avsep_jpeg_enc_image* __restrict__ images, int n_images,
+                                                                 const avsep_jpeg_image* __restrict__ images, int n_images,
                                                                  long long n_intervals, const int32_t* __restrict__ tables,
                                                                  long long table_words, const long long* __restrict__ pos,
                                                                  const long long* __restrict__ ivl_off, uint32_t* __restrict__ words,
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_stuff_kernel(const uint8_t*
   }
 }
 // lane = one interval: the marker after it, RSTn or EOI; an image's last interval also says where the image lies
-__global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_marker_kernel(const avsep_jpeg_enc_image* __restrict__ images, int n_images,
+__global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_marker_kernel(const avsep_jpeg_image* __restrict__ images, int n_images,
                                                                    long long ws_blocks, long long n_intervals,
                                                                    const long long* __restrict__ out_off, uint8_t* __restrict__ out,
                                                                    long long out_bytes, long long* __restrict__ sizes) {
@@ -456,21 +456,16 @@ __global__ __launch_bounds__(JE_BLOCK) void jpeg_enc_marker_kernel(const avsep_j
   }
 }
 
-extern "C" int avsep_jpeg_enc_plan_check(const avsep_jpeg_enc_image* images, int32_t n_images, int64_t pixel_bytes, int64_t table_words,
+extern "C" int avsep_jpeg_enc_plan_check(const avsep_jpeg_image* images, int32_t n_images, int64_t pixel_bytes, int64_t table_words,
                                          int64_t ws_blocks, int64_t n_intervals) {
   if (!images || n_images < 1 || n_images > (1 << 24) || pixel_bytes < 1 || table_words < 1 || ws_blocks < 1 || ws_blocks > (1LL << 32) ||
       n_intervals < 1)
     return AVSEP_ERR_ARG;
   long long block = 0, interval = 0;
   for (int i = 0; i < n_images; ++i) {
-    const avsep_jpeg_enc_image& im = images[i];
     long long nblocks = 0, nintervals = 0;
-    if (!jp_enc_image_ok(im, &nblocks, &nintervals) || im.block0 != block || im.interval0 != interval) return AVSEP_ERR_ARG;
-    if (!jp_inside(im.pix_off, (long long)im.H * im.W * im.ncomp, pixel_bytes)) return AVSEP_ERR_ARG;
-    for (int c = 0; c < im.ncomp; ++c)
-      if (!jp_inside(im.quant[c], JP_QUANT_WORDS, table_words) || !jp_inside(im.dc[c], JP_ENC_HUFF_WORDS, table_words) ||
-          !jp_inside(im.ac[c], JP_ENC_HUFF_WORDS, table_words))
-        return AVSEP_ERR_ARG;
+    if (!jp_row_ok(images[i], images[i].ncomp, JP_ENC_HUFF_WORDS, pixel_bytes, table_words, &nblocks, &nintervals)) return AVSEP_ERR_ARG;
+    if (images[i].block0 != block || images[i].interval0 != interval) return AVSEP_ERR_ARG;
     block += nblocks, interval += nintervals;
   }
   return block == ws_blocks && interval == n_intervals ? AVSEP_OK : AVSEP_ERR_ARG;
@@ -481,7 +476,7 @@ static bool je_counts_ok(int32_t n_images, int64_t ws_blocks, int64_t n_interval
          n_intervals <= ws_blocks && table_words >= 1;
 }
 
-extern "C" int avsep_jpeg_enc_coef(const uint8_t* pixels, int64_t pixel_bytes, const avsep_jpeg_enc_image* images, int32_t n_images,
+extern "C" int avsep_jpeg_enc_coef(const uint8_t* pixels, int64_t pixel_bytes, const avsep_jpeg_image* images, int32_t n_images,
                                    const int32_t* tables, int64_t table_words, int16_t* coef, int64_t ws_blocks, avsep_stream_t stream) {
   if (!pixels || !images || !tables || !coef || pixel_bytes < 1 || !je_counts_ok(n_images, ws_blocks, 1, table_words)) return AVSEP_ERR_ARG;
   if ((uintptr_t)coef % 16) return AVSEP_ERR_ARG;                              // a block is moved as eight 16-byte pieces
@@ -491,7 +486,7 @@ extern "C" int avsep_jpeg_enc_coef(const uint8_t* pixels, int64_t pixel_bytes, c
   return AVSEP_OK;
 }
 
-extern "C" int avsep_jpeg_enc_count(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_enc_image* images, int32_t n_images,
+extern "C" int avsep_jpeg_enc_count(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_image* images, int32_t n_images,
                                     int64_t n_intervals, const int32_t* tables, int64_t table_words, int32_t* bits, int64_t* pos,
                                     int32_t* ivl_bytes, int64_t* ivl_off, int64_t* tiles, int64_t tile_words, avsep_stream_t stream) {
   if (!coef || !images || !tables || !bits || !pos || !ivl_bytes || !ivl_off || !tiles) return AVSEP_ERR_ARG;
@@ -509,7 +504,7 @@ extern "C" int avsep_jpeg_enc_count(const int16_t* coef, int64_t ws_blocks, cons
   return je_running_sum(ivl_bytes, n_intervals, (long long*)ivl_off, (long long*)tiles, s);
 }
 
-extern "C" int avsep_jpeg_enc_pack(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_enc_image* images, int32_t n_images,
+extern "C" int avsep_jpeg_enc_pack(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_image* images, int32_t n_images,
                                    int64_t n_intervals, const int32_t* tables, int64_t table_words, const int64_t* pos,
                                    const int64_t* ivl_off, uint8_t* stream_buf, int64_t stream_bytes, int32_t* groups, int64_t* ffpos,
                                    int64_t* ff0, int32_t* ivl_out, int64_t* out_off, int64_t* tiles, int64_t tile_words,
@@ -538,7 +533,7 @@ extern "C" int avsep_jpeg_enc_pack(const int16_t* coef, int64_t ws_blocks, const
   return je_running_sum(ivl_out, n_intervals, (long long*)out_off, (long long*)tiles, s);
 }
 
-extern "C" int avsep_jpeg_enc_stuff(const uint8_t* stream_buf, int64_t stream_bytes, const avsep_jpeg_enc_image* images, int32_t n_images,
+extern "C" int avsep_jpeg_enc_stuff(const uint8_t* stream_buf, int64_t stream_bytes, const avsep_jpeg_image* images, int32_t n_images,
                                     int64_t n_intervals, const int64_t* ivl_off, const int64_t* ffpos, const int64_t* ff0,
                                     const int64_t* out_off, uint8_t* out, int64_t out_bytes, int64_t* sizes, avsep_stream_t stream) {
   if (!stream_buf || !images || !ivl_off || !ffpos || !ff0 || !out_off || !out || !sizes) return AVSEP_ERR_ARG;

@@ -1,4 +1,5 @@
-// The parts of the JPEG decoder (include/avsep.h) that the device and a plain host compiler share: the limits of a row, the
+// The parts of the JPEG decoder and encoder (include/avsep.h) that the device and a plain host compiler share: the limits of a
+// row (one row type and one check for both directions) and the two plan checks' test of a host row against its buffers, the
 // entropy decoder of one segment (jp_decode_segment: the body of jpeg_entropy_kernel's lanes, and of the host program the
 // damaged-input test builds under the sanitizers), and the islow inverse DCT pass.  No HIP header is needed to compile it.
 #pragma once
@@ -19,19 +20,36 @@ enum {
   JP_ST_BOUND = 128, JP_ST_ROW = 256, JP_ST_LEFTOVER = 512
 };
 
-// What a row says about its image, checked: false = outside the limits of include/avsep.h.  nblocks: all its blocks.
-JP_HD bool jp_image_ok(const avsep_jpeg_image& im, long long* nblocks) {
+constexpr int JP_ENC_HUFF_WORDS = 256;       // an encoder's table, by symbol: (code length << 16) | code, 0 = the table has no such symbol
+static_assert(sizeof(avsep_jpeg_image) == 96, "one row for both directions (include/avsep.h); jpeg.py's IMAGE is its dtype");
+
+// What a row says about its image, checked: false = outside the limits of include/avsep.h.  nblocks: all its blocks (an
+// encoder's dummy ones included); nintervals: its restart intervals (1 without restarts).
+JP_HD bool jp_image_ok(const avsep_jpeg_image& im, long long* nblocks, long long* nintervals) {
   if (im.H < 1 || im.H > JP_MAX_SIDE || im.W < 1 || im.W > JP_MAX_SIDE) return false;
   if (im.ncomp != 1 && im.ncomp != 3) return false;
   const bool form = im.ncomp == 1 ? (im.hs == 1 && im.vs == 1) : ((im.hs == 1 || im.hs == 2) && (im.vs == 1 || im.vs == 2) && im.vs <= im.hs);
   if (!form) return false;
   if (im.mcux != (im.W + 8 * im.hs - 1) / (8 * im.hs) || im.mcuy != (im.H + 8 * im.vs - 1) / (8 * im.vs)) return false;
-  if (im.restart < 0 || im.restart > 65535) return false;
-  *nblocks = (long long)im.mcux * im.mcuy * (im.hs * im.vs + im.ncomp - 1);
+  if (im.restart < 0 || im.restart > 65535 || im.pix_off < 0 || im.block0 < 0 || im.interval0 < 0) return false;
+  const long long mcus = (long long)im.mcux * im.mcuy;
+  *nblocks = mcus * (im.hs * im.vs + im.ncomp - 1);
+  *nintervals = im.restart ? (mcus + im.restart - 1) / im.restart : 1;
   return true;
 }
 // [off, off + len) inside [0, size), without forming off + len
 JP_HD bool jp_inside(long long off, long long len, long long size) { return off >= 0 && len >= 0 && len <= size && off <= size - len; }
+// A HOST row against its limits and its buffers, for the two plan checks: its pixels (H*W*pixel_comps bytes) inside pixel_bytes
+// and every component's three tables (Huffman tables of huff_words) inside table_words.
+static inline bool jp_row_ok(const avsep_jpeg_image& im, int pixel_comps, int huff_words, long long pixel_bytes, long long table_words,
+                             long long* nblocks, long long* nintervals) {
+  if (!jp_image_ok(im, nblocks, nintervals) || !jp_inside(im.pix_off, (long long)im.H * im.W * pixel_comps, pixel_bytes)) return false;
+  for (int c = 0; c < im.ncomp; ++c)
+    if (!jp_inside(im.quant[c], JP_QUANT_WORDS, table_words) || !jp_inside(im.dc[c], huff_words, table_words) ||
+        !jp_inside(im.ac[c], huff_words, table_words))
+      return false;
+  return true;
+}
 
 // The bits of one segment, most significant first.  Bytes are read from p[pos], pos in [begin, end) only; FF 00 is one FF;
 // FF followed by anything else (or by the end) ends the real bits.  Past them the reader hands out zeros, as many as asked,
@@ -122,8 +140,8 @@ JP_HD int jp_decode_segment(const uint8_t* __restrict__ bytes, long long nbytes,
   int32_t* word = status + seg.image;
 #define JP_STOP(bit) do { JP_FLAG(word, (bit)); return (bit); } while (0)
   const avsep_jpeg_image im = images[seg.image];
-  long long nblocks = 0;
-  if (!jp_image_ok(im, &nblocks) || !jp_inside(im.block0, nblocks, ws_blocks)) JP_STOP(JP_ST_ROW);
+  long long nblocks = 0, nintervals = 0;
+  if (!jp_image_ok(im, &nblocks, &nintervals) || !jp_inside(im.block0, nblocks, ws_blocks)) JP_STOP(JP_ST_ROW);
   const long long mcus_all = (long long)im.mcux * im.mcuy;
   if (seg.mcus < 1 || !jp_inside(seg.mcu0, seg.mcus, mcus_all)) JP_STOP(JP_ST_BLOCK);
   if (seg.begin < 0 || seg.end < seg.begin || seg.end > nbytes) JP_STOP(JP_ST_RANGE);
@@ -220,22 +238,7 @@ JP_HD void jp_idct_1d(const int d0, const int d1, const int d2, const int d3, co
   o[3] = (tmp13 + tmp0 + half) >> shift, o[4] = (tmp13 - tmp0 + half) >> shift;
 }
 
-// ---- the encoder (jpeg_enc.hip): what a row of avsep_jpeg_enc_image says, checked as jp_image_ok checks a decoder's row.
-// nblocks: all its blocks, the dummy ones included; nintervals: its restart intervals (1 without restarts).
-constexpr int JP_ENC_HUFF_WORDS = 256;       // by symbol: (code length << 16) | code, 0 = the table has no such symbol
-JP_HD bool jp_enc_image_ok(const avsep_jpeg_enc_image& im, long long* nblocks, long long* nintervals) {
-  if (im.H < 1 || im.H > JP_MAX_SIDE || im.W < 1 || im.W > JP_MAX_SIDE) return false;
-  if (im.ncomp != 1 && im.ncomp != 3) return false;
-  const bool form = im.ncomp == 1 ? (im.hs == 1 && im.vs == 1) : ((im.hs == 1 || im.hs == 2) && (im.vs == 1 || im.vs == 2) && im.vs <= im.hs);
-  if (!form) return false;
-  if (im.mcux != (im.W + 8 * im.hs - 1) / (8 * im.hs) || im.mcuy != (im.H + 8 * im.vs - 1) / (8 * im.vs)) return false;
-  if (im.restart < 0 || im.restart > 65535 || im.pix_off < 0 || im.block0 < 0 || im.interval0 < 0) return false;
-  const long long mcus = (long long)im.mcux * im.mcuy;
-  *nblocks = mcus * (im.hs * im.vs + im.ncomp - 1);
-  *nintervals = im.restart ? (mcus + im.restart - 1) / im.restart : 1;
-  return true;
-}
-
+// ---- the encoder (jpeg_enc.hip)
 // One pass of libjpeg's islow forward DCT over eight values, in place: CONST_BITS = 13, PASS1_BITS = 2.  The row pass
 // (second = false) leaves its results scaled up by 4, the column pass (second = true) takes that scaling out again, so a block
 // ends 8 times the true DCT.  Samples are 8 bit less 128: no value formed in either pass leaves int32.

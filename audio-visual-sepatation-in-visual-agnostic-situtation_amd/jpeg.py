@@ -11,19 +11,21 @@ for every input, and a file Pillow cannot read raises as it does there.
 The output layout is the one ``frames.plan_batch`` takes: every frame [H,W,3] uint8, back to back, in file order.
 
 The way back (csrc/jpeg_enc.hip): ``encode`` writes uint8 pictures on the device as baseline JPEG files, byte for byte the files
-Pillow's ``save`` writes; ``encode_header`` / ``encode_plan`` / ``encode_launch`` are its parts.  See the second half of this file."""
+Pillow's ``save`` writes; ``encode_header`` / ``encode_plan`` / ``encode_launch`` are its parts.  See the second half of this file.
+Both planners lay pictures out through the same pieces: ``Form``, ``Tables``, ``_cut``, ``_rows`` and ``Chunk``, over one IMAGE row."""
 import io
 import os
 import struct
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import kernels as K
-from .lib import AvsepError, JpegEncImage, JpegImage, JpegSegment, got
+from .lib import AvsepError, JpegImage, JpegSegment, got
 
-IMAGE = np.dtype(JpegImage)          # include/avsep.h: avsep_jpeg_image
+IMAGE = np.dtype(JpegImage)          # include/avsep.h: avsep_jpeg_image, the row of both directions
 SEGMENT = np.dtype(JpegSegment)      # include/avsep.h: avsep_jpeg_segment
 MAX_SIDE = 16384                     # csrc/jpeg_parts.h: JP_MAX_SIDE
 HUFF_WORDS = 256 + 17 + 17 + 256     # look-ahead, maxcode, value offset, values (csrc/jpeg_parts.h: JP_HUFF_WORDS)
@@ -204,11 +206,33 @@ def probe(data):
     return Info(H, W, comps, qt, huff, restart, scan, begin, end)
 
 
+class Form(namedtuple("Form", "H W ncomp hs vs mcux mcuy restart")):
+    """One picture as both directions lay it out: its size, components (1 | 3), luma sampling, MCUs across and down, and MCUs
+    per restart interval (0 = none).  ``of`` counts the MCUs; restart_rows = MCU rows per interval, which win, as in libjpeg."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, H, W, ncomp, hs, vs, restart, restart_rows=0):
+        mcux = -(-W // (8 * hs))
+        return cls(H, W, ncomp, hs, vs, mcux, -(-H // (8 * vs)), min(restart_rows * mcux, 65535) if restart_rows else restart)
+
+    @property
+    def blocks(self):
+        return self.mcux * self.mcuy * (self.hs * self.vs + self.ncomp - 1)
+
+    @property
+    def intervals(self):
+        return -(-(self.mcux * self.mcuy) // self.restart) if self.restart else 1
+
+
+def _form(info):
+    return Form.of(info.H, info.W, len(info.components), info.components[0][1], info.components[0][2], info.restart)
+
+
 def geometry(info):
     """-> (hs, vs, MCUs across, MCUs down, blocks) of a probed file."""
-    hs, vs = info.components[0][1], info.components[0][2]
-    mcux, mcuy = -(-info.W // (8 * hs)), -(-info.H // (8 * vs))
-    return hs, vs, mcux, mcuy, mcux * mcuy * (hs * vs + len(info.components) - 1)
+    f = _form(info)
+    return f.hs, f.vs, f.mcux, f.mcuy, f.blocks
 
 
 def segments(info, data):
@@ -252,12 +276,71 @@ def huffman_words(counts, values):
     return w
 
 
-class Chunk:
-    """The images [a, b) of a plan's rows that share one coefficient workspace: their segment rows (image indices count from
-    a), the blocks they need, and the most blocks and pixels any one of them has (the launch grids)."""
+class Tables:
+    """Tables interned into one int32 buffer: ``at(key, make, *args)`` -> the word offset of the table of ``key``, which
+    ``make(*args)`` gives the first time the key is seen; ``buffer()`` -> all of them back to back."""
 
-    def __init__(self, a, b, segs, blocks, max_blocks, max_pixels):
-        self.a, self.b, self.segs, self.blocks, self.max_blocks, self.max_pixels = a, b, segs, blocks, max_blocks, max_pixels
+    def __init__(self):
+        self.parts, self.where, self.words = [], {}, 0
+
+    def at(self, key, make, *args):
+        if key not in self.where:
+            t = np.asarray(make(*args), dtype=np.int32)
+            self.where[key] = self.words
+            self.parts.append(t)
+            self.words += len(t)
+        return self.where[key]
+
+    def buffer(self):
+        return np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=np.int32)
+
+
+class Chunk:
+    """The images [a, b) of a plan that share one coefficient workspace: their rows (``images``, a view; blocks and intervals
+    count from 0 in the chunk) and how many blocks and restart intervals they have.  ``plan`` adds what decoding needs: the
+    SEGMENT rows (image indices count from a) and the most blocks and pixels any one image has (the launch grids)."""
+
+    def __init__(self, a, b, images, blocks, intervals):
+        self.a, self.b, self.images, self.blocks, self.intervals = a, b, images, blocks, intervals
+        self.segs, self.max_blocks, self.max_pixels = None, 0, 0
+
+
+def _cap_blocks(who, cap):
+    if int(cap) // BLOCK_BYTES < 1:
+        raise AvsepError(f"{who} takes a workspace cap of at least {BLOCK_BYTES} bytes, got {cap!r}")
+    return int(cap) // BLOCK_BYTES
+
+
+def _cut(blocks, cap_blocks, most):
+    """Images of ``blocks`` blocks each (none above cap_blocks) -> the ranges [(a, b)] that share a workspace of at most
+    cap_blocks blocks and ``most`` images: chunks of about equal size, as few as the cap allows, none of them a small remainder."""
+    total = sum(blocks)
+    target = -(-total // max(1, -(-total // cap_blocks)))
+    cuts, a, block0 = [], 0, 0
+    for r, nb in enumerate(blocks):
+        if block0 and (block0 + nb > cap_blocks or block0 >= target or r - a >= most):
+            cuts.append((a, r))
+            a, block0 = r, 0
+        block0 += nb
+    return cuts + [(a, len(blocks))] if blocks else cuts
+
+
+def _rows(forms, pix_off, table_off, cuts):
+    """One IMAGE row per form -> (rows, [Chunk]).  pix_off: every image's first byte in the pixel buffer; table_off: per image
+    and component the word offsets (quantiser, DC table, AC table); block0 and interval0 count from 0 in each range of ``cuts``."""
+    rows = np.zeros(len(forms), dtype=IMAGE)
+    rows["pix_off"] = pix_off
+    for name, column in zip(Form._fields, zip(*forms)):
+        rows[name] = column
+    for r, t in enumerate(table_off):
+        rows["quant"][r, :len(t)], rows["dc"][r, :len(t)], rows["ac"][r, :len(t)] = zip(*t)
+    counts = np.array([(f.blocks, f.intervals) for f in forms], dtype=np.int64).reshape(-1, 2)
+    before = np.cumsum(counts, axis=0) - counts                              # blocks and intervals before an image, over all rows
+    chunks = []
+    for a, b in cuts:
+        rows["block0"][a:b], rows["interval0"][a:b] = (before[a:b] - before[a]).T
+        chunks.append(Chunk(a, b, rows[a:b], *(int(v) for v in counts[a:b].sum(axis=0))))
+    return rows, chunks
 
 
 class DecodePlan:
@@ -273,10 +356,17 @@ def _pillow(data):
     return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)
 
 
+def _natural(q):
+    t = np.zeros(64, dtype=np.int32)
+    t[ZIGZAG] = q
+    return t
+
+
 def plan(files, cap=WORKSPACE_CAP):
     """Pack what the kernels read for ``files`` (a list of bytes) -> DecodePlan:
     bytes: the entropy-coded bytes of the supported files back to back (uint8);
-    images: one IMAGE row per supported file (``index`` = its position in ``files``), block offsets counted per chunk;
+    images: one IMAGE row per supported file (``index`` = its position in ``files``), block offsets counted per chunk and
+      interval0 = the image's first row in its chunk's segments;
     chunks: the images cut so that a chunk's coefficient workspace stays within ``cap`` bytes, each with its SEGMENT rows;
     tables: quantisation tables (64 words, natural order) and Huffman tables (``huffman_words``) in one int32 buffer, equal
       tables shared;
@@ -285,17 +375,17 @@ def plan(files, cap=WORKSPACE_CAP):
     files = [bytes(f) for f in files]
     if not files:
         raise AvsepError("jpeg.plan takes at least one file")
-    cap_blocks = int(cap) // BLOCK_BYTES
-    if cap_blocks < 1:
-        raise AvsepError(f"jpeg.plan takes a workspace cap of at least {BLOCK_BYTES} bytes, got {cap!r}")
-    shapes, fallback, reasons, kept = [], [], {}, []
+    cap_blocks = _cap_blocks("jpeg.plan", cap)
+    shapes, fallback, reasons, kept, forms = [], [], {}, [], []
     for i, f in enumerate(files):
         try:
             info = probe(f)
             segs = segments(info, f)
-            if geometry(info)[4] > cap_blocks:
-                raise Unsupported(f"{geometry(info)[4]} blocks, more than the workspace cap of {cap_blocks}")
+            form = _form(info)
+            if form.blocks > cap_blocks:
+                raise Unsupported(f"{form.blocks} blocks, more than the workspace cap of {cap_blocks}")
             kept.append((i, info, segs))
+            forms.append(form)
             shapes.append((info.H, info.W))
         except Unsupported as e:
             from PIL import Image
@@ -304,55 +394,30 @@ def plan(files, cap=WORKSPACE_CAP):
             w, h = Image.open(io.BytesIO(f)).size
             shapes.append((h, w))
     offsets = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in shapes], dtype=np.int64)])
-    parts, where, words = [], {}, 0
+    tables = Tables()
 
-    def table(key, make):
-        nonlocal words
-        if key not in where:
-            t = make()
-            where[key] = words
-            parts.append(t)
-            words += len(t)
-        return where[key]
-
-    images = np.zeros(len(kept), dtype=IMAGE)
-    chunks, data, nbytes = [], [], 0
-    a, block0, segs_rows, max_blocks, max_pixels = 0, 0, [], 0, 0
-    # chunks of about equal size: as few as the cap allows, none of them a small remainder
-    total = sum(geometry(info)[4] for _, info, _ in kept)
-    target = -(-total // max(1, -(-total // cap_blocks)))
-    for r, (i, info, segs) in enumerate(kept):
-        hs, vs, mcux, mcuy, blocks = geometry(info)
-        if block0 and (block0 + blocks > cap_blocks or block0 >= target or r - a >= MAX_IMAGES):
-            chunks.append(Chunk(a, r, np.array(segs_rows, dtype=SEGMENT), block0, max_blocks, max_pixels))
-            a, block0, segs_rows, max_blocks, max_pixels = r, 0, [], 0, 0
-        row = images[r]
-        row["pix_off"], row["block0"], row["H"], row["W"], row["ncomp"] = offsets[i], block0, info.H, info.W, len(info.components)
-        row["hs"], row["vs"], row["mcux"], row["mcuy"], row["restart"] = hs, vs, mcux, mcuy, info.restart
-        for c, (comp, (d, ac)) in enumerate(zip(info.components, info.scan)):
+    def tables_of(info):
+        for comp, (d, ac) in zip(info.components, info.scan):
             q = info.qtables[comp[3]]
-
-            def natural(q=q):
-                t = np.zeros(64, dtype=np.int32)
-                t[ZIGZAG] = q
-                return t
-            row["quant"][c] = table(("q", q.tobytes()), natural)
-            for name, cls, idx in (("dc", 0, d), ("ac", 1, ac)):
-                counts, values = info.huffman[(cls, idx)]
-                row[name][c] = table(("h", counts.tobytes(), values.tobytes()), lambda: huffman_words(counts, values))
-        shift = nbytes - info.data_begin
-        segs_rows += [(b + shift, e + shift, r - a, m0, n, 0) for b, e, m0, n in segs]
-        data.append(np.frombuffer(files[i], dtype=np.uint8)[info.data_begin:info.data_end])
-        nbytes += info.data_end - info.data_begin
-        block0 += blocks
-        max_blocks, max_pixels = max(max_blocks, blocks), max(max_pixels, info.H * info.W)
-    if kept:
-        chunks.append(Chunk(a, len(kept), np.array(segs_rows, dtype=SEGMENT), block0, max_blocks, max_pixels))
-    data = np.concatenate(data) if data else np.zeros(0, dtype=np.uint8)
-    tables = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-    p = DecodePlan(data, images, [i for i, _, _ in kept], chunks, tables, fallback, reasons, shapes, offsets, int(offsets[-1]))
+            yield [tables.at(("q", q.tobytes()), _natural, q)] + [tables.at(("h", c.tobytes(), v.tobytes()), huffman_words, c, v)
+                                                                   for c, v in (info.huffman[0, d], info.huffman[1, ac])]
+    images, chunks = _rows(forms, [offsets[i] for i, _, _ in kept], [list(tables_of(info)) for _, info, _ in kept],
+                           _cut([f.blocks for f in forms], cap_blocks, MAX_IMAGES))
+    data, nbytes = [], 0
     for ch in chunks:
-        K.jpeg_plan_check(images[ch.a:ch.b], ch.segs, max(len(data), 1), len(tables), p.pixel_bytes, ch.blocks)
+        segs_rows = []
+        for r in range(ch.a, ch.b):
+            i, info, segs = kept[r]
+            shift = nbytes - info.data_begin
+            segs_rows += [(b + shift, e + shift, r - ch.a, m0, n, 0) for b, e, m0, n in segs]
+            data.append(np.frombuffer(files[i], dtype=np.uint8)[info.data_begin:info.data_end])
+            nbytes += info.data_end - info.data_begin
+        ch.segs = np.array(segs_rows, dtype=SEGMENT)
+        ch.max_blocks, ch.max_pixels = max(f.blocks for f in forms[ch.a:ch.b]), max(f.H * f.W for f in forms[ch.a:ch.b])
+    data = np.concatenate(data) if data else np.zeros(0, dtype=np.uint8)
+    p = DecodePlan(data, images, [i for i, _, _ in kept], chunks, tables.buffer(), fallback, reasons, shapes, offsets, int(offsets[-1]))
+    for ch in chunks:
+        K.jpeg_plan_check(ch.images, ch.segs, max(len(data), 1), len(p.tables), p.pixel_bytes, ch.blocks)
     return p
 
 
@@ -419,9 +484,8 @@ def decode_stack(paths, device):
 # ---- writing: uint8 pictures on the device -> baseline JPEG files, byte for byte what Pillow's save gives (csrc/jpeg_enc.hip;
 # include/avsep.h and DESIGN §33 have the rule)
 
-ENC_IMAGE = np.dtype(JpegEncImage)   # include/avsep.h: avsep_jpeg_enc_image
 ENC_HUFF_WORDS = 256                 # by symbol: (length << 16) | code (csrc/jpeg_parts.h: JP_ENC_HUFF_WORDS)
-MAX_ENC_IMAGES = 1 << 24             # images per chunk
+MAX_PICTURES = 1 << 24               # images per chunk
 SAMPLING = {0: (1, 1), 1: (2, 1), 2: (2, 2), "4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
 
 # ITU-T T.81 Annex K: the example quantisers (natural order) and the typical Huffman tables (counts by length, values)
@@ -463,7 +527,7 @@ def huffman_codes(counts, values):
 
 
 def _encode_form(shape, quality, subsampling, restart_blocks, restart_rows):
-    """One picture's arguments, checked -> (H, W, components, hs, vs, MCUs across, MCUs down, restart interval in MCUs)."""
+    """One picture's arguments, checked -> its Form (restart: the interval in MCUs)."""
     shape = tuple(int(s) for s in shape)
     if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
         raise AvsepError(f"jpeg.encode takes pictures [H,W] (grey) or [H,W,3] (RGB), got a shape of {shape}")
@@ -478,10 +542,7 @@ def _encode_form(shape, quality, subsampling, restart_blocks, restart_rows):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 65535:
             raise AvsepError(f"jpeg.encode takes {name} of 0 .. 65535, got {v!r}")
     ncomp = 1 if len(shape) == 2 else 3
-    hs, vs = SAMPLING[subsampling] if ncomp == 3 else (1, 1)
-    mcux, mcuy = -(-W // (8 * hs)), -(-H // (8 * vs))
-    restart = min(int(restart_rows) * mcux, 65535) if restart_rows else int(restart_blocks)      # rows win, as in libjpeg
-    return H, W, ncomp, hs, vs, mcux, mcuy, restart
+    return Form.of(H, W, ncomp, *(SAMPLING[subsampling] if ncomp == 3 else (1, 1)), int(restart_blocks), int(restart_rows))
 
 
 def _segment(marker, body):
@@ -506,14 +567,6 @@ def encode_header(shape, quality=75, subsampling="4:2:0", restart_blocks=0, rest
     return out + _segment(0xDA, bytes([ncomp]) + scan + bytes([0, 63, 0]))
 
 
-class EncodeChunk:
-    """The images [a, b) of an encoding plan that share one workspace: their rows (blocks and intervals count from 0 in the
-    chunk), and how many blocks and restart intervals they have."""
-
-    def __init__(self, a, b, images, blocks, intervals):
-        self.a, self.b, self.images, self.blocks, self.intervals = a, b, images, blocks, intervals
-
-
 class EncodePlan:
     """What the encoding kernels read for a list of pictures: see ``encode_plan``."""
 
@@ -534,58 +587,29 @@ def encode_plan(shapes, quality=75, subsampling="4:2:0", restart_blocks=0, resta
     """Pack what the kernels read to encode pictures of ``shapes`` ((H, W) grey, (H, W, 3) RGB; uint8, back to back in one buffer)
     -> EncodePlan.  quality, subsampling, restart_blocks and restart_rows are one value for all pictures or a list with one
     per picture.
-    forms: per picture (H, W, components, hs, vs, MCUs across, MCUs down, restart interval); headers: its bytes up to SOS;
-    chunks: the pictures cut so that a chunk's coefficient workspace stays within ``cap`` bytes, each with its ENC_IMAGE rows;
+    forms: per picture its Form (H, W, components, hs, vs, MCUs across, MCUs down, restart interval); headers: its bytes up to SOS;
+    chunks: the pictures cut so that a chunk's coefficient workspace stays within ``cap`` bytes, each with its IMAGE rows;
     tables: quantisers (64 words, natural order) and Huffman code tables (``huffman_codes``) in one int32 buffer;
     offsets, pixel_bytes: every picture's first byte in the pixel buffer."""
     shapes = [tuple(int(x) for x in s) for s in shapes]
     n = len(shapes)
     if n < 1:
         raise AvsepError("jpeg.encode_plan takes at least one picture")
-    cap_blocks = int(cap) // BLOCK_BYTES
-    if cap_blocks < 1:
-        raise AvsepError(f"jpeg.encode_plan takes a workspace cap of at least {BLOCK_BYTES} bytes, got {cap!r}")
+    cap_blocks = _cap_blocks("jpeg.encode_plan", cap)
     args = [_per_image(v, n, name) for v, name in ((quality, "quality"), (subsampling, "subsampling"),
                                                    (restart_blocks, "restart_blocks"), (restart_rows, "restart_rows"))]
     forms = [_encode_form(s, *a) for s, a in zip(shapes, zip(*args))]
     headers = [encode_header(s, *a) for s, a in zip(shapes, zip(*args))]
-    offsets = np.concatenate([[0], np.cumsum([f[0] * f[1] * f[2] for f in forms], dtype=np.int64)])
-    parts, where, words = [], {}, 0
-
-    def table(key, make):
-        nonlocal words
-        if key not in where:
-            t = np.asarray(make(), dtype=np.int32)
-            where[key] = words
-            parts.append(t)
-            words += len(t)
-        return where[key]
-
-    blocks_of = [f[5] * f[6] * (f[3] * f[4] + f[2] - 1) for f in forms]
-    for i, nb in enumerate(blocks_of):
-        if nb > cap_blocks:
-            raise AvsepError(f"jpeg.encode_plan: picture {i} has {nb} blocks, more than the workspace cap of {cap_blocks}")
-    total = sum(blocks_of)
-    target = -(-total // max(1, -(-total // cap_blocks)))                      # chunks of about equal size, as in plan
-    rows = np.zeros(n, dtype=ENC_IMAGE)
-    chunks, a, block0, interval0 = [], 0, 0, 0
-    for r, (f, q) in enumerate(zip(forms, args[0])):
-        H, W, ncomp, hs, vs, mcux, mcuy, restart = f
-        if block0 and (block0 + blocks_of[r] > cap_blocks or block0 >= target or r - a >= MAX_ENC_IMAGES):
-            chunks.append(EncodeChunk(a, r, rows[a:r], block0, interval0))
-            a, block0, interval0 = r, 0, 0
-        row = rows[r]
-        row["pix_off"], row["block0"], row["interval0"], row["H"], row["W"], row["ncomp"] = offsets[r], block0, interval0, H, W, ncomp
-        row["hs"], row["vs"], row["mcux"], row["mcuy"], row["restart"] = hs, vs, mcux, mcuy, restart
-        for c in range(ncomp):
-            t = 0 if c == 0 else 1
-            row["quant"][c] = table(("q", int(q), t), lambda: quantisers(int(q), t))
-            row["dc"][c] = table(("h", 0, t), lambda: huffman_codes(*STD_HUFFMAN[(0, t)]))
-            row["ac"][c] = table(("h", 1, t), lambda: huffman_codes(*STD_HUFFMAN[(1, t)]))
-        block0 += blocks_of[r]
-        interval0 += -(-(mcux * mcuy) // restart) if restart else 1
-    chunks.append(EncodeChunk(a, n, rows[a:n], block0, interval0))
-    p = EncodePlan(shapes, forms, headers, chunks, np.concatenate(parts), offsets, int(offsets[-1]))
+    offsets = np.concatenate([[0], np.cumsum([f.H * f.W * f.ncomp for f in forms], dtype=np.int64)])
+    for i, f in enumerate(forms):
+        if f.blocks > cap_blocks:
+            raise AvsepError(f"jpeg.encode_plan: picture {i} has {f.blocks} blocks, more than the workspace cap of {cap_blocks}")
+    tables = Tables()
+    table_off = [[(tables.at(("q", int(q), t), quantisers, int(q), t), tables.at(("h", 0, t), huffman_codes, *STD_HUFFMAN[0, t]),
+                   tables.at(("h", 1, t), huffman_codes, *STD_HUFFMAN[1, t])) for t in (0, 1, 1)[:f.ncomp]]
+                 for f, q in zip(forms, args[0])]
+    _, chunks = _rows(forms, offsets[:-1], table_off, _cut([f.blocks for f in forms], cap_blocks, MAX_PICTURES))
+    p = EncodePlan(shapes, forms, headers, chunks, tables.buffer(), offsets, int(offsets[-1]))
     for ch in chunks:
         K.jpeg_enc_plan_check(ch.images, p.pixel_bytes, len(p.tables), ch.blocks, ch.intervals)
     return p

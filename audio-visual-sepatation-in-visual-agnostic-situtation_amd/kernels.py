@@ -1212,17 +1212,27 @@ def _jpeg_buffers(who, first, typed):
             raise lib.AvsepError(f"{who}: a buffer must be {dtype} [n], contiguous, on {first.device}, got {lib.got(t)}")
 
 
+def _jpeg_rows(who, images, sized, row=lib.JpegImage):
+    """The row count of `images` (uint8 rows of `row`); sized: (tensor, name, least elements)."""
+    n = images.numel() // C.sizeof(row)
+    if n < 1 or images.numel() != n * C.sizeof(row):
+        raise lib.AvsepError(f"{who}: {images.numel()} bytes of rows of {C.sizeof(row)}")
+    for t, name, least in sized:
+        if t.numel() < least:
+            raise lib.AvsepError(f"{who}: {name} has {t.numel()} elements, {least} are needed")
+    return n
+
+
 def jpeg_entropy(data, images, segments, tables, coef, ws_blocks, status):
     """avsep_jpeg_entropy (include/avsep.h): data uint8 [bytes], images / segments uint8 (the checked rows of one chunk), tables
     int32 [words], coef int16 [>= 64 * ws_blocks], status int32 [images] (zeroed), all on one GPU.  coef[:64 * ws_blocks] is
     zeroed and filled; a lane that stops sets its image's status word."""
     _jpeg_buffers("jpeg_entropy", data, ((data, torch.uint8), (images, torch.uint8), (segments, torch.uint8), (tables, torch.int32),
                                          (coef, torch.int16), (status, torch.int32)))
-    n, ns = images.numel() // C.sizeof(lib.JpegImage), segments.numel() // C.sizeof(lib.JpegSegment)
-    if images.numel() != n * C.sizeof(lib.JpegImage) or segments.numel() != ns * C.sizeof(lib.JpegSegment) or status.numel() != n \
-            or coef.numel() < 64 * int(ws_blocks):
-        raise lib.AvsepError(f"jpeg_entropy: {images.numel()} bytes of image rows, {segments.numel()} of segment rows, "
-                             f"{status.numel()} status words, {coef.numel()} coefficients for {ws_blocks} blocks")
+    n = _jpeg_rows("jpeg_entropy", images, ((coef, "coef", 64 * int(ws_blocks)),))
+    ns = _jpeg_rows("jpeg_entropy", segments, (), lib.JpegSegment)
+    if status.numel() != n:
+        raise lib.AvsepError(f"jpeg_entropy: {status.numel()} status words for {n} images")
     call("avsep_jpeg_entropy", ptr(data), data.numel(), ptr(images), n, ptr(segments), ns, ptr(tables), tables.numel(), ptr(coef),
          int(ws_blocks), ptr(status))
 
@@ -1232,17 +1242,15 @@ def jpeg_pixels(coef, planes, ws_blocks, images, max_blocks, max_pixels, tables,
     frames in pixels uint8 [bytes]; images whose status word is set are skipped."""
     _jpeg_buffers("jpeg_pixels", coef, ((coef, torch.int16), (planes, torch.uint8), (images, torch.uint8), (tables, torch.int32),
                                         (status, torch.int32), (pixels, torch.uint8)))
-    n = images.numel() // C.sizeof(lib.JpegImage)
-    if images.numel() != n * C.sizeof(lib.JpegImage) or status.numel() != n or coef.numel() < 64 * int(ws_blocks) \
-            or planes.numel() < 64 * int(ws_blocks):
-        raise lib.AvsepError(f"jpeg_pixels: {images.numel()} bytes of image rows, {status.numel()} status words, {coef.numel()} "
-                             f"coefficients and {planes.numel()} plane bytes for {ws_blocks} blocks")
+    n = _jpeg_rows("jpeg_pixels", images, ((coef, "coef", 64 * int(ws_blocks)), (planes, "planes", 64 * int(ws_blocks))))
+    if status.numel() != n:
+        raise lib.AvsepError(f"jpeg_pixels: {status.numel()} status words for {n} images")
     call("avsep_jpeg_pixels", ptr(coef), ptr(planes), int(ws_blocks), ptr(images), n, int(max_blocks), int(max_pixels), ptr(tables),
          tables.numel(), ptr(status), ptr(pixels), pixels.numel())
 
 
 def jpeg_enc_plan_check(images, pixel_bytes, table_words, ws_blocks, n_intervals):
-    """avsep_jpeg_enc_plan_check (include/avsep.h; host only, no GPU): images = a NumPy array of dtype np.dtype(lib.JpegEncImage),
+    """avsep_jpeg_enc_plan_check (include/avsep.h; host only, no GPU): images = a NumPy array of dtype np.dtype(lib.JpegImage),
     the rows of one chunk.  AvsepError for anything the library refuses."""
     images = np.ascontiguousarray(images)
     rc = lib.load().avsep_jpeg_enc_plan_check(images.ctypes.data, len(images), int(pixel_bytes), int(table_words), int(ws_blocks),
@@ -1253,22 +1261,11 @@ def jpeg_enc_plan_check(images, pixel_bytes, table_words, ws_blocks, n_intervals
                              f"its buffer ({rc})")
 
 
-def _jpeg_enc_rows(who, images, sized):
-    """The row count of `images` (uint8); sized: (tensor, name, least elements)."""
-    n = images.numel() // C.sizeof(lib.JpegEncImage)
-    if n < 1 or images.numel() != n * C.sizeof(lib.JpegEncImage):
-        raise lib.AvsepError(f"{who}: {images.numel()} bytes of image rows")
-    for t, name, least in sized:
-        if t.numel() < least:
-            raise lib.AvsepError(f"{who}: {name} has {t.numel()} elements, {least} are needed")
-    return n
-
-
 def jpeg_enc_coef(pixels, images, tables, coef, ws_blocks):
     """avsep_jpeg_enc_coef (include/avsep.h): pixels uint8 [bytes], images uint8 (the checked rows of one chunk), tables int32
     [words] -> coef int16 [>= 64 * ws_blocks]: every block of the chunk, scan order, zig-zag inside."""
     _jpeg_buffers("jpeg_enc_coef", pixels, ((pixels, torch.uint8), (images, torch.uint8), (tables, torch.int32), (coef, torch.int16)))
-    n = _jpeg_enc_rows("jpeg_enc_coef", images, ((coef, "coef", 64 * int(ws_blocks)),))
+    n = _jpeg_rows("jpeg_enc_coef", images, ((coef, "coef", 64 * int(ws_blocks)),))
     call("avsep_jpeg_enc_coef", ptr(pixels), pixels.numel(), ptr(images), n, ptr(tables), tables.numel(), ptr(coef), int(ws_blocks))
 
 
@@ -1278,8 +1275,8 @@ def jpeg_enc_count(coef, ws_blocks, images, n_intervals, tables, bits, pos, ivl_
     _jpeg_buffers("jpeg_enc_count", coef, ((coef, torch.int16), (images, torch.uint8), (tables, torch.int32), (bits, torch.int32),
                                            (pos, torch.int64), (ivl_bytes, torch.int32), (ivl_off, torch.int64), (tiles, torch.int64)))
     B, I = int(ws_blocks), int(n_intervals)
-    n = _jpeg_enc_rows("jpeg_enc_count", images, ((coef, "coef", 64 * B), (bits, "bits", B), (pos, "pos", B + 1),
-                                                  (ivl_bytes, "ivl_bytes", I), (ivl_off, "ivl_off", I + 1)))
+    n = _jpeg_rows("jpeg_enc_count", images, ((coef, "coef", 64 * B), (bits, "bits", B), (pos, "pos", B + 1),
+                                              (ivl_bytes, "ivl_bytes", I), (ivl_off, "ivl_off", I + 1)))
     call("avsep_jpeg_enc_count", ptr(coef), B, ptr(images), n, I, ptr(tables), tables.numel(), ptr(bits), ptr(pos), ptr(ivl_bytes),
          ptr(ivl_off), ptr(tiles), tiles.numel())
 
@@ -1292,9 +1289,9 @@ def jpeg_enc_pack(coef, ws_blocks, images, n_intervals, tables, pos, ivl_off, st
                                           (ivl_off, torch.int64), (stream_buf, torch.uint8), (groups, torch.int32), (ffpos, torch.int64),
                                           (ff0, torch.int64), (ivl_out, torch.int32), (out_off, torch.int64), (tiles, torch.int64)))
     B, I, G = int(ws_blocks), int(n_intervals), -(-stream_buf.numel() // 64)
-    n = _jpeg_enc_rows("jpeg_enc_pack", images, ((coef, "coef", 64 * B), (pos, "pos", B + 1), (ivl_off, "ivl_off", I + 1),
-                                                 (groups, "groups", G), (ffpos, "ffpos", G + 1), (ff0, "ff0", I), (ivl_out, "ivl_out", I),
-                                                 (out_off, "out_off", I + 1)))
+    n = _jpeg_rows("jpeg_enc_pack", images, ((coef, "coef", 64 * B), (pos, "pos", B + 1), (ivl_off, "ivl_off", I + 1),
+                                             (groups, "groups", G), (ffpos, "ffpos", G + 1), (ff0, "ff0", I), (ivl_out, "ivl_out", I),
+                                             (out_off, "out_off", I + 1)))
     call("avsep_jpeg_enc_pack", ptr(coef), B, ptr(images), n, I, ptr(tables), tables.numel(), ptr(pos), ptr(ivl_off), ptr(stream_buf),
          stream_buf.numel(), ptr(groups), ptr(ffpos), ptr(ff0), ptr(ivl_out), ptr(out_off), ptr(tiles), tiles.numel())
 
@@ -1306,8 +1303,8 @@ def jpeg_enc_stuff(stream_buf, images, n_intervals, ivl_off, ffpos, ff0, out_off
                                                  (ffpos, torch.int64), (ff0, torch.int64), (out_off, torch.int64), (out, torch.uint8),
                                                  (sizes, torch.int64)))
     I, G = int(n_intervals), -(-stream_buf.numel() // 64)
-    n = _jpeg_enc_rows("jpeg_enc_stuff", images, ((ivl_off, "ivl_off", I + 1), (ffpos, "ffpos", G + 1), (ff0, "ff0", I),
-                                                  (out_off, "out_off", I + 1), (out, "out", 1)))
+    n = _jpeg_rows("jpeg_enc_stuff", images, ((ivl_off, "ivl_off", I + 1), (ffpos, "ffpos", G + 1), (ff0, "ff0", I),
+                                              (out_off, "out_off", I + 1), (out, "out", 1)))
     if sizes.numel() != 2 * n:
         raise lib.AvsepError(f"jpeg_enc_stuff: {sizes.numel()} size words for {n} images")
     call("avsep_jpeg_enc_stuff", ptr(stream_buf), stream_buf.numel(), ptr(images), n, I, ptr(ivl_off), ptr(ffpos), ptr(ff0), ptr(out_off),

@@ -51,22 +51,16 @@ class FramesRow(C.Structure):
 
 
 class JpegImage(C.Structure):
-    """avsep_jpeg_image (include/avsep.h): one image of avsep_jpeg_entropy / avsep_jpeg_pixels; np.dtype(JpegImage) is the
-    layout of a table of rows on the host and on the device."""
-    _fields_ = [("pix_off", C.c_int64), ("block0", C.c_int64)] + [(n, C.c_int32) for n in "H W ncomp hs vs mcux mcuy".split()] + \
+    """avsep_jpeg_image (include/avsep.h): one image of the avsep_jpeg_* entry points, decoding and encoding;
+    np.dtype(JpegImage) is the layout of a table of rows on the host and on the device."""
+    _fields_ = [("pix_off", C.c_int64), ("block0", C.c_int64), ("interval0", C.c_int64)] + \
+               [(n, C.c_int32) for n in "H W ncomp hs vs mcux mcuy".split()] + \
                [(n, C.c_int32 * 3) for n in "quant dc ac".split()] + [("restart", C.c_int32), ("reserved", C.c_int32)]
 
 
 class JpegSegment(C.Structure):
     """avsep_jpeg_segment (include/avsep.h): one entropy-coded segment."""
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64)] + [(n, C.c_int32) for n in "image mcu0 mcus reserved".split()]
-
-
-class JpegEncImage(C.Structure):
-    """avsep_jpeg_enc_image (include/avsep.h): one image of the avsep_jpeg_enc_* entry points."""
-    _fields_ = [("pix_off", C.c_int64), ("block0", C.c_int64), ("interval0", C.c_int64)] + \
-               [(n, C.c_int32) for n in "H W ncomp hs vs mcux mcuy".split()] + \
-               [(n, C.c_int32 * 3) for n in "quant dc ac".split()] + [("restart", C.c_int32), ("reserved", C.c_int32)]
 
 
 _P, _I, _F, _D, _Z = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t

@@ -823,17 +823,21 @@ int avsep_frames_prepare_batch(const uint8_t* pixels, int64_t pixel_bytes, const
  *   tables int32 [table_words]: quantisation tables (64 words, NATURAL order) and Huffman tables (546 words: look[256] =
  *     (length << 8) | value by the next 8 bits, 0 = a longer code; maxcode[17] by length, -1 = none; valoff[17], a code's value
  *     is values[valoff[length] + code]; values[256]) anywhere in it, shared by the images that have them;
- *   one row per image and one per entropy-coded segment (a file without restart intervals is one segment): */
+ *   one row per image and one per entropy-coded segment (a file without restart intervals is one segment).  The image row is
+ *   the one the encoder below takes too.  Decoding, block0 is anywhere inside the workspace and interval0 is the index of the
+ *   image's first segment row (the planner fills it; no decoding kernel reads it).  Encoding, the rows' block0 and interval0 run
+ *   on from 0: every row starts where the row before it ends. */
 typedef struct avsep_jpeg_image {
-  int64_t pix_off;                          /* the image's first byte in `pixels` */
+  int64_t pix_off;                          /* the image's first byte in `pixels`: H*W*3 bytes decoded; encoded, H*W*ncomp */
   int64_t block0;                           /* its first block in the coefficient workspace (64 int16 per block) */
+  int64_t interval0;                        /* its first restart interval (1 per image without restarts), counted over the rows */
   int32_t H, W, ncomp;                      /* 1 <= H, W <= 16384; ncomp 1 | 3 */
   int32_t hs, vs;                           /* luma sampling: (1,1), (2,1) or (2,2); (1,1) with one component */
   int32_t mcux, mcuy;                       /* MCUs across and down: ceil(W / (8 hs)), ceil(H / (8 vs)) */
   int32_t quant[3], dc[3], ac[3];           /* word offsets in `tables`, per component */
-  int32_t restart;                          /* MCUs per restart interval, 0 = none */
+  int32_t restart;                          /* MCUs per restart interval, 0 = none (one interval) */
   int32_t reserved;
-} avsep_jpeg_image;
+} avsep_jpeg_image;                         /* 96 bytes.  pix_off, block0, interval0 >= 0 */
 typedef struct avsep_jpeg_segment {
   int64_t begin, end;                       /* its bytes: bytes[begin .. end) */
   int32_t image;                            /* row of `images` */
@@ -895,19 +899,9 @@ int avsep_jpeg_pixels(const int16_t* coef, uint8_t* planes, int64_t ws_blocks, c
  *            size s is written as v + 2^s - 1.  Every 0xFF byte is followed by 0x00.  The last byte of every restart interval
  *            and of the scan is padded with 1-bits; RSTn (n = 0 .. 7 in turn) stands between intervals, EOI at the end.
  * In DEVICE memory: pixels (the images back to back, anywhere in it), tables int32 [table_words] (quantisers: 64 words, NATURAL
- * order, 1 .. 255; Huffman codes: 256 words by symbol, (length << 16) | code, length <= 16, 0 = no such symbol), one row per image: */
-typedef struct avsep_jpeg_enc_image {
-  int64_t pix_off;                          /* the image's first byte in `pixels`: H*W bytes (one component) or H*W*3 */
-  int64_t block0;                           /* its first block in the workspace: the rows' blocks lie back to back from 0 */
-  int64_t interval0;                        /* its first restart interval: the rows' intervals count on from 0 */
-  int32_t H, W, ncomp;                      /* 1 <= H, W <= 16384; ncomp 1 | 3 */
-  int32_t hs, vs;                           /* luma sampling: (1,1), (2,1) or (2,2); (1,1) with one component */
-  int32_t mcux, mcuy;                       /* MCUs across and down: ceil(W / (8 hs)), ceil(H / (8 vs)) */
-  int32_t quant[3], dc[3], ac[3];           /* word offsets in `tables`, per component */
-  int32_t restart;                          /* MCUs per restart interval, 0 = none (one interval) */
-  int32_t reserved;
-} avsep_jpeg_enc_image;
-/* An image's blocks lie in SCAN order: MCU after MCU, in an MCU hs*vs luma blocks, then Cb, then Cr; a block is 64 int16 in
+ * order, 1 .. 255; Huffman codes: 256 words by symbol, (length << 16) | code, length <= 16, 0 = no such symbol), one avsep_jpeg_image row
+ * per image (above), its pixels H*W bytes (one component) or H*W*3.
+ * An image's blocks lie in SCAN order: MCU after MCU, in an MCU hs*vs luma blocks, then Cb, then Cr; a block is 64 int16 in
  * ZIG-ZAG order; dummy blocks are there like any other.  Four stages on the caller's stream, none of which reads anything back
  * (the caller copies the two totals it sizes the next buffer by):
  * avsep_jpeg_enc_plan_check (host only): every HOST row against the limits, block0 and interval0 running on from 0 to ws_blocks
@@ -930,18 +924,18 @@ typedef struct avsep_jpeg_enc_image {
  * every store is checked against its buffer's size: a wrong row gives wrong bytes, not an access outside a buffer.  A null
  * pointer, a count or size < 1, ws_blocks above 2^32, n_images above 2^24, a misaligned coef or stream_buf, or scratch too
  * small is AVSEP_ERR_ARG before any launch. */
-int avsep_jpeg_enc_plan_check(const avsep_jpeg_enc_image* images, int32_t n_images, int64_t pixel_bytes, int64_t table_words,
+int avsep_jpeg_enc_plan_check(const avsep_jpeg_image* images, int32_t n_images, int64_t pixel_bytes, int64_t table_words,
                               int64_t ws_blocks, int64_t n_intervals);
-int avsep_jpeg_enc_coef(const uint8_t* pixels, int64_t pixel_bytes, const avsep_jpeg_enc_image* images, int32_t n_images,
+int avsep_jpeg_enc_coef(const uint8_t* pixels, int64_t pixel_bytes, const avsep_jpeg_image* images, int32_t n_images,
                         const int32_t* tables, int64_t table_words, int16_t* coef, int64_t ws_blocks, avsep_stream_t stream);
-int avsep_jpeg_enc_count(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_enc_image* images, int32_t n_images,
+int avsep_jpeg_enc_count(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_image* images, int32_t n_images,
                          int64_t n_intervals, const int32_t* tables, int64_t table_words, int32_t* bits, int64_t* pos,
                          int32_t* ivl_bytes, int64_t* ivl_off, int64_t* tiles, int64_t tile_words, avsep_stream_t stream);
-int avsep_jpeg_enc_pack(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_enc_image* images, int32_t n_images,
+int avsep_jpeg_enc_pack(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_image* images, int32_t n_images,
                         int64_t n_intervals, const int32_t* tables, int64_t table_words, const int64_t* pos, const int64_t* ivl_off,
                         uint8_t* stream_buf, int64_t stream_bytes, int32_t* groups, int64_t* ffpos, int64_t* ff0, int32_t* ivl_out,
                         int64_t* out_off, int64_t* tiles, int64_t tile_words, avsep_stream_t stream);
-int avsep_jpeg_enc_stuff(const uint8_t* stream_buf, int64_t stream_bytes, const avsep_jpeg_enc_image* images, int32_t n_images,
+int avsep_jpeg_enc_stuff(const uint8_t* stream_buf, int64_t stream_bytes, const avsep_jpeg_image* images, int32_t n_images,
                          int64_t n_intervals, const int64_t* ivl_off, const int64_t* ffpos, const int64_t* ff0,
                          const int64_t* out_off, uint8_t* out, int64_t out_bytes, int64_t* sizes, avsep_stream_t stream);
 

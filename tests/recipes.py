@@ -1,7 +1,7 @@
 """The recipes the pipeline tests share: the small net pairs, the tone mixtures, the CLI argument namespace, the PCM writer,
-the "launches are unreachable" guard and a few one-liners.  A plain helper module like glue_cases.py: no fixtures, no
-tests, and the package is imported only inside the functions that need it.  A recipe that only one test file uses, and
-every float64 reference (*ref.py), stays with that file."""
+the "launches are unreachable" guard, buffers with guard elements around them and a few one-liners.  A plain helper module
+like glue_cases.py: no fixtures, no tests, and the package is imported only inside the functions that need it.  A recipe that
+only one test file uses, and every float64 reference (*ref.py), stays with that file."""
 import argparse
 import itertools
 
@@ -143,6 +143,20 @@ def istft_gain(n_fft, hop, frames):
         s2[m * hop:m * hop + n_fft] += w * w
     keep = slice(n_fft // 2, len(s1) - n_fft // 2)
     return float((s1[keep] / s2[keep]).max())
+
+
+# ---- guarded buffers ---------------------------------------------------------------------------------------------------
+GUARD = 256                                            # elements before and after every buffer
+
+
+def _guarded(n, dtype, fill, dev):
+    """A buffer of n elements inside a larger one filled with ``fill`` -> (the whole, the view)."""
+    whole = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=dev)
+    return whole, whole[GUARD:GUARD + n]
+
+
+def _guards_intact(whole, fill):
+    return bool((whole[:GUARD] == fill).all()) and bool((whole[-GUARD:] == fill).all())
 
 
 # ---- files -------------------------------------------------------------------------------------------------------------

@@ -17,20 +17,9 @@ from avsep_amd import separate as S
 
 import jpeg_cases as JC
 import jpeg_ref as R
-from recipes import tone_mix
+from recipes import _guarded, _guards_intact, tone_mix
 
 pytestmark = pytest.mark.gpu
-GUARD = 256                                            # elements before and after every buffer
-
-
-def _guarded(n, dtype, fill, dev):
-    """A buffer of n elements inside a larger one filled with ``fill`` -> (the whole, the view)."""
-    whole = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=dev)
-    return whole, whole[GUARD:GUARD + n]
-
-
-def _guards_intact(whole, fill):
-    return bool((whole[:GUARD] == fill).all()) and bool((whole[-GUARD:] == fill).all())
 
 
 def _launch(p, dev):

@@ -16,19 +16,10 @@ from avsep_amd import visuals as V
 
 import jpeg_encode_cases as EC
 import recipes
+from recipes import _guarded, _guards_intact
 
 pytestmark = pytest.mark.gpu
-GUARD = 256                                            # elements before and after every buffer
 KEYS = ("quality", "subsampling", "restart_blocks", "restart_rows")
-
-
-def _guarded(n, dtype, fill, dev):
-    whole = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=dev)
-    return whole, whole[GUARD:GUARD + n]
-
-
-def _guards_intact(whole, fill):
-    return bool((whole[:GUARD] == fill).all()) and bool((whole[-GUARD:] == fill).all())
 
 
 def _grid_args():

@@ -134,3 +134,26 @@ def test_wrong_arguments_raise():
         K.jpeg_enc_plan_check(rows, p.pixel_bytes, len(p.tables), ch.blocks, ch.intervals)
     with pytest.raises(AvsepError):
         K.jpeg_enc_plan_check(ch.images, p.pixel_bytes, len(p.tables), ch.blocks + 1, ch.intervals)
+
+
+def test_both_planners_lay_pictures_out_alike():
+    """jpeg.plan over Pillow's files and jpeg.encode_plan over the same shapes and settings: the same rows, chunks and counts."""
+    cases = [(EC.content("smooth", H, W, sub is None), sub, restart) for H, W in ((1, 1), (8, 8), (17, 23), (9, 40), (33, 65))
+             for _, sub in EC.FORMS for _, restart in EC.RESTARTS]
+    assert len(cases) == 80
+    files = [EC.pillow_file(a, **EC.pillow_args(sub, 75, restart)) for a, sub, restart in cases]
+    args = dict(subsampling=[2 if sub is None else sub for _, sub, _ in cases],
+                restart_blocks=[r.get("restart_blocks", 0) for _, _, r in cases], restart_rows=[r.get("restart_rows", 0) for _, _, r in cases])
+    for cap, chunks in ((jpeg.WORKSPACE_CAP, 1), (200 * 128, 13), (135 * 128, 20)):    # 135 blocks: 33 x 65 at 4:4:4, the largest
+        d, e = jpeg.plan(files, cap), jpeg.encode_plan([a.shape for a, _, _ in cases], cap=cap, **args)
+        assert not d.fallback and len(d.images) == 80
+        assert [(c.a, c.b) for c in d.chunks] == [(c.a, c.b) for c in e.chunks] and len(d.chunks) == chunks
+        for c, f in zip(d.chunks, e.chunks):
+            assert c.blocks == f.blocks and len(c.segs) == f.intervals == c.intervals, (cap, c.a)
+        rows = np.concatenate([c.images for c in e.chunks])
+        for field in "H W ncomp hs vs mcux mcuy restart block0 interval0".split():
+            assert np.array_equal(d.images[field], rows[field]), (cap, field)
+        # interval0 is where the image's segment rows begin
+        for c in d.chunks:
+            first = [int(np.flatnonzero(c.segs["image"] == r)[0]) for r in range(c.b - c.a)]
+            assert np.array_equal(d.images["interval0"][c.a:c.b], first), cap

@@ -179,7 +179,7 @@ def test_plan_check_refusals():
     assert L.avsep_jpeg_plan_check(None, 1, ch.segs.ctypes.data, 1, 1, 1, 1, 1) == -1
     with pytest.raises(P.lib.AvsepError, match="avsep_jpeg_plan_check refused"):
         P.kernels.jpeg_plan_check(p.images, ch.segs, len(p.bytes), len(p.tables), p.pixel_bytes, ch.blocks - 1)
-    assert np.dtype(P.lib.JpegImage).itemsize == 88 and np.dtype(P.lib.JpegSegment).itemsize == 32
+    assert np.dtype(P.lib.JpegImage).itemsize == 96 and np.dtype(P.lib.JpegSegment).itemsize == 32
 
 
 # ---- the loader --------------------------------------------------------------------------------------------------------
