@@ -4,6 +4,8 @@
 //                        jp_decode_segment; the same body runs on the host under the sanitizers in the damaged-input test);
 //   jpeg_idct_kernel     one lane per block: dequantise, islow inverse DCT, + 128, clamp -> 64 bytes of the block's plane;
 //   jpeg_colour_kernel   one lane per pixel: fancy chroma upsampling over the component's real size, YCbCr -> RGB.
+// A progressive file (SOF2) fills the same workspace scan by scan: jpeg_scans_kernel, one lane per (scan, restart interval) of one
+// level, launched level after level, then jpeg_bound_kernel over the finished coefficients (include/avsep.h).
 // The rows of images and segments live in device memory and are not trusted with addresses: each kernel checks what it reads
 // from a row against the buffer sizes it was given, and a row that fails leaves its output untouched.
 #include "common.h"
@@ -19,6 +21,47 @@ __global__ __launch_bounds__(1) void jpeg_entropy_kernel(const uint8_t* __restri
                                                          const int32_t* __restrict__ tables, long long table_words,
                                                          int16_t* __restrict__ coef, long long ws_blocks, int32_t* __restrict__ status) {
   jp_decode_segment(bytes, nbytes, images, n_images, segments[blockIdx.x], tables, table_words, coef, ws_blocks, status);
+}
+
+// grid (n_scans), one lane each, as above: the scan rows of ONE level of a chunk's progressive images (jpeg_parts.h: jp_decode_scan)
+__global__ __launch_bounds__(1) void jpeg_scans_kernel(const uint8_t* __restrict__ bytes, long long nbytes,
+                                                       const avsep_jpeg_image* __restrict__ images, int n_images,
+                                                       const avsep_jpeg_scan* __restrict__ scans, int level,
+                                                       const int32_t* __restrict__ tables, long long table_words,
+                                                       int16_t* __restrict__ coef, long long ws_blocks, int32_t* status) {
+  jp_decode_scan(bytes, nbytes, images, n_images, scans[blockIdx.x], level, tables, table_words, coef, ws_blocks, status);
+}
+
+// grid (ceil(max_blocks / JP_BLOCK), n_images): lane = one block of image blockIdx.y, whose 64 finished coefficients it holds
+// against AVSEP_JPEG_MAX_COEF (a baseline lane does this as it decodes; a progressive coefficient is whole only after its last scan)
+__global__ __launch_bounds__(JP_BLOCK) void jpeg_bound_kernel(const int16_t* __restrict__ coef, long long ws_blocks,
+                                                              const avsep_jpeg_image* __restrict__ images,
+                                                              const int32_t* __restrict__ tables, long long table_words,
+                                                              int32_t* status) {
+  const int img = blockIdx.y;
+  const avsep_jpeg_image im = images[img];
+  long long nblocks = 0, nintervals = 0;
+  if (!jp_image_ok(im, &nblocks, &nintervals) || !jp_inside(im.block0, nblocks, ws_blocks)) return;
+  const long long blk = (long long)blockIdx.x * JP_BLOCK + threadIdx.x;
+  if (blk >= nblocks) return;
+  const long long luma = (long long)im.mcux * im.mcuy * im.hs * im.vs;
+  const int c = blk < luma ? 0 : 1 + (int)((blk - luma) / ((long long)im.mcux * im.mcuy));
+  const int qoff = c == 0 ? im.quant[0] : (c == 1 ? im.quant[1] : im.quant[2]);
+  if (c > 2 || !jp_inside(qoff, JP_QUANT_WORDS, table_words)) return;
+  const int32_t* __restrict__ q = tables + qoff;
+  const uint4* __restrict__ src = (const uint4*)(coef + (im.block0 + blk) * 64);
+  bool over = false;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const uint4 v = src[r];
+    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long lo = (long long)(int16_t)(u[j] & 0xffffu) * q[r * 8 + 2 * j], hi = (long long)(int16_t)(u[j] >> 16) * q[r * 8 + 2 * j + 1];
+      over |= lo > AVSEP_JPEG_MAX_COEF || lo < -AVSEP_JPEG_MAX_COEF || hi > AVSEP_JPEG_MAX_COEF || hi < -AVSEP_JPEG_MAX_COEF;
+    }
+  }
+  if (over) atomicOr(status + img, JP_ST_BOUND);
 }
 
 // grid (ceil(max_blocks / JP_BLOCK), n_images): lane = one block of image blockIdx.y
@@ -159,6 +202,55 @@ extern "C" int avsep_jpeg_entropy(const uint8_t* bytes, int64_t nbytes, const av
   if (hipMemsetAsync(coef, 0, (size_t)ws_blocks * 128, (hipStream_t)stream) != hipSuccess) return AVSEP_ERR_LAUNCH;
   hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(n_segments), dim3(1), 0, (hipStream_t)stream, bytes, (long long)nbytes, images,
                      n_images, segments, tables, (long long)table_words, coef, (long long)ws_blocks, status);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_jpeg_scan_check(const avsep_jpeg_image* images, int32_t n_images, const avsep_jpeg_scan* scans, int32_t n_scans,
+                                     int64_t nbytes, int64_t table_words, int64_t pixel_bytes, int64_t ws_blocks) {
+  if (!images || !scans || n_images < 1 || n_scans < 1 || nbytes < 1 || table_words < 1 || pixel_bytes < 1 || ws_blocks < 1)
+    return AVSEP_ERR_ARG;
+  for (int i = 0; i < n_images; ++i) {
+    long long nblocks = 0, nintervals = 0;
+    if (!jp_row_ok(images[i], 3, JP_HUFF_WORDS, pixel_bytes, table_words, &nblocks, &nintervals)) return AVSEP_ERR_ARG;
+    if (!jp_inside(images[i].block0, nblocks, ws_blocks)) return AVSEP_ERR_ARG;
+  }
+  for (int s = 0; s < n_scans; ++s) {
+    const avsep_jpeg_scan& g = scans[s];
+    if (g.image < 0 || g.image >= n_images) return AVSEP_ERR_ARG;
+    long long bw = 0, units_all = 0;
+    int ncmp = 0, c1 = 0;
+    if (!jp_scan_ok(images[g.image], g, &ncmp, &c1, &bw, &units_all)) return AVSEP_ERR_ARG;
+    if (g.begin < 0 || g.end < g.begin || g.end > nbytes) return AVSEP_ERR_ARG;
+    if (g.units < 1 || !jp_inside(g.unit0, g.units, units_all)) return AVSEP_ERR_ARG;
+    if (g.ss > 0 || g.ah == 0)
+      for (int c = 0; c < 3; ++c)
+        if (((g.comps >> c) & 1) && !jp_inside(g.table[c], JP_HUFF_WORDS, table_words)) return AVSEP_ERR_ARG;
+  }
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_jpeg_scans(const uint8_t* bytes, int64_t nbytes, const avsep_jpeg_image* images, int32_t n_images,
+                                const avsep_jpeg_scan* scans, int32_t n_scans, int32_t level, int32_t zero, const int32_t* tables,
+                                int64_t table_words, int16_t* coef, int64_t ws_blocks, int32_t* status, avsep_stream_t stream) {
+  if (!bytes || !images || !scans || !tables || !coef || !status) return AVSEP_ERR_ARG;
+  if (nbytes < 1 || n_images < 1 || n_scans < 1 || table_words < 1 || ws_blocks < 1 || ws_blocks > (1LL << 32)) return AVSEP_ERR_ARG;
+  if (level < 0 || level >= AVSEP_JPEG_MAX_SCANS) return AVSEP_ERR_ARG;
+  if (zero && hipMemsetAsync(coef, 0, (size_t)ws_blocks * 128, (hipStream_t)stream) != hipSuccess) return AVSEP_ERR_LAUNCH;
+  hipLaunchKernelGGL(jpeg_scans_kernel, dim3(n_scans), dim3(1), 0, (hipStream_t)stream, bytes, (long long)nbytes, images, n_images,
+                     scans, (int)level, tables, (long long)table_words, coef, (long long)ws_blocks, status);
+  AVSEP_LAUNCH_CHECK();
+  return AVSEP_OK;
+}
+
+extern "C" int avsep_jpeg_coef_bound(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_image* images, int32_t n_images,
+                                     int32_t max_blocks, const int32_t* tables, int64_t table_words, int32_t* status,
+                                     avsep_stream_t stream) {
+  if (!coef || !images || !tables || !status) return AVSEP_ERR_ARG;
+  if (ws_blocks < 1 || ws_blocks > (1LL << 32) || n_images < 1 || n_images > 65535 || table_words < 1) return AVSEP_ERR_ARG;
+  if ((uintptr_t)coef % 16 || max_blocks < 1 || max_blocks > ws_blocks) return AVSEP_ERR_ARG;      // 16-byte loads of a block's rows
+  hipLaunchKernelGGL(jpeg_bound_kernel, dim3(cdiv(max_blocks, JP_BLOCK), n_images), dim3(JP_BLOCK), 0, (hipStream_t)stream, coef,
+                     (long long)ws_blocks, images, tables, (long long)table_words, status);
   AVSEP_LAUNCH_CHECK();
   return AVSEP_OK;
 }

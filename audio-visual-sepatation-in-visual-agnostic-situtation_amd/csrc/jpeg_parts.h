@@ -1,7 +1,8 @@
 // The parts of the JPEG decoder and encoder (include/avsep.h) that the device and a plain host compiler share: the limits of a
 // row (one row type and one check for both directions) and the two plan checks' test of a host row against its buffers, the
 // entropy decoder of one segment (jp_decode_segment: the body of jpeg_entropy_kernel's lanes, and of the host program the
-// damaged-input test builds under the sanitizers), and the islow inverse DCT pass.  No HIP header is needed to compile it.
+// damaged-input test builds under the sanitizers), the decoder of one scan row of a progressive file (jp_decode_scan: the body of
+// jpeg_scans_kernel's lanes and of a second such host program), and the islow inverse DCT pass.  No HIP header is needed to compile it.
 #pragma once
 #include <stdint.h>
 #include "avsep.h"
@@ -17,8 +18,9 @@ constexpr int JP_QUANT_WORDS = 64;
 constexpr int JP_HUFF_LOOK = 0, JP_HUFF_MAXCODE = 256, JP_HUFF_VALOFF = 273, JP_HUFF_VALUES = 290, JP_HUFF_WORDS = 546;
 enum {
   JP_ST_RANGE = 1, JP_ST_NOCODE = 2, JP_ST_DCSIZE = 4, JP_ST_INDEX = 8, JP_ST_MARKER = 16, JP_ST_BLOCK = 32, JP_ST_TABLE = 64,
-  JP_ST_BOUND = 128, JP_ST_ROW = 256, JP_ST_LEFTOVER = 512
+  JP_ST_BOUND = 128, JP_ST_ROW = 256, JP_ST_LEFTOVER = 512, JP_ST_REFINE = 1024, JP_ST_EOBRUN = 2048
 };
+static_assert(sizeof(avsep_jpeg_scan) == 72, "include/avsep.h; jpeg.py's SCAN is its dtype");
 
 constexpr int JP_ENC_HUFF_WORDS = 256;       // an encoder's table, by symbol: (code length << 16) | code, 0 = the table has no such symbol
 static_assert(sizeof(avsep_jpeg_image) == 96, "one row for both directions (include/avsep.h); jpeg.py's IMAGE is its dtype");
@@ -207,6 +209,212 @@ JP_HD int jp_decode_segment(const uint8_t* __restrict__ bytes, long long nbytes,
   jp_fill(b);
   if (b.marker) JP_STOP(JP_ST_MARKER);
   if (b.pos < b.end || b.real >= 8) JP_STOP(JP_ST_LEFTOVER);
+#undef JP_STOP
+  return 0;
+}
+
+// ---- progressive files: one scan of one restart interval (include/avsep.h: avsep_jpeg_scan)
+// k further bits as they stand (no sign extension), 0 <= k <= 16; false when they are not all real
+JP_HD bool jp_bits(JpBits& b, int k, int* v) {
+  *v = 0;
+  if (k == 0) return true;
+  jp_fill(b);
+  const int r = (int)jp_peek(b, k);
+  if (!jp_take(b, k)) return false;
+  *v = r;
+  return true;
+}
+// What a scan row says, checked against its (checked) image: false = outside the rules of include/avsep.h.  ncmp: components in
+// the mask; c1: the component of a one-component scan and bw its REAL blocks across; units_all: the units the image has for the mask.
+JP_HD bool jp_scan_ok(const avsep_jpeg_image& im, const avsep_jpeg_scan& sc, int* ncmp, int* c1, long long* bw, long long* units_all) {
+  if (sc.comps < 1 || sc.comps >= (1 << im.ncomp)) return false;
+  if (sc.ss < 0 || sc.se < sc.ss || sc.se > 63 || (sc.ss == 0 && sc.se != 0)) return false;
+  if (sc.ah < 0 || sc.ah > 13 || sc.al < 0 || sc.al > 13 || (sc.ah != 0 && sc.al != sc.ah - 1)) return false;
+  if (sc.level < 0 || sc.level >= AVSEP_JPEG_MAX_SCANS) return false;
+  const int n = (sc.comps & 1) + ((sc.comps >> 1) & 1) + ((sc.comps >> 2) & 1);
+  if (sc.ss > 0 && n != 1) return false;
+  *ncmp = n, *c1 = sc.comps == 1 ? 0 : (sc.comps == 2 ? 1 : 2), *bw = 0;
+  if (n == 1) {
+    const long long cw = *c1 == 0 ? im.W : (im.W + im.hs - 1) / im.hs, ch = *c1 == 0 ? im.H : (im.H + im.vs - 1) / im.vs;
+    *bw = (cw + 7) / 8;
+    *units_all = *bw * ((ch + 7) / 8);
+  } else {
+    *units_all = (long long)im.mcux * im.mcuy;
+  }
+  return true;
+}
+// one correction bit for the non-zero coefficient *at (T.81 G.1.2.3): applied away from zero where bit `al` (p1 = 1 << al) is clear
+JP_HD int jp_correct(JpBits& b, int16_t* at, int p1) {
+  int bit = 0, v = *at;
+  if (!jp_bits(b, 1, &bit)) return b.marker ? JP_ST_MARKER : JP_ST_RANGE;
+  if (bit && (v & p1) == 0) {
+    v += v >= 0 ? p1 : -p1;
+    if (v > 32767 || v < -32768) return JP_ST_BOUND;
+    *at = (int16_t)v;
+  }
+  return 0;
+}
+
+// The non-zero coefficients of one block as a mask by zig-zag position (bit k = position k, 1 <= k <= 63): 63 loads that wait for
+// nothing but each other, so that a refinement lane, which passes every coefficient of its band, does not wait for memory at each
+// one (DESIGN §34 has the measurement).  jp_natural folds to a constant in every round.
+JP_HD uint64_t jp_nonzero_mask(const int16_t* __restrict__ blk) {
+  uint64_t m = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int k = 1; k < 64; ++k) m |= (uint64_t)(blk[jp_natural(k)] != 0) << k;
+  return m;
+}
+
+// One scan row: the stream bytes[sc.begin .. sc.end) -> its band and bit position of the coefficients of its blocks, in coef (zeroed
+// before level 0; the earlier scans of its coefficients done).  `level`: the level this launch runs.  Returns the status bits it
+// set, also ORed into status[sc.image].  Nothing is trusted, as in jp_decode_segment.
+JP_HD int jp_decode_scan(const uint8_t* __restrict__ bytes, long long nbytes, const avsep_jpeg_image* __restrict__ images, int n_images,
+                         const avsep_jpeg_scan sc, int level, const int32_t* __restrict__ tables, long long table_words,
+                         int16_t* __restrict__ coef, long long ws_blocks, int32_t* status) {
+  if (sc.image < 0 || sc.image >= n_images) return JP_ST_ROW;                // no status word to set
+  int32_t* word = status + sc.image;
+  if (level > 0 && *word != 0) return 0;                                     // an earlier level gave the image up
+#define JP_STOP(bit) do { JP_FLAG(word, (bit)); return (bit); } while (0)
+#define JP_OUT_OF_BITS (b.marker ? JP_ST_MARKER : JP_ST_RANGE)
+  const avsep_jpeg_image im = images[sc.image];
+  long long nblocks = 0, nintervals = 0, bw = 0, units_all = 0;
+  int ncmp = 0, c1 = 0;
+  if (!jp_image_ok(im, &nblocks, &nintervals) || !jp_inside(im.block0, nblocks, ws_blocks)) JP_STOP(JP_ST_ROW);
+  if (!jp_scan_ok(im, sc, &ncmp, &c1, &bw, &units_all) || sc.level != level) JP_STOP(JP_ST_ROW);
+  if (sc.units < 1 || !jp_inside(sc.unit0, sc.units, units_all)) JP_STOP(JP_ST_BLOCK);
+  if (sc.begin < 0 || sc.end < sc.begin || sc.end > nbytes) JP_STOP(JP_ST_RANGE);
+  const bool dc = sc.ss == 0, first = sc.ah == 0;
+  const bool coded = !dc || first;                                           // a DC refinement scan reads no table
+  for (int c = 0; c < 3; ++c)
+    if (coded && ((sc.comps >> c) & 1) && !jp_inside(sc.table[c], JP_HUFF_WORDS, table_words)) JP_STOP(JP_ST_TABLE);
+  JpBits b = {bytes, sc.begin, sc.end, 0, 0, 0, false};
+  const int luma = im.hs * im.vs, per_unit = ncmp == 1 ? 1 : luma + im.ncomp - 1;
+  const long long mcus_all = (long long)im.mcux * im.mcuy, lw = (long long)im.mcux * im.hs, chroma0 = mcus_all * luma;
+  const long long base1 = c1 == 0 ? 0 : chroma0 + (c1 - 1) * mcus_all, stride1 = c1 == 0 ? lw : im.mcux;
+  const long long last = (long long)sc.unit0 + sc.units;
+  const int p1 = 1 << sc.al;
+  int pred0 = 0, pred1 = 0, pred2 = 0, eobrun = 0;                           // no run-time index: they stay in registers
+  for (long long u = sc.unit0; u < last; ++u) {
+    for (int i = 0; i < per_unit; ++i) {
+      int c;
+      long long blk;
+      if (ncmp == 1) {
+        const long long by = u / bw;
+        c = c1, blk = base1 + by * stride1 + (u - by * bw);
+      } else {
+        c = i < luma ? 0 : i - luma + 1;
+        if (!((sc.comps >> c) & 1)) continue;
+        const long long my = u / im.mcux, mx = u - my * im.mcux;
+        if (c == 0) blk = (my * im.vs + i / im.hs) * lw + mx * im.hs + i % im.hs;
+        else blk = chroma0 + (c - 1) * mcus_all + u;
+      }
+      if (blk < 0 || blk >= nblocks) JP_STOP(JP_ST_BLOCK);                   // cannot happen under the checks above: kept as the store's premise
+      int16_t* out = coef + (im.block0 + blk) * 64;
+      const int32_t* t = tables + (coded ? (c == 0 ? sc.table[0] : (c == 1 ? sc.table[1] : sc.table[2])) : 0);
+      if (dc && first) {
+        int v = 0;
+        const int s = jp_symbol(b, t);
+        if (s < 0) JP_STOP(s == -1 ? JP_ST_NOCODE : JP_OUT_OF_BITS);
+        if (s > 11) JP_STOP(JP_ST_DCSIZE);
+        if (!jp_receive(b, s, &v)) JP_STOP(JP_OUT_OF_BITS);
+        const int pred = (c == 0 ? pred0 : (c == 1 ? pred1 : pred2)) + v;       // |both| < 2^16: the sum cannot wrap
+        if (c == 0) pred0 = pred;
+        else if (c == 1) pred1 = pred;
+        else pred2 = pred;
+        const int val = pred * p1;
+        if (pred > 32767 || pred < -32768 || val > 32767 || val < -32768) JP_STOP(JP_ST_BOUND);
+        out[0] = (int16_t)val;
+      } else if (dc) {
+        int bit = 0;
+        if (!jp_bits(b, 1, &bit)) JP_STOP(JP_OUT_OF_BITS);
+        if (bit) out[0] = (int16_t)(out[0] | p1);
+      } else if (first) {
+        if (eobrun > 0) {
+          --eobrun;
+          continue;
+        }
+        int k = sc.ss;
+        while (k <= sc.se) {                                                 // every round moves k on by at least 1, or ends the block
+          const int rs = jp_symbol(b, t);
+          if (rs < 0) JP_STOP(rs == -1 ? JP_ST_NOCODE : JP_OUT_OF_BITS);
+          const int run = rs >> 4, s = rs & 15;
+          int v = 0;
+          if (s == 0) {
+            if (run == 15) {                                                 // ZRL
+              k += 16;
+              if (k > sc.se + 1) JP_STOP(JP_ST_INDEX);
+              continue;
+            }
+            if (!jp_bits(b, run, &v)) JP_STOP(JP_OUT_OF_BITS);
+            eobrun = (1 << run) + v - 1;                                     // further blocks that end at once
+            if (eobrun > last - 1 - u) JP_STOP(JP_ST_EOBRUN);
+            break;
+          }
+          k += run;
+          if (k > sc.se) JP_STOP(JP_ST_INDEX);
+          if (!jp_receive(b, s, &v)) JP_STOP(JP_OUT_OF_BITS);
+          const int val = v * p1;                                            // |v| < 2^15, p1 <= 2^13
+          if (val > 32767 || val < -32768) JP_STOP(JP_ST_BOUND);
+          out[jp_natural(k)] = (int16_t)val;
+          ++k;
+        }
+      } else {
+        int k = sc.ss;
+        const uint64_t nonzero = jp_nonzero_mask(out);                       // as the block stands before this scan: k only moves on
+        if (eobrun == 0) {
+          while (k <= sc.se) {                                               // every round moves k on by at least 1, or ends the block
+            const int rs = jp_symbol(b, t);
+            if (rs < 0) JP_STOP(rs == -1 ? JP_ST_NOCODE : JP_OUT_OF_BITS);
+            int run = rs >> 4, val = 0;
+            const int s = rs & 15;
+            if (s != 0) {
+              int bit = 0;
+              if (s != 1) JP_STOP(JP_ST_REFINE);
+              if (!jp_bits(b, 1, &bit)) JP_STOP(JP_OUT_OF_BITS);
+              val = bit ? p1 : -p1;
+            } else if (run != 15) {
+              int v = 0;
+              if (!jp_bits(b, run, &v)) JP_STOP(JP_OUT_OF_BITS);
+              eobrun = (1 << run) + v;                                       // this block and eobrun - 1 further ones
+              if (eobrun - 1 > last - 1 - u) JP_STOP(JP_ST_EOBRUN);
+              break;
+            }
+            // over `run` coefficients that are still zero (16 for ZRL, the last one below); the non-zero ones passed are corrected
+            while (k <= sc.se) {
+              if ((nonzero >> k) & 1) {
+                const int e = jp_correct(b, out + jp_natural(k), p1);
+                if (e) JP_STOP(e);
+              } else if (--run < 0) {
+                break;
+              }
+              ++k;
+            }
+            if (s != 0) {
+              if (k > sc.se) JP_STOP(JP_ST_INDEX);
+              out[jp_natural(k)] = (int16_t)val;                             // where the run ends, not earlier
+            }
+            ++k;
+          }
+        }
+        if (eobrun > 0) {                                                    // the rest of the band: correction bits only
+          for (; k <= sc.se; ++k) {
+            if ((nonzero >> k) & 1) {
+              const int e = jp_correct(b, out + jp_natural(k), p1);
+              if (e) JP_STOP(e);
+            }
+          }
+          --eobrun;
+        }
+      }
+    }
+  }
+  // what is left must be the padding of the last byte: less than 8 real bits, no byte unread, no marker met
+  jp_fill(b);
+  if (b.marker) JP_STOP(JP_ST_MARKER);
+  if (b.pos < b.end || b.real >= 8) JP_STOP(JP_ST_LEFTOVER);
+#undef JP_OUT_OF_BITS
 #undef JP_STOP
   return 0;
 }

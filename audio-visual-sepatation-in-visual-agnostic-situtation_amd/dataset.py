@@ -277,14 +277,17 @@ class MUSICMixDataset(torch.utils.data.Dataset):
     def _load_jpeg_frames(self, paths):
         """The clip as it lies in its files, with the same draws in the same order -> (uint8 [bytes]: the files back to back,
         int64 [T] their lengths, int32 [T,2] the frames' (H, W), crop, flip, [(t, uint8 pixels [H*W*3])] for the files the GPU
-        decoder refuses (jpeg.probe), decoded here as ``_open_frames`` decodes them)."""
+        decoder refuses (jpeg.probe and jpeg.probe_scans), decoded here as ``_open_frames`` decodes them)."""
         from . import jpeg
         files, shapes, fallback = [], [], []
         for t, path in enumerate(paths):
             with open(path, "rb") as f:
                 files.append(f.read())
             try:
-                info = jpeg.probe(files[-1])
+                try:
+                    info = jpeg.probe(files[-1])
+                except jpeg.Unsupported:
+                    info = jpeg.probe_scans(files[-1])       # a progressive file: to_device decodes those on the GPU too
                 shapes.append((info.H, info.W))
             except jpeg.Unsupported:
                 a = np.asarray(self._open_frames([path])[0], dtype=np.uint8)
@@ -399,7 +402,7 @@ def _decode_jpeg(batch, device):
         n = shapes[i][0] * shapes[i][1] * 3
         decoded[i] = batch["fallback_u8"][at:at + n].numpy().reshape(shapes[i][0], shapes[i][1], 3)
         at += n
-    pixels, got = jpeg.decode(files, device, decoded=decoded)
+    pixels, got = jpeg.decode(files, device, decoded=decoded, progressive=True)
     if [list(s) for s in got] != shapes:
         raise ValueError("the frames' sizes changed between the workers' probe and the decode")
     return pixels

@@ -8,6 +8,10 @@ without restart intervals.  Anything else is *refused* by ``probe`` with a reaso
 is *flagged* in a status word, and both kinds of file are decoded by Pillow into their slot: ``decode`` returns Pillow's pixels
 for every input, and a file Pillow cannot read raises as it does there.
 
+With ``progressive=True`` (what the ``--gpu_decode`` paths pass) progressive files (SOF2) are decoded too: ``probe_scans`` reads
+every scan, ``plan`` adds one SCAN row per scan and restart interval, and the scans of a file run as lanes of their own, level
+after level (csrc/jpeg_parts.h: jp_decode_scan), into the same workspace and the same pixel stage.
+
 The output layout is the one ``frames.plan_batch`` takes: every frame [H,W,3] uint8, back to back, in file order.
 
 The way back (csrc/jpeg_enc.hip): ``encode`` writes uint8 pictures on the device as baseline JPEG files, byte for byte the files
@@ -23,10 +27,12 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .lib import AvsepError, JpegImage, JpegSegment, got
+from .lib import AvsepError, JpegImage, JpegScan, JpegSegment, got
 
 IMAGE = np.dtype(JpegImage)          # include/avsep.h: avsep_jpeg_image, the row of both directions
 SEGMENT = np.dtype(JpegSegment)      # include/avsep.h: avsep_jpeg_segment
+SCAN = np.dtype(JpegScan)            # include/avsep.h: avsep_jpeg_scan, one (scan, restart interval) of a progressive file
+MAX_SCANS = 64                       # include/avsep.h: AVSEP_JPEG_MAX_SCANS, scans per progressive file
 MAX_SIDE = 16384                     # csrc/jpeg_parts.h: JP_MAX_SIDE
 HUFF_WORDS = 256 + 17 + 17 + 256     # look-ahead, maxcode, value offset, values (csrc/jpeg_parts.h: JP_HUFF_WORDS)
 QUANT_WORDS = 64
@@ -42,7 +48,8 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
 STATUS = {1: "a read outside the segment", 2: "no Huffman code within 16 bits", 4: "a DC size above 11",
           8: "a coefficient index past 63", 16: "a marker inside the segment", 32: "a block outside the segment's blocks",
           64: "a table outside the table buffer", 128: "a coefficient beyond the 32-bit bound", 256: "a row outside its limits",
-          512: "bytes left over after the last block"}
+          512: "bytes left over after the last block", 1024: "a refinement symbol of a size other than 0 or 1",
+          2048: "an end-of-band run past the segment's blocks"}
 
 
 class Unsupported(ValueError):
@@ -63,6 +70,65 @@ class Info:
 
 
 _SOF_NAMES = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)"}
+
+
+def _read_dqt(body, qt):
+    """The tables of one DQT marker into qt {index: uint8 [64], zig-zag order}."""
+    p = 0
+    while p < len(body):
+        if body[p] >> 4:
+            raise Unsupported("a 16-bit quantisation table")
+        if (body[p] & 15) > 3 or p + 65 > len(body):
+            raise Unsupported("a malformed DQT marker")
+        qt[body[p] & 15] = np.frombuffer(body[p + 1:p + 65], dtype=np.uint8)
+        p += 65
+
+
+def _read_dht(body, huff):
+    """The tables of one DHT marker into huff {(class, index): (counts uint8 [16], values)}."""
+    p = 0
+    while p < len(body):
+        if p + 17 > len(body) or (body[p] >> 4) > 1 or (body[p] & 15) > 3:
+            raise Unsupported("a malformed DHT marker")
+        counts = np.frombuffer(body[p + 1:p + 17], dtype=np.uint8)
+        total = int(counts.sum())
+        if total > 256 or p + 17 + total > len(body):
+            raise Unsupported("a malformed DHT marker")
+        code = 0
+        for length, c in enumerate(counts, 1):               # the codes of a length must fit that length
+            code += int(c)
+            if code > (1 << length):
+                raise Unsupported("a Huffman table with more codes than a length holds")
+            code <<= 1
+        huff[(body[p] >> 4, body[p] & 15)] = (counts, np.frombuffer(body[p + 17:p + 17 + total], dtype=np.uint8))
+        p += 17 + total
+
+
+def _frame_rules(frame, jfif, adobe):
+    """The frame header (H, W, components) against what the kernels decode -> (H, W, components as the readers return them)."""
+    if frame is None:
+        raise Unsupported("SOS before a frame header")
+    H, W, comps = frame
+    if H == 0 or W == 0:
+        raise Unsupported(f"a frame of {H} x {W}")
+    if H > MAX_SIDE or W > MAX_SIDE:
+        raise Unsupported(f"a frame of {H} x {W}: sides above {MAX_SIDE}")
+    if len(comps) not in (1, 3):
+        raise Unsupported(f"{len(comps)} components")
+    if len(comps) == 3:
+        if adobe is not None and adobe != 1:
+            raise Unsupported(f"Adobe colour transform {adobe}")
+        ids = tuple(c[0] for c in comps)
+        if ids != (1, 2, 3):
+            raise Unsupported(f"three components with ids {ids}" + ("" if jfif or adobe is not None else
+                                                                    " and neither a JFIF nor an Adobe marker"))
+        if (comps[1][1], comps[1][2], comps[2][1], comps[2][2]) != (1, 1, 1, 1):
+            raise Unsupported("chroma sampling other than 1x1")
+        if (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)):
+            raise Unsupported(f"luma sampling {comps[0][1]}x{comps[0][2]}")
+    else:
+        comps = [(comps[0][0], 1, 1, comps[0][3])]   # one component: not interleaved, its factors do not count
+    return H, W, comps
 
 
 def probe(data):
@@ -111,31 +177,9 @@ def probe(data):
         elif m == 0xDC:
             raise Unsupported("a DNL marker")
         elif m == 0xDB:
-            p = 0
-            while p < len(body):
-                if body[p] >> 4:
-                    raise Unsupported("a 16-bit quantisation table")
-                if (body[p] & 15) > 3 or p + 65 > len(body):
-                    raise Unsupported("a malformed DQT marker")
-                qt[body[p] & 15] = np.frombuffer(body[p + 1:p + 65], dtype=np.uint8)
-                p += 65
+            _read_dqt(body, qt)
         elif m == 0xC4:
-            p = 0
-            while p < len(body):
-                if p + 17 > len(body) or (body[p] >> 4) > 1 or (body[p] & 15) > 3:
-                    raise Unsupported("a malformed DHT marker")
-                counts = np.frombuffer(body[p + 1:p + 17], dtype=np.uint8)
-                total = int(counts.sum())
-                if total > 256 or p + 17 + total > len(body):
-                    raise Unsupported("a malformed DHT marker")
-                code = 0
-                for length, c in enumerate(counts, 1):               # the codes of a length must fit that length
-                    code += int(c)
-                    if code > (1 << length):
-                        raise Unsupported("a Huffman table with more codes than a length holds")
-                    code <<= 1
-                huff[(body[p] >> 4, body[p] & 15)] = (counts, np.frombuffer(body[p + 17:p + 17 + total], dtype=np.uint8))
-                p += 17 + total
+            _read_dht(body, huff)
         elif m == 0xDD:
             if len(body) != 2:
                 raise Unsupported("a malformed DRI marker")
@@ -145,28 +189,7 @@ def probe(data):
         elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
             adobe = body[11]
         # any other APPn, COM: skipped
-    if frame is None:
-        raise Unsupported("SOS before a frame header")
-    H, W, comps = frame
-    if H == 0 or W == 0:
-        raise Unsupported(f"a frame of {H} x {W}")
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise Unsupported(f"a frame of {H} x {W}: sides above {MAX_SIDE}")
-    if len(comps) not in (1, 3):
-        raise Unsupported(f"{len(comps)} components")
-    if len(comps) == 3:
-        if adobe is not None and adobe != 1:
-            raise Unsupported(f"Adobe colour transform {adobe}")
-        ids = tuple(c[0] for c in comps)
-        if ids != (1, 2, 3):
-            raise Unsupported(f"three components with ids {ids}" + ("" if jfif or adobe is not None else
-                                                                    " and neither a JFIF nor an Adobe marker"))
-        if (comps[1][1], comps[1][2], comps[2][1], comps[2][2]) != (1, 1, 1, 1):
-            raise Unsupported("chroma sampling other than 1x1")
-        if (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)):
-            raise Unsupported(f"luma sampling {comps[0][1]}x{comps[0][2]}")
-    else:
-        comps = [(comps[0][0], 1, 1, comps[0][3])]   # one component: not interleaved, its factors do not count
+    H, W, comps = _frame_rules(frame, jfif, adobe)
     if len(body) < 1 or len(body) != 4 + 2 * body[0]:
         raise Unsupported("a malformed SOS marker")
     if body[0] != len(comps):
@@ -253,6 +276,188 @@ def segments(info, data):
     return [(int(b), int(e), k * per, min(per, total - k * per)) for k, (b, e) in enumerate(zip(begins, ends))]
 
 
+@dataclass
+class Scan:
+    """One scan of a progressive file, as its SOS header and the markers before it give it."""
+    comps: list                      # indices of its components in the frame, rising
+    ss: int                          # the band of zig-zag positions [ss, se] ...
+    se: int
+    ah: int                          # ... and the bit positions: ah = 0 a first scan, else a refinement down to al = ah - 1
+    al: int
+    tables: list                     # per component (counts, values) of the DC (ss = 0) or AC table in force; None when DC is refined
+    restart: int                     # units per restart interval in force, 0 = none
+    begin: int                       # the entropy-coded bytes are data[begin:end]; end is the next marker
+    end: int
+    rst: np.ndarray                  # where in the file its RSTn markers stand
+    units: int                       # MCUs (several components) or the component's own blocks over its real size (one)
+    level: int                       # 1 + the highest level of an earlier scan with a component and a coefficient in common; else 0
+
+
+@dataclass
+class ScanInfo:
+    H: int
+    W: int
+    components: list                 # as Info's
+    qtables: dict
+    scans: list                      # Scan, in file order
+    restart = 0                      # the image row of a progressive file has none: every scan row carries its own units
+
+
+def _scan_units(H, W, comps, which):
+    """The units of a scan over the components ``which`` (indices): MCUs, or one component's blocks over its real size."""
+    hs, vs = comps[0][1], comps[0][2]
+    if len(which) > 1:
+        return -(-W // (8 * hs)) * -(-H // (8 * vs))
+    cw, ch = (W, H) if which[0] == 0 else (-(-W // hs), -(-H // vs))
+    return -(-cw // 8) * -(-ch // 8)
+
+
+def probe_scans(data):
+    """Walk every marker of a progressive (SOF2) file from SOI to EOI -> ScanInfo; raises Unsupported with the reason for anything
+    outside what avsep_jpeg_scans decodes: the baseline limits on the frame, T.81 G.1.1.1's rules for every scan, a complete
+    progression (every coefficient of every component down to Al = 0 at EOI: libjpeg smooths an incomplete one, the kernels do
+    not), no quantisation table after the first scan, at most MAX_SCANS scans, restart markers that match each scan's interval."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[0:2] != b"\xff\xd8":
+        raise Unsupported("not a JPEG file: no SOI marker")
+    a = np.frombuffer(data, dtype=np.uint8)
+    ff = np.flatnonzero(a[:-1] == 0xFF)
+    nxt = a[ff + 1]
+    is_rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+    # RSTn; what ends a scan's bytes: the next marker with a meaning (a stray TEM, FF 01, is left to the lane that meets it)
+    rst_at, stop_at = ff[is_rst], ff[(nxt > 1) & (nxt != 0xFF) & ~is_rst]
+    at, frame, qt, huff, restart, jfif, adobe = 2, None, {}, {}, 0, False, None
+    H = W = comps = state = None
+    scans = []
+    while True:
+        if at + 2 > n:
+            raise Unsupported("no EOI marker")
+        if data[at] != 0xFF:
+            raise Unsupported(f"byte {at}: 0x{data[at]:02x} where a marker starts")
+        m = data[at + 1]
+        if m == 0xFF:                                # fill byte
+            at += 1
+            continue
+        at += 2
+        if m == 0x01 or 0xD0 <= m <= 0xD7:           # stand-alone
+            continue
+        if m == 0xD9:
+            break
+        if at + 2 > n:
+            raise Unsupported("no EOI marker")
+        L = struct.unpack(">H", data[at:at + 2])[0]
+        if L < 2 or at + L > n:
+            raise Unsupported("no EOI marker" if at + L > n else f"marker 0x{m:02x} of length {L}")
+        body = data[at + 2:at + L]
+        at += L
+        if m == 0xC2:
+            if frame is not None:
+                raise Unsupported("more than one frame header")
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise Unsupported("a malformed SOF2 marker")
+            if body[0] != 8:
+                raise Unsupported(f"{body[0]}-bit samples")
+            frame = (struct.unpack(">H", body[1:3])[0], struct.unpack(">H", body[3:5])[0],
+                     [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(body[5])])
+        elif m == 0xC0:
+            raise Unsupported("not progressive: a baseline frame (SOF0)")
+        elif m in _SOF_NAMES or (0xC5 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC)):
+            raise Unsupported(_SOF_NAMES.get(m, f"SOF{m - 0xC0} (differential or arithmetic-coded)"))
+        elif m == 0xCC:
+            raise Unsupported("arithmetic coding (DAC)")
+        elif m == 0xDC:
+            raise Unsupported("a DNL marker")
+        elif m == 0xDB:
+            if scans:
+                raise Unsupported("a quantisation table after the first scan")
+            _read_dqt(body, qt)
+        elif m == 0xC4:
+            _read_dht(body, huff)
+        elif m == 0xDD:
+            if len(body) != 2:
+                raise Unsupported("a malformed DRI marker")
+            restart = struct.unpack(">H", body)[0]
+        elif m == 0xE0 and body[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xDA:
+            if state is None:
+                H, W, comps = _frame_rules(frame, jfif, adobe)
+                for c in comps:
+                    if c[3] not in qt:
+                        raise Unsupported(f"quantisation table {c[3]} is referenced but not defined")
+                state = [[-1] * 64 for _ in comps]               # per component and coefficient: the Al reached, -1 = untouched
+            if len(scans) >= MAX_SCANS:
+                raise Unsupported(f"more than {MAX_SCANS} scans")
+            if len(body) < 1 or len(body) != 4 + 2 * body[0] or not 1 <= body[0] <= len(comps):
+                raise Unsupported("a malformed SOS marker")
+            ids = [c[0] for c in comps]
+            which = [ids.index(body[1 + 2 * i]) if body[1 + 2 * i] in ids else -1 for i in range(body[0])]
+            if -1 in which:
+                raise Unsupported("a scan component the frame does not have")
+            if any(y <= x for x, y in zip(which, which[1:])):
+                raise Unsupported("scan components out of frame order")
+            ss, se, ah, al = body[-3], body[-2], body[-1] >> 4, body[-1] & 15
+            what = f"a scan with Ss={ss}, Se={se}, Ah={ah}, Al={al}"
+            if (ss == 0 and se != 0) or (ss > 0 and not ss <= se <= 63):
+                raise Unsupported(f"{what}: a band outside T.81 G.1.1.1")
+            if ss > 0 and len(which) != 1:
+                raise Unsupported(f"{what} over {len(which)} components: an AC scan takes one")
+            if ah > 13 or al > 13:
+                raise Unsupported(f"{what}: a bit position above 13")
+            for c in which:
+                if ss > 0 and state[c][0] < 0:
+                    raise Unsupported(f"{what}: AC of component {c} before its DC")
+                for k in range(ss, se + 1):
+                    if (ah != 0) if state[c][k] < 0 else (ah != state[c][k] or al != ah - 1):
+                        raise Unsupported(f"{what}: coefficient {k} of component {c} " +
+                                          ("has no first scan" if state[c][k] < 0 else f"stands at Al={state[c][k]}"))
+                    state[c][k] = al
+            chosen = []
+            for i, c in enumerate(which):
+                cls, idx = (0, body[2 + 2 * i] >> 4) if ss == 0 else (1, body[2 + 2 * i] & 15)
+                if ss == 0 and ah != 0:
+                    chosen.append(None)
+                    continue
+                if (cls, idx) not in huff:
+                    raise Unsupported(f"{'AD'[cls]}C Huffman table {idx} is referenced but not defined")
+                chosen.append(huff[cls, idx])
+            begin = at
+            j = int(np.searchsorted(stop_at, begin))
+            if j == len(stop_at):
+                raise Unsupported("no EOI marker")
+            end = int(stop_at[j])
+            rst = rst_at[np.searchsorted(rst_at, begin):np.searchsorted(rst_at, end)]
+            units = _scan_units(H, W, comps, which)
+            want = -(-units // restart) if restart else 1
+            if len(rst) != want - 1:
+                raise Unsupported(f"scan {len(scans)}: {len(rst)} restart markers where the interval of {restart} units asks for {want - 1}")
+            if len(rst) and not np.array_equal(a[rst + 1] - 0xD0, np.arange(len(rst)) % 8):
+                raise Unsupported("restart markers out of order")
+            level = 1 + max((s.level for s in scans if set(s.comps) & set(which) and s.ss <= se and ss <= s.se), default=-1)
+            scans.append(Scan(which, ss, se, ah, al, chosen, restart, begin, end, rst, units, level))
+            at = end
+        # any other APPn, COM: skipped
+    if not scans:
+        raise Unsupported("EOI before any scan")
+    for c, st in enumerate(state):
+        if any(v != 0 for v in st):
+            k = next(k for k, v in enumerate(st) if v != 0)
+            raise Unsupported(f"an incomplete progression: coefficient {k} of component {c} " +
+                              ("has no scan" if st[k] < 0 else f"ends at Al={st[k]}"))
+    return ScanInfo(H, W, comps, qt, scans)
+
+
+def scan_segments(scan):
+    """The entropy-coded segments of one scan -> [(begin, end, first unit, units)], cut at its RSTn markers."""
+    per = scan.restart if scan.restart else scan.units
+    begins = [scan.begin] + [int(p) + 2 for p in scan.rst]
+    ends = [int(p) for p in scan.rst] + [scan.end]
+    return [(b, e, k * per, min(per, scan.units - k * per)) for k, (b, e) in enumerate(zip(begins, ends))]
+
+
 def huffman_words(counts, values):
     """One Huffman table as the kernels read it -> int32 [HUFF_WORDS]: look[256] ((length << 8) | value for codes of up to 8
     bits, by the next 8 bits; 0 = longer), maxcode[17] (by length; -1 = no code of that length), valoff[17] (index of a code's
@@ -298,11 +503,13 @@ class Tables:
 class Chunk:
     """The images [a, b) of a plan that share one coefficient workspace: their rows (``images``, a view; blocks and intervals
     count from 0 in the chunk) and how many blocks and restart intervals they have.  ``plan`` adds what decoding needs: the
-    SEGMENT rows (image indices count from a) and the most blocks and pixels any one image has (the launch grids)."""
+    SEGMENT rows of its baseline images and the SCAN rows of its progressive ones, in rising order of level (image indices
+    count from a), ``levels`` = [(level, first row, end row)] of those, one launch each, and the most blocks and pixels any one
+    image has (the launch grids)."""
 
     def __init__(self, a, b, images, blocks, intervals):
         self.a, self.b, self.images, self.blocks, self.intervals = a, b, images, blocks, intervals
-        self.segs, self.max_blocks, self.max_pixels = None, 0, 0
+        self.segs, self.scans, self.levels, self.max_blocks, self.max_pixels = None, None, [], 0, 0
 
 
 def _cap_blocks(who, cap):
@@ -362,7 +569,23 @@ def _natural(q):
     return t
 
 
-def plan(files, cap=WORKSPACE_CAP):
+def _read(f, cap_blocks, progressive):
+    """One file for ``plan`` -> (Info, its segments, Form), or (ScanInfo, None, Form) for a progressive file when those are
+    taken; Unsupported otherwise."""
+    try:
+        info = probe(f)
+        segs = segments(info, f)
+    except Unsupported as e:
+        if not progressive or str(e) != _SOF_NAMES[0xC2]:
+            raise
+        info, segs = probe_scans(f), None
+    form = _form(info)
+    if form.blocks > cap_blocks:
+        raise Unsupported(f"{form.blocks} blocks, more than the workspace cap of {cap_blocks}")
+    return info, segs, form
+
+
+def plan(files, cap=WORKSPACE_CAP, progressive=False):
     """Pack what the kernels read for ``files`` (a list of bytes) -> DecodePlan:
     bytes: the entropy-coded bytes of the supported files back to back (uint8);
     images: one IMAGE row per supported file (``index`` = its position in ``files``), block offsets counted per chunk and
@@ -371,7 +594,11 @@ def plan(files, cap=WORKSPACE_CAP):
     tables: quantisation tables (64 words, natural order) and Huffman tables (``huffman_words``) in one int32 buffer, equal
       tables shared;
     fallback: the indices of files ``probe`` (or the limits here) refused, ``reasons`` why; their sizes come from Pillow;
-    shapes, offsets, pixel_bytes: every file's (H, W) and its first byte in the output, all frames back to back."""
+    shapes, offsets, pixel_bytes: every file's (H, W) and its first byte in the output, all frames back to back.
+    progressive: a file ``probe`` refuses as progressive (SOF2) is read by ``probe_scans``; one it takes gets an IMAGE row like
+      any other (dc / ac: its first DC table, restart 0) and, in its chunk's ``scans``, one SCAN row per (scan, restart interval)
+      with the tables, band, units and level of that scan, the rows of a chunk in rising order of level.  Its bytes in ``bytes``
+      are its scans' entropy-coded bytes back to back."""
     files = [bytes(f) for f in files]
     if not files:
         raise AvsepError("jpeg.plan takes at least one file")
@@ -379,11 +606,7 @@ def plan(files, cap=WORKSPACE_CAP):
     shapes, fallback, reasons, kept, forms = [], [], {}, [], []
     for i, f in enumerate(files):
         try:
-            info = probe(f)
-            segs = segments(info, f)
-            form = _form(info)
-            if form.blocks > cap_blocks:
-                raise Unsupported(f"{form.blocks} blocks, more than the workspace cap of {cap_blocks}")
+            info, segs, form = _read(f, cap_blocks, progressive)
             kept.append((i, info, segs))
             forms.append(form)
             shapes.append((info.H, info.W))
@@ -396,35 +619,61 @@ def plan(files, cap=WORKSPACE_CAP):
     offsets = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in shapes], dtype=np.int64)])
     tables = Tables()
 
+    def huffman_at(table):
+        return tables.at(("h", table[0].tobytes(), table[1].tobytes()), huffman_words, *table)
+
     def tables_of(info):
-        for comp, (d, ac) in zip(info.components, info.scan):
+        if isinstance(info, ScanInfo):               # the scan rows carry the tables: the image row points at a valid one
+            pairs = [(info.scans[0].tables[0],) * 2] * len(info.components)
+        else:
+            pairs = [(info.huffman[0, d], info.huffman[1, ac]) for d, ac in info.scan]
+        for comp, pair in zip(info.components, pairs):
             q = info.qtables[comp[3]]
-            yield [tables.at(("q", q.tobytes()), _natural, q)] + [tables.at(("h", c.tobytes(), v.tobytes()), huffman_words, c, v)
-                                                                   for c, v in (info.huffman[0, d], info.huffman[1, ac])]
+            yield [tables.at(("q", q.tobytes()), _natural, q)] + [huffman_at(t) for t in pair]
     images, chunks = _rows(forms, [offsets[i] for i, _, _ in kept], [list(tables_of(info)) for _, info, _ in kept],
                            _cut([f.blocks for f in forms], cap_blocks, MAX_IMAGES))
     data, nbytes = [], 0
     for ch in chunks:
-        segs_rows = []
+        segs_rows, scan_rows = [], []
         for r in range(ch.a, ch.b):
             i, info, segs = kept[r]
+            if segs is None:
+                for s in info.scans:
+                    shift = nbytes - s.begin
+                    at = [huffman_at(s.tables[s.comps.index(c)]) if c in s.comps and s.tables[s.comps.index(c)] is not None else 0
+                          for c in range(3)]
+                    scan_rows += [(b + shift, e + shift, r - ch.a, sum(1 << c for c in s.comps), s.ss, s.se, s.ah, s.al, at, u0, n,
+                                   s.level, (0, 0)) for b, e, u0, n in scan_segments(s)]
+                    data.append(np.frombuffer(files[i], dtype=np.uint8)[s.begin:s.end])
+                    nbytes += s.end - s.begin
+                continue
             shift = nbytes - info.data_begin
             segs_rows += [(b + shift, e + shift, r - ch.a, m0, n, 0) for b, e, m0, n in segs]
             data.append(np.frombuffer(files[i], dtype=np.uint8)[info.data_begin:info.data_end])
             nbytes += info.data_end - info.data_begin
         ch.segs = np.array(segs_rows, dtype=SEGMENT)
+        ch.scans = np.array(scan_rows, dtype=SCAN)
+        ch.scans = ch.scans[np.argsort(ch.scans["level"], kind="stable")]
+        levels, first = np.unique(ch.scans["level"], return_index=True)
+        ch.levels = list(zip(levels.tolist(), first.tolist(), first.tolist()[1:] + [len(ch.scans)]))
         ch.max_blocks, ch.max_pixels = max(f.blocks for f in forms[ch.a:ch.b]), max(f.H * f.W for f in forms[ch.a:ch.b])
     data = np.concatenate(data) if data else np.zeros(0, dtype=np.uint8)
     p = DecodePlan(data, images, [i for i, _, _ in kept], chunks, tables.buffer(), fallback, reasons, shapes, offsets, int(offsets[-1]))
     for ch in chunks:
-        K.jpeg_plan_check(ch.images, ch.segs, max(len(data), 1), len(p.tables), p.pixel_bytes, ch.blocks)
+        if len(ch.segs) or not len(ch.scans):
+            K.jpeg_plan_check(ch.images, ch.segs, max(len(data), 1), len(p.tables), p.pixel_bytes, ch.blocks)
+        if len(ch.scans):
+            K.jpeg_scan_check(ch.images, ch.scans, max(len(data), 1), len(p.tables), p.pixel_bytes, ch.blocks)
     return p
 
 
 def launch(p, device, pixels=None, coef=None, planes=None):
     """Upload a plan and run its chunks on the current stream of ``device`` -> (pixels uint8 [bytes], status int32 [images] on the
     device, the coefficient workspace and planes as the last chunk left them).  Nothing is read back.  pixels, coef (int16) and
-    planes (uint8), when given, are the buffers to use: the plan's bytes, and 64 per block of the largest chunk."""
+    planes (uint8), when given, are the buffers to use: the plan's bytes, and 64 per block of the largest chunk.  Per chunk: the
+    baseline segments (avsep_jpeg_entropy), then the scan rows of its progressive images level after level (avsep_jpeg_scans, the
+    first launch zeroing the workspace when the chunk has no baseline segment) and the bound check of the finished coefficients
+    (avsep_jpeg_coef_bound), then the pixel stage."""
     device = torch.device(device)
     if pixels is None:
         pixels = torch.empty(p.pixel_bytes, dtype=torch.uint8, device=device)
@@ -438,20 +687,29 @@ def launch(p, device, pixels=None, coef=None, planes=None):
         planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device) if planes is None else planes
         for ch in p.chunks:
             rows = images[ch.a * IMAGE.itemsize:ch.b * IMAGE.itemsize]
-            segs = torch.from_numpy(ch.segs.view(np.uint8)).to(device, non_blocking=True)
             st = status[ch.a:ch.b]
-            K.jpeg_entropy(data, rows, segs, tables, coef, ch.blocks, st)
+            if len(ch.segs):
+                segs = torch.from_numpy(ch.segs.view(np.uint8)).to(device, non_blocking=True)
+                K.jpeg_entropy(data, rows, segs, tables, coef, ch.blocks, st)
+            if ch.scans is not None and len(ch.scans):
+                # level after level: the rows are in rising order of level, and a level's lanes touch disjoint coefficients
+                scans = torch.from_numpy(ch.scans.view(np.uint8)).to(device, non_blocking=True)
+                for level, a, b in ch.levels:
+                    K.jpeg_scans(data, rows, scans[a * SCAN.itemsize:b * SCAN.itemsize], level, a == 0 and not len(ch.segs), tables,
+                                 coef, ch.blocks, st)
+                K.jpeg_coef_bound(coef, ch.blocks, rows, ch.max_blocks, tables, st)
             K.jpeg_pixels(coef, planes, ch.blocks, rows, ch.max_blocks, ch.max_pixels, tables, st, pixels)
     return pixels, status, coef, planes
 
 
-def decode(files, device, cap=WORKSPACE_CAP, decoded=None):
+def decode(files, device, cap=WORKSPACE_CAP, decoded=None, progressive=False):
     """files: a list of bytes, each one image file -> (pixels uint8 [bytes] on ``device``, every frame [H,W,3] back to back in
     file order, and shapes [(H, W)]).  Supported files are decoded by the kernels; the status words are read once, and every
     refused or flagged file is decoded by Pillow and copied into its slot, so the result is Pillow's for every input.
-    ``decoded`` {index: uint8 [H,W,3]} hands over pixels the caller already has for refused files."""
+    ``decoded`` {index: uint8 [H,W,3]} hands over pixels the caller already has for refused files.  ``progressive``: progressive
+    files go through the kernels too (``plan``)."""
     files = [bytes(f) for f in files]
-    p = plan(files, cap)
+    p = plan(files, cap, progressive)
     pixels, status, _, _ = launch(p, device)
     again = list(p.fallback)
     if len(p.images):
@@ -465,15 +723,15 @@ def decode(files, device, cap=WORKSPACE_CAP, decoded=None):
     return pixels, list(p.shapes)
 
 
-def decode_stack(paths, device):
-    """The image files ``paths`` of one clip -> uint8 [T,H,W,3] on ``device``: baseline JPEGs through the kernels, everything else
-    through Pillow.  Frames of unequal size end with SystemExit, as in ``frames.load_stack``."""
+def decode_stack(paths, device, progressive=False):
+    """The image files ``paths`` of one clip -> uint8 [T,H,W,3] on ``device``: baseline JPEGs (with ``progressive``, progressive
+    ones too) through the kernels, everything else through Pillow.  Frames of unequal size end with SystemExit, as in ``frames.load_stack``."""
     paths = list(paths)
     files = []
     for q in paths:
         with open(q, "rb") as f:
             files.append(f.read())
-    pixels, shapes = decode(files, device)
+    pixels, shapes = decode(files, device, progressive=progressive)
     for q, s in zip(paths, shapes):
         if s != shapes[0]:
             raise SystemExit(f"{os.path.dirname(q)}: frames of unequal size: {os.path.basename(q)} is {s[0]} x {s[1]}, "

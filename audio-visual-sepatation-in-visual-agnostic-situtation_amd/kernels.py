@@ -1249,6 +1249,40 @@ def jpeg_pixels(coef, planes, ws_blocks, images, max_blocks, max_pixels, tables,
          tables.numel(), ptr(status), ptr(pixels), pixels.numel())
 
 
+def jpeg_scan_check(images, scans, nbytes, table_words, pixel_bytes, ws_blocks):
+    """avsep_jpeg_scan_check (include/avsep.h; host only, no GPU): images and scans = NumPy arrays of dtype np.dtype(lib.JpegImage)
+    and np.dtype(lib.JpegScan), the rows of one chunk.  AvsepError for anything the library refuses."""
+    images, scans = np.ascontiguousarray(images), np.ascontiguousarray(scans)
+    rc = lib.load().avsep_jpeg_scan_check(images.ctypes.data, len(images), scans.ctypes.data, len(scans), int(nbytes),
+                                          int(table_words), int(pixel_bytes), int(ws_blocks))
+    if rc != 0:
+        raise lib.AvsepError(f"avsep_jpeg_scan_check refused {len(images)} images in {len(scans)} scan rows: a band, bit position, "
+                             f"component mask or level outside the rules, or a byte, unit, table or pixel range outside its buffer ({rc})")
+
+
+def jpeg_scans(data, images, scans, level, zero, tables, coef, ws_blocks, status):
+    """avsep_jpeg_scans (include/avsep.h): the scan rows (uint8, checked) of ONE level of a chunk's progressive images, one lane
+    each, into coef int16 [>= 64 * ws_blocks]; zero: zero coef[:64 * ws_blocks] first.  The other buffers as jpeg_entropy's."""
+    _jpeg_buffers("jpeg_scans", data, ((data, torch.uint8), (images, torch.uint8), (scans, torch.uint8), (tables, torch.int32),
+                                       (coef, torch.int16), (status, torch.int32)))
+    n = _jpeg_rows("jpeg_scans", images, ((coef, "coef", 64 * int(ws_blocks)),))
+    ns = _jpeg_rows("jpeg_scans", scans, (), lib.JpegScan)
+    if status.numel() != n:
+        raise lib.AvsepError(f"jpeg_scans: {status.numel()} status words for {n} images")
+    call("avsep_jpeg_scans", ptr(data), data.numel(), ptr(images), n, ptr(scans), ns, int(level), int(bool(zero)), ptr(tables),
+         tables.numel(), ptr(coef), int(ws_blocks), ptr(status))
+
+
+def jpeg_coef_bound(coef, ws_blocks, images, max_blocks, tables, status):
+    """avsep_jpeg_coef_bound (include/avsep.h): the finished coefficients of one chunk against AVSEP_JPEG_MAX_COEF; an image
+    with one beyond it gets status bit 128."""
+    _jpeg_buffers("jpeg_coef_bound", coef, ((coef, torch.int16), (images, torch.uint8), (tables, torch.int32), (status, torch.int32)))
+    n = _jpeg_rows("jpeg_coef_bound", images, ((coef, "coef", 64 * int(ws_blocks)),))
+    if status.numel() != n:
+        raise lib.AvsepError(f"jpeg_coef_bound: {status.numel()} status words for {n} images")
+    call("avsep_jpeg_coef_bound", ptr(coef), int(ws_blocks), ptr(images), n, int(max_blocks), ptr(tables), tables.numel(), ptr(status))
+
+
 def jpeg_enc_plan_check(images, pixel_bytes, table_words, ws_blocks, n_intervals):
     """avsep_jpeg_enc_plan_check (include/avsep.h; host only, no GPU): images = a NumPy array of dtype np.dtype(lib.JpegImage),
     the rows of one chunk.  AvsepError for anything the library refuses."""

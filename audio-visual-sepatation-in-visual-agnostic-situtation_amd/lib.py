@@ -63,7 +63,13 @@ class JpegSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64)] + [(n, C.c_int32) for n in "image mcu0 mcus reserved".split()]
 
 
-_P, _I, _F, _D, _Z = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t
+class JpegScan(C.Structure):
+    """avsep_jpeg_scan (include/avsep.h): one scan of one restart interval of a progressive file."""
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64)] + [(n, C.c_int32) for n in "image comps ss se ah al".split()] + \
+               [("table", C.c_int32 * 3)] + [(n, C.c_int32) for n in "unit0 units level".split()] + [("reserved", C.c_int32 * 2)]
+
+
+_P, _I, _F, _D, _Z =C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t
 _CD, _KD = C.POINTER(ConvDesc), C.POINTER(CatDesc)
 _L = C.c_int64
 
@@ -136,7 +142,10 @@ SIGNATURES = {
     "avsep_jpeg_plan_check": (C.c_int, [_P, _I, _P, _I, _L, _L, _L, _L]),
     "avsep_jpeg_entropy": (C.c_int, [_P, _L, _P, _I, _P, _I, _P, _L, _P, _L, _P, _P]),
     "avsep_jpeg_pixels": (C.c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _L, _P, _P, _L, _P]),
-    "avsep_jpeg_enc_plan_check": (C.c_int, [_P, _I, _L, _L, _L, _L]),
+    "avsep_jpeg_scan_check": (C.c_int, [_P, _I, _P, _I, _L, _L, _L, _L]),
+    "avsep_jpeg_scans": (C.c_int, [_P, _L, _P, _I, _P, _I, _I, _I, _P, _L, _P, _L, _P, _P]),
+    "avsep_jpeg_coef_bound": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _P]),
+    "avsep_jpeg_enc_plan_check":(C.c_int, [_P, _I, _L, _L, _L, _L]),
     "avsep_jpeg_enc_coef": (C.c_int, [_P, _L, _P, _I, _P, _L, _P, _L, _P]),
     "avsep_jpeg_enc_count": (C.c_int, [_P, _L, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P]),
     "avsep_jpeg_enc_pack": (C.c_int, [_P, _L, _P, _I, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _P]),

@@ -538,7 +538,7 @@ def build_parser():
                                                            "shot: a uint8 .npy [H,W,3] or [T,H,W,3], or a folder of .jpg / .png "
                                                            "files in name order, prepared on the GPU at --imgSize")
     p.add_argument("--gpu_decode", action="store_true",
-                   help="decode the .jpg / .jpeg files of a --frames folder on the GPU (baseline JPEGs; anything else, .png included, "
+                   help="decode the .jpg / .jpeg files of a --frames folder on the GPU (baseline and progressive JPEGs; anything else, .png included, "
                         "is read through Pillow as without the flag): the same pixels, without the one-core decode")
     p.add_argument("--fps", type=float, default=None, help="video frames per second of the .npy stacks (needs the spatial visual "
                                                            "features of --not_pool_vis)")

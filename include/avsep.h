@@ -872,6 +872,56 @@ int avsep_jpeg_pixels(const int16_t* coef, uint8_t* planes, int64_t ws_blocks, c
                       int32_t max_blocks, int32_t max_pixels, const int32_t* tables, int64_t table_words, const int32_t* status,
                       uint8_t* pixels, int64_t pixel_bytes, avsep_stream_t stream);
 
+/* ---- Progressive JPEG frames (SOF2; csrc/jpeg.hip, csrc/jpeg_parts.h: jp_decode_scan; avsep_amd/jpeg.py: probe_scans).
+ * A progressive file fills the same coefficient workspace through several scans, and avsep_jpeg_pixels turns it into pixels as it
+ * does for a baseline file.  Its image row is the baseline one (dc / ac point at any valid table, restart = 0); what differs per
+ * scan travels in one row per (scan, restart interval): */
+#define AVSEP_JPEG_MAX_SCANS 64             /* scans per file the host accepts (jpeg.MAX_SCANS) */
+typedef struct avsep_jpeg_scan {
+  int64_t begin, end;                       /* its bytes: bytes[begin .. end) */
+  int32_t image;                            /* row of `images` */
+  int32_t comps;                            /* mask of the frame's components in the scan: bit c = component c; 1 .. 7 */
+  int32_t ss, se, ah, al;                   /* the band of zig-zag positions and the bit positions, as in the SOS header */
+  int32_t table[3];                         /* per frame component in the scan: word offset of its DC (ss = 0) or AC Huffman table;
+                                               not read by a DC refinement scan */
+  int32_t unit0, units;                     /* first unit and unit count */
+  int32_t level;                            /* scans of one level of an image touch disjoint (component, coefficient) sets */
+  int32_t reserved[2];
+} avsep_jpeg_scan;                          /* 72 bytes */
+/* Units: with more than one component in the mask, the image's MCUs in raster order (each the blocks of the masked components
+ * in frame order, padding blocks included); with one component c, that component's own blocks in raster order over its REAL
+ * block grid, ceil(ceil(W h / hmax) / 8) across and ceil(ceil(H v / vmax) / 8) down, so padding blocks are never visited.
+ * Rules of a row: 0 <= ss <= se <= 63; ss = 0 implies se = 0; ss > 0 implies one component; ah, al <= 13; ah = 0 or al = ah - 1.
+ *   ss = 0, ah = 0  DC first: per block a size symbol (<= 11), receive-and-extend, a predictor per component (0 at a row's
+ *                   start); stores predictor << al.
+ *   ss = 0, ah > 0  DC refinement: one bit per block, ORs 1 << al into the stored value.  No table.
+ *   ss > 0, ah = 0  AC first: run/size symbols over [ss, se], value << al stored; ZRL; size 0 with run r < 15 starts an
+ *                   end-of-band run of (1 << r) + r further bits - 1 more blocks, carried across the row's blocks.
+ *   ss > 0, ah > 0  AC refinement (T.81 G.1.2.3): a size of 0 or 1; non-zero coefficients passed take one correction bit each,
+ *                   applied away from zero where bit al is clear; the new +-(1 << al) lands where the run of zeros ends.
+ * avsep_jpeg_scan_check (host only): every HOST image row as avsep_jpeg_plan_check checks it, and every scan row: the rules
+ *   above, bytes inside nbytes, image inside n_images, mask inside the image's components, units inside the units of its
+ *   image and mask, every table it reads inside table_words, 0 <= level < AVSEP_JPEG_MAX_SCANS.  AVSEP_ERR_ARG on the first
+ *   row that fails.
+ * avsep_jpeg_scans: one lane (a wavefront of its own, as avsep_jpeg_entropy's) per row of `scans`, all of ONE level; the caller
+ *   launches the levels of a chunk in rising order on one stream.  zero != 0 first zeroes coef[0 .. 64 ws_blocks) (a chunk
+ *   without baseline segments, whose workspace avsep_jpeg_entropy has not zeroed).  A lane trusts neither rows nor stream and
+ *   sets the status bits of avsep_jpeg_entropy, with: a band, mask, level (a row whose level is not `level`) or bit position
+ *   outside the rules (256), a coefficient index past its band (8), a value that leaves int16 after its shift (128), a
+ *   refinement symbol whose size is neither 0 nor 1 (1024), an end-of-band run longer than the row's remaining blocks (2048).
+ *   A lane of level > 0 does nothing for an image whose status word is already set.
+ * avsep_jpeg_coef_bound: after the last level, one lane per block of every image of the chunk (max_blocks: the most any
+ *   one has): |coefficient x quantiser| above AVSEP_JPEG_MAX_COEF sets bit 128 (a progressive coefficient is only whole then;
+ *   a baseline image's lanes have checked theirs already).  coef off a 16-byte boundary is AVSEP_ERR_ARG.
+ * A null pointer, a count < 1 or a size < 1 is AVSEP_ERR_ARG before any launch. */
+int avsep_jpeg_scan_check(const avsep_jpeg_image* images, int32_t n_images, const avsep_jpeg_scan* scans, int32_t n_scans,
+                          int64_t nbytes, int64_t table_words, int64_t pixel_bytes, int64_t ws_blocks);
+int avsep_jpeg_scans(const uint8_t* bytes, int64_t nbytes, const avsep_jpeg_image* images, int32_t n_images,
+                     const avsep_jpeg_scan* scans, int32_t n_scans, int32_t level, int32_t zero, const int32_t* tables,
+                     int64_t table_words, int16_t* coef, int64_t ws_blocks, int32_t* status, avsep_stream_t stream);
+int avsep_jpeg_coef_bound(const int16_t* coef, int64_t ws_blocks, const avsep_jpeg_image* images, int32_t n_images,
+                          int32_t max_blocks, const int32_t* tables, int64_t table_words, int32_t* status, avsep_stream_t stream);
+
 /* ---- Baseline JPEG files written (csrc/jpeg_enc.hip, csrc/jpeg_parts.h; avsep_amd/jpeg.py: encode): uint8 [H][W] (grey, one
  * component) or [H][W][3] (RGB -> YCbCr, three components) -> the entropy-coded bytes of a file, byte for byte what libjpeg-turbo's
  * default encoder (Pillow's `save(f, "JPEG", quality=, subsampling=, restart_marker_blocks=)`) puts after its SOS segment, EOI

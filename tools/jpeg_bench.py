@@ -11,7 +11,11 @@ writes the MUSIC frames.
   (d) the loader at the train_MUSIC shape (tools/loader_bench.py's dataset): ds[i] on one core, to_device of a batch and the
       one-worker loader rate, for --gpu_frames alone (the parent commit's path, unchanged) and with --gpu_decode, in the same run.
 Prints each figure as it is measured and writes --out (default profiles/jpeg_bench.json); the last line is one JSON object.
-Usage: python tools/jpeg_bench.py [--files 384] [--clip 4800] [--reps 10] [--sections batch,pillow,clip,loader] [--out FILE]"""
+  --progressive: (a) and, over the same pictures saved with progressive=True: the entropy stage level by level and in
+      all, the bound check, the pixel stage, jpeg.plan, jpeg.decode end to end, Pillow on one core on the progressive files, and
+      the stages of ONE file alone (its serial part); written to profiles/jpeg_progressive_bench.json.
+Usage: python tools/jpeg_bench.py [--files 384] [--clip 4800] [--reps 10] [--sections batch,pillow,clip,loader] [--progressive]
+       [--out FILE]"""
 import argparse
 import io
 import json
@@ -36,8 +40,8 @@ from loader_bench import event_ms, loader_flags, spread, sync_ms, write_dataset 
 H, W = 360, 640
 
 
-def make_files(n):
-    """n seeded pictures with smooth structure and grain, as JPEG bytes."""
+def make_files(n, **form):
+    """n seeded pictures with smooth structure and grain, as JPEG bytes (form: further arguments of Pillow's save)."""
     from PIL import Image
     rs, out = np.random.RandomState(0), []
     yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
@@ -46,7 +50,7 @@ def make_files(n):
         img = np.stack([127 + 100 * np.sin(xx / (20 + 9 * c) + ph[c, 0] + i / 9) * np.cos(yy / (15 + 7 * c) + ph[c, 1]) for c in range(3)], 2)
         img += rs.randn(H, W, 3) * 12
         b = io.BytesIO()
-        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(b, "JPEG", quality=75, subsampling=2)
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(b, "JPEG", quality=75, subsampling=2, **form)
         out.append(b.getvalue())
     return out
 
@@ -102,6 +106,91 @@ def batch_rows(o, dev, files, result):
           f"{ent:.2f} ms = {r['entropy_us_per_frame']:.0f} us per frame, pixel stage {r['pixels_ms']:.2f} ms = "
           f"{r['pixels_us_per_frame']:.1f} us per frame (both stages {tot:.2f} ms, the difference); equal to Pillow on {r['checked']} files: "
           f"{same}", flush=True)
+
+
+def scan_stage(p, dev):
+    """The device buffers of a one-chunk progressive plan and one launcher per step of its entropy stage -> (steps, buffers):
+    steps = [(name, fn)]: every level (the first one zeroes the workspace), the bound check, the pixel stage."""
+    ch = p.chunks[0]
+    assert len(p.chunks) == 1 and not len(ch.segs)
+    data, tables, images, scans = (torch.from_numpy(a).to(dev) for a in (p.bytes, p.tables, p.images.view(np.uint8), ch.scans.view(np.uint8)))
+    coef = torch.empty(ch.blocks * 64, dtype=torch.int16, device=dev)
+    planes = torch.empty(ch.blocks * 64, dtype=torch.uint8, device=dev)
+    pixels = torch.empty(p.pixel_bytes, dtype=torch.uint8, device=dev)
+    status = torch.zeros(len(p.images), dtype=torch.int32, device=dev)
+    size = jpeg.SCAN.itemsize
+    steps = [(f"level_{level}", lambda level=level, a=a, b=b: K.jpeg_scans(data, images, scans[a * size:b * size], level, a == 0, tables,
+                                                                            coef, ch.blocks, status)) for level, a, b in ch.levels]
+    steps.append(("bound", lambda: K.jpeg_coef_bound(coef, ch.blocks, images, ch.max_blocks, tables, status)))
+    steps.append(("pixels", lambda: K.jpeg_pixels(coef, planes, ch.blocks, images, ch.max_blocks, ch.max_pixels, tables, status, pixels)))
+    return steps, (pixels, status)
+
+
+def sequence_ms(steps, status, reps):
+    """The steps in their order, an event between each two (a level only means something after the levels before it) ->
+    {name: median ms}, "entropy": everything before the pixel stage."""
+    runs = []
+    for r in range(1 + reps):
+        status.zero_()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(steps) + 1)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for k, (_, fn) in enumerate(steps):
+            fn()
+            ev[k + 1].record()
+        torch.cuda.synchronize()
+        if r:
+            runs.append([ev[k].elapsed_time(ev[k + 1]) for k in range(len(steps))] + [ev[0].elapsed_time(ev[len(steps) - 1])])
+    return {name: statistics.median(v) for name, v in zip([n for n, _ in steps] + ["entropy"], zip(*runs))}
+
+
+def progressive_rows(o, dev, files, result):
+    """The same pictures saved progressive, beside the baseline rows of this run: the entropy stage level by level and in
+    all, the pixel stage, jpeg.plan on the host, jpeg.decode end to end, Pillow on one core on the PROGRESSIVE files, and the
+    serial part of ONE file (a plan of one file: one lane baseline, one lane per scan and level progressive)."""
+    prog = make_files(len(files), progressive=True)
+    t0 = time.perf_counter()
+    p = jpeg.plan(prog, progressive=True)
+    plan_ms = (time.perf_counter() - t0) * 1e3
+    n = len(p.images)
+    assert not p.fallback and n == len(prog)
+    steps, (pixels, status) = scan_stage(p, dev)
+    for _, fn in steps:
+        fn()
+    torch.cuda.synchronize()
+    assert not status.any().item()
+    got = pixels.cpu().numpy()
+    same = all(np.array_equal(got[int(p.offsets[i]):int(p.offsets[i + 1])].reshape(H, W, 3), pillow(prog[i])) for i in range(min(o.check, n)))
+    row = {"files": n, "file_bytes_mean": sum(map(len, prog)) / n, "scan_rows": int(len(p.chunks[0].scans)), "plan_ms": plan_ms,
+           "equals_pillow": bool(same), "checked": min(o.check, n)}
+    row.update({f"{name}_ms": ms for name, ms in sequence_ms(steps, status, o.reps).items()})
+    row["entropy_us_per_frame"] = 1e3 * row["entropy_ms"] / n
+    row["decode_ms"] = statistics.median(sync_ms(lambda: jpeg.decode(prog, dev, progressive=True), o.reps, warmup=1))
+    row["decode_ms_baseline"] = statistics.median(sync_ms(lambda: jpeg.decode(files, dev), o.reps, warmup=1))
+    t0 = time.perf_counter()
+    jpeg.plan(files)
+    row["plan_ms_baseline"] = (time.perf_counter() - t0) * 1e3
+    threads, m = torch.get_num_threads(), min(o.cpu_files, n)
+    torch.set_num_threads(1)
+    try:
+        for name, fs in (("pillow_ms_per_file", prog), ("pillow_ms_per_file_baseline", files)):
+            pillow(fs[0])
+            t0 = time.perf_counter()
+            for f in fs[:m]:
+                pillow(f)
+            row[name] = (time.perf_counter() - t0) * 1e3 / m
+    finally:
+        torch.set_num_threads(threads)
+    # one file alone: what a file's slowest chain of lanes costs
+    one, (_, status1) = scan_stage(jpeg.plan(prog[:1], progressive=True), dev)
+    row["one_file"] = sequence_ms(one, status1, o.reps)
+    q = jpeg.plan(files[:1])
+    d1, t1, i1, s1 = (torch.from_numpy(a).to(dev) for a in (q.bytes, q.tables, q.images.view(np.uint8), q.chunks[0].segs.view(np.uint8)))
+    c1, st1 = torch.empty(q.chunks[0].blocks * 64, dtype=torch.int16, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    row["one_file"]["baseline_entropy"] = statistics.median(event_ms(lambda: K.jpeg_entropy(d1, i1, s1, t1, c1, q.chunks[0].blocks, st1),
+                                                                      o.reps, warmup=1))
+    result["progressive"] = row
+    print("progressive: " + json.dumps(row), flush=True)
 
 
 def pillow_row(o, files, result):
@@ -188,8 +277,14 @@ def main():
     ap.add_argument("--items", type=int, default=24)
     ap.add_argument("--batches", type=int, default=4)
     ap.add_argument("--sections", type=lambda v: v.split(","), default=["batch", "pillow", "clip", "loader"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_bench.json"))
+    ap.add_argument("--progressive", action="store_true",
+                    help="the pass over the same pictures saved progressive, beside the baseline batch rows (writes "
+                         "profiles/jpeg_progressive_bench.json unless --out is given)")
+    ap.add_argument("--out", default=None)
     o = ap.parse_args()
+    if o.progressive:
+        o.sections = ["batch", "progressive"]
+    o.out = o.out or os.path.join(ROOT, "profiles", "jpeg_progressive_bench.json" if o.progressive else "jpeg_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_bench measures on an MI355X; there is nothing to report without one")
     dev = torch.device("cuda", 0)
@@ -198,13 +293,15 @@ def main():
     files = make_files(o.files)
     if "batch" in o.sections:
         batch_rows(o, dev, files, result)
+    if "progressive" in o.sections:
+        progressive_rows(o, dev, files, result)
     if "pillow" in o.sections:
         pillow_row(o, files, result)
     if "clip" in o.sections:
         clip_row(o, dev, files, result)
     if "loader" in o.sections:
         loader_rows(o, dev, result)
-    result["command"] = "python tools/jpeg_bench.py"
+    result["command"] = "python tools/jpeg_bench.py" + (" --progressive" if o.progressive else "")
     os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
     with open(o.out, "w") as f:
         json.dump(result, f, indent=1)
