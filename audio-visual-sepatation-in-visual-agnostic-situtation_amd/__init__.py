@@ -17,7 +17,7 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # `separate`, `localise`, `score` (and what only they use) are imported on first use, not here: `python -m avsep_amd.separate` / `.localise` / `.score` must find
     # the module un-imported (runpy refuses one that the alias has already registered under the package's real name)
-    if name in ("separate", "localise", "score", "levels", "frames", "visuals", "jpeg"):
+    if name in ("separate", "localise", "score", "levels", "frames", "visuals", "jpeg", "png"):
         import importlib
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -287,15 +287,16 @@ def load_stack(path, device=None):
     frames, the earlier form); a ``.npy`` of uint8 must be [T,H,W,3] or [H,W,3] and comes back as uint8 [T,H,W,3]; a directory
     gives its .jpg / .jpeg / .png files in name order, each read as ``dataset._load_frames`` reads it, as uint8 [T,H,W,3].
     What cannot be read ends with SystemExit: this is the command lines' reader.
-    With ``device`` (a GPU) a folder's frames are decoded there (``jpeg.decode_stack``: baseline and progressive .jpg / .jpeg files through the
-    kernels, .png files and whatever the kernels refuse through Pillow) and the stack comes back on that device, the same bytes."""
+    With ``device`` (a GPU) a folder's frames are decoded there (``png.decode_stack``: baseline and progressive JPEG files and
+    8-bit PNG files through the kernels, whatever the kernels refuse through Pillow) and the stack comes back on that device, the
+    same bytes."""
     if os.path.isdir(path):
         names = sorted(n for n in os.listdir(path) if n.lower().endswith(IMAGE_SUFFIXES))
         if not names:
             raise SystemExit(f"{path}: no .jpg, .jpeg or .png file in this folder")
         if device is not None:
-            from . import jpeg
-            return jpeg.decode_stack([os.path.join(path, n) for n in names], device, progressive=True)
+            from . import png
+            return png.decode_stack([os.path.join(path, n) for n in names], device)
         try:
             from PIL import Image
         except ImportError:

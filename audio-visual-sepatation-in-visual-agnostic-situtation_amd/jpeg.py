@@ -13,6 +13,8 @@ every scan, ``plan`` adds one SCAN row per scan and restart interval, and the sc
 after level (csrc/jpeg_parts.h: jp_decode_scan), into the same workspace and the same pixel stage.
 
 The output layout is the one ``frames.plan_batch`` takes: every frame [H,W,3] uint8, back to back, in file order.
+PNG files are not this module's: ``plan`` refuses them as "not a JPEG", and ``png.decode_stack`` (what ``frames.load_stack``
+calls) sends them to the kernels of csrc/png.hip and everything else here.
 
 The way back (csrc/jpeg_enc.hip): ``encode`` writes uint8 pictures on the device as baseline JPEG files, byte for byte the files
 Pillow's ``save`` writes; ``encode_header`` / ``encode_plan`` / ``encode_launch`` are its parts.  See the second half of this file.
@@ -659,12 +661,25 @@ def plan(files, cap=WORKSPACE_CAP, progressive=False):
         ch.max_blocks, ch.max_pixels = max(f.blocks for f in forms[ch.a:ch.b]), max(f.H * f.W for f in forms[ch.a:ch.b])
     data = np.concatenate(data) if data else np.zeros(0, dtype=np.uint8)
     p = DecodePlan(data, images, [i for i, _, _ in kept], chunks, tables.buffer(), fallback, reasons, shapes, offsets, int(offsets[-1]))
-    for ch in chunks:
-        if len(ch.segs) or not len(ch.scans):
-            K.jpeg_plan_check(ch.images, ch.segs, max(len(data), 1), len(p.tables), p.pixel_bytes, ch.blocks)
-        if len(ch.scans):
-            K.jpeg_scan_check(ch.images, ch.scans, max(len(data), 1), len(p.tables), p.pixel_bytes, ch.blocks)
+    _check(p)
     return p
+
+
+def _check(p):
+    """Every chunk of a DecodePlan against its buffer sizes (avsep_jpeg_plan_check, avsep_jpeg_scan_check)."""
+    for ch in p.chunks:
+        if len(ch.segs) or not len(ch.scans):
+            K.jpeg_plan_check(ch.images, ch.segs, max(len(p.bytes), 1), len(p.tables), p.pixel_bytes, ch.blocks)
+        if len(ch.scans):
+            K.jpeg_scan_check(ch.images, ch.scans, max(len(p.bytes), 1), len(p.tables), p.pixel_bytes, ch.blocks)
+
+
+def rebase(p, offsets, pixel_bytes):
+    """Move a DecodePlan into a pixel buffer it shares with other decoders (png.decode_stack): file i of the plan starts at
+    offsets[i] of a buffer of pixel_bytes bytes.  The rows are checked again against the new size."""
+    p.offsets, p.pixel_bytes = np.asarray(offsets, dtype=np.int64), int(pixel_bytes)
+    p.images["pix_off"] = [p.offsets[i] for i in p.index]
+    _check(p)
 
 
 def launch(p, device, pixels=None, coef=None, planes=None):
@@ -715,12 +730,20 @@ def decode(files, device, cap=WORKSPACE_CAP, decoded=None, progressive=False):
     if len(p.images):
         st = status.cpu().numpy()
         again += [p.index[r] for r in np.flatnonzero(st[:len(p.images)])]
+    fill_from_pillow(pixels, files, again, p.shapes, p.offsets, decoded)
+    return pixels, list(p.shapes)
+
+
+def fill_from_pillow(pixels, files, again, shapes, offsets, decoded=None, who="jpeg.decode"):
+    """The files ``again`` (indices into ``files``) decoded by Pillow, each copied into its slot of ``pixels``: H * W * 3 bytes
+    from offsets[i].  ``decoded`` {index: uint8 [H,W,3]} hands over pixels the caller already has.  A file Pillow cannot read
+    raises as it does there."""
     for i in sorted(again):
         a = decoded[i] if decoded is not None and i in decoded else _pillow(files[i])
-        if a.shape != p.shapes[i] + (3,):
-            raise AvsepError(f"jpeg.decode: file {i} is {p.shapes[i]} by its header and {a.shape[:2]} once decoded")
-        pixels[int(p.offsets[i]):int(p.offsets[i + 1])] = torch.from_numpy(np.array(a)).reshape(-1).to(pixels.device)
-    return pixels, list(p.shapes)
+        if a.shape != tuple(shapes[i]) + (3,):
+            raise AvsepError(f"{who}: file {i} is {shapes[i]} by its header and {a.shape[:2]} once decoded")
+        at = int(offsets[i])
+        pixels[at:at + a.size] = torch.from_numpy(np.array(a)).reshape(-1).to(pixels.device)
 
 
 def decode_stack(paths, device, progressive=False):

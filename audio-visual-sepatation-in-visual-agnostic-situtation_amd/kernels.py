@@ -1345,6 +1345,40 @@ def jpeg_enc_stuff(stream_buf, images, n_intervals, ivl_off, ffpos, ff0, out_off
          ptr(out), out.numel(), ptr(sizes))
 
 
+def png_plan_check(images, nbytes, table_bytes, pixel_bytes, ws_bytes):
+    """avsep_png_plan_check (include/avsep.h; host only, no GPU): images = a NumPy array of dtype np.dtype(lib.PngImage), the
+    rows of one chunk.  AvsepError for anything the library refuses."""
+    images = np.ascontiguousarray(images)
+    rc = lib.load().avsep_png_plan_check(images.ctypes.data, len(images), int(nbytes), int(table_bytes), int(pixel_bytes), int(ws_bytes))
+    if rc != 0:
+        raise lib.AvsepError(f"avsep_png_plan_check refused {len(images)} images: a size, colour type or channel count outside the "
+                             f"limits, or a stream, scanline, palette or pixel range outside its buffer ({rc})")
+
+
+def png_inflate(data, images, ws, ws_bytes, status):
+    """avsep_png_inflate (include/avsep.h): data uint8 [bytes], images uint8 (the checked rows of one chunk), ws uint8
+    [>= ws_bytes], status int32 [images] (zeroed), all on one GPU.  Every image's zlib stream is inflated into its scanlines in
+    ws; a lane that stops sets its image's status word."""
+    _jpeg_buffers("png_inflate", data, ((data, torch.uint8), (images, torch.uint8), (ws, torch.uint8), (status, torch.int32)))
+    n = _jpeg_rows("png_inflate", images, ((ws, "ws", int(ws_bytes)),), lib.PngImage)
+    if status.numel() != n:
+        raise lib.AvsepError(f"png_inflate: {status.numel()} status words for {n} images")
+    call("avsep_png_inflate", ptr(data), data.numel(), ptr(images), n, ptr(ws), int(ws_bytes), ptr(status))
+
+
+def png_pixels(ws, ws_bytes, images, max_pixels, tables, status, pixels, stages=3):
+    """avsep_png_pixels (include/avsep.h): the scanlines of one chunk are unfiltered in place and turned into the chunk's frames
+    in pixels uint8 [bytes]; tables uint8 [bytes] holds the palettes; images whose status word is set are skipped.  stages: 1 =
+    unfilter only, 2 = colour only, 3 = both."""
+    _jpeg_buffers("png_pixels", ws, ((ws, torch.uint8), (images, torch.uint8), (tables, torch.uint8), (status, torch.int32),
+                                     (pixels, torch.uint8)))
+    n = _jpeg_rows("png_pixels", images, ((ws, "ws", int(ws_bytes)),), lib.PngImage)
+    if status.numel() != n:
+        raise lib.AvsepError(f"png_pixels: {status.numel()} status words for {n} images")
+    call("avsep_png_pixels", ptr(ws), int(ws_bytes), ptr(images), n, int(max_pixels), ptr(tables), tables.numel(), ptr(status),
+         ptr(pixels), pixels.numel(), int(stages))
+
+
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 

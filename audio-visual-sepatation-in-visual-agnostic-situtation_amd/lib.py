@@ -69,6 +69,13 @@ class JpegScan(C.Structure):
                [("table", C.c_int32 * 3)] + [(n, C.c_int32) for n in "unit0 units level".split()] + [("reserved", C.c_int32 * 2)]
 
 
+class PngImage(C.Structure):
+    """avsep_png_image (include/avsep.h): one image of the avsep_png_* entry points; np.dtype(PngImage) is the layout of a table
+    of rows on the host and on the device."""
+    _fields_ = [(n, C.c_int64) for n in "pix_off begin end ws_off".split()] + \
+               [(n, C.c_int32) for n in "H W colour channels palette entries".split()] + [("reserved", C.c_int32 * 2)]
+
+
 _P, _I, _F, _D, _Z =C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t
 _CD, _KD = C.POINTER(ConvDesc), C.POINTER(CatDesc)
 _L = C.c_int64
@@ -150,6 +157,9 @@ SIGNATURES = {
     "avsep_jpeg_enc_count": (C.c_int, [_P, _L, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P]),
     "avsep_jpeg_enc_pack": (C.c_int, [_P, _L, _P, _I, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
     "avsep_jpeg_enc_stuff": (C.c_int, [_P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
+    "avsep_png_plan_check": (C.c_int, [_P, _I, _L, _L, _L, _L]),
+    "avsep_png_inflate": (C.c_int, [_P, _L, _P, _I, _P, _L, _P, _P]),
+    "avsep_png_pixels": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _P, _L, _I, _P]),
     "avsep_fusion_av_fwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "avsep_fusion_av_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                       _P, _P, _P, _P]),

@@ -538,8 +538,8 @@ def build_parser():
                                                            "shot: a uint8 .npy [H,W,3] or [T,H,W,3], or a folder of .jpg / .png "
                                                            "files in name order, prepared on the GPU at --imgSize")
     p.add_argument("--gpu_decode", action="store_true",
-                   help="decode the .jpg / .jpeg files of a --frames folder on the GPU (baseline and progressive JPEGs; anything else, .png included, "
-                        "is read through Pillow as without the flag): the same pixels, without the one-core decode")
+                   help="decode the image files of a --frames folder on the GPU (baseline and progressive JPEGs and 8-bit PNGs, .png files included; "
+                        "anything else is read through Pillow as without the flag): the same pixels, without the one-core decode")
     p.add_argument("--fps", type=float, default=None, help="video frames per second of the .npy stacks (needs the spatial visual "
                                                            "features of --not_pool_vis)")
     p.add_argument("--frame_offset", type=float, default=0.0, help="time of the first video frame, seconds from the WAV's start")

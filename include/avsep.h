@@ -989,6 +989,57 @@ int avsep_jpeg_enc_stuff(const uint8_t* stream_buf, int64_t stream_bytes, const 
                          int64_t n_intervals, const int64_t* ivl_off, const int64_t* ffpos, const int64_t* ff0,
                          const int64_t* out_off, uint8_t* out, int64_t out_bytes, int64_t* sizes, avsep_stream_t stream);
 
+/* ---- PNG frames (csrc/png.hip, csrc/png_parts.h; avsep_amd/png.py): bit depth 8, colour type 0 (grey), 2 (RGB),
+ * 3 (palette), 4 (grey + alpha) or 6 (RGBA), not interlaced -> uint8 RGB [H][W][3], the pixels of Pillow's
+ * `Image.open(p).convert("RGB")`.  The host walks the chunks, checks their CRCs and hands over, in DEVICE memory,
+ *   bytes  uint8 [nbytes]: the zlib streams (the IDAT payloads of a file joined) of the images back to back;
+ *   tables uint8 [table_bytes]: the palettes, 3 bytes (R, G, B) per entry, anywhere in it, equal palettes shared;
+ *   one row per image.  THE RULE:
+ *   inflate   RFC 1950 / 1951, at least as strict as zlib 1.2.11's inflate(): the stream must fill exactly the image's
+ *             H * (1 + W * channels) filtered bytes, end with the Adler-32 of those bytes and have nothing after it;
+ *   unfilter  per scanline its filter byte 0 .. 4: None, Sub, Up, Average = floor((a + b) / 2) on the 9-bit sum, Paeth with
+ *             p = a + b - c and the first of a, b, c nearest to p; a = the byte `channels` to the left, b the one above,
+ *             c the one above a; zero outside the image; sums modulo 256;
+ *   colour    grey -> (g, g, g); RGB as it is; grey + alpha and RGBA lose their alpha (no compositing); palette -> the
+ *             entry's three bytes, an index at or past `entries` being an error. */
+typedef struct avsep_png_image {
+  int64_t pix_off;                          /* the image's first byte in `pixels`: H*W*3 bytes */
+  int64_t begin, end;                       /* its zlib stream: bytes[begin .. end) */
+  int64_t ws_off;                           /* its filtered scanlines in the workspace: H * (1 + W * channels) bytes */
+  int32_t H, W;                             /* 1 <= H, W <= 16384, H * W <= 2^26 */
+  int32_t colour, channels;                 /* colour type 0 | 2 | 3 | 4 | 6 and its bytes per pixel 1 | 3 | 1 | 2 | 4 */
+  int32_t palette, entries;                 /* colour type 3: byte offset in `tables` and entry count 1 .. 256; else 0, 0 */
+  int32_t reserved[2];
+} avsep_png_image;                          /* 64 bytes.  pix_off, begin, ws_off >= 0; end >= begin */
+/* avsep_png_plan_check (host only, nothing is launched): every HOST row against the limits above and against the buffer
+ *   sizes: stream inside nbytes, scanlines inside ws_bytes, pixels inside pixel_bytes, palette inside table_bytes, channels
+ *   matching the colour type.  AVSEP_ERR_ARG on the first row that fails.
+ * avsep_png_inflate: one lane (a wavefront of its own: one stream is serial, and lanes that walk different streams pay for
+ *   each other's branches) per image inflates its stream straight into its scanlines in `ws`, which are also the
+ *   LZ77 window; the block's Huffman tables are built by the lane in LDS.  A lane trusts neither its row nor the stream.  Each
+ *   of these stops it and ORs the bit into status[image]: a read outside the stream (1); a zlib header with CM != 8,
+ *   CINFO > 7, a failing FCHECK or FDICT (2); block type 3 (4); a stored block whose LEN is not the complement of NLEN (8);
+ *   HLIT > 286 or HDIST > 30 (16); a length repeat with no previous length or past HLIT + HDIST (32); an over-subscribed code
+ *   set (64); an incomplete one, but for zlib's exception, a literal/length or distance set whose longest code is 1 bit
+ *   (128); no end-of-block code (256); no code within 15 bits or a code the set leaves unused (512); literal/length symbol
+ *   286 / 287 or distance symbol 30 / 31 (1024); a distance beyond the bytes written (2048); output past the image's
+ *   scanlines (4096); a final block that ends short of them (8192); bytes left after the Adler-32 (16384); an Adler-32 that
+ *   does not match (32768); the loop bound, output bytes + stream bits, exceeded (65536); a row outside its limits or its
+ *   buffers (524288).  No check reads or writes out of range.  status: int32 [n_images], zeroed by the caller.
+ * avsep_png_pixels: the scanlines of every image whose status is 0 are unfiltered in place (one wavefront per image, lane k
+ *   = row k of a group of 64 rows, one pixel behind lane k - 1; a filter byte above 4 sets bit 131072) and then turned into
+ *   pixels, one lane per pixel (max_pixels: the most any one image has; a palette index at or past `entries` sets bit 262144).
+ *   Images whose status is not 0 are skipped: their pixels are left as they were.  stages: 3 = both; 1 = unfilter only, 2 =
+ *   colour only (for a caller that times them apart; colour alone takes scanlines that are already unfiltered).
+ * A null pointer, a count < 1 (or n_images above 65535), a size < 1 or stages outside 1 .. 3 is AVSEP_ERR_ARG before any launch. */
+int avsep_png_plan_check(const avsep_png_image* images, int32_t n_images, int64_t nbytes, int64_t table_bytes, int64_t pixel_bytes,
+                         int64_t ws_bytes);
+int avsep_png_inflate(const uint8_t* bytes, int64_t nbytes, const avsep_png_image* images, int32_t n_images, uint8_t* ws,
+                      int64_t ws_bytes, int32_t* status, avsep_stream_t stream);
+int avsep_png_pixels(uint8_t* ws, int64_t ws_bytes, const avsep_png_image* images, int32_t n_images, int32_t max_pixels,
+                     const uint8_t* tables, int64_t table_bytes, int32_t* status, uint8_t* pixels, int64_t pixel_bytes,
+                     int32_t stages, avsep_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * AVSEP_FMT_B16 images (bf16, [N][C/16][H][W][16]; csrc/b16.hip): what travels between the bf16 convolution kernels.
  * HW = H*W positions; every entry point is one HBM pass with 16-byte accesses.  Statistics buffers are pre-zeroed doubles
